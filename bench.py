@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- DipGenie diploid hot path on MI355X (see DESIGN.md s6 for what every field means).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 N = 1 (BASELINE.json configs[2], the configuration the metric is quoted on): synthetic MHC-24 -- 24 walks over the MHC_4
@@ -23,6 +23,9 @@ all-to-all of (hash, count) runs, sharded merge, one fused all-reduce of range s
 sketch_reads_per_s, `value` = reads x steps / max-over-ranks time, "scaling": "strong" (the read set is fixed); rank 0
 re-scores the whole set alone afterwards and every replicated output must be identical.  One DP instance per rank is
 timed beside it as `dp_replicated` (informational).
+
+--dump-outputs DIR writes what the last timed step computed (N = 1: the DP outcome and the scoring result; N > 1: rank 0's
+scoring result) as DIR/<name>.npy in float64, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -317,6 +320,42 @@ def config5_block(cache, device, cores):
     return blk
 
 
+DUMP_MAX_ROWS = 1 << 20           # --dump-outputs: a longer array is written as a fixed, seeded sample of this many rows (8 MB as float64)
+
+
+def step_outputs(out=None, score=None):
+    """what a caller of the timed path receives from its last step: the DP outcome (capi.DpOutcome) and the scoring result
+    (dist_sketch.Score), as named host arrays"""
+    d = {}
+    if out is not None:
+        d.update(dp_value=[out.value], dp_s_het=[out.s_het], dp_cells=[out.cells], dp_relaxations=[out.relaxations],
+                 dp_p1=np.asarray(out.p1, np.int64).reshape(-1, 2), dp_p2=np.asarray(out.p2, np.int64).reshape(-1, 2))
+    if score is not None:
+        h = score.range_hash.cpu().numpy().view(np.uint64)
+        d.update(sketch_counts=score.counts.cpu().numpy(), sketch_ids=score.ids.cpu().numpy(), sketch_hist=score.hist.cpu().numpy(),
+                 sketch_n_distinct=[score.n_distinct], sketch_range_hash_hi32=h >> np.uint64(32), sketch_range_hash_lo32=h & np.uint64(0xFFFFFFFF),
+                 sketch_range_count=score.range_count.cpu().numpy())
+    return d
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """<dirname>/<name>.npy in float64 (every output is an integer below 2^53, so exact; 64-bit hashes are split in halves).  An
+    array of more than DUMP_MAX_ROWS rows keeps the rows at a sorted sample of indices drawn from a generator seeded with `seed`
+    and the row count: the same for every build that computes an array of that length."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.shape[0] > DUMP_MAX_ROWS:
+            a = a[np.sort(np.random.default_rng([seed, a.shape[0]]).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))]
+        a = a.astype(np.float64)
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs wrote {total} bytes, more than 64 MB")
+    log(f"dumped {len(arrays)} outputs of the last timed step to {dirname} ({total / 2**20:.1f} MB)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -333,7 +372,10 @@ def main():
     ap.add_argument("--no-config4", action="store_true", help="N = 1 only: skip the 30x read-set scoring measurement (BASELINE configs[3])")
     ap.add_argument("--no-config5", action="store_true", help="N = 1 only: skip the 5 Mbp x 100-walk run of the CLI (BASELINE configs[4] at a tenth of its size, about 25 s)")
     ap.add_argument("--ref-sample-frac", type=float, default=0.05, help="prefix of the bench panel the reference binary is timed on (cpu_baseline); 0.1 takes 74 s (161 M cells/s at 16 threads, profiles/r04_bench_mhc24.json)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -486,6 +528,8 @@ def main():
         acc["on"] = True
         elapsed = timed(step, 0, args.steps)
         out, score = last["out"], last["score"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, step_outputs(out, score))
         sk4 = None
         if cfg4 is not None:                                             # BASELINE configs[3] at one rank: the N = 1 point of the scaling curve
             (b4, o4), _resident, n4, rl4 = cfg4
@@ -505,6 +549,8 @@ def main():
             last["s4"] = sk.score(b4, o4, dict_t, K, W)
         elapsed = timed(step, args.warmup, args.steps)
         s4 = last["s4"]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(score=s4))
         local_ms = max_over_ranks(ctx_sk.sketch_timing().total_ms)[0]
         # untimed cross-check: rank 0 scores the whole read set alone; every replicated output must be identical
         ok = 1.0

@@ -37,16 +37,21 @@ def compare(g, fx):
         assert hashlib.sha256(d.astype("<u8").tobytes()).hexdigest() == fx["digests_sha256"]
 
 
+def dump_graph(harness, fx, tmp_path):
+    """the levelized graph our host pipeline builds from the fixture's GFA + reads (-X: dump, no DP)"""
+    subprocess.run([harness, "-q", "-t2", *fx["args"], "-X", "-D", str(tmp_path / "g"), "-g", os.path.join(ROOT, fx["gfa"]), "-r", os.path.join(ROOT, fx["reads"]),
+                    "-o", str(tmp_path / "o.fa")], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return capi.DpGraphArrays.load(str(tmp_path / "g.dpg"))
+
+
 @pytest.mark.parametrize("name", SMALL)
 def test_oracle_cells_equal_reference_cells(name, built_cpu, tmp_path):
-    fx = FIX[name]
-    subprocess.run([built_cpu, "-q", "-t2", *fx["args"], "-X", "-D", str(tmp_path / "g"), "-g", os.path.join(ROOT, fx["gfa"]), "-r", os.path.join(ROOT, fx["reads"]),
-                    "-o", str(tmp_path / "o.fa")], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    compare(capi.DpGraphArrays.load(str(tmp_path / "g.dpg")), fx)
+    compare(dump_graph(built_cpu, FIX[name], tmp_path), FIX[name])
 
 
-def test_oracle_cells_equal_reference_cells_mhc4():
-    """full-size MHC_4 (BASELINE configs[1] graph with the CHM13 reads): 120,362 levels, 421 M cells; the levelized graph is the
-    committed dump tests/data/mhc4.dpg (written by the host pipeline; tests/test_gpu_parity.py re-derives it from the GFA on the
-    GPU box and compares every digest of the HIP path with the oracle's)"""
-    compare(capi.DpGraphArrays.load(os.path.join(HERE, "data", "mhc4.dpg")), FIX["mhc4_p2"])
+@pytest.mark.slow
+def test_oracle_cells_equal_reference_cells_mhc4(built_cpu, tmp_path):
+    """full-size MHC_4 (BASELINE configs[1] graph with the CHM13 reads): 120,362 levels, 421 M cells; the levelized graph is
+    rebuilt here by the host pipeline from tests/data/MHC_4.gfa.gz + CHM13_reads.fq.gz, as for the small cases
+    (tests/test_gpu_parity.py derives it the same way on the GPU box and compares every digest of the HIP path with the oracle's)"""
+    compare(dump_graph(built_cpu, FIX["mhc4_p2"], tmp_path), FIX["mhc4_p2"])
