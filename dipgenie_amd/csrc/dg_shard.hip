@@ -40,9 +40,9 @@ struct Rccl {                                            // librccl entry points
         for (const char *n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
             if ((lib = dlopen(n, RTLD_LAZY | RTLD_LOCAL))) break;
         if (!lib) { err = std::string("librccl not found: ") + dlerror(); return false; }
-#define DG_SYM(F) do { F = (decltype(F))dlsym(lib, "nccl" #F); if (!F) { err = "librccl lacks nccl" #F; return false; } } while (0)
-        DG_SYM(CommInitAll); DG_SYM(CommDestroy); DG_SYM(GetErrorString); DG_SYM(AllReduce); DG_SYM(Send); DG_SYM(Recv); DG_SYM(GroupStart); DG_SYM(GroupEnd);
-#undef DG_SYM
+#define DG_DLSYM(F) do { F = (decltype(F))dlsym(lib, "nccl" #F); if (!F) { err = "librccl lacks nccl" #F; return false; } } while (0)
+        DG_DLSYM(CommInitAll); DG_DLSYM(CommDestroy); DG_DLSYM(GetErrorString); DG_DLSYM(AllReduce); DG_DLSYM(Send); DG_DLSYM(Recv); DG_DLSYM(GroupStart); DG_DLSYM(GroupEnd);
+#undef DG_DLSYM
         return true;
     }
 };

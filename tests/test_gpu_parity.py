@@ -5,7 +5,6 @@ import hashlib
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -323,27 +322,35 @@ def test_dp_alternative_kernels(gpu_ctx, mode):
             gpu_ctx.dp_set_option(k, v)
 
 
-def test_dp_symmetric_form_measurement_build(built_hip):
-    """The symmetric form of the sweep (dp_sweep_sym_kernel, dipgenie_amd/csrc/dg_dp_sweep_sym.hip: cells (i2, j2 >= i2) computed, value
-    and own back-pointer stored for both (i2, j2) and (j2, i2)) is correct and slower than the plain form on the levels it was built for
-    (DESIGN.md s3.3), so it lives in a measurement build only (make -C dipgenie_amd/csrc sym -> bin/libdipgenie_hip_sym.so; not built
-    by __graft_entry__.build(), so this test makes it; the record of this test on the MI355X: profiles/r04_sym_parity_and_ab.txt).  Forced onto EVERY level that
-    can take it (sym = 2): value, s_het, edge lists and every level digest -- the value and the winning predecessor pair of every cell,
-    mirror cells included, whose tie-break order (approximator.cpp:657-659) is NOT the transpose of their twin's -- must equal the
-    oracle's, for 1 / 2 / 3 / 4 / 6 / 8 recombination counts per task, fan-in rows inline, plain launches, host-built tables, no row
-    matrices.  Graphs: the 12 shapes of test_dp_random_levelized, fan-in rows (workgroups of their own), giant columns (in-degree > 64),
-    vertices without in-edges (dead rows / columns), widths around the 16-row tile and the 64-lane block, R + 1 not a multiple of the
-    chunk.  The product library must not know the option at all."""
+DP_SHAPES = [dict(), dict(max_width=30, n_levels=40, R=6), dict(max_width=3, n_levels=200, R=2), dict(R=0), dict(p_w1=0.9, R=18),
+             dict(p_colour=0.0), dict(p_colour=1.0, max_list=9, n_colours=10), dict(max_width=70, n_levels=10, R=4, extra_edges=3.0),
+             dict(min_width=1, max_width=1, n_levels=30, R=3), dict(max_width=12, n_levels=300, R=5, p_colour=0.1),
+             dict(max_width=40, n_levels=25, R=33, p_w1=0.5), dict(n_levels=2, R=2),
+             dict(max_width=30, n_levels=60, R=18, p_w1=0.3, p_colour=0.5), dict(max_width=60, n_levels=30, R=32, p_w1=0.6),
+             dict(max_width=64, n_levels=30, R=3, p_w1=0.5, p_colour=0.8), dict(max_width=3, n_levels=8, R=2, extra_edges=100.0),
+             dict(min_width=20, max_width=24, n_levels=8, R=2, extra_edges=70.0), dict(min_width=15, max_width=18, n_levels=40, R=7, p_colour=0.6),
+             dict(min_width=63, max_width=66, n_levels=12, R=9, p_w1=0.4, p_colour=0.3), dict(min_width=120, max_width=200, n_levels=6, R=5, p_colour=0.3, extra_edges=0.5),
+             dict(min_width=40, max_width=90, n_levels=10, R=4, p_colour=0.3, extra_edges=0.05), dict(min_width=100, max_width=140, n_levels=5, R=3, extra_edges=0.02)]
+
+
+@pytest.mark.parametrize("mode", ["default", "no_coop", "plain_launches", "host_tables", "no_rowx"])
+def test_dp_shapes_every_level_digest(gpu_ctx, mode):
+    """value, s_het, edge lists, cells, relaxations and every level digest against the oracle, in each option mode, on 22 graph shapes
+    (fan-in rows, vertices without in-edges, widths around the 64-lane block, R + 1 not a multiple of the chunk) and two fan-in rows
+    of in-degree 90 and 200"""
+    opts = {"default": {}, "no_coop": {"coop": 0}, "plain_launches": {"graph_batch": 0}, "host_tables": {"host_tables": 1}, "no_rowx": {"rowx": 0}}[mode]
     with pytest.raises(capi.DgError):
-        c = capi.Context(0)
-        try:
-            c.dp_set_option("sym", 1)
-        finally:
-            c.close()
-    lib = os.path.join(ROOT, "bin", "libdipgenie_hip_sym.so")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "dipgenie_amd", "csrc"), "sym"])     # one hipcc over every source (minutes)
-    p = subprocess.run([sys.executable, os.path.join(HERE, "sym_parity_main.py")], env=dict(os.environ, DG_LIB=lib), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0 and b"symmetric form parity ok" in p.stdout, p.stdout.decode()[-2000:] + p.stderr.decode()[-3000:]
+        gpu_ctx.dp_set_option("sym", 1)      # the symmetric form of the sweep was removed (DESIGN.md s3.3)
+    try:
+        for k, v in opts.items():
+            gpu_ctx.dp_set_option(k, v)
+        for q, kw in enumerate(DP_SHAPES):
+            _dp_both(gpu_ctx, graphgen.random_levelized(9700 + q, **kw))
+        for k in (90, 200):
+            _dp_both(gpu_ctx, _fan_in_graph(k))
+    finally:
+        for k, v in {"coop": 1, "graph_batch": -1, "host_tables": 0, "rowx": 1}.items():
+            gpu_ctx.dp_set_option(k, v)
 
 
 @pytest.mark.parametrize("lean", [1, 0])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of dg_dp_set_option sets on a dumped levelized graph: per option set, DP timings of a few passes, the launch profile, and -- with
 every level's digest collected -- equality of value, s_het, edge lists and all digests with the first set (the reference).
-usage: python tools/dp_opt_ab.py graph.dpg "k=v,k=v" ["k=v,k=v" ...]      (e.g. "symmetric=0" "symmetric=1"; options named in any set
+usage: python tools/dp_opt_ab.py graph.dpg "k=v,k=v" ["k=v,k=v" ...]      (e.g. "coop=0" "coop=1"; options named in any set
 are put back to the value they have in the FIRST set before the next set runs; load-time options reload the graph)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
