@@ -328,7 +328,7 @@ class Context:
         return h, p
 
     def hash_kmers(self, kmers, k):
-        n = len(kmers) // k
+        n = len(kmers) // k if k > 0 else 0          # (k outside 1..255 is the library's to reject)
         out = np.zeros(n, np.uint64)
         _check(lib.dg_hash_kmers(self.h, kmers, n, k, out.ctypes.data), "dg_hash_kmers")
         return out

@@ -50,6 +50,54 @@ def kat_sketch():
     return dict(windows=out, kmers=[dict(kmer=a, hash=b) for a, b in zip(kmers, hk)])
 
 
+def kat_sketch_kw():
+    """kat_sketch_kw.json: the same two kinds of vectors over the whole k, w range (1..255)"""
+    kmers = kat_long_kmers()
+    hk = sh([HARNESS, "hash"] + kmers).stdout.decode().split()
+    return dict(windows=kat_sketch_kw_range(), kmers=[dict(kmer=a, hash=b) for a, b in zip(kmers, hk)])
+
+
+# (k, w) pairs of kat_sketch_kw.json: every k meets a w < 64, one in 64..127 and one >= 128; every w meets a k <= 32 and a k > 32
+KW_RANGE = [(1, 1), (1, 64), (1, 255), (2, 2), (2, 127), (2, 128), (8, 33), (8, 65), (8, 129), (16, 63), (16, 64), (16, 200),
+            (17, 1), (17, 127), (17, 128), (24, 2), (24, 65), (24, 255), (32, 33), (32, 127), (32, 129), (33, 1), (33, 64), (33, 128),
+            (64, 2), (64, 65), (64, 200), (100, 33), (100, 127), (100, 129), (255, 63), (255, 64), (255, 255)]
+
+
+def kat_sketch_kw_range():
+    """the KW_RANGE pairs on a few sequences sized for the pair: k + w - 2 bases (no window), k + w - 1 (one window), nwin =
+    3 (w + 1) windows (a handful of minimizers; more than one tile of 128 windows once w >= 42) of mixed-case random bases with
+    an N run, an IUPAC code and a dinucleotide repeat, and a homopolymer (ties: the newest k-mer wins).  The tile
+    shapes themselves are the GPU tests' (tests/test_gpu_sketch_domain.py, against the oracle these vectors pin)."""
+    rng = np.random.default_rng(2025)
+    def rnd(n, alpha=b"ACGT"):
+        return bytes(rng.choice(np.frombuffer(alpha, np.uint8), n).tobytes()).decode()
+    out = []
+    for (k, w) in KW_RANGE:
+        L = k + w - 2 + 3 * (w + 1)
+        x = rnd(L, b"acgtACGT")
+        a, b = L // 3, 2 * L // 3
+        r = min(2 * w + 2, L - b)
+        mixed = x[:a] + "NNNNN" + x[a + 5:b] + "R" + ("AC" * r)[:r - 1] + x[b + r:]
+        seqs = [rnd(k + w - 2), rnd(k + w - 1), mixed, "C" * (k + w + 9)]
+        inp = ("\n".join(seqs) + "\n").encode()
+        hs = sh([HARNESS, "hashes", str(k), str(w)], inp).stdout.decode().split("\n")
+        ms = sh([HARNESS, "minimizers", str(k), str(w)], inp).stdout.decode().split("\n")
+        for s_, h, m in zip(seqs, hs, ms):
+            out.append(dict(seq=s_, k=k, w=w, hashes=h.split(), minimizers=m.split()))
+    return out
+
+
+def kat_long_kmers():
+    """k-mers of 101..255 bases (the byte hash's 16-byte blocks and every tail length of 0..15 among them)"""
+    rng = np.random.default_rng(2026)
+    def rnd(n, alpha=b"ACGT"):
+        return bytes(rng.choice(np.frombuffer(alpha, np.uint8), n).tobytes()).decode()
+    ks = [101, 104, 111, 112, 113, 120, 127, 128, 129, 136, 143, 150, 160, 175, 183, 192, 200, 209, 224, 239, 240, 241, 250, 254, 255]
+    out = [rnd(k) for k in ks]
+    out += [rnd(255, b"ACGTNacgt"), "A" * 255, rnd(128, b"ACGTRYKM*"), "ACGT" * 63]
+    return out
+
+
 def kat_fit():
     hists = {
         "mhc4_chm13_0.5x": {1: 116960, 2: 18754, 3: 2506, 4: 353, 5: 95, 6: 44, 7: 30, 8: 21, 9: 13, 10: 7, 11: 8, 12: 3, 13: 4, 14: 4,
@@ -183,14 +231,38 @@ def e2e():
                                        "58 s wall, DP 12.3 s")
     cases["mhc4_p1"] = dict(gfa="tests/data/MHC_4.gfa.gz", reads="tests/data/CHM13_reads.fq.gz", args=["-p1"],
                             fasta_md5="0c4df87ded10634a36db0a2c90521ff0", best_r_haploid=0, spectrum=138834, slow=True)
+    e2e_kw(cases)
     return cases
 
 
-def anchors(cases):
+def e2e_kw(cases):
+    """cases at non-default k and w (the drop-in CLI passes -k / -w through as the reference does): bubble chains
+    of short segments, so that one k-mer spans many vertices, and reads long enough for the window.  Appended to e2e.json; the
+    returned names get anchor goldens of their own."""
+    specs = [
+        ("kw_k33_w64", dict(seed=33, n_bubbles=16, n_haps=5, seg_len=(10, 40), coverage=6.0, read_len=400), ["-p2", "-R4", "-k33", "-w64"]),
+        ("kw_k8_w130", dict(seed=8, n_bubbles=16, n_haps=5, seg_len=(10, 40), coverage=6.0, read_len=400), ["-p2", "-R4", "-k8", "-w130"]),
+        ("kw_k64_w17", dict(seed=64, n_bubbles=16, n_haps=5, seg_len=(10, 40), coverage=6.0, read_len=400, sub_rate=0.005),
+         ["-p2", "-R5", "-k64", "-w17"]),
+        ("kw_k100_w129", dict(seed=100, n_bubbles=16, n_haps=5, seg_len=(10, 40), coverage=6.0, read_len=400), ["-p1", "-R3", "-k100", "-w129"]),
+    ]
+    ed = os.path.join(HERE, "e2e")
+    for name, kw, args in specs:
+        gfa, reads = os.path.join(ed, name + ".gfa"), os.path.join(ed, name + ".fa")
+        if not os.path.exists(gfa):
+            segs, links, walks, rd = synth.random_bubble_graph(**kw)
+            synth.write_gfa(gfa, segs, links, walks)
+            synth.write_fasta(reads, rd)
+        cases[name] = dict(gfa=f"tests/golden/e2e/{name}.gfa", reads=f"tests/golden/e2e/{name}.fa", **run_ref(gfa, reads, args))
+        print(name, cases[name].get("dp_value"), cases[name].get("r1"), cases[name].get("r2"), cases[name]["fasta_md5"], flush=True)
+    return [name for name, _, _ in specs]
+
+
+def anchors(cases, max_dump=65536):
     """Anchor_hits + homo_bv of the REAL reference (ref_harness anchors = Solver::read_gfa + read_ip_reads +
     compute_and_classify_anchors, solver.cpp:27-245, 449-887) for every e2e case with inputs on disk: the text dump
     ("id hap v0,v1,..." per occurrence in Anchor_hits order, then "homo id" lines), its sha256 and counts; dumps below
-    64 KB are committed verbatim."""
+    max_dump bytes are committed verbatim."""
     out = {}
     seen = {}
     for name, c in cases.items():
@@ -215,7 +287,7 @@ def anchors(cases):
         occ = [l for l in lines if not l.startswith("homo")]
         d = dict(k=int(k), w=int(w), T=float(T), n_occ=len(occ), n_ids=len({l.split()[0] for l in occ}), n_homo=len(lines) - len(occ),
                  sha256=hashlib.sha256(txt.encode()).hexdigest())
-        if len(txt) < 65536:
+        if len(txt) < max_dump:
             d["dump"] = lines
         out[name] = d
         print("anchors", name, d["n_occ"], d["n_ids"], d["n_homo"], d["sha256"][:12], flush=True)
@@ -300,12 +372,20 @@ if __name__ == "__main__":
     what = sys.argv[1:] or ["sketch", "fit", "e2e"]
     if "sketch" in what:
         json.dump(kat_sketch(), open(os.path.join(HERE, "kat_sketch.json"), "w"), indent=0)
+        json.dump(kat_sketch_kw(), open(os.path.join(HERE, "kat_sketch_kw.json"), "w"), indent=0)
     if "e2e" in what:
         json.dump(e2e(), open(os.path.join(HERE, "e2e.json"), "w"), indent=1)
     if "io" in what:                                              # adds the ingestion corner cases to the existing e2e.json
         cases = json.load(open(os.path.join(HERE, "e2e.json")))
         io_corners(cases)
         json.dump(cases, open(os.path.join(HERE, "e2e.json"), "w"), indent=1)
+    if "kw" in what:                                              # adds the non-default k / w cases to e2e.json and their anchors to anchors.json
+        cases = json.load(open(os.path.join(HERE, "e2e.json")))
+        names = e2e_kw(cases)
+        json.dump(cases, open(os.path.join(HERE, "e2e.json"), "w"), indent=1)
+        anch = json.load(open(os.path.join(HERE, "anchors.json")))
+        anch.update(anchors({n: cases[n] for n in names}, max_dump=0))   # (counts + sha256, no verbatim dump)
+        json.dump(anch, open(os.path.join(HERE, "anchors.json"), "w"), indent=0)
     if "anchors" in what:
         json.dump(anchors(json.load(open(os.path.join(HERE, "e2e.json")))), open(os.path.join(HERE, "anchors.json"), "w"), indent=0)
     if "dpg" in what:

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 KAT = json.load(open(os.path.join(HERE, "golden", "kat_sketch.json")))
+KAT_KW = json.load(open(os.path.join(HERE, "golden", "kat_sketch_kw.json")))     # the whole k, w range (1..255)
 CASES = json.load(open(os.path.join(HERE, "golden", "e2e.json")))
 
 
@@ -26,7 +27,7 @@ def _rnd(rng, n, alpha=b"ACGT"):
 
 # ------------------------------------------------------------------------------------- sketch
 def test_hash_kat(gpu_ctx):
-    kmers = [e for e in KAT["kmers"]]
+    kmers = [e for e in KAT["kmers"] + KAT_KW["kmers"]]
     for e in kmers:
         k = len(e["kmer"])
         assert int(gpu_ctx.hash_kmers(e["kmer"].encode(), k)[0]) == int(e["hash"], 16)
@@ -39,7 +40,7 @@ def test_hash_kat(gpu_ctx):
 
 def test_sketch_golden_vectors(gpu_ctx):
     """reference compute_hashes / index_kmers outputs for ACGT, N, lower-case, repeats, short inputs"""
-    for e in KAT["windows"]:
+    for e in KAT["windows"] + KAT_KW["windows"]:
         s = e["seq"].encode()
         h, c = gpu_ctx.sketch_reads([s], e["k"], e["w"])
         assert [f"{int(x):016x}" for x in h] == e["hashes"], (e["k"], e["w"], e["seq"][:24])
