@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- DipGenie diploid hot path on MI355X (see DESIGN.md s6 for what every field means).
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run does what the headline needs: it generates the seeded inputs (in a fresh directory unless --cache names one),
+runs the CLI once to dump the levelized DP graph, warms up, times the K steps and prints the line.  Everything else below --
+the timed end-to-end CLI runs and the checks against them, and at N = 1 `sketch_config4`, `concurrent_instances`,
+`cpu_baseline`, `native_runtime_check`, `config4_one_run` and `config5` -- runs only with --full.
 
 N = 1 (BASELINE.json configs[2], the configuration the metric is quoted on): synthetic MHC-24 -- 24 walks over the MHC_4
 segment set (5 real + 19 seeded mosaics with private variants), diploid -p2 -R18, 4x synthetic 150-bp reads.  A *step* is
 one pass of the hot path over that input, every input already resident in HBM: (a) minimizer scoring of the read set
 (HIP sketch, dictionary join, ids, histogram), then (b) the pair-of-paths DP (delta precompute, level sweep, traceback).
-`value` = DP state cells / s.  The same line carries `sketch_config4`: the 30x read set (configs[3]) scored on this one
+`value` = DP state cells / s.  With --full the same line carries `sketch_config4`: the 30x read set (configs[3]) scored on this one
 rank -- the N = 1 point of the scaling curve below -- and, measured by child processes after this process has released its device
 memory: `hip_runtime.native_runtime_check` (the DP passes again from bin/dg_dp_bench, plain C++ over the C ABI on the HIP runtime the
 library was built against), `config4_one_run` (configs[3] as one job: the plain CLI, bin/DipGenie --gpus 1 over RCCL and
@@ -28,10 +33,13 @@ timed beside it as `dp_replicated` (informational).
 scoring result) as DIR/<name>.npy in float64, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
+import atexit
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -362,7 +370,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="mhc24", choices=["mhc24", "mhc4"])
-    ap.add_argument("--cache", default=os.environ.get("DG_BENCH_CACHE", "/tmp/dg_bench_cache"))
+    ap.add_argument("--cache", default=os.environ.get("DG_BENCH_CACHE"),
+                    help="directory for the generated inputs, kept and reused across runs (default: a fresh one per run, removed at exit)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beside the headline (the --no-* options below thin it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-cells", type=float, default=6e8)
     ap.add_argument("--no-concurrent", action="store_true", help="skip the multi-instance-per-GPU measurement")
@@ -419,6 +429,15 @@ def main():
     from dipgenie_amd import capi, synth
     from dipgenie_amd.dist_sketch import HipOps, ShardedSketch, shard_bounds
 
+    # A fresh directory: no run reads inputs an earlier run generated.  It is removed at exit; a run killed by a signal
+    # leaves it behind as $TMPDIR/dg_bench_* (inputs and .dpg; with --full also the 30x reads and the config-5 panel).
+    if args.cache is None:
+        tmp = [tempfile.mkdtemp(prefix="dg_bench_") if rank == 0 else None]
+        if world > 1:
+            dist.broadcast_object_list(tmp, src=0)
+        args.cache = tmp[0]
+        if rank == 0:
+            atexit.register(shutil.rmtree, args.cache, True)
     os.makedirs(args.cache, exist_ok=True)
     if args.workload == "mhc24":
         name = "synthetic MHC-24 (5 real + 19 mosaic walks, seed 24), -p2 -R18, 4x 150-bp reads (seed 4)"
@@ -435,9 +454,15 @@ def main():
     cli = os.path.join(ROOT, "bin", "DipGenie")
     e2e = None
     if rank == 0:
-        # one end-to-end run of the drop-in CLI (HIP sketch + HIP DP): produces the levelized DP graph
-        # (.dpg) that the timed steps re-solve, and the end-to-end seconds with per-stage breakdown.
         base_cmd = [cli, "-t", str(usable_cores()), "-p2", f"-R{R}", "-g", gfa, "-r", reads_path, "-o", pre + ".fa", "-G", str(local_rank)]
+    if rank == 0 and not args.full:
+        # the drop-in CLI up to the levelized DP graph (.dpg) that the timed steps re-solve (-X: stop after the dump, no DP).
+        # It has mapped the lattice ahead of the DP all the same, so this process waits as after the runs below.
+        subprocess.run(base_cmd + ["-D", pre, "-X"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        time.sleep(args.e2e_gap_s)
+    elif rank == 0:
+        # end-to-end runs of the drop-in CLI (HIP sketch + HIP DP) with per-stage breakdown, then the same run again
+        # dumping the levelized DP graph (.dpg) that the timed steps re-solve.
         # Three timed runs, the median reported.  A run that has just exited leaves ~100 GB of HBM that the driver releases in the
         # background for 3-4 s, and the next process's first allocations wait for it (tools/back_to_back.sh): runs are spaced by
         # E2E_GAP_S so that each one sees the device a lone run sees.
@@ -488,7 +513,7 @@ def main():
     dict_t = torch.from_numpy(D.view(np.int64).copy()).to(device)
     del seqs, walks, dict_parts
     cfg4 = None
-    if args.workload == "mhc24" and (world > 1 or not args.no_config4):
+    if args.workload == "mhc24" and (world > 1 or (args.full and not args.no_config4)):
         if rank == 0:
             synth.ensure_mhc24_reads(os.path.join(args.cache, "mhc24"))
         barrier()
@@ -610,7 +635,7 @@ def main():
                 "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic", "config": config,
                 "Gbp_per_s": n4 * rl4 * steps / elapsed / 1e9, "local_sketch_ms_max_rank": local_ms, "distinct_hashes": s4.n_distinct,
                 "range_sizes": s4.range_sizes, "dictionary_hits": int((s4.counts > 0).sum().item()), "matches_single_rank": True,
-                "n1_reference": "the N = 1 run reports the same measurement as sketch_config4.reads_per_s",
+                "n1_reference": "the N = 1 run with --full reports the same measurement as sketch_config4.reads_per_s",
                 "dp_replicated": {"value": world * cells * 2 / dp_el, "unit": "cells/s", "passes_each": 2,
                                   "note": "one independent DP instance per rank (the DP does not shard); informational, not `value`"},
             }
@@ -623,7 +648,7 @@ def main():
             built, bound = capi.hip_versions()
             line["hip_runtime"] = {"library_built_against": built, "bound_in_this_process": bound,
                                    "note": "bench.py imports torch first, so the library runs on torch's bundled HIP runtime here; the CLI (end_to_end_s) runs on the system's"}
-        if world == 1 and not args.no_concurrent:
+        if world == 1 and args.full and not args.no_concurrent:
             # Not the headline: several INDEPENDENT instances (samples) of the same workload in flight on this one GPU,
             # one dg_ctx + stream + host thread each.  A single instance is a chain of 140 k dependent level launches
             # that leaves most of the chip idle; this is what that idle capacity is worth to a cohort run.
@@ -656,7 +681,7 @@ def main():
                                                 "note": "independent samples on one GPU (one dg_ctx per sample); informational, not `value`"}
                 for c2 in extra:
                     c2.close()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_py as orc                           # the checker, timed as the CPU baseline ("port")
             gs, P = truncated_graph(g, args.cpu_sample_cells)
@@ -676,7 +701,7 @@ def main():
     ctx.close()
     ctx_sk.close()
     if rank == 0:
-        if world == 1:
+        if world == 1 and args.full:
             # the remaining two blocks run as child processes on the system's HIP runtime, after this process has released its device memory
             del ctx, ctx_sk
             torch.cuda.empty_cache()
