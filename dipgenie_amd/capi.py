@@ -62,6 +62,7 @@ SYMBOLS = [
     "dg_anchor_begin", "dg_anchor_add_haplotype", "dg_anchor_finish", "dg_dp_solve_haploid", "dg_dp_get_table_digest", "dg_hip_versions", "dg_anchor_add_haplotype_sketched",
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
+    "dg_dp_run_budgets", "dg_dp_get_budget_values",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -75,6 +76,8 @@ lib.dg_device_info.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_in
 lib.dg_dp_prealloc.argtypes = [C.c_void_p, C.c_int64]
 lib.dg_dp_load_graph.argtypes = [C.c_void_p, C.POINTER(DpGraph)]
 lib.dg_dp_run.argtypes = [C.c_void_p, C.POINTER(DpResult)]
+lib.dg_dp_run_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DpResult)]
+lib.dg_dp_get_budget_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -260,6 +263,26 @@ class Context:
         res, bufs = make_result(self._g.R + 8)
         _check(lib.dg_dp_run(self.h, C.byref(res)), "dg_dp_run")
         return outcome_from(res, bufs)
+
+    def dp_run_budgets(self, budgets):
+        """one sweep of the loaded graph, then the read-out of every listed budget (0..R, distinct, any order): a DpOutcome per
+        entry, equal to what a graph loaded with R = budget gives; an unreachable budget has value NEG_INF and empty paths"""
+        budgets = [int(b) for b in budgets]
+        arr = (DpResult * max(len(budgets), 1))()
+        keep = []
+        for q, b in enumerate(budgets):
+            res, bufs = make_result(max(b, 0) + 8)
+            arr[q] = res
+            keep.append(bufs)
+        want = np.asarray(budgets, np.int32)
+        _check(lib.dg_dp_run_budgets(self.h, want.ctypes.data if want.size else None, len(budgets), arr), "dg_dp_run_budgets")
+        return [outcome_from(arr[q], keep[q]) for q in range(len(budgets))]
+
+    def dp_budget_values(self):
+        """the sink's value on planes 0..R of the last dp_run / dp_run_budgets (int32[R + 1], NEG_INF where unreachable)"""
+        out = np.zeros(self._g.R + 1, np.int32)
+        _check(lib.dg_dp_get_budget_values(self.h, out.ctypes.data, out.size), "dg_dp_get_budget_values")
+        return out
 
     def dp_solve(self, g):
         self.dp_load_graph(g)

@@ -1,5 +1,5 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
-// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_run.hip).
+// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -69,6 +69,11 @@ struct LevelDesc {                                      // transition (l-1) -> l
 
 struct TraceOut { int32_t value, s_het, n_e, overflow, corrupt, path_score; };   // path_score: sum of the score deltas along the walked path (must equal value)
 struct ChainState { int32_t i, j, r, value; };
+// dg_dp_run_budgets: walker block q of the multi-chain launch walks chain `chain` (the caller's index) from plane `budget` of the
+// sink; blocks 0 .. G - 1 hold the group leaders, whose helpers read `planes` planes per level (dg_dp_trace.hip)
+struct BudgetSlot { int32_t chain, budget, planes, pad_; };
+constexpr int BUDGET_SYNC_STRIDE = 128;                 // bytes between the ChainSync records of two chains (a cache line each)
+constexpr int BUDGET_HELPER_BLOCKS = 80;                // blocks beyond the walkers: ten per XCD, LEAN_PREFETCHERS of them find a ticket
 struct ColourCsr { const int64_t *hom_off, *het_off; const int32_t *hom_col, *het_col; };
 
 struct SweepArgs {                                      // generic sweep kernel
@@ -202,6 +207,14 @@ struct DpState {
     } pool;
     std::vector<int> chunk_begin;              // destination levels [chunk_begin[c], chunk_begin[c+1]) live in chunk c
     int seg_chunks = 1;                        // chunks per lattice segment (= all of them when the lattice is resident)
+    // ---- every budget from one pass (dg_dp_run_budgets, dg_dp_budgets.hip) ----
+    // One chain per requested budget: its own path slice (L hop words), ChainState, ChainSync, TraceOut and edge block; d_mc_tab
+    // holds the budgets and the walker placement (BudgetSlot per block).  d_sink keeps the sink's RP values of the last run, taken
+    // when the sweep reaches the sink (the second pass of a segmented run overwrites the state ring).
+    DevBuf d_sink, d_mc_path, d_mc_chain, d_mc_sync, d_mc_trace, d_mc_edges, d_mc_tab;
+    std::vector<int32_t> sink_host;            // the sink's value on planes 0..R (dg_dp_get_budget_values); empty before the first run
+    int mc_groups = 0;                         // walker groups of the run at hand (chains of neighbouring budgets share an XCD and its helpers)
+    mutable int mc_seq = 0;                    // per-launch number of the multi-chain walk (counted from 0 in every dg_dp_run_budgets)
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -253,5 +266,13 @@ void trace_launch_warm_rows(const DpState &S, int lb, int le, hipStream_t s);
 void trace_launch_chain(const DpState &S, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s);
 void trace_launch_finish(const DpState &S, hipStream_t s);
 void trace_debug_report(const DpState &S);
+void trace_launch_finish_chain(const DpState &S, const uint2 *path, int32_t *edges, const ChainState *st, TraceOut *out, hipStream_t s);   // the finish kernel on one chain's buffers
+
+// ---- every budget from one pass (dg_dp_budgets.hip; the walkers themselves live beside the single walk in dg_dp_trace.hip) ----
+void trace_launch_chains(const DpState &S, int n, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s);
+void trace_debug_report_chains(const DpState &S, int n);
+void budgets_launch_sink_copy(const DpState &S, const int32_t *sink_state, hipStream_t s);   // sink values of planes 0..R -> d_sink
+int budgets_prepare(DpState &S, const int32_t *budgets, int n, hipStream_t s);                // buffers of n chains + walker placement
+void budgets_launch_finish(const DpState &S, int n, hipStream_t s);                           // the finish kernel once per chain
 
 }  // namespace dgi

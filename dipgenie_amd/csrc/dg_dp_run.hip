@@ -102,6 +102,7 @@ struct Run {
     int64_t n_launch = 0;
     int next_warm = 0;                                  // next level at which the look-ahead launch is due
     double host_enqueue_s = 0;                          // host time spent issuing the sweep's launches (DG_DEBUG)
+    int n_chains = 0;                                   // dg_dp_run_budgets: chains walked from the sink (0: the one chain of dg_dp_run)
     std::vector<uint16_t *> pool_base;
 
     Run(dg_ctx *c_, DpState &S_) : c(c_), S(S_), s(c_->stream) { sweep_prepare(S, X); }
@@ -229,7 +230,7 @@ struct Run {
             if (int rc = sweep_range(lb, le, biased[ch - c0])) return rc;
             host_enqueue_s += wall_s() - th0;
         }
-        if (mark_forward_end) DG_HIP(hipEventRecord(S.ev[2], s));
+        if (mark_forward_end) { DG_HIP(hipEventRecord(S.ev[2], s)); budgets_launch_sink_copy(S, state_ptr(S.L - 1), s); }
         if (S.test_poison_level > 0 && S.test_poison_level < S.L)        // tests: a level nobody swept / a damaged lattice
             for (int ch = c0; ch < c1; ++ch) {
                 const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1], lp = (int)S.test_poison_level;
@@ -238,7 +239,9 @@ struct Run {
         for (int ch = c1 - 1; ch >= c0; --ch) {
             const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1];
             trace_launch_warm_rows(S, lb, le, s);
-            trace_launch_chain(S, le - 1, lb, biased[ch - c0], from_sink && ch == c1 - 1 ? state_ptr(S.L - 1) : (const int32_t *)nullptr, s);
+            const int32_t *final_val = from_sink && ch == c1 - 1 ? state_ptr(S.L - 1) : (const int32_t *)nullptr;
+            if (n_chains) trace_launch_chains(S, n_chains, le - 1, lb, biased[ch - c0], final_val, s);
+            else trace_launch_chain(S, le - 1, lb, biased[ch - c0], final_val, s);
         }
         return DG_OK;
     }
@@ -274,6 +277,7 @@ struct Run {
                 if (int rc = sweep_range(S.seg_begin[sg], S.seg_begin[sg + 1], nullptr)) return rc;
             }
             DG_HIP(hipEventRecord(S.ev[2], s));                 // (the re-sweeps below are booked under traceback_ms)
+            budgets_launch_sink_copy(S, state_ptr(S.L - 1), s);  // the second pass overwrites the state ring
             // pass 2: last segment first -- restore its input state, re-sweep its chunks with back-pointers, walk them
             S.want_digest = 0;                                  // digests were accumulated in pass 1
             // Along a path the recombination count only grows, and a cell of plane r gathers from planes r, r - 1, r - 2 of the level
@@ -289,7 +293,18 @@ struct Run {
                     sweep_init_state(S, s);
                 const int c0 = sg * S.seg_chunks, c1 = std::min(n_chunks_all, c0 + S.seg_chunks);
                 if (int rc = sweep_and_walk(c0, c1, sg == n_seg - 1, false)) { S.want_digest = dig; S.rp_active = S.RP; return rc; }
-                if (S.plane_limit && sg > 0) {
+                if (S.plane_limit && sg > 0 && n_chains) {
+                    // several chains: up to the largest plane any of them left the segment on (an unreachable budget walks nothing)
+                    std::vector<ChainState> cs((size_t)n_chains);
+                    if (hipMemcpyAsync(cs.data(), S.d_mc_chain.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
+                    int planes = 1;
+                    for (const ChainState &q : cs) {
+                        if (q.value == NEG_INF) continue;
+                        planes = std::max(planes, (q.value != CHAIN_CORRUPT && q.r >= 0 && q.r < S.RP) ? q.r + 1 : S.RP);
+                    }
+                    S.rp_active = planes;
+                    planes_swept += (int64_t)S.rp_active * (S.seg_begin[sg] - S.seg_begin[sg - 1]);
+                } else if (S.plane_limit && sg > 0) {
                     ChainState cs{0, 0, S.RP - 1, 0};
                     if (hipMemcpyAsync(&cs, S.d_chain.p, sizeof cs, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
                     S.rp_active = (cs.value != CHAIN_CORRUPT && cs.r >= 0 && cs.r < S.RP) ? cs.r + 1 : S.RP;
@@ -301,7 +316,8 @@ struct Run {
             if (getenv("DG_DEBUG") && S.plane_limit) fprintf(stderr, "[dipgenie_hip] run: second pass swept %.1f %% of the (level, plane) pairs before the last segment\n",
                                                               100.0 * (double)planes_swept / std::max(1.0, (double)S.RP * (S.seg_begin[n_seg - 1] - 1)));
         }
-        trace_launch_finish(S, s);
+        if (n_chains) budgets_launch_finish(S, n_chains, s);
+        else trace_launch_finish(S, s);
         DG_HIP(hipEventRecord(S.ev[3], s));
         DG_HIP(hipGetLastError());
         return DG_OK;
@@ -310,54 +326,15 @@ struct Run {
 
 }  // namespace
 
-static int dp_run(dg_ctx *c, dg_dp_result *res) {
-    DpState *Sp = c->dp;
-    if (!Sp || !Sp->loaded) { set_error("dg_dp_run: no graph loaded"); return DG_ERR_STATE; }
-    if (!res) { set_error("dg_dp_run: null result"); return DG_ERR_ARG; }
-    DpState &S = *Sp;
-    Run run(c, S);
-    hipStream_t s = c->stream;
-    if (int rc = run.wait_for_chunks()) return rc;
-    TraceOut to;
-    std::vector<int32_t> edges(4 * (size_t)S.cap);
-    memset(S.launch_hist, 0, sizeof S.launch_hist);
-    run.n_launch = 0;
-    if (int rc = run.forward_and_trace()) return rc;
-    DG_HIP(hipMemcpyAsync(&to, S.d_trace.p, sizeof to, hipMemcpyDeviceToHost, s));
-    DG_HIP(hipMemcpyAsync(edges.data(), S.d_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
-    if (S.want_digest) {
-        S.digest_host.assign(S.L, 0);
-        DG_HIP(hipMemcpyAsync(S.digest_host.data(), S.d_digest.p, 8 * (size_t)S.L, hipMemcpyDeviceToHost, s));
-    }
-    DG_HIP(hipStreamSynchronize(s));
-#ifdef DG_SWEEP_PROBE
-    if (const char *po = getenv("DG_PROBE_OUT")) {
-        std::vector<unsigned long long> pr((size_t)S.L * 8);
-        DG_HIP(hipMemcpy(pr.data(), S.d_probe.p, 8 * pr.size(), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(po, "wb")) { fwrite(pr.data(), 8, pr.size(), f); fclose(f); }
-    }
-#endif
-    if (getenv("DG_DEBUG") && S.lean_chain) trace_debug_report(S);
-    if (getenv("DG_DEBUG") && S.pf_stream) {
-        int w[4] = {0, 0, 0, 0};
-        if (hipStreamSynchronize(S.pf_stream) == hipSuccess && hipMemcpy(w, S.d_pfctl.p, sizeof w, hipMemcpyDeviceToHost) == hipSuccess)
-            fprintf(stderr, "[dipgenie_hip] run: L2 table prefetcher covered %d levels (since load)\n", w[2]);
-    }
-    if (getenv("DG_DEBUG"))
-        fprintf(stderr, "[dipgenie_hip] run: host issued %lld sweep launches in %.1f ms (%.2f us each)\n", (long long)run.n_launch, 1e3 * run.host_enqueue_s,
-                1e6 * run.host_enqueue_s / (double)std::max<int64_t>(run.n_launch, 1));
-    DG_HIP(hipEventElapsedTime(&S.timing.delta_ms, S.ev[0], S.ev[1]));
-    DG_HIP(hipEventElapsedTime(&S.timing.forward_ms, S.ev[1], S.ev[2]));
-    DG_HIP(hipEventElapsedTime(&S.timing.traceback_ms, S.ev[2], S.ev[3]));
-    DG_HIP(hipEventElapsedTime(&S.timing.total_ms, S.ev[0], S.ev[3]));
-    S.timing.n_forward_launches = run.n_launch;
-    S.timing.n_segments = (int32_t)S.seg_begin.size() - 1;
-    S.timing.n_chunks = (int32_t)S.chunk_begin.size() - 1;
-    if (to.value == CHAIN_CORRUPT || to.corrupt) { set_error("back-pointer lattice is corrupt: the chain walk left its level (a level was not swept?)"); return DG_ERR_STATE; }
+// checks one chain's TraceOut and turns its edge records into the two weighted-edge lists; budget < 0: the chain of dg_dp_run
+static int emit_result(const DpState &S, const TraceOut &to, const int32_t *edges, dg_dp_result *res, int budget) {
+    char who[32] = "";
+    if (budget >= 0) snprintf(who, sizeof who, " (budget %d)", budget);
+    if (to.value == CHAIN_CORRUPT || to.corrupt) { set_error("back-pointer lattice is corrupt: the chain walk left its level (a level was not swept?)%s", who); return DG_ERR_STATE; }
     if (to.value != NEG_INF && to.path_score != to.value) {
-        set_error("traceback path scores %d but the DP value is %d: sweep, lattice and walk disagree", to.path_score, to.value); return DG_ERR_STATE;
+        set_error("traceback path scores %d but the DP value is %d: sweep, lattice and walk disagree%s", to.path_score, to.value, who); return DG_ERR_STATE;
     }
-    if (to.overflow || to.n_e > S.cap) { set_error("traceback edge list overflow (%d > %d)", to.n_e, S.cap); return DG_ERR_STATE; }
+    if (to.overflow || to.n_e > S.cap) { set_error("traceback edge list overflow (%d > %d)%s", to.n_e, S.cap, who); return DG_ERR_STATE; }
     res->value = to.value; res->s_het = to.s_het;
     res->cells = S.cells; res->relaxations = S.relaxations;
     // records arrive in arbitrary order: path order = ascending level (the two records of the last level are equal)
@@ -374,6 +351,80 @@ static int dp_run(dg_ctx *c, dg_dp_result *res) {
     return DG_OK;
 }
 
+// One pass over the resident graph.  n_budgets == 0: dg_dp_run (one chain from plane R of the sink into *res); otherwise
+// dg_dp_run_budgets: one chain per budgets[q] into res[q], all walked by one launch per lattice chunk (dg_dp_trace.hip).
+static int dp_run(dg_ctx *c, dg_dp_result *res, const int32_t *budgets = nullptr, int n_budgets = 0) {
+    const char *fn = n_budgets ? "dg_dp_run_budgets" : "dg_dp_run";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", fn); return DG_ERR_STATE; }
+    if (!res) { set_error("%s: null result", fn); return DG_ERR_ARG; }
+    DpState &S = *Sp;
+    Run run(c, S);
+    hipStream_t s = c->stream;
+    if (int rc = run.wait_for_chunks()) return rc;
+    const size_t n_out = (size_t)std::max(n_budgets, 1);
+    std::vector<TraceOut> to(n_out);
+    std::vector<int32_t> edges(4 * (size_t)S.cap * n_out);
+    if (n_budgets) { if (int rc = budgets_prepare(S, budgets, n_budgets, s)) return rc; }
+    run.n_chains = n_budgets;
+    memset(S.launch_hist, 0, sizeof S.launch_hist);
+    run.n_launch = 0;
+    S.sink_host.clear();
+    if (int rc = run.forward_and_trace()) return rc;
+    DG_HIP(hipMemcpyAsync(to.data(), n_budgets ? S.d_mc_trace.p : S.d_trace.p, sizeof(TraceOut) * n_out, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(edges.data(), n_budgets ? S.d_mc_edges.p : S.d_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
+    std::vector<int32_t> sink((size_t)S.RP);
+    DG_HIP(hipMemcpyAsync(sink.data(), S.d_sink.p, 4 * sink.size(), hipMemcpyDeviceToHost, s));
+    if (S.want_digest) {
+        S.digest_host.assign(S.L, 0);
+        DG_HIP(hipMemcpyAsync(S.digest_host.data(), S.d_digest.p, 8 * (size_t)S.L, hipMemcpyDeviceToHost, s));
+    }
+    DG_HIP(hipStreamSynchronize(s));
+    S.sink_host.swap(sink);
+#ifdef DG_SWEEP_PROBE
+    if (const char *po = getenv("DG_PROBE_OUT")) {
+        std::vector<unsigned long long> pr((size_t)S.L * 8);
+        DG_HIP(hipMemcpy(pr.data(), S.d_probe.p, 8 * pr.size(), hipMemcpyDeviceToHost));
+        if (FILE *f = fopen(po, "wb")) { fwrite(pr.data(), 8, pr.size(), f); fclose(f); }
+    }
+#endif
+    if (getenv("DG_DEBUG") && S.lean_chain) { if (n_budgets) trace_debug_report_chains(S, n_budgets); else trace_debug_report(S); }
+    if (getenv("DG_DEBUG") && S.pf_stream) {
+        int w[4] = {0, 0, 0, 0};
+        if (hipStreamSynchronize(S.pf_stream) == hipSuccess && hipMemcpy(w, S.d_pfctl.p, sizeof w, hipMemcpyDeviceToHost) == hipSuccess)
+            fprintf(stderr, "[dipgenie_hip] run: L2 table prefetcher covered %d levels (since load)\n", w[2]);
+    }
+    if (getenv("DG_DEBUG"))
+        fprintf(stderr, "[dipgenie_hip] run: host issued %lld sweep launches in %.1f ms (%.2f us each)\n", (long long)run.n_launch, 1e3 * run.host_enqueue_s,
+                1e6 * run.host_enqueue_s / (double)std::max<int64_t>(run.n_launch, 1));
+    DG_HIP(hipEventElapsedTime(&S.timing.delta_ms, S.ev[0], S.ev[1]));
+    DG_HIP(hipEventElapsedTime(&S.timing.forward_ms, S.ev[1], S.ev[2]));
+    DG_HIP(hipEventElapsedTime(&S.timing.traceback_ms, S.ev[2], S.ev[3]));
+    DG_HIP(hipEventElapsedTime(&S.timing.total_ms, S.ev[0], S.ev[3]));
+    S.timing.n_forward_launches = run.n_launch;
+    S.timing.n_segments = (int32_t)S.seg_begin.size() - 1;
+    S.timing.n_chunks = (int32_t)S.chunk_begin.size() - 1;
+    if (!n_budgets) return emit_result(S, to[0], edges.data(), res, -1);
+    for (int q = 0; q < n_budgets; ++q)                                  // any corrupt or mis-scored chain fails the call
+        if (int rc = emit_result(S, to[q], edges.data() + 4 * (size_t)S.cap * (size_t)q, res + q, budgets[q])) return rc;
+    return DG_OK;
+}
+
+static int dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n, dg_dp_result *results) {
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("dg_dp_run_budgets: no graph loaded"); return DG_ERR_STATE; }
+    if (!budgets || !results || n <= 0) { set_error("dg_dp_run_budgets: budgets, results and n_budgets > 0 are required"); return DG_ERR_ARG; }
+    std::vector<char> seen((size_t)Sp->RP, 0);
+    for (int q = 0; q < n; ++q) {
+        const int b = budgets[q];
+        if (b < 0 || b > Sp->R) { set_error("dg_dp_run_budgets: budget %d (entry %d) outside 0..%d, the R of the loaded graph", b, q, Sp->R); return DG_ERR_ARG; }
+        if (seen[b]) { set_error("dg_dp_run_budgets: budget %d listed twice", b); return DG_ERR_ARG; }
+        seen[b] = 1;
+        if (results[q].cap < b + 2) { set_error("dg_dp_run_budgets: results[%d].cap = %d, budget %d needs %d", q, results[q].cap, b, b + 2); return DG_ERR_ARG; }
+    }
+    return dp_run(c, results, budgets, n);
+}
+
 }  // namespace dgi
 
 extern "C" int dg_dp_load_graph(dg_ctx *c, const dg_dp_graph *g) {
@@ -383,6 +434,18 @@ extern "C" int dg_dp_load_graph(dg_ctx *c, const dg_dp_graph *g) {
 extern "C" int dg_dp_run(dg_ctx *c, dg_dp_result *r) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_run(c, r);
+}
+extern "C" int dg_dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_run_budgets(c, budgets, n_budgets, results);
+}
+extern "C" int dg_dp_get_budget_values(dg_ctx *c, int32_t *out, int32_t n) {
+    if (!c || !c->dp || !out) { dgi::set_error("dg_dp_get_budget_values: no state"); return DG_ERR_STATE; }
+    const std::vector<int32_t> &v = c->dp->sink_host;
+    if (v.empty()) { dgi::set_error("dg_dp_get_budget_values: no completed dg_dp_run / dg_dp_run_budgets on the loaded graph"); return DG_ERR_STATE; }
+    if (n < (int32_t)v.size()) { dgi::set_error("dg_dp_get_budget_values: out has %d entries, R + 1 = %zu needed", n, v.size()); return DG_ERR_ARG; }
+    memcpy(out, v.data(), 4 * v.size());
+    return DG_OK;
 }
 extern "C" int dg_dp_solve_diploid(dg_ctx *c, const dg_dp_graph *g, dg_dp_result *r) {
     if (int rc = dg_dp_load_graph(c, g)) return rc;

@@ -588,6 +588,8 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     if (int rc = S.d_probe.ensure(64 * (size_t)L)) return rc;
 #endif
     if (int rc = S.d_trace.ensure(sizeof(TraceOut))) return rc;
+    if (int rc = S.d_sink.ensure(4 * (size_t)S.RP)) return rc;    // the sink's value on every plane (dg_dp_get_budget_values)
+    S.sink_host.clear();
     S.cap = 2 * (R + 8);                               // edge records of both paths
     if (int rc = S.d_edges.ensure(4 * 4 * (size_t)S.cap)) return rc;
     if (int rc = S.d_path.ensure(8 * (size_t)L)) return rc;

@@ -93,11 +93,12 @@ __device__ __forceinline__ void chain_spec_step(ChainWalk &W, int l, int l_lo, i
     }
 }
 
-__global__ __launch_bounds__(64) void dp_trace_chain_spec_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
-                                                                 const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
-                                                                 const int32_t *__restrict__ final_val /* non-null on the first call */,
-                                                                 const uint4 *__restrict__ rowrec, const uint32_t *__restrict__ in_edge,
-                                                                 uint2 *__restrict__ path, ChainState *st) {
+// the walk of one wave; R = plane of the starting cell (the kernels below: the graph's R, or one chain's budget)
+__device__ __forceinline__ void chain_spec_walk(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
+                                                const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
+                                                const int32_t *__restrict__ final_val /* non-null on the first call */,
+                                                const uint4 *__restrict__ rowrec, const uint32_t *__restrict__ in_edge,
+                                                uint2 *__restrict__ path, ChainState *st) {
     const int lane = threadIdx.x & 63;
     ChainWalk W;
     W.csel = 0;
@@ -145,6 +146,13 @@ __global__ __launch_bounds__(64) void dp_trace_chain_spec_kernel(const LevelDesc
     if (lane == 0) { st->i = W.i; st->j = W.j; st->r = W.r; st->value = W.value; }
 }
 
+__global__ __launch_bounds__(64) void dp_trace_chain_spec_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
+                                                                 const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
+                                                                 const int32_t *__restrict__ final_val /* non-null on the first call */,
+                                                                 const uint4 *__restrict__ rowrec, const uint32_t *__restrict__ in_edge,
+                                                                 uint2 *__restrict__ path, ChainState *st) {
+    chain_spec_walk(descs, l_hi, l_lo, RP, R, bp, final_val, rowrec, in_edge, path, st);
+}
 
 // Lean chain walk: the same speculation, for lattices without wide levels whose per-level offsets fit 32 bits (every
 // graph the fast sweep takes).  One wave issues one instruction every four cycles whatever its kind, and the step above
@@ -298,15 +306,12 @@ __device__ __forceinline__ void lean_prefetch(const LevelDesc *__restrict__ desc
 #undef DG_DROP_LOAD
 }
 
-__global__ __launch_bounds__(64) void dp_trace_chain_lean_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
-                                                                 const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
-                                                                 const int32_t *__restrict__ final_val /* non-null on the first call */,
-                                                                 const uint4 *__restrict__ rowrec_, const uint32_t *__restrict__ in_edge,
-                                                                 uint2 *__restrict__ path, ChainState *st, ChainSync *sy, int seq) {
-    __shared__ int dump_s[64];
-    const int lane = threadIdx.x & 63;
-    const char *rowrec = (const char *)rowrec_;
-    if (blockIdx.x != 0) { lean_prefetch(descs, l_hi, l_lo, RP, bp, rowrec, sy, seq, dump_s, lane); return; }
+// the walk of one wave, publishing its position in *sy; R = plane of the starting cell (the graph's R, or one chain's budget)
+__device__ __forceinline__ void lean_walk(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
+                                          const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
+                                          const int32_t *__restrict__ final_val /* non-null on the first call */,
+                                          const char *__restrict__ rowrec, const uint32_t *__restrict__ in_edge,
+                                          uint2 *__restrict__ path, ChainState *st, ChainSync *sy, int seq, int lane) {
     int value, si, sj;
     LeanWalk W;
     W.cs = 0; W.bad = false; W.pu = W.pv = 0;
@@ -362,6 +367,124 @@ __global__ __launch_bounds__(64) void dp_trace_chain_lean_kernel(const LevelDesc
     }
     if (lane == 0) { DG_PUBLISH(INT32_MIN, 0); st->i = si; st->j = sj; st->r = W.r; st->value = value; }
 #undef DG_PUBLISH
+}
+
+__global__ __launch_bounds__(64) void dp_trace_chain_lean_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
+                                                                 const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
+                                                                 const int32_t *__restrict__ final_val /* non-null on the first call */,
+                                                                 const uint4 *__restrict__ rowrec_, const uint32_t *__restrict__ in_edge,
+                                                                 uint2 *__restrict__ path, ChainState *st, ChainSync *sy, int seq) {
+    __shared__ int dump_s[64];
+    const int lane = threadIdx.x & 63;
+    const char *rowrec = (const char *)rowrec_;
+    if (blockIdx.x != 0) { lean_prefetch(descs, l_hi, l_lo, RP, bp, rowrec, sy, seq, dump_s, lane); return; }
+    lean_walk(descs, l_hi, l_lo, RP, R, bp, final_val, rowrec, in_edge, path, st, sy, seq, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One chain per requested budget (dg_dp_run_budgets): all chains of a lattice chunk in ONE launch
+// ---------------------------------------------------------------------------------------------
+// Plane r of the sink holds the cell a run with limit r would read out, so the chain of budget b starts at cell (0, b, 0) and is
+// walked by the code above, unchanged: one walker wave per chain (block q < n_chains walks the chain of BudgetSlot q), each with
+// its own path slice, ChainState and ChainSync.  Placement: blocks b and b + 8 share an XCD (observed round-robin dispatch; only
+// speed depends on it), so the host deals the chains, sorted by falling budget, into G = min(8, n) groups of neighbouring budgets and
+// gives group g the blocks g, g + G, g + 2G, ...  The chains of a group start on adjacent planes and stay close (each uses its
+// recombinations at much the same places), so ONE set of LEAN_PREFETCHERS helper workgroups serves a group: the helpers follow the
+// position of the group's leader (its largest budget, blocks 0 .. G - 1) and read `planes` = group size + 1 planes from the leader's
+// r downwards instead of two.  A helper finds its group by its own XCC id, as in the single walk; on a chip that deals blocks
+// differently the helpers of a group are fewer or none and the walkers' loads miss the L2 -- slower, never wrong.
+__device__ __forceinline__ ChainSync *chain_sync_of(char *sy_base, int chain) { return (ChainSync *)(sy_base + (size_t)chain * BUDGET_SYNC_STRIDE); }
+
+__device__ __forceinline__ void lean_prefetch_group(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, const uint16_t *__restrict__ bp,
+                                                    const char *__restrict__ rowrec, const BudgetSlot *__restrict__ tab, int n_groups, char *sy_base, int seq,
+                                                    int *dump /* LDS, 64 words */, int lane) {
+#define DG_DROP_LOAD(PTR) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(PTR), (__attribute__((address_space(3))) void *)dump, 4, 0, 0)
+    // the group to help: the first one whose leader runs on this XCD and has a helper ticket left
+    const int my_xcc = xcc_id();
+    ChainSync *sy = nullptr;
+    int me = 0, planes = 2;
+    unsigned long long pos = 0;
+    for (int g = 0; g < n_groups && !sy; ++g) {
+        ChainSync *c = chain_sync_of(sy_base, tab[g].chain);
+        int spins = 0;
+        do {                                                            // the leader's first words of THIS launch
+            pos = __hip_atomic_load(&c->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((int)(pos >> 32) != seq) { __builtin_amdgcn_s_sleep(32); if (++spins > (1 << 20)) return; }
+        } while ((int)(pos >> 32) != seq);
+        if ((int)(uint32_t)pos == INT32_MIN) continue;                  // nothing to walk (an unreachable budget), or done already
+        if (__hip_atomic_load(&c->xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != my_xcc) continue;
+        if (lane == 0) me = atomicAdd(&c->ticket[seq & 1], 1);
+        me = __builtin_amdgcn_readfirstlane(me);
+        if (me < LEAN_PREFETCHERS) { sy = c; planes = tab[g].planes; }
+    }
+    if (!sy) return;
+    // from here on lean_prefetch, reading `planes` planes of every level
+    int done = 0, lw = l_hi, rw = RP - 1;
+    bool live = true;
+    for (int lp = l_hi - me; live && lp >= l_lo; lp -= LEAN_PREFETCHERS * 64) {
+        const int my_l = max(lp - LEAN_PREFETCHERS * lane, l_lo);
+        const LevelDesc &dd = descs[my_l];
+        const int64_t bo = dd.bp_off * 2;
+        int bo_lo = (int)bo, bo_hi = (int)(bo >> 32), kk = dd.k2, bb = dd.b0;
+        for (int j = 0; j < 64 && live; ++j) {
+            const int l = lp - LEAN_PREFETCHERS * j;
+            if (l < l_lo) break;
+            const int k2 = __builtin_amdgcn_readlane(kk, j), b0 = __builtin_amdgcn_readlane(bb, j);
+            const char *lvl = (const char *)bp + (((int64_t)__builtin_amdgcn_readlane(bo_hi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane(bo_lo, j));
+            const int ahead = max(8, min(LEAN_AHEAD_MAX, LEAN_AHEAD_BYTES / (2 * planes * k2 * k2)));
+            for (bool first = true; live; first = false) {              // fresh position: every few levels, and while too far ahead
+                if (!first || j % LEAN_POLL_EVERY == 0) {
+                    pos = __hip_atomic_load(&sy->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    lw = __builtin_amdgcn_readfirstlane((int)(uint32_t)pos);
+                    rw = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&sy->r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                    if (lw == INT32_MIN || (int)(pos >> 32) != seq) live = false;
+                }
+                if (!live || lw - l <= ahead) break;
+                __builtin_amdgcn_s_sleep(16);
+            }
+            if (!live) break;
+            if (l > lw) continue;                                       // overtaken
+            const int r_hi = min(max(rw, 0), RP - 1);
+            const int row_bytes = 2 * k2, lines = (row_bytes + 127) >> 7;   // 128-byte lines of one (i, r) row of back-pointers
+            const int n = planes * k2 * lines;
+            for (int t = lane; t < n; t += 64) {
+                const int ln = t % lines, q = t / lines, i = q / planes, r = max(r_hi - (q % planes), 0);
+                const uint32_t off = (uint32_t)(((uint32_t)i * (uint32_t)RP + (uint32_t)r) * (uint32_t)k2) * 2u + (uint32_t)min(ln << 7, row_bytes - 2);
+                DG_DROP_LOAD(lvl + (off & ~3u));
+            }
+            for (int t = lane; t < ((k2 * 16 + 127) >> 7); t += 64) {
+                const uint32_t off = ((uint32_t)b0 << 4) + (uint32_t)min(t << 7, k2 * 16 - 4);
+                DG_DROP_LOAD(rowrec + off);
+            }
+            ++done;
+        }
+    }
+    if (lane == 0) { atomicAdd(&sy->n_helpers, 1); atomicAdd(&sy->n_levels, done); }
+#undef DG_DROP_LOAD
+}
+
+__global__ __launch_bounds__(64) void dp_trace_chains_lean_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int L,
+                                                                  const BudgetSlot *__restrict__ tab, int n_chains, int n_groups,
+                                                                  const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
+                                                                  const int32_t *__restrict__ final_val /* non-null on the first call */,
+                                                                  const uint4 *__restrict__ rowrec_, const uint32_t *__restrict__ in_edge,
+                                                                  uint2 *__restrict__ path /* n_chains slices of L words */, ChainState *st, char *sy_base, int seq) {
+    __shared__ int dump_s[64];
+    const int lane = threadIdx.x & 63;
+    const char *rowrec = (const char *)rowrec_;
+    if ((int)blockIdx.x >= n_chains) { lean_prefetch_group(descs, l_hi, l_lo, RP, bp, rowrec, tab, n_groups, sy_base, seq, dump_s, lane); return; }
+    const BudgetSlot b = tab[blockIdx.x];
+    lean_walk(descs, l_hi, l_lo, RP, b.budget, bp, final_val, rowrec, in_edge, path + (size_t)b.chain * (size_t)L, st + b.chain, chain_sync_of(sy_base, b.chain), seq, lane);
+}
+
+// the general walk, one wave per chain (lattices the lean walk does not take: wide levels, offsets beyond 32 bits); no helpers
+__global__ __launch_bounds__(64) void dp_trace_chains_spec_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int L,
+                                                                  const BudgetSlot *__restrict__ tab,
+                                                                  const uint16_t *__restrict__ bp, const int32_t *__restrict__ final_val,
+                                                                  const uint4 *__restrict__ rowrec, const uint32_t *__restrict__ in_edge,
+                                                                  uint2 *__restrict__ path, ChainState *st) {
+    const BudgetSlot b = tab[blockIdx.x];
+    chain_spec_walk(descs, l_hi, l_lo, RP, b.budget, bp, final_val, rowrec, in_edge, path + (size_t)b.chain * (size_t)L, st + b.chain);
 }
 
 // levels in parallel over the whole grid; *out is zeroed by the host before the launch (value is written by block 0)
@@ -421,6 +544,33 @@ void trace_debug_report(const DpState &S) {                            // DG_DEB
     ChainSync sy;
     if (hipMemcpy(&sy, S.d_chain.as<char>() + 64, sizeof sy, hipMemcpyDeviceToHost) == hipSuccess)
         fprintf(stderr, "[dg] chain walk helpers: %d block-launches prefetched %d levels (since load)\n", sy.n_helpers, sy.n_levels);
+}
+
+// the n chains of dg_dp_run_budgets over destination levels [l_lo, l_hi] (buffers and placement: budgets_prepare)
+void trace_launch_chains(const DpState &S, int n, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s) {
+    if (S.lean_chain)
+        hipLaunchKernelGGL(dp_trace_chains_lean_kernel, dim3(n + BUDGET_HELPER_BLOCKS), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.L,
+                           S.d_mc_tab.as<BudgetSlot>(), n, S.mc_groups, bp_biased, final_val, S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(),
+                           S.d_mc_path.as<uint2>(), S.d_mc_chain.as<ChainState>(), S.d_mc_sync.as<char>(), ++S.mc_seq);
+    else
+        hipLaunchKernelGGL(dp_trace_chains_spec_kernel, dim3(n), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.L, S.d_mc_tab.as<BudgetSlot>(),
+                           bp_biased, final_val, S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(), S.d_mc_path.as<uint2>(), S.d_mc_chain.as<ChainState>());
+}
+
+void trace_debug_report_chains(const DpState &S, int n) {               // DG_DEBUG: where every walker ran and what the helpers of its group covered
+    std::vector<char> sy((size_t)n * BUDGET_SYNC_STRIDE);
+    std::vector<BudgetSlot> tab(n);
+    if (hipMemcpy(sy.data(), S.d_mc_sync.p, sy.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tab.data(), S.d_mc_tab.p, sizeof(BudgetSlot) * n, hipMemcpyDeviceToHost) != hipSuccess) return;
+    for (int b = 0; b < n; ++b) {
+        const ChainSync &c = *(const ChainSync *)(sy.data() + (size_t)tab[b].chain * BUDGET_SYNC_STRIDE);
+        fprintf(stderr, "[dg] multi-chain walk: block %d budget %d on XCC %d%s", b, tab[b].budget, c.xcc, b < S.mc_groups ? " (group leader" : "\n");
+        if (b < S.mc_groups) fprintf(stderr, ", %d planes): %d helper block-launches prefetched %d levels\n", tab[b].planes, c.n_helpers, c.n_levels);
+    }
+}
+
+void trace_launch_finish_chain(const DpState &S, const uint2 *path, int32_t *edges, const ChainState *st, TraceOut *out, hipStream_t s) {
+    hipLaunchKernelGGL(dp_trace_finish_kernel, dim3((unsigned)std::min(1024, (S.L + 255) / 256)), dim3(256), 0, s, S.d_descs.as<LevelDesc>(), S.L, path, colour_csr(S), S.cap,
+                       edges, st, out);
 }
 
 void trace_launch_finish(const DpState &S, hipStream_t s) {

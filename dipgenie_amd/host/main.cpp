@@ -4,6 +4,7 @@
 // -T -d are honoured; -a -q -N -m -P -H -l -c are accepted and ignored exactly as the reference's DP
 // path ignores them. The two device loops go through libdipgenie_hip.so; there is no
 // CPU fallback: without a usable gfx950 device the program exits with an error.
+#include <algorithm>
 #include <sys/resource.h>
 #include <unistd.h>
 
@@ -78,9 +79,7 @@ static int b_sketch_hap(void *c, const char *s, int64_t len, int k, int w, uint6
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_sketch_haplotype(x, s, len, k, w, h, p, n) : DG_ERR_NO_DEVICE;
 }
-static int b_dp(void *c, const dg_dp_graph *g, dg_dp_result *r) {
-    dg_ctx *x = ((LazyCtx *)c)->get();
-    if (!x) return DG_ERR_NO_DEVICE;
+static int apply_dp_options(dg_ctx *x) {
     // DG_DP_OPTIONS="key=value,key=value": dg_dp_set_option tuning knobs for profiling and for the segmented-lattice tests (none needed
     // in normal use).  Honoured with a notice on stderr; the fault-injection keys (test_*) are refused here -- they exist for the
     // library's own tests, which set them through the C ABI.
@@ -100,7 +99,24 @@ static int b_dp(void *c, const dg_dp_graph *g, dg_dp_result *r) {
             a = b + 1;
         }
     }
+    return DG_OK;
+}
+static int b_dp(void *c, const dg_dp_graph *g, dg_dp_result *r) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    if (!x) return DG_ERR_NO_DEVICE;
+    if (int rc = apply_dp_options(x)) return rc;
     return dg_dp_solve_diploid(x, g, r);
+}
+// --budgets: the graph loaded once, every listed budget read out of one sweep
+static int b_dp_load(void *c, const dg_dp_graph *g) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    if (!x) return DG_ERR_NO_DEVICE;
+    if (int rc = apply_dp_options(x)) return rc;
+    return dg_dp_load_graph(x, g);
+}
+static int b_dp_budgets(void *c, const int32_t *budgets, int32_t n, dg_dp_result *r) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_run_budgets(x, budgets, n, r) : DG_ERR_NO_DEVICE;
 }
 static int b_hap(void *c, const dg_hap_graph *g, int32_t *dp, int32_t *bv, int32_t *br) {
     dg_ctx *x = ((LazyCtx *)c)->get();
@@ -205,6 +221,8 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    -o INT       Output haplotype [%s]\n", o.hap_file.c_str());
     fprintf(fp, "    -d bool      Debug mode [%d]\n", (int)o.debug);
     fprintf(fp, "    -G INT       (MI355X build) HIP device ordinal [0]\n");
+    fprintf(fp, "    --budgets all|a,b,c   (MI355X build, -p2) also answer these recombination limits below -R from the same DP pass: <haplotype.fasta>.R<r>\n");
+    fprintf(fp, "    --budget-table FILE   (MI355X build) with --budgets: one line r, DP value, r1, r2, len1, len2 per listed limit\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
 
@@ -223,6 +241,8 @@ int main(int argc, char **argv) {
     //   --gpus N, --shard-transport rccl|host (host: tests on a one-GPU box), --shard-devices a,b,c (default 0 .. N-1; host transport: -G for every rank)
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
+    std::string budgets_arg;
+    bool have_budgets = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -235,6 +255,8 @@ int main(int argc, char **argv) {
             if (!strncmp(argv[i], "--gpus", 6)) { const char *v = val("--gpus"); if (v) { n_gpus = atoi(v); continue; } }
             if (!strncmp(argv[i], "--shard-transport", 17)) { const char *v = val("--shard-transport"); if (v) { shard_transport = !strcmp(v, "host") ? 1 : 0; continue; } }
             if (!strncmp(argv[i], "--shard-devices", 15)) { const char *v = val("--shard-devices"); if (v) { for (const char *q = v; *q;) { shard_devices.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; } continue; } }
+            if (!strncmp(argv[i], "--budgets", 9) && (argv[i][9] == 0 || argv[i][9] == '=')) { const char *v = val("--budgets"); if (v) { budgets_arg = v; have_budgets = true; continue; } }
+            if (!strncmp(argv[i], "--budget-table", 14)) { const char *v = val("--budget-table"); if (v) { p.opt.budget_table = v; continue; } }
             argv[w++] = argv[i];
         }
         argc = w;
@@ -270,11 +292,34 @@ int main(int argc, char **argv) {
     const bool sharded = n_gpus > 1 || shard_transport >= 0;
     if (n_gpus < 1 || n_gpus > 64) { fprintf(stderr, "[E::main] --gpus must be 1 .. 64\n"); return 1; }
     if (sharded && p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --gpus shards the diploid path (-p2)\n"); return 1; }
+    // --budgets all|a,b,c: checked here, before any device is asked for
+    if (!p.opt.budget_table.empty() && !have_budgets) { fprintf(stderr, "[E::main] --budget-table needs --budgets\n"); return 1; }
+    if (have_budgets) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --budgets answers the diploid route (-p2); the haploid route (-p1) already evaluates every r\n"); return 1; }
+        if (p.opt.R < 0) { fprintf(stderr, "[E::main] --budgets needs -R >= 0\n"); return 1; }
+        if (budgets_arg == "all") for (int r = 0; r <= p.opt.R; ++r) p.opt.budgets.push_back(r);
+        else {
+            for (size_t a = 0; a <= budgets_arg.size();) {
+                size_t b = budgets_arg.find(',', a);
+                if (b == std::string::npos) b = budgets_arg.size();
+                const std::string item = budgets_arg.substr(a, b - a);
+                if (item.empty() || item.size() > 9 || item.find_first_not_of("0123456789") != std::string::npos) {
+                    fprintf(stderr, "[E::main] --budgets: '%s' is not a recombination limit (all, or non-negative integers separated by commas)\n", item.c_str()); return 1;
+                }
+                const int r = atoi(item.c_str());
+                if (r > p.opt.R) { fprintf(stderr, "[E::main] --budgets: %d is above -R %d (one pass answers the limits 0..R)\n", r, p.opt.R); return 1; }
+                if (std::find(p.opt.budgets.begin(), p.opt.budgets.end(), r) == p.opt.budgets.end()) p.opt.budgets.push_back(r);
+                a = b + 1;
+            }
+        }
+    }
     if (!sharded) g_lazy.start(device, p.opt.k, p.opt.w);
     p.be.ctx = &g_lazy;
     p.be.sketch_reads = b_sketch_reads;
     p.be.sketch_haplotype = b_sketch_hap;
     p.be.dp_solve_diploid = b_dp;
+    p.be.dp_load_graph = b_dp_load;
+    p.be.dp_run_budgets = b_dp_budgets;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -325,7 +370,17 @@ int main(int argc, char **argv) {
                     have_tm ? (long long)tm.n_forward_launches : 0LL, have_tm ? (unsigned long long)tm.edge_pairs : 0ULL, have_tm ? (unsigned long long)tm.colour_entries : 0ULL);
             for (size_t i = 0; i < p.sum.stage_s.size(); ++i)
                 fprintf(f, "%s\"%s\": %.6f", i ? ", " : "", p.sum.stage_s[i].first.c_str(), p.sum.stage_s[i].second);
-            fprintf(f, "}}\n");
+            fprintf(f, "}");
+            if (have_budgets) {                                         // one entry per listed limit; null fields: unreachable
+                fprintf(f, ", \"budgets\": [");
+                for (size_t i = 0; i < p.sum.budget_rows.size(); ++i) {
+                    const dg::BudgetRow &b = p.sum.budget_rows[i];
+                    if (b.reachable) fprintf(f, "%s{\"r\": %d, \"dp_value\": %d, \"r1\": %d, \"r2\": %d, \"len1\": %lld, \"len2\": %lld}", i ? ", " : "", b.r, b.dp_value, b.r1, b.r2, (long long)b.len1, (long long)b.len2);
+                    else fprintf(f, "%s{\"r\": %d, \"dp_value\": null, \"r1\": null, \"r2\": null, \"len1\": null, \"len2\": null}", i ? ", " : "", b.r);
+                }
+                fprintf(f, "]");
+            }
+            fprintf(f, "}\n");
             fclose(f);
         }
     }

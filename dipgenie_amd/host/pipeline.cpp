@@ -1353,8 +1353,32 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     memset(&res, 0, sizeof(res));
     res.p1_from = p1f.data(); res.p1_to = p1t.data(); res.p2_from = p2f.data(); res.p2_to = p2t.data();
     res.cap = cap;
-    int rc = be.dp_solve_diploid(be.ctx, &view, &res);
-    if (rc != 0) { err = std::string("dp_solve_diploid failed: ") + (be.last_error ? be.last_error() : "?"); return -1; }
+    // --budgets: the listed budgets and -R itself from ONE sweep of the graph loaded with R (plane r of the sink is the cell a run
+    // with -R r reads out; one chain walk per budget).  Without the option: the plain call, as ever.
+    std::vector<int32_t> blist(opt.budgets.begin(), opt.budgets.end());
+    std::vector<dg_dp_result> bres;
+    std::vector<std::vector<int32_t>> bbuf;
+    int rc;
+    if (!blist.empty()) {
+        if (!be.dp_load_graph || !be.dp_run_budgets) { err = "--budgets: this backend has no dp_run_budgets"; return -1; }
+        if (std::find(blist.begin(), blist.end(), (int32_t)R) == blist.end()) blist.push_back(R);
+        bres.resize(blist.size());
+        bbuf.assign(4 * blist.size(), std::vector<int32_t>(cap));
+        for (size_t q = 0; q < blist.size(); ++q) {
+            memset(&bres[q], 0, sizeof(dg_dp_result));
+            bres[q].p1_from = bbuf[4 * q].data(); bres[q].p1_to = bbuf[4 * q + 1].data(); bres[q].p2_from = bbuf[4 * q + 2].data(); bres[q].p2_to = bbuf[4 * q + 3].data();
+            bres[q].cap = cap;
+        }
+        rc = be.dp_load_graph(be.ctx, &view);
+        if (rc == 0) rc = be.dp_run_budgets(be.ctx, blist.data(), (int32_t)blist.size(), bres.data());
+        if (rc != 0) { err = std::string("dp_run_budgets failed: ") + (be.last_error ? be.last_error() : "?"); return -1; }
+        const size_t qR = (size_t)(std::find(blist.begin(), blist.end(), (int32_t)R) - blist.begin());
+        res = bres[qR];
+        p1f = bbuf[4 * qR]; p1t = bbuf[4 * qR + 1]; p2f = bbuf[4 * qR + 2]; p2t = bbuf[4 * qR + 3];
+    } else {
+        rc = be.dp_solve_diploid(be.ctx, &view, &res);
+        if (rc != 0) { err = std::string("dp_solve_diploid failed: ") + (be.last_error ? be.last_error() : "?"); return -1; }
+    }
     stamp("dp_level_loop", t0);
     t0 = now_s();
     sum.dp_value = res.value; sum.s_het = res.s_het; sum.cells = res.cells; sum.relaxations = res.relaxations;
@@ -1382,11 +1406,12 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         return -1;
     };
 
-    std::unordered_map<int, int> p_color_freq[2];
-    std::vector<int> p_colors[2];
-    std::string hap_seq[2];
+    // weighted-edge lists -> the two sequences and the colours met on the way (:790-923).  primary: the answer at -R, which speaks on
+    // stdout as the reference does; the other budgets of --budgets leave stdout alone
+    auto sequences = [&](const std::vector<std::pair<int, int>> &w1, const std::vector<std::pair<int, int>> &w2, bool primary, std::string *hap_seq,
+                         std::unordered_map<int, int> *p_color_freq, std::vector<int> *p_colors) {
     for (int which = 0; which < 2; ++which) {                                 // :790-923
-        const auto &wedges = which == 0 ? wp1 : wp2;
+        const auto &wedges = which == 0 ? w1 : w2;
         const char *tag = which == 0 ? "P1" : "P2";
         std::string &hs = hap_seq[which];
         const int first_vertex = g.level_off.at(0);                   // vertices_in_level[0][0]
@@ -1422,9 +1447,31 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
             int next_hap = g.haplotype.at(next_edge.first);
             int next_start = find_next_zero_hap(edge.second, next_hap);
             if (next_start != -1) start_exp = next_start;
-            else std::cout << tag << " (path recovery) Could not find next_hap=" << next_hap << " from " << edge.second << " via 0-weight edges\n";
+            else (primary ? std::cout : std::cerr) << tag << " (path recovery) Could not find next_hap=" << next_hap << " from " << edge.second << " via 0-weight edges\n";
         }
     }
+    };
+    // :1314-1325 -- same bytes (80 columns, '\n' line ends), assembled in memory and written once instead of one flushed line at a time
+    auto write_fasta = [&](const std::string &path, const std::string *hs) -> bool {
+        std::string text;
+        text.reserve(hs[0].size() + hs[1].size() + (hs[0].size() + hs[1].size()) / 80 + 128);
+        for (int q = 0; q < 2; ++q) {
+            text += q == 0 ? ">sol_1 bp:" : ">sol_2 bp:";
+            text += std::to_string(hs[q].size());
+            text += '\n';
+            for (size_t i = 0; i < hs[q].size(); i += 80) { text.append(hs[q], i, 80); text += '\n'; }
+        }
+        std::ofstream f(path, std::ios::out | std::ios::binary);
+        if (!f.is_open()) { err = "cannot open output file " + path; return false; }
+        f.write(text.data(), (std::streamsize)text.size());
+        f.close();
+        if (!f.good()) { err = "write to " + path + " failed"; return false; }
+        return true;
+    };
+    std::unordered_map<int, int> p_color_freq[2];
+    std::vector<int> p_colors[2];
+    std::string hap_seq[2];
+    sequences(wp1, wp2, true, hap_seq, p_color_freq, p_colors);
     sum.r1 = r1; sum.r2 = r2;
     sum.len1 = (int64_t)hap_seq[0].size(); sum.len2 = (int64_t)hap_seq[1].size();
 
@@ -1459,22 +1506,37 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     if (!opt.quiet)
         std::cout << "recombinations in P1: " << r1 << ", recombinations in P2: " << r2 << ", bp of P1: " << hap_seq[0].length()
                   << ", bp of P2: " << hap_seq[1].length() << std::endl;                 // :1307-1308
-    {
-        // :1314-1325 -- same bytes (80 columns, '\n' line ends), assembled in memory and written once instead of one
-        // flushed line at a time
-        std::string text;
-        text.reserve(hap_seq[0].size() + hap_seq[1].size() + (hap_seq[0].size() + hap_seq[1].size()) / 80 + 128);
-        for (int q = 0; q < 2; ++q) {
-            text += q == 0 ? ">sol_1 bp:" : ">sol_2 bp:";
-            text += std::to_string(hap_seq[q].size());
-            text += '\n';
-            for (size_t i = 0; i < hap_seq[q].size(); i += 80) { text.append(hap_seq[q], i, 80); text += '\n'; }
+    if (!write_fasta(opt.hap_file, hap_seq)) return -1;
+    // --budgets: every other listed budget r gets <hap_file>.R<r>, the FASTA a run with -R r writes (an unreachable one: no file)
+    for (size_t q = 0; q < opt.budgets.size(); ++q) {
+        const dg_dp_result &b = bres[q];                                      // blist starts with the listed budgets, in order
+        BudgetRow row;
+        row.r = opt.budgets[q];
+        row.reachable = b.value != INT32_MIN / 4;
+        if (row.r == R) { row.dp_value = res.value; row.r1 = r1; row.r2 = r2; row.len1 = sum.len1; row.len2 = sum.len2; }
+        else if (row.reachable) {
+            std::vector<std::pair<int, int>> w1, w2;
+            for (int i = 0; i < b.n_p1 && i < cap; ++i) w1.emplace_back(b.p1_from[i], b.p1_to[i]);
+            for (int i = 0; i < b.n_p2 && i < cap; ++i) w2.emplace_back(b.p2_from[i], b.p2_to[i]);
+            std::unordered_map<int, int> freq[2];
+            std::vector<int> cols[2];
+            std::string hs[2];
+            sequences(w1, w2, false, hs, freq, cols);
+            if (!write_fasta(opt.hap_file + ".R" + std::to_string(row.r), hs)) return -1;
+            row.dp_value = b.value; row.r1 = (int)w1.size() - 1; row.r2 = (int)w2.size() - 1;
+            row.len1 = (int64_t)hs[0].size(); row.len2 = (int64_t)hs[1].size();
         }
-        std::ofstream f(opt.hap_file, std::ios::out | std::ios::binary);
-        if (!f.is_open()) { err = "cannot open output file " + opt.hap_file; return -1; }
-        f.write(text.data(), (std::streamsize)text.size());
+        sum.budget_rows.push_back(row);
+    }
+    if (!opt.budget_table.empty()) {                                          // r  dp_value  r1  r2  len1  len2, NA for an unreachable budget
+        std::ofstream f(opt.budget_table, std::ios::out | std::ios::binary);
+        if (!f.is_open()) { err = "cannot open budget table " + opt.budget_table; return -1; }
+        for (const BudgetRow &row : sum.budget_rows) {
+            if (row.reachable) f << row.r << '\t' << row.dp_value << '\t' << row.r1 << '\t' << row.r2 << '\t' << row.len1 << '\t' << row.len2 << '\n';
+            else f << row.r << "\tNA\tNA\tNA\tNA\tNA\n";
+        }
         f.close();
-        if (!f.good()) { err = "write to " + opt.hap_file + " failed"; return -1; }
+        if (!f.good()) { err = "write to " + opt.budget_table + " failed"; return -1; }
     }
     stamp("traceback+write", t0);
     return 0;

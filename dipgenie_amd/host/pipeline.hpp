@@ -54,6 +54,10 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // optional (sharded runs): a haplotype whose minimizer list was sketched by another rank
     int (*anchor_add_haplotype_sketched)(void *, int32_t h, int64_t len, const uint64_t *hash, const int64_t *pos, int64_t n, const int32_t *step_vtx,
                                          const int64_t *step_start, int64_t n_steps) = nullptr;
+    // optional (--budgets): the diploid graph loaded once, then the read-out of several recombination budgets from one sweep
+    // (dg_dp_load_graph + dg_dp_run_budgets); nothing in a run without --budgets needs them
+    int (*dp_load_graph)(void *, const dg_dp_graph *) = nullptr;
+    int (*dp_run_budgets)(void *, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) = nullptr;
     void (*hint_dp_soon)(void *, int64_t est_cells) = nullptr;   // optional, may be called repeatedly (latest wins): the DP will run later with about est_cells cells
     const char *(*last_error)() = nullptr;
 };
@@ -72,6 +76,8 @@ struct Options {
     std::string anchor_dump;  // (ours, tests) if set, write Anchor_hits + homo_bv as text (format of oracle/ref_harness.cpp `anchors`)
     int haploid_mode = 0;        // (ours) haploid (vertex, r) tables: 0 = by graph shape, 1 = host gather loop, 2 = device (if the backend offers it)
     bool leak_at_exit = false;   // (ours) the process exits right after run(): skip the teardown of the big graph objects
+    std::vector<int> budgets;    // (ours) --budgets: recombination budgets below -R answered from the same DP pass (diploid); -R itself is always solved
+    std::string budget_table;    // (ours) --budget-table: TSV of the listed budgets
     bool host_anchors = false;   // (ours, tests) keep the anchor join / filter / sort on the host even if the backend offers it
 };
 
@@ -140,6 +146,13 @@ struct DpGraphStorage {
     bool load(const std::string &path, int &R);
 };
 
+struct BudgetRow {            // --budgets: one listed budget (reachable = the sink's plane r holds a path)
+    int32_t r = 0;
+    bool reachable = false;
+    int32_t dp_value = 0, r1 = -1, r2 = -1;
+    int64_t len1 = 0, len2 = 0;
+};
+
 struct Summary {              // what tests and the CLI report
     int32_t dp_value = 0, s_het = 0, r1 = -1, r2 = -1, obj = 0, best_r_haploid = -1;
     int64_t len1 = 0, len2 = 0;
@@ -148,6 +161,7 @@ struct Summary {              // what tests and the CLI report
     std::vector<int64_t> minimizers_per_hap, anchors_per_hap;
     KGFitResult fit;
     std::vector<std::pair<std::string, double>> stage_s;
+    std::vector<BudgetRow> budget_rows;   // --budgets: in the order listed
 };
 
 // One anchor occurrence: vertex list vpool[off, off+len) of read-minimizer id `a` on haplotype `h`.

@@ -91,6 +91,20 @@ int dg_dp_load_graph(dg_ctx *, const dg_dp_graph *);   /* validate + upload + bu
 int dg_dp_run(dg_ctx *, dg_dp_result *);               /* all kernels on the resident graph; synchronises */
 int dg_dp_get_timing(dg_ctx *, dg_dp_timing *);
 int dg_dp_solve_diploid(dg_ctx *, const dg_dp_graph *, dg_dp_result *);   /* = load_graph + run */
+/* Every recombination budget from ONE pass.  The source level starts at 0 on all R + 1 planes and a cell of plane r gathers from
+ * planes r, r - 1, r - 2 only, so after one sweep with the graph's R plane r of the sink is the cell a run with limit r reads out.
+ * After dg_dp_load_graph: one sweep, then the read-out of every listed budget -- one chain walk per budget, all of a lattice chunk
+ * in one launch, each re-scored against its plane's value.  budgets[q] in 0..R, distinct, any order; results[q] is filled as
+ * dg_dp_run would fill it for a graph loaded with R = budgets[q] (value, s_het, both edge lists, n_p1, n_p2; cells / relaxations
+ * are those of the one sweep that ran).  Caller-provided edge buffers per result, cap >= budgets[q] + 2.  An unreachable budget
+ * answers value = NEG_INF (INT32_MIN / 4), n_p1 = n_p2 = 0 and is not an error.  DG_ERR_ARG (n_budgets <= 0, a budget outside
+ * 0..R, a duplicate, a cap too small) and DG_ERR_STATE (no graph loaded) leave the context as it was; DG_ERR_STATE with the
+ * budget named if any chain is corrupt or scores differently from its plane's value.  dg_dp_get_timing: traceback_ms covers all
+ * chains.  Synchronises. */
+int dg_dp_run_budgets(dg_ctx *, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results);
+/* the sink's value on planes 0..R (NEG_INF where unreachable) of the last dg_dp_run / dg_dp_run_budgets on the loaded graph;
+ * out has n >= R + 1 entries */
+int dg_dp_get_budget_values(dg_ctx *, int32_t *out, int32_t n);
 /* debug/parity: copy the per-level digest (same definition as the oracle's level_digest) of the
  * last run; out has n_levels entries, entry 0 unused. Requires dg_dp_set_option("digest",1). */
 int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
