@@ -69,7 +69,7 @@ struct LevelDesc {                                      // transition (l-1) -> l
 
 struct TraceOut { int32_t value, s_het, n_e, overflow, corrupt, path_score; };   // path_score: sum of the score deltas along the walked path (must equal value)
 struct ChainState { int32_t i, j, r, value; };
-// dg_dp_run_budgets: walker block q of the multi-chain launch walks chain `chain` (the caller's index) from plane `budget` of the
+// walker block q of the chain launch walks chain `chain` (the caller's index; dg_dp_run: its one chain) from plane `budget` of the
 // sink; blocks 0 .. G - 1 hold the group leaders, whose helpers read `planes` planes per level (dg_dp_trace.hip)
 struct BudgetSlot { int32_t chain, budget, planes, pad_; };
 constexpr int BUDGET_SYNC_STRIDE = 128;                 // bytes between the ChainSync records of two chains (a cache line each)
@@ -152,7 +152,6 @@ struct DpState {
     bool pf_active = false;                             // a prefetcher accompanies the sweep range being issued
     int64_t pf_far = 128;                               // pf_far: > 0 = prefetcher blocks also pull the tables pf_far levels ahead into the Infinity Cache (then no periodic look-ahead launches)
     int pf_tested = 0;                                  // 0: the side stream's concurrency with the sweep's stream not yet probed, 1: probed
-    mutable int chain_seq = 0;                          // per-launch number of the lean chain walk (ChainSync, dg_dp_trace.hip)
     int64_t use_rowx = 1;                               // rowx: row in-edge matrices (0: every fan-in row fetches its list from in_edge[])
     int64_t delta_cap_entries = (int64_t)4 << 30;       // delta_cap_entries: budget of resident score-delta entries
     int64_t rc_cap = 65536, rc_t0_ns = 3000, rc_tg_ps = 20000, rc_tw_ps = 50;   // rc_*: cost model of the per-level RC choice
@@ -182,7 +181,7 @@ struct DpState {
     std::vector<int32_t> level_dmax;                    // largest in-degree among the level's vertices
     int64_t n_grp = 0, n_dead = 0, n_heavy_rows = 0, n_slot_records = 0, n_rowx_words = 0, n_dtrans = 0, n_edges = 0;   // logical table sizes (dg_dp_get_table_digest)
     DevBuf d_descs, d_in_off, d_in_edge, d_in_dst, d_hom_off, d_het_off, d_hom_col, d_het_col, d_eflag, d_eself;
-    DevBuf d_delta, d_bp, d_ring, d_digest, d_trace, d_edges, d_dblk_first, d_dtrans, d_grp, d_dead, d_heavy, d_rowrec, d_rowx, d_slots, d_path, d_ckpt, d_chain, d_pfctl;
+    DevBuf d_delta, d_bp, d_ring, d_digest, d_dblk_first, d_dtrans, d_grp, d_dead, d_heavy, d_rowrec, d_rowx, d_slots, d_ckpt, d_pfctl;
 #ifdef DG_SWEEP_PROBE
     DevBuf d_probe;
 #endif
@@ -207,14 +206,15 @@ struct DpState {
     } pool;
     std::vector<int> chunk_begin;              // destination levels [chunk_begin[c], chunk_begin[c+1]) live in chunk c
     int seg_chunks = 1;                        // chunks per lattice segment (= all of them when the lattice is resident)
-    // ---- every budget from one pass (dg_dp_run_budgets, dg_dp_budgets.hip) ----
-    // One chain per requested budget: its own path slice (L hop words), ChainState, ChainSync, TraceOut and edge block; d_mc_tab
-    // holds the budgets and the walker placement (BudgetSlot per block).  d_sink keeps the sink's RP values of the last run, taken
-    // when the sweep reaches the sink (the second pass of a segmented run overwrites the state ring).
-    DevBuf d_sink, d_mc_path, d_mc_chain, d_mc_sync, d_mc_trace, d_mc_edges, d_mc_tab;
+    // ---- the chains of a run (dg_dp_budgets.hip): one per requested budget, dg_dp_run = the one chain of budget R ----
+    // Every chain has its own path slice (L hop words), ChainState, ChainSync, TraceOut and edge block; d_ch_tab holds the budgets
+    // and the walker placement (BudgetSlot per block).  d_sink keeps the sink's RP values of the last run, taken when the sweep
+    // reaches the sink (the second pass of a segmented run overwrites the state ring).
+    DevBuf d_sink, d_ch_path, d_ch_state, d_ch_sync, d_ch_trace, d_ch_edges, d_ch_tab;
     std::vector<int32_t> sink_host;            // the sink's value on planes 0..R (dg_dp_get_budget_values); empty before the first run
-    int mc_groups = 0;                         // walker groups of the run at hand (chains of neighbouring budgets share an XCD and its helpers)
-    mutable int mc_seq = 0;                    // per-launch number of the multi-chain walk (counted from 0 in every dg_dp_run_budgets)
+    std::vector<BudgetSlot> tab_host;          // host copy of d_ch_tab (the run at hand)
+    int n_groups = 0;                          // walker groups of the run at hand (chains of neighbouring budgets share an XCD and its helpers)
+    mutable int walk_seq = 0;                  // per-launch number of the chain walk (ChainSync; counted from 0 in every run)
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -263,15 +263,13 @@ void sweep_prefetch_free(DpState &S);
 
 // ---- traceback (dg_dp_trace.hip) ----
 void trace_launch_warm_rows(const DpState &S, int lb, int le, hipStream_t s);
-void trace_launch_chain(const DpState &S, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s);
-void trace_launch_finish(const DpState &S, hipStream_t s);
-void trace_debug_report(const DpState &S);
+void trace_launch_chains(const DpState &S, int n, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s);   // all n chains, one launch
 void trace_launch_finish_chain(const DpState &S, const uint2 *path, int32_t *edges, const ChainState *st, TraceOut *out, hipStream_t s);   // the finish kernel on one chain's buffers
+void trace_debug_report(const DpState &S, int n);
 
-// ---- every budget from one pass (dg_dp_budgets.hip; the walkers themselves live beside the single walk in dg_dp_trace.hip) ----
-void trace_launch_chains(const DpState &S, int n, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s);
-void trace_debug_report_chains(const DpState &S, int n);
+// ---- the chains of a run: buffers, placement, sink values, finish (dg_dp_budgets.hip) ----
 void budgets_launch_sink_copy(const DpState &S, const int32_t *sink_state, hipStream_t s);   // sink values of planes 0..R -> d_sink
+int budgets_reserve(DpState &S, int n);                                                      // buffers of n chains (grow-only)
 int budgets_prepare(DpState &S, const int32_t *budgets, int n, hipStream_t s);                // buffers of n chains + walker placement
 void budgets_launch_finish(const DpState &S, int n, hipStream_t s);                           // the finish kernel once per chain
 

@@ -102,7 +102,7 @@ struct Run {
     int64_t n_launch = 0;
     int next_warm = 0;                                  // next level at which the look-ahead launch is due
     double host_enqueue_s = 0;                          // host time spent issuing the sweep's launches (DG_DEBUG)
-    int n_chains = 0;                                   // dg_dp_run_budgets: chains walked from the sink (0: the one chain of dg_dp_run)
+    int n_chains = 1;                                   // chains walked from the sink, one per budget (dg_dp_run: 1)
     std::vector<uint16_t *> pool_base;
 
     Run(dg_ctx *c_, DpState &S_) : c(c_), S(S_), s(c_->stream) { sweep_prepare(S, X); }
@@ -240,8 +240,7 @@ struct Run {
             const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1];
             trace_launch_warm_rows(S, lb, le, s);
             const int32_t *final_val = from_sink && ch == c1 - 1 ? state_ptr(S.L - 1) : (const int32_t *)nullptr;
-            if (n_chains) trace_launch_chains(S, n_chains, le - 1, lb, biased[ch - c0], final_val, s);
-            else trace_launch_chain(S, le - 1, lb, biased[ch - c0], final_val, s);
+            trace_launch_chains(S, n_chains, le - 1, lb, biased[ch - c0], final_val, s);
         }
         return DG_OK;
     }
@@ -283,8 +282,9 @@ struct Run {
             // Along a path the recombination count only grows, and a cell of plane r gathers from planes r, r - 1, r - 2 of the level
             // before: once the walk has left segment sg on plane r*, the cells it can meet in the segments before lie on planes
             // <= r*, and those depend on planes <= r* only.  Every earlier segment is therefore re-swept up to the plane its
-            // successor's walk ended on (one 16-byte read per segment) -- the path uses its recombinations along the whole panel, so
-            // about half of the second pass goes away.  (The finish kernel re-scores the walked path against the DP value as ever.)
+            // successor's walk ended on (one 16-byte read per chain and segment; several chains: the largest plane any of them left
+            // on, an unreachable budget walks nothing) -- the path uses its recombinations along the whole panel, so about half of
+            // the second pass goes away.  (The finish kernel re-scores the walked path against the DP value as ever.)
             for (int sg = n_seg - 1; sg >= 0; --sg) {
                 const int lb = S.seg_begin[sg];
                 if (sg > 0)
@@ -293,21 +293,15 @@ struct Run {
                     sweep_init_state(S, s);
                 const int c0 = sg * S.seg_chunks, c1 = std::min(n_chunks_all, c0 + S.seg_chunks);
                 if (int rc = sweep_and_walk(c0, c1, sg == n_seg - 1, false)) { S.want_digest = dig; S.rp_active = S.RP; return rc; }
-                if (S.plane_limit && sg > 0 && n_chains) {
-                    // several chains: up to the largest plane any of them left the segment on (an unreachable budget walks nothing)
+                if (S.plane_limit && sg > 0) {
                     std::vector<ChainState> cs((size_t)n_chains);
-                    if (hipMemcpyAsync(cs.data(), S.d_mc_chain.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
+                    if (hipMemcpyAsync(cs.data(), S.d_ch_state.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
                     int planes = 1;
                     for (const ChainState &q : cs) {
                         if (q.value == NEG_INF) continue;
                         planes = std::max(planes, (q.value != CHAIN_CORRUPT && q.r >= 0 && q.r < S.RP) ? q.r + 1 : S.RP);
                     }
                     S.rp_active = planes;
-                    planes_swept += (int64_t)S.rp_active * (S.seg_begin[sg] - S.seg_begin[sg - 1]);
-                } else if (S.plane_limit && sg > 0) {
-                    ChainState cs{0, 0, S.RP - 1, 0};
-                    if (hipMemcpyAsync(&cs, S.d_chain.p, sizeof cs, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
-                    S.rp_active = (cs.value != CHAIN_CORRUPT && cs.r >= 0 && cs.r < S.RP) ? cs.r + 1 : S.RP;
                     planes_swept += (int64_t)S.rp_active * (S.seg_begin[sg] - S.seg_begin[sg - 1]);
                 }
             }
@@ -316,8 +310,7 @@ struct Run {
             if (getenv("DG_DEBUG") && S.plane_limit) fprintf(stderr, "[dipgenie_hip] run: second pass swept %.1f %% of the (level, plane) pairs before the last segment\n",
                                                               100.0 * (double)planes_swept / std::max(1.0, (double)S.RP * (S.seg_begin[n_seg - 1] - 1)));
         }
-        if (n_chains) budgets_launch_finish(S, n_chains, s);
-        else trace_launch_finish(S, s);
+        budgets_launch_finish(S, n_chains, s);
         DG_HIP(hipEventRecord(S.ev[3], s));
         DG_HIP(hipGetLastError());
         return DG_OK;
@@ -326,7 +319,7 @@ struct Run {
 
 }  // namespace
 
-// checks one chain's TraceOut and turns its edge records into the two weighted-edge lists; budget < 0: the chain of dg_dp_run
+// checks one chain's TraceOut and turns its edge records into the two weighted-edge lists; budget < 0: not named in the messages (dg_dp_run)
 static int emit_result(const DpState &S, const TraceOut &to, const int32_t *edges, dg_dp_result *res, int budget) {
     char who[32] = "";
     if (budget >= 0) snprintf(who, sizeof who, " (budget %d)", budget);
@@ -351,28 +344,23 @@ static int emit_result(const DpState &S, const TraceOut &to, const int32_t *edge
     return DG_OK;
 }
 
-// One pass over the resident graph.  n_budgets == 0: dg_dp_run (one chain from plane R of the sink into *res); otherwise
-// dg_dp_run_budgets: one chain per budgets[q] into res[q], all walked by one launch per lattice chunk (dg_dp_trace.hip).
-static int dp_run(dg_ctx *c, dg_dp_result *res, const int32_t *budgets = nullptr, int n_budgets = 0) {
-    const char *fn = n_budgets ? "dg_dp_run_budgets" : "dg_dp_run";
-    DpState *Sp = c->dp;
-    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", fn); return DG_ERR_STATE; }
-    if (!res) { set_error("%s: null result", fn); return DG_ERR_ARG; }
-    DpState &S = *Sp;
+// One pass over the resident graph (the callers have checked that one is loaded): one chain per budgets[q] into res[q], all walked
+// by one launch per lattice chunk (dg_dp_trace.hip).  name_budget: error texts say which budget's chain failed.
+static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result *res, bool name_budget) {
+    DpState &S = *c->dp;
     Run run(c, S);
     hipStream_t s = c->stream;
     if (int rc = run.wait_for_chunks()) return rc;
-    const size_t n_out = (size_t)std::max(n_budgets, 1);
-    std::vector<TraceOut> to(n_out);
-    std::vector<int32_t> edges(4 * (size_t)S.cap * n_out);
-    if (n_budgets) { if (int rc = budgets_prepare(S, budgets, n_budgets, s)) return rc; }
+    std::vector<TraceOut> to((size_t)n_budgets);
+    std::vector<int32_t> edges(4 * (size_t)S.cap * (size_t)n_budgets);
+    if (int rc = budgets_prepare(S, budgets, n_budgets, s)) return rc;
     run.n_chains = n_budgets;
     memset(S.launch_hist, 0, sizeof S.launch_hist);
     run.n_launch = 0;
     S.sink_host.clear();
     if (int rc = run.forward_and_trace()) return rc;
-    DG_HIP(hipMemcpyAsync(to.data(), n_budgets ? S.d_mc_trace.p : S.d_trace.p, sizeof(TraceOut) * n_out, hipMemcpyDeviceToHost, s));
-    DG_HIP(hipMemcpyAsync(edges.data(), n_budgets ? S.d_mc_edges.p : S.d_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(to.data(), S.d_ch_trace.p, sizeof(TraceOut) * to.size(), hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(edges.data(), S.d_ch_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
     std::vector<int32_t> sink((size_t)S.RP);
     DG_HIP(hipMemcpyAsync(sink.data(), S.d_sink.p, 4 * sink.size(), hipMemcpyDeviceToHost, s));
     if (S.want_digest) {
@@ -388,7 +376,7 @@ static int dp_run(dg_ctx *c, dg_dp_result *res, const int32_t *budgets = nullptr
         if (FILE *f = fopen(po, "wb")) { fwrite(pr.data(), 8, pr.size(), f); fclose(f); }
     }
 #endif
-    if (getenv("DG_DEBUG") && S.lean_chain) { if (n_budgets) trace_debug_report_chains(S, n_budgets); else trace_debug_report(S); }
+    if (getenv("DG_DEBUG") && S.lean_chain) trace_debug_report(S, n_budgets);
     if (getenv("DG_DEBUG") && S.pf_stream) {
         int w[4] = {0, 0, 0, 0};
         if (hipStreamSynchronize(S.pf_stream) == hipSuccess && hipMemcpy(w, S.d_pfctl.p, sizeof w, hipMemcpyDeviceToHost) == hipSuccess)
@@ -404,9 +392,8 @@ static int dp_run(dg_ctx *c, dg_dp_result *res, const int32_t *budgets = nullptr
     S.timing.n_forward_launches = run.n_launch;
     S.timing.n_segments = (int32_t)S.seg_begin.size() - 1;
     S.timing.n_chunks = (int32_t)S.chunk_begin.size() - 1;
-    if (!n_budgets) return emit_result(S, to[0], edges.data(), res, -1);
     for (int q = 0; q < n_budgets; ++q)                                  // any corrupt or mis-scored chain fails the call
-        if (int rc = emit_result(S, to[q], edges.data() + 4 * (size_t)S.cap * (size_t)q, res + q, budgets[q])) return rc;
+        if (int rc = emit_result(S, to[q], edges.data() + 4 * (size_t)S.cap * (size_t)q, res + q, name_budget ? budgets[q] : -1)) return rc;
     return DG_OK;
 }
 
@@ -422,7 +409,16 @@ static int dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n, dg_dp_re
         seen[b] = 1;
         if (results[q].cap < b + 2) { set_error("dg_dp_run_budgets: results[%d].cap = %d, budget %d needs %d", q, results[q].cap, b, b + 2); return DG_ERR_ARG; }
     }
-    return dp_run(c, results, budgets, n);
+    return dp_run(c, budgets, n, results, true);
+}
+
+// dg_dp_run: the one-chain case -- the chain of budget R, named by no budget in its messages.  (No check of res->cap against the
+// budget: edges beyond cap are counted, not stored.)
+static int dp_run_single(dg_ctx *c, dg_dp_result *res) {
+    if (!c->dp || !c->dp->loaded) { set_error("dg_dp_run: no graph loaded"); return DG_ERR_STATE; }
+    if (!res) { set_error("dg_dp_run: null result"); return DG_ERR_ARG; }
+    const int32_t budget = c->dp->R;
+    return dp_run(c, &budget, 1, res, false);
 }
 
 }  // namespace dgi
@@ -433,7 +429,7 @@ extern "C" int dg_dp_load_graph(dg_ctx *c, const dg_dp_graph *g) {
 }
 extern "C" int dg_dp_run(dg_ctx *c, dg_dp_result *r) {
     if (int rc = dgi::bind(c)) return rc;
-    return dgi::dp_run(c, r);
+    return dgi::dp_run_single(c, r);
 }
 extern "C" int dg_dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) {
     if (int rc = dgi::bind(c)) return rc;

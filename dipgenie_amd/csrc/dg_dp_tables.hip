@@ -565,7 +565,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     const size_t n_edges = (size_t)g->out_off[nV];
     const size_t st_bytes = (size_t)S.max_level_cells * 4 * 2, dl_bytes = (size_t)S.delta_buf_entries * 2;
     size_t bp_bytes = 0, ck_bytes = 0;
-    // (the tables are allocated already; what follows: edge flags + self scores, digests, the path)
+    // (the tables are allocated already; what follows: edge flags + self scores, digests, one chain's path)
     if (int rc = plan_lattice(c, S, st_bytes, dl_bytes, 3 * n_edges + 16 * (size_t)L + (1 << 20), bp_bytes, ck_bytes, dbg)) return rc;
     lap("plan lattice");
     if (int rc = S.d_eflag.ensure(n_edges + 16)) return rc;
@@ -574,10 +574,8 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     if (int rc = S.d_delta.ensure(dl_bytes)) return rc;
     DG_HIP(hipMemsetAsync(S.d_delta.p, 0, 2 * DELTA_PAD, s));
     if (int rc = S.d_ckpt.ensure(ck_bytes)) return rc;
-    if (int rc = S.d_chain.ensure(128)) return rc;                 // ChainState, and ChainSync at +64
     if (int rc = S.d_pfctl.ensure(256)) return rc;                  // PfCtl of the L2 table prefetcher
     DG_HIP(hipMemsetAsync(S.d_pfctl.p, 0, 256, s));
-    DG_HIP(hipMemsetAsync(S.d_chain.p, 0, 128, s)); S.chain_seq = 0;
     S.pad_front = 2 * (int64_t)max_k;
     const size_t pad_bytes = 4 * (size_t)(S.pad_front + 33 * (int64_t)max_k);
     S.state_alloc_bytes = (((size_t)S.max_level_cells * 4 + pad_bytes) + 255) & ~(size_t)255;   // one slot
@@ -587,12 +585,10 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
 #ifdef DG_SWEEP_PROBE
     if (int rc = S.d_probe.ensure(64 * (size_t)L)) return rc;
 #endif
-    if (int rc = S.d_trace.ensure(sizeof(TraceOut))) return rc;
     if (int rc = S.d_sink.ensure(4 * (size_t)S.RP)) return rc;    // the sink's value on every plane (dg_dp_get_budget_values)
     S.sink_host.clear();
     S.cap = 2 * (R + 8);                               // edge records of both paths
-    if (int rc = S.d_edges.ensure(4 * 4 * (size_t)S.cap)) return rc;
-    if (int rc = S.d_path.ensure(8 * (size_t)L)) return rc;
+    if (int rc = budgets_reserve(S, 1)) return rc;    // one chain's path, edge block and words: dg_dp_run (more chains: at their first run)
     lap("allocs");
     for (auto &e : S.ev) if (!e) DG_HIP(hipEventCreate(&e));
     memset(&S.timing, 0, sizeof S.timing);

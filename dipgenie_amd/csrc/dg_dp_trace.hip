@@ -1,11 +1,12 @@
 // Traceback of the diploid DP (approximator.cpp:757-785).
-// Chain kernel (one wave): walk the back-pointer lattice downwards from a known cell.  The chain is one dependent HBM
-// load per level, so everything else is kept off it: the level descriptors of the next 64 levels are fetched one per
-// lane and broadcast with readlane, and the hop words are parked in path[].  In segmented mode it is called once per
-// chunk, last chunk first, carrying the cell in ChainState.
-// Finish kernel (whole grid, levels in parallel): re-derive s_het from the colour lists of the winning edge pairs
-// (:662) and emit the weighted edges (:673-692; both final edges unconditionally) as (level, from, to, which) records;
-// the host orders them by level.
+// Chain kernels (one walker wave per chain; dg_dp_run is the one-chain case of dg_dp_run_budgets): walk the back-pointer lattice
+// downwards from cell (0, budget, 0) of the sink.  A chain is one dependent HBM load per level, so everything else is kept
+// off it: the level descriptors of the next 64 levels are fetched one per lane and broadcast with readlane, and the hop words
+// are parked in the chain's path slice.  In segmented mode they are launched once per chunk, last chunk first, carrying every
+// chain's cell in its ChainState.
+// Finish kernel (whole grid, levels in parallel, one launch per chain): re-derive s_het from the colour lists of the winning
+// edge pairs (:662) and emit the weighted edges (:673-692; both final edges unconditionally) as (level, from, to, which)
+// records; the host orders them by level.
 #include <algorithm>
 
 #include "dg_dp_setops.hpp"
@@ -146,14 +147,6 @@ __device__ __forceinline__ void chain_spec_walk(const LevelDesc *__restrict__ de
     if (lane == 0) { st->i = W.i; st->j = W.j; st->r = W.r; st->value = W.value; }
 }
 
-__global__ __launch_bounds__(64) void dp_trace_chain_spec_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
-                                                                 const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
-                                                                 const int32_t *__restrict__ final_val /* non-null on the first call */,
-                                                                 const uint4 *__restrict__ rowrec, const uint32_t *__restrict__ in_edge,
-                                                                 uint2 *__restrict__ path, ChainState *st) {
-    chain_spec_walk(descs, l_hi, l_lo, RP, R, bp, final_val, rowrec, in_edge, path, st);
-}
-
 // Lean chain walk: the same speculation, for lattices without wide levels whose per-level offsets fit 32 bits (every
 // graph the fast sweep takes).  One wave issues one instruction every four cycles whatever its kind, and the step above
 // costs ~250 of them (0.5 us) -- more than the two overlapped HBM round trips it hides.  This one is written around the
@@ -223,88 +216,13 @@ __device__ __forceinline__ void lean_step(LeanWalk &W, int RP, const LeanDesc &N
     park_v = lane == slot ? pv : park_v;
 }
 
-// Prefetch workgroups.  With ~90 instructions per level the walk is bound by memory latency: the HBM round trip of its
-// back-pointer load (two in flight) and the row-record load that leads to the next candidates (~0.34 us per level).  The
-// walker cannot know its cell any earlier, but r only ever decreases along the walk, and rarely: the cell of a level
-// some tens of levels down lies in plane r or r - 1 of that level, 2 * k2 rows of k2 back-pointers -- 16 KB on a 64-wide
-// level.  Helper workgroups ON THE WALKER'S XCD (the L2 is per XCD; a helper wave on the walker's own CU was measured
-// and is worse than none: 80 vs 54 ms, its misses queue in front of the walker's loads in the CU's in-order memory
-// pipeline) read those planes, one load per 128-byte line with the data dropped, and the level's row records, keeping
-// up to LEAN_AHEAD_MAX levels ahead of the position the walker publishes every 16 levels; the walker's loads then
-// hit the L2.  A wrong guess (a third recombination inside the window) costs an ordinary miss, nothing else.
-// Protocol (ChainSync, in global memory; relaxed agent-scope atomics -- hints, nothing depends on their order): the
-// walker (block 0) publishes its XCC id and seq << 32 | level; every other block of the launch whose XCC id matches
-// takes a ticket, the first LEAN_PREFETCHERS tickets prefetch, everybody else leaves.  seq (a per-launch number) keeps a
-// helper from acting on the previous launch's words; whatever it reads, it only ever touches levels of [l_lo, l_hi].
+// the helper workgroups of the lean walk (lean_prefetch_group below) and the words they share with the walker
 constexpr int LEAN_AHEAD_MAX = 96, LEAN_AHEAD_BYTES = 3 << 19;      // window: at most 96 levels and ~1.5 MB of planes
-constexpr int LEAN_PREFETCHERS = 8, LEAN_BLOCKS = 80, LEAN_POLL_EVERY = 4;
+constexpr int LEAN_PREFETCHERS = 8, LEAN_POLL_EVERY = 4;
 constexpr int LEAN_PUBLISH_MASK = 8;             // the walker publishes its position every 16 levels (every 8: 47.0 ms, 16: 44.5, 32: 44.9 on MHC-24)
 struct ChainSync { unsigned long long pos; int r, xcc; int ticket[2]; int n_helpers, n_levels, pad_[2]; };   // (n_helpers, n_levels: DG_DEBUG statistics)
 
 __device__ __forceinline__ int xcc_id() { return (int)__builtin_amdgcn_s_getreg((3 << 11) | 20); }   // HW_REG_XCC_ID[3:0]
-
-__device__ __forceinline__ void lean_prefetch(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, const uint16_t *__restrict__ bp,
-                                              const char *__restrict__ rowrec, ChainSync *sy, int seq, int *dump /* LDS, 64 words */, int lane) {
-    // a load whose data nobody wants: straight into an LDS dump word per lane -- no destination register that a later value
-    // could be sharing when the data arrives, nothing to wait for
-#define DG_DROP_LOAD(PTR) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(PTR), (__attribute__((address_space(3))) void *)dump, 4, 0, 0)
-    unsigned long long pos;
-    int spins = 0;
-    do {                                                                // the walker's first words of THIS launch
-        pos = __hip_atomic_load(&sy->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)(pos >> 32) != seq) { __builtin_amdgcn_s_sleep(32); if (++spins > (1 << 20)) return; }
-    } while ((int)(pos >> 32) != seq);
-    if ((int)(uint32_t)pos == INT32_MIN) return;
-    if (__hip_atomic_load(&sy->xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != xcc_id()) return;
-    int me = 0;
-    if (lane == 0) me = atomicAdd(&sy->ticket[seq & 1], 1);
-    me = __builtin_amdgcn_readfirstlane(me);
-    if (me >= LEAN_PREFETCHERS) return;
-    // this block's levels: l_hi - me - LEAN_PREFETCHERS * q.  Their descriptors are fetched 64 at a time, one per lane, so that no
-    // level waits for a dependent descriptor load of its own; the position is polled every LEAN_POLL_EVERY levels (an L2 round trip)
-    int done = 0, lw = l_hi, rw = RP - 1;
-    bool live = true;
-    for (int lp = l_hi - me; live && lp >= l_lo; lp -= LEAN_PREFETCHERS * 64) {
-        const int my_l = max(lp - LEAN_PREFETCHERS * lane, l_lo);
-        const LevelDesc &dd = descs[my_l];
-        const int64_t bo = dd.bp_off * 2;
-        int bo_lo = (int)bo, bo_hi = (int)(bo >> 32), kk = dd.k2, bb = dd.b0;
-        for (int j = 0; j < 64 && live; ++j) {
-            const int l = lp - LEAN_PREFETCHERS * j;
-            if (l < l_lo) break;
-            const int k2 = __builtin_amdgcn_readlane(kk, j), b0 = __builtin_amdgcn_readlane(bb, j);
-            const char *lvl = (const char *)bp + (((int64_t)__builtin_amdgcn_readlane(bo_hi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane(bo_lo, j));
-            const int ahead = max(8, min(LEAN_AHEAD_MAX, LEAN_AHEAD_BYTES / (4 * k2 * k2)));
-            for (bool first = true; live; first = false) {              // fresh position: every few levels, and while too far ahead
-                if (!first || j % LEAN_POLL_EVERY == 0) {
-                    pos = __hip_atomic_load(&sy->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    lw = __builtin_amdgcn_readfirstlane((int)(uint32_t)pos);
-                    rw = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&sy->r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    if (lw == INT32_MIN || (int)(pos >> 32) != seq) live = false;
-                }
-                if (!live || lw - l <= ahead) break;
-                __builtin_amdgcn_s_sleep(16);
-            }
-            if (!live) break;
-            if (l > lw) continue;                                       // overtaken
-            const int r_hi = min(max(rw, 0), RP - 1);
-            const int row_bytes = 2 * k2, lines = (row_bytes + 127) >> 7;   // 128-byte lines of one (i, r) row of back-pointers
-            const int n = 2 * k2 * lines;
-            for (int t = lane; t < n; t += 64) {
-                const int ln = t % lines, q = t / lines, i = q >> 1, r = max(r_hi - (q & 1), 0);
-                const uint32_t off = (uint32_t)(((uint32_t)i * (uint32_t)RP + (uint32_t)r) * (uint32_t)k2) * 2u + (uint32_t)min(ln << 7, row_bytes - 2);
-                DG_DROP_LOAD(lvl + (off & ~3u));
-            }
-            for (int t = lane; t < ((k2 * 16 + 127) >> 7); t += 64) {
-                const uint32_t off = ((uint32_t)b0 << 4) + (uint32_t)min(t << 7, k2 * 16 - 4);
-                DG_DROP_LOAD(rowrec + off);
-            }
-            ++done;
-        }
-    }
-    if (lane == 0) { atomicAdd(&sy->n_helpers, 1); atomicAdd(&sy->n_levels, done); }
-#undef DG_DROP_LOAD
-}
 
 // the walk of one wave, publishing its position in *sy; R = plane of the starting cell (the graph's R, or one chain's budget)
 __device__ __forceinline__ void lean_walk(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
@@ -369,30 +287,35 @@ __device__ __forceinline__ void lean_walk(const LevelDesc *__restrict__ descs, i
 #undef DG_PUBLISH
 }
 
-__global__ __launch_bounds__(64) void dp_trace_chain_lean_kernel(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, int R,
-                                                                 const uint16_t *__restrict__ bp /* biased by the segment's first unit */,
-                                                                 const int32_t *__restrict__ final_val /* non-null on the first call */,
-                                                                 const uint4 *__restrict__ rowrec_, const uint32_t *__restrict__ in_edge,
-                                                                 uint2 *__restrict__ path, ChainState *st, ChainSync *sy, int seq) {
-    __shared__ int dump_s[64];
-    const int lane = threadIdx.x & 63;
-    const char *rowrec = (const char *)rowrec_;
-    if (blockIdx.x != 0) { lean_prefetch(descs, l_hi, l_lo, RP, bp, rowrec, sy, seq, dump_s, lane); return; }
-    lean_walk(descs, l_hi, l_lo, RP, R, bp, final_val, rowrec, in_edge, path, st, sy, seq, lane);
-}
-
 // ---------------------------------------------------------------------------------------------
-// One chain per requested budget (dg_dp_run_budgets): all chains of a lattice chunk in ONE launch
+// One walker wave per chain, all chains of a lattice chunk in ONE launch, and the helper workgroups that prefetch for them
 // ---------------------------------------------------------------------------------------------
-// Plane r of the sink holds the cell a run with limit r would read out, so the chain of budget b starts at cell (0, b, 0) and is
-// walked by the code above, unchanged: one walker wave per chain (block q < n_chains walks the chain of BudgetSlot q), each with
-// its own path slice, ChainState and ChainSync.  Placement: blocks b and b + 8 share an XCD (observed round-robin dispatch; only
-// speed depends on it), so the host deals the chains, sorted by falling budget, into G = min(8, n) groups of neighbouring budgets and
-// gives group g the blocks g, g + G, g + 2G, ...  The chains of a group start on adjacent planes and stay close (each uses its
-// recombinations at much the same places), so ONE set of LEAN_PREFETCHERS helper workgroups serves a group: the helpers follow the
-// position of the group's leader (its largest budget, blocks 0 .. G - 1) and read `planes` = group size + 1 planes from the leader's
-// r downwards instead of two.  A helper finds its group by its own XCC id, as in the single walk; on a chip that deals blocks
-// differently the helpers of a group are fewer or none and the walkers' loads miss the L2 -- slower, never wrong.
+// Chains.  Plane r of the sink holds the cell a run with limit r would read out, so the chain of budget b starts at cell (0, b, 0)
+// and is walked by the code above: block q < n_chains walks the chain of BudgetSlot q, each with its own path slice, ChainState and
+// ChainSync.  dg_dp_run is the one-chain case: budget R, one group, planes = 2.
+// Helpers.  With ~90 instructions per level the walk is bound by memory latency: the HBM round trip of its back-pointer load (two in
+// flight) and the row-record load that leads to the next candidates (~0.34 us per level).  The walker cannot know its cell any
+// earlier, but r only ever decreases along the walk, and rarely: the cell of a level some tens of levels down lies in plane r or
+// r - 1 of that level, 2 * k2 rows of k2 back-pointers -- 16 KB on a 64-wide level.  Helper workgroups ON THE WALKER'S XCD (the L2
+// is per XCD; a helper wave on the walker's own CU was measured and is worse than none: 80 vs 54 ms, its misses queue in front of
+// the walker's loads in the CU's in-order memory pipeline) read those planes, one load per 128-byte line with the data dropped, and
+// the level's row records, keeping up to LEAN_AHEAD_MAX levels ahead of the position the walker publishes every 16 levels (every 8:
+// 47.0 ms, 16: 44.5, 32: 44.9 on MHC-24); the walker's loads then hit the L2.  A wrong guess (one more recombination inside the
+// window than the planes read) costs an ordinary miss, nothing else.
+// Placement.  Blocks b and b + 8 share an XCD (observed round-robin dispatch; only speed depends on it), so the host deals the
+// chains, sorted by falling budget, into G = min(8, n) groups of neighbouring budgets and gives group g the blocks g, g + G,
+// g + 2G, ...  The chains of a group start on adjacent planes and stay close (each uses its recombinations at much the same places),
+// so ONE set of LEAN_PREFETCHERS helpers serves a group: they follow the position of the group's leader (its largest budget, blocks
+// 0 .. G - 1) and read `planes` = group size + 1 planes from the leader's r downwards.  On a chip that deals blocks differently the
+// helpers of a group are fewer or none and the walkers' loads miss the L2 -- slower, never wrong.
+// Protocol (ChainSync, in global memory; relaxed agent-scope atomics -- hints, nothing depends on their order): a walker publishes
+// its XCC id and seq << 32 | level; every block beyond the walkers looks for the first group whose leader runs on its own XCC id
+// and takes a ticket there, the first LEAN_PREFETCHERS tickets prefetch, everybody else leaves.  seq (a per-launch number) keeps a
+// helper from acting on the previous launch's words; whatever it reads, it only ever touches levels of [l_lo, l_hi].
+// Helper me of a group takes the levels l_hi - me - LEAN_PREFETCHERS * q.  Their descriptors are fetched 64 at a time, one per lane,
+// so that no level waits for a dependent descriptor load of its own; the position is polled every LEAN_POLL_EVERY levels (an L2
+// round trip).  A load whose data nobody wants goes straight into an LDS dump word per lane (global_load_lds): no destination
+// register that a later value could be sharing when the data arrives, nothing to wait for.
 __device__ __forceinline__ ChainSync *chain_sync_of(char *sy_base, int chain) { return (ChainSync *)(sy_base + (size_t)chain * BUDGET_SYNC_STRIDE); }
 
 __device__ __forceinline__ void lean_prefetch_group(const LevelDesc *__restrict__ descs, int l_hi, int l_lo, int RP, const uint16_t *__restrict__ bp,
@@ -418,7 +341,6 @@ __device__ __forceinline__ void lean_prefetch_group(const LevelDesc *__restrict_
         if (me < LEAN_PREFETCHERS) { sy = c; planes = tab[g].planes; }
     }
     if (!sy) return;
-    // from here on lean_prefetch, reading `planes` planes of every level
     int done = 0, lw = l_hi, rw = RP - 1;
     bool live = true;
     for (int lp = l_hi - me; live && lp >= l_lo; lp -= LEAN_PREFETCHERS * 64) {
@@ -530,53 +452,31 @@ void trace_launch_warm_rows(const DpState &S, int lb, int le, hipStream_t s) {  
     if (n > 0) hipLaunchKernelGGL(dp_warm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S.d_rowrec.as<uint4>() + (v1 - n), n);
 }
 
-void trace_launch_chain(const DpState &S, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s) {
-    if (S.lean_chain)
-        hipLaunchKernelGGL(dp_trace_chain_lean_kernel, dim3(LEAN_BLOCKS), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.R, bp_biased, final_val,
-                           S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(), S.d_path.as<uint2>(), S.d_chain.as<ChainState>(),
-                           (ChainSync *)(S.d_chain.as<char>() + 64), ++S.chain_seq);
-    else
-        hipLaunchKernelGGL(dp_trace_chain_spec_kernel, dim3(1), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.R, bp_biased, final_val,
-                           S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(), S.d_path.as<uint2>(), S.d_chain.as<ChainState>());
-}
-
-void trace_debug_report(const DpState &S) {                            // DG_DEBUG: how much of the walk the helpers covered
-    ChainSync sy;
-    if (hipMemcpy(&sy, S.d_chain.as<char>() + 64, sizeof sy, hipMemcpyDeviceToHost) == hipSuccess)
-        fprintf(stderr, "[dg] chain walk helpers: %d block-launches prefetched %d levels (since load)\n", sy.n_helpers, sy.n_levels);
-}
-
-// the n chains of dg_dp_run_budgets over destination levels [l_lo, l_hi] (buffers and placement: budgets_prepare)
+// the n chains of a run over destination levels [l_lo, l_hi] (buffers and placement: budgets_prepare)
 void trace_launch_chains(const DpState &S, int n, int l_hi, int l_lo, const uint16_t *bp_biased, const int32_t *final_val, hipStream_t s) {
     if (S.lean_chain)
         hipLaunchKernelGGL(dp_trace_chains_lean_kernel, dim3(n + BUDGET_HELPER_BLOCKS), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.L,
-                           S.d_mc_tab.as<BudgetSlot>(), n, S.mc_groups, bp_biased, final_val, S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(),
-                           S.d_mc_path.as<uint2>(), S.d_mc_chain.as<ChainState>(), S.d_mc_sync.as<char>(), ++S.mc_seq);
+                           S.d_ch_tab.as<BudgetSlot>(), n, S.n_groups, bp_biased, final_val, S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(),
+                           S.d_ch_path.as<uint2>(), S.d_ch_state.as<ChainState>(), S.d_ch_sync.as<char>(), ++S.walk_seq);
     else
-        hipLaunchKernelGGL(dp_trace_chains_spec_kernel, dim3(n), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.L, S.d_mc_tab.as<BudgetSlot>(),
-                           bp_biased, final_val, S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(), S.d_mc_path.as<uint2>(), S.d_mc_chain.as<ChainState>());
+        hipLaunchKernelGGL(dp_trace_chains_spec_kernel, dim3(n), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), l_hi, l_lo, S.RP, S.L, S.d_ch_tab.as<BudgetSlot>(),
+                           bp_biased, final_val, S.d_rowrec.as<uint4>(), S.d_in_edge.as<uint32_t>(), S.d_ch_path.as<uint2>(), S.d_ch_state.as<ChainState>());
 }
 
-void trace_debug_report_chains(const DpState &S, int n) {               // DG_DEBUG: where every walker ran and what the helpers of its group covered
+void trace_debug_report(const DpState &S, int n) {                      // DG_DEBUG: where every walker ran and what the helpers of its group covered (this run)
     std::vector<char> sy((size_t)n * BUDGET_SYNC_STRIDE);
-    std::vector<BudgetSlot> tab(n);
-    if (hipMemcpy(sy.data(), S.d_mc_sync.p, sy.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tab.data(), S.d_mc_tab.p, sizeof(BudgetSlot) * n, hipMemcpyDeviceToHost) != hipSuccess) return;
+    const std::vector<BudgetSlot> &tab = S.tab_host;
+    if ((int)tab.size() != n || hipMemcpy(sy.data(), S.d_ch_sync.p, sy.size(), hipMemcpyDeviceToHost) != hipSuccess) return;
     for (int b = 0; b < n; ++b) {
         const ChainSync &c = *(const ChainSync *)(sy.data() + (size_t)tab[b].chain * BUDGET_SYNC_STRIDE);
-        fprintf(stderr, "[dg] multi-chain walk: block %d budget %d on XCC %d%s", b, tab[b].budget, c.xcc, b < S.mc_groups ? " (group leader" : "\n");
-        if (b < S.mc_groups) fprintf(stderr, ", %d planes): %d helper block-launches prefetched %d levels\n", tab[b].planes, c.n_helpers, c.n_levels);
+        fprintf(stderr, "[dg] chain walk: block %d budget %d on XCC %d%s", b, tab[b].budget, c.xcc, b < S.n_groups ? " (group leader" : "\n");
+        if (b < S.n_groups) fprintf(stderr, ", %d planes), helpers: %d block-launches prefetched %d levels\n", tab[b].planes, c.n_helpers, c.n_levels);
     }
 }
 
 void trace_launch_finish_chain(const DpState &S, const uint2 *path, int32_t *edges, const ChainState *st, TraceOut *out, hipStream_t s) {
     hipLaunchKernelGGL(dp_trace_finish_kernel, dim3((unsigned)std::min(1024, (S.L + 255) / 256)), dim3(256), 0, s, S.d_descs.as<LevelDesc>(), S.L, path, colour_csr(S), S.cap,
                        edges, st, out);
-}
-
-void trace_launch_finish(const DpState &S, hipStream_t s) {
-    (void)hipMemsetAsync(S.d_trace.p, 0, sizeof(TraceOut), s);
-    hipLaunchKernelGGL(dp_trace_finish_kernel, dim3((unsigned)std::min(1024, (S.L + 255) / 256)), dim3(256), 0, s, S.d_descs.as<LevelDesc>(), S.L, S.d_path.as<uint2>(), colour_csr(S), S.cap,
-                       S.d_edges.as<int32_t>(), S.d_chain.as<ChainState>(), S.d_trace.as<TraceOut>());
 }
 
 }  // namespace dgi

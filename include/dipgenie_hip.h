@@ -88,7 +88,7 @@ typedef struct dg_dp_timing {         /* HIP-event times of the last dg_dp_run, 
  * only host work follows; dg_dp_load_graph adopts the chunks and dg_dp_run waits for any still missing. */
 int dg_dp_prealloc(dg_ctx *, int64_t bytes);
 int dg_dp_load_graph(dg_ctx *, const dg_dp_graph *);   /* validate + upload + build in-CSR; resident until next load */
-int dg_dp_run(dg_ctx *, dg_dp_result *);               /* all kernels on the resident graph; synchronises */
+int dg_dp_run(dg_ctx *, dg_dp_result *);               /* all kernels on the resident graph (dg_dp_run_budgets with the one budget R); synchronises */
 int dg_dp_get_timing(dg_ctx *, dg_dp_timing *);
 int dg_dp_solve_diploid(dg_ctx *, const dg_dp_graph *, dg_dp_result *);   /* = load_graph + run */
 /* Every recombination budget from ONE pass.  The source level starts at 0 on all R + 1 planes and a cell of plane r gathers from
