@@ -1,0 +1,317 @@
+// ======================================================================================
+// diploid_dp_approximation_solver minus the level loop  (approximator.cpp:362-453, 720-1011)
+// ======================================================================================
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <iterator>
+#include <queue>
+#include <stdexcept>
+#include <unordered_map>
+#include <unordered_set>
+
+#include "stage_util.hpp"
+
+namespace dg {
+
+namespace {
+
+using AnchorsByHap = std::vector<std::vector<AnchorRec>>;
+using EdgeList = std::vector<std::pair<int, int>>;                     // the weight-1 edges of one path, source to sink
+
+// One chain's answer: the dg_dp_result and the four edge arrays (cap entries each) it points into.
+struct ChainAnswer {
+    dg_dp_result res;
+    std::vector<int32_t> p1_from, p1_to, p2_from, p2_to;
+    explicit ChainAnswer(int cap) : p1_from(cap), p1_to(cap), p2_from(cap), p2_to(cap) {
+        memset(&res, 0, sizeof(res));
+        res.p1_from = p1_from.data(); res.p1_to = p1_to.data(); res.p2_from = p2_from.data(); res.p2_to = p2_to.data();
+        res.cap = cap;
+    }
+    ChainAnswer(ChainAnswer &&) = default;                             // (a moved vector keeps its buffer, so res still points into it)
+    ChainAnswer(const ChainAnswer &) = delete;
+    bool reachable() const { return res.value != INT32_MIN / 4; }
+    std::pair<EdgeList, EdgeList> edge_lists() const {
+        EdgeList w1, w2;
+        for (int i = 0; i < res.n_p1 && i < res.cap; ++i) w1.emplace_back(p1_from[i], p1_to[i]);
+        for (int i = 0; i < res.n_p2 && i < res.cap; ++i) w2.emplace_back(p2_from[i], p2_to[i]);
+        return {w1, w2};
+    }
+};
+
+// what one pair of paths reads out of the graph: the two sequences and the colours met on the way
+struct PathReadout {
+    std::string seq[2];
+    std::unordered_map<int, int> color_freq[2];
+    std::vector<int> colors[2];
+};
+
+// The flat graph already is the dg_dp_graph layout (vertex ids are level-sorted: ExpandedGraph.hpp:360-407).
+// Topology arrays are handed to the device library in place (no copies); only the HOM / HET colour CSR (:431-453,
+// lists are sorted-unique already) is new: counts, prefix sums, fill -- in parallel over vertex blocks.
+void split_colours(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_bv, DpGraphStorage &dpg) {
+    if (g.colours_split) {                                             // the fused route wrote the split lists directly
+        dpg.hom_off.swap(g.hom_off); dpg.het_off.swap(g.het_off); dpg.hom_col.swap(g.hom_col); dpg.het_col.swap(g.het_col);
+        return;
+    }
+    const int nV = g.n;
+    dpg.hom_off.assign((size_t)nV + 1, 0);
+    dpg.het_off.assign((size_t)nV + 1, 0);
+    for (int c : g.col_pool) (void)color_homo_bv.at(c);                // same out_of_range behaviour as the reference's .at()
+#pragma omp parallel for schedule(static)
+    for (int v = 0; v < nV; ++v) {
+        int64_t nh = 0;
+        for (int64_t q = g.col_off[v]; q < g.col_off[v + 1]; ++q) nh += color_homo_bv[g.col_pool[q]] == 1;
+        dpg.hom_off[v + 1] = nh;
+        dpg.het_off[v + 1] = (g.col_off[v + 1] - g.col_off[v]) - nh;
+    }
+    for (int v = 0; v < nV; ++v) { dpg.hom_off[v + 1] += dpg.hom_off[v]; dpg.het_off[v + 1] += dpg.het_off[v]; }
+    dpg.hom_col.resize((size_t)dpg.hom_off[nV]);
+    dpg.het_col.resize((size_t)dpg.het_off[nV]);
+#pragma omp parallel for schedule(static)
+    for (int v = 0; v < nV; ++v) {
+        int64_t ph = dpg.hom_off[v], pt = dpg.het_off[v];
+        for (int64_t q = g.col_off[v]; q < g.col_off[v + 1]; ++q) {
+            const int c = g.col_pool[q];
+            if (color_homo_bv[c] == 1) dpg.hom_col[ph++] = c; else dpg.het_col[pt++] = c;
+        }
+    }
+}
+
+void dump_graph(DpGraphStorage &dpg, const ExpandedGraph &g, const std::string &path, int R) {   // the dump wants the topology too
+    dpg.level_off = g.level_off; dpg.out_off = g.adj_off; dpg.out_dst = g.adj_dst; dpg.out_w = g.adj_w;
+    dpg.save(path, R);
+    uvec<int32_t>().swap(dpg.level_off); uvec<int64_t>().swap(dpg.out_off);
+    uvec<int32_t>().swap(dpg.out_dst); uvec<uint8_t>().swap(dpg.out_w);
+}
+
+// ---- the level loop + sink read-out: DEVICE (approximator.cpp:532-716, 774-785) ----
+// answers[q] is filled for budgets[q].  --budgets: the listed budgets and -R itself from ONE sweep of the graph loaded with R
+// (plane r of the sink is the cell a run with -R r reads out; one chain walk per budget).  Without the option: the plain call, as ever.
+std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &budgets, std::vector<ChainAnswer> &answers) {
+    const Backend &be = p.be;
+    dg_dp_graph view = p.dpg.view(p.opt.R);
+    view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
+    view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
+    if (p.opt.budgets.empty()) {
+        if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
+        return "";
+    }
+    if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
+    std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
+    for (const ChainAnswer &a : answers) res.push_back(a.res);
+    int rc = be.dp_load_graph(be.ctx, &view);
+    if (rc == 0) rc = be.dp_run_budgets(be.ctx, budgets.data(), (int32_t)budgets.size(), res.data());
+    if (rc != 0) return backend_error(be, "dp_run_budgets");
+    for (size_t q = 0; q < answers.size(); ++q) answers[q].res = res[q];
+    return "";
+}
+
+int find_next_zero_hap(const ExpandedGraph &g, int src, int target_hap) {   // :732-755
+    if (g.haplotype.at(src) == target_hap && g.orig_len.at(src) > 0) return src;
+    std::queue<int> q;
+    std::unordered_set<int> visited;
+    q.push(src); visited.insert(src);
+    while (!q.empty()) {
+        int u = q.front(); q.pop();
+        for (int64_t e = g.adj_off[u]; e < g.adj_off[u + 1]; ++e) {
+            const int v = g.adj_dst[e];
+            if (g.adj_w[e] != 0) continue;
+            if (!visited.insert(v).second) continue;
+            if (g.haplotype.at(v) == target_hap && g.orig_len.at(v) > 0) return v;
+            q.push(v);
+        }
+    }
+    return -1;
+}
+
+// weighted-edge list -> the sequence and the colours met on the way (:790-923), for path `which` (0: P1, 1: P2).  primary: the
+// answer at -R, which speaks on stdout as the reference does; the other budgets of --budgets leave stdout alone
+void path_sequence(const Pipeline &p, const ExpandedGraph &g, const AnchorsByHap &anchorsByHap, const EdgeList &wedges, int which, bool primary, PathReadout &out) {
+    const auto &paths = p.paths;
+    const int L = (int)g.level_off.size() - 1;
+    const char *tag = which == 0 ? "P1" : "P2";
+    std::string &hs = out.seq[which];
+    auto &color_freq = out.color_freq[which];
+    const int first_vertex = g.level_off.at(0);                        // vertices_in_level[0][0]
+    int start_exp = first_vertex;
+    for (int i = 0; i < (int)wedges.size(); i++) {
+        const auto &edge = wedges.at(i);
+        if (g.orig_len[edge.first] != 1) {
+            std::cout << tag << ": Vertex " << edge.first << " in map back has " << g.orig_len[edge.first]
+                      << " original vertices" << std::endl;
+            exit(1);
+        }
+        int end_exp = edge.first;
+        int h = g.haplotype.at(end_exp);
+        if (start_exp == first_vertex)
+            for (int v = g.level_off.at(1); v < g.level_off.at(2); ++v) if (g.haplotype.at(v) == h) start_exp = v;
+        if (g.orig_len.at(start_exp) < 1 || g.orig_len.at(end_exp) < 1) throw std::out_of_range("original_vertex.at(0)");
+        int start_org = g.orig_pool[g.orig_off[start_exp]];
+        int end_org = g.orig_pool[g.orig_off[end_exp]];
+        bool activated = false;
+        for (int t = 0; t < (int)paths[h].size(); t++) {
+            if ((int)paths[h][t] == start_org) activated = true;
+            if (activated) hs += p.node_seq[paths[h][t]];
+            if ((int)paths[h][t] == end_org) { activated = false; break; }
+        }
+        for (const auto &a : anchorsByHap[h])
+            if (a.startOrg > start_org && a.endOrg < end_org)
+                for (auto c : a.colours) {
+                    if (color_freq.find(c) == color_freq.end()) { color_freq[c] = 1; out.colors[which].push_back(c); }
+                    else color_freq[c] += 1;
+                }
+        if (g.haplotype.at(edge.second), edge.second >= g.level_off[L - 1]) break;   // level[edge.second] == L - 1 (ids are level-sorted)
+        const auto &next_edge = wedges.at(i + 1);
+        int next_hap = g.haplotype.at(next_edge.first);
+        int next_start = find_next_zero_hap(g, edge.second, next_hap);
+        if (next_start != -1) start_exp = next_start;
+        else (primary ? std::cout : std::cerr) << tag << " (path recovery) Could not find next_hap=" << next_hap << " from " << edge.second << " via 0-weight edges\n";
+    }
+}
+
+// :1314-1325 -- same bytes (80 columns, '\n' line ends), assembled in memory and written once instead of one flushed line at a time
+std::string write_diploid_fasta(const std::string &path, const std::string *hs) {
+    std::string text;
+    text.reserve(hs[0].size() + hs[1].size() + (hs[0].size() + hs[1].size()) / 80 + 128);
+    for (int q = 0; q < 2; ++q) {
+        text += q == 0 ? ">sol_1 bp:" : ">sol_2 bp:";
+        text += std::to_string(hs[q].size());
+        text += '\n';
+        for (size_t i = 0; i < hs[q].size(); i += 80) { text.append(hs[q], i, 80); text += '\n'; }
+    }
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open output file " + path;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + path + " failed";
+    return "";
+}
+
+void split_sorted_unique(const std::vector<uint8_t> &color_homo_bv, const std::vector<int> &cs, std::vector<int> &hom, std::vector<int> &het) {
+    for (auto c : cs) { if (color_homo_bv[c]) hom.push_back(c); else het.push_back(c); }
+    std::sort(hom.begin(), hom.end()); hom.erase(std::unique(hom.begin(), hom.end()), hom.end());
+    std::sort(het.begin(), het.end()); het.erase(std::unique(het.begin(), het.end()), het.end());
+}
+
+// score + approximation certificate (:933-1004) -- stdout only
+void certificate(Pipeline &p, const std::vector<uint8_t> &color_homo_bv, const PathReadout &out, int s_het) {
+    std::vector<int> h1, t1, h2, t2, inter, symd;
+    split_sorted_unique(color_homo_bv, out.colors[0], h1, t1);
+    split_sorted_unique(color_homo_bv, out.colors[1], h2, t2);
+    std::set_intersection(h1.begin(), h1.end(), h2.begin(), h2.end(), std::back_inserter(inter));
+    std::set_symmetric_difference(t1.begin(), t1.end(), t2.begin(), t2.end(), std::back_inserter(symd));
+    int intersection_count = (int)inter.size(), symdiff_count = (int)symd.size();
+    int m_G_hom = 0, m_G_het = 0;
+    auto freq = [&](int which, int c) { auto it = out.color_freq[which].find(c); return it == out.color_freq[which].end() ? 0 : it->second; };
+    for (auto c : inter) { int k1 = freq(0, c), k2 = freq(1, c); m_G_hom += (k1 >= k2 ? k1 : k2); }
+    for (auto c : symd) m_G_het += freq(0, c) + freq(1, c);
+    float m_G_hom_avg = m_G_hom / (float)intersection_count;
+    float m_G_het_avg = m_G_het / (float)symdiff_count;
+    float m_bar = std::max(m_G_hom_avg, m_G_het_avg);
+    int loss_het = s_het - m_G_het;
+    float additive_term = loss_het / (float)m_G_het_avg;
+    int obj = intersection_count + symdiff_count;
+    p.sum.obj = obj;
+    if (!p.opt.quiet) {
+        std::cout << "r: " << p.opt.R << " obj: " << obj << std::endl;
+        float ub = m_bar * (obj + additive_term);
+        std::cout << "Approximation certificate: multiplicative factor: " << ub / (float)obj << std::endl;
+    }
+}
+
+// --budgets: every listed budget r other than -R gets <hap_file>.R<r>, the FASTA a run with -R r writes (an unreachable one: no
+// file), and every listed budget its row (answers starts with the listed budgets, in order)
+std::string write_budget_fastas(Pipeline &p, const ExpandedGraph &g, const AnchorsByHap &anchorsByHap, const std::vector<ChainAnswer> &answers) {
+    for (size_t q = 0; q < p.opt.budgets.size(); ++q) {
+        const ChainAnswer &b = answers[q];
+        BudgetRow row;
+        row.r = p.opt.budgets[q];
+        row.reachable = b.reachable();
+        if (row.r == p.opt.R) { row.dp_value = p.sum.dp_value; row.r1 = p.sum.r1; row.r2 = p.sum.r2; row.len1 = p.sum.len1; row.len2 = p.sum.len2; }
+        else if (row.reachable) {
+            const auto [w1, w2] = b.edge_lists();
+            PathReadout out;
+            path_sequence(p, g, anchorsByHap, w1, 0, false, out);
+            path_sequence(p, g, anchorsByHap, w2, 1, false, out);
+            const std::string e = write_diploid_fasta(p.opt.hap_file + ".R" + std::to_string(row.r), out.seq);
+            if (!e.empty()) return e;
+            row.dp_value = b.res.value; row.r1 = (int)w1.size() - 1; row.r2 = (int)w2.size() - 1;
+            row.len1 = (int64_t)out.seq[0].size(); row.len2 = (int64_t)out.seq[1].size();
+        }
+        p.sum.budget_rows.push_back(row);
+    }
+    return "";
+}
+
+// r  dp_value  r1  r2  len1  len2, NA for an unreachable budget
+std::string write_budget_table(const std::string &path, const std::vector<BudgetRow> &rows) {
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open budget table " + path;
+    for (const BudgetRow &row : rows) {
+        if (row.reachable) f << row.r << '\t' << row.dp_value << '\t' << row.r1 << '\t' << row.r2 << '\t' << row.len1 << '\t' << row.len2 << '\n';
+        else f << row.r << "\tNA\tNA\tNA\tNA\tNA\n";
+    }
+    f.close();
+    if (!f.good()) return "write to " + path + " failed";
+    return "";
+}
+
+}  // namespace
+
+int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_bv,
+                      const std::vector<std::vector<AnchorRec>> &anchorsByHap, std::string &err) {
+    double t0 = now_s();
+    const int L = (int)g.level_off.size() - 1;
+    const int R = opt.R;
+    if (be.hint_dp_soon && !g.colours_split) {                         // level widths are final: the exact lattice size (the fused route has said so already)
+        double cells = 0;
+        for (int l = 1; l < L; ++l) { const double kw = (double)(g.level_off[l + 1] - g.level_off[l]); cells += kw * kw; }
+        be.hint_dp_soon(be.ctx, (int64_t)std::min(9.0e18, cells * (R + 1)));
+    }
+    if (!opt.quiet && g.level_off[1] - g.level_off[0] > 1) std::cout << "There is more than one source on level zero!" << std::endl;
+    dpg = DpGraphStorage();
+    if (!opt.quiet) std::cout << "Creating hetro/hom-zygous colors per vertex lists" << std::endl;
+    split_colours(g, color_homo_bv, dpg);
+    sum.n_levels = L;
+    sum.n_vertices = g.n;
+    stamp("dp_prologue_flatten", t0);
+    if (!opt.dump_prefix.empty()) dump_graph(dpg, g, opt.dump_prefix + ".dpg", R);
+    if (opt.dump_only) { err = "dump_only"; return 1; }
+
+    t0 = now_s();
+    if (!opt.quiet) std::cout << "Running DP" << std::endl;
+    // one answer per budget: the listed ones in order, then -R itself unless it is listed (without --budgets: -R alone)
+    std::vector<int32_t> budgets(opt.budgets.begin(), opt.budgets.end());
+    if (std::find(budgets.begin(), budgets.end(), (int32_t)R) == budgets.end()) budgets.push_back(R);
+    std::vector<ChainAnswer> answers;
+    answers.reserve(budgets.size());
+    for (size_t q = 0; q < budgets.size(); ++q) answers.emplace_back(R + 8);
+    if (failed(run_dp(*this, g, budgets, answers), err)) return -1;
+    stamp("dp_level_loop", t0);
+
+    t0 = now_s();
+    const ChainAnswer &top = answers[(size_t)(std::find(budgets.begin(), budgets.end(), (int32_t)R) - budgets.begin())];
+    sum.dp_value = top.res.value; sum.s_het = top.res.s_het; sum.cells = top.res.cells; sum.relaxations = top.res.relaxations;
+    if (!opt.quiet) std::cout << "DP value: " << top.res.value << std::endl;   // :776
+    const auto [wp1, wp2] = top.edge_lists();
+    PathReadout out;
+    path_sequence(*this, g, anchorsByHap, wp1, 0, true, out);
+    path_sequence(*this, g, anchorsByHap, wp2, 1, true, out);
+    sum.r1 = (int)wp1.size() - 1; sum.r2 = (int)wp2.size() - 1;        // :784-785
+    sum.len1 = (int64_t)out.seq[0].size(); sum.len2 = (int64_t)out.seq[1].size();
+    certificate(*this, color_homo_bv, out, top.res.s_het);
+    if (!opt.quiet)
+        std::cout << "recombinations in P1: " << sum.r1 << ", recombinations in P2: " << sum.r2 << ", bp of P1: " << out.seq[0].length()
+                  << ", bp of P2: " << out.seq[1].length() << std::endl;                 // :1307-1308
+    if (failed(write_diploid_fasta(opt.hap_file, out.seq), err)) return -1;
+    if (failed(write_budget_fastas(*this, g, anchorsByHap, answers), err)) return -1;
+    if (!opt.budget_table.empty() && failed(write_budget_table(opt.budget_table, sum.budget_rows), err)) return -1;
+    stamp("traceback+write", t0);
+    return 0;
+}
+
+}  // namespace dg

@@ -1,5 +1,5 @@
 // Pipeline::build_levelized_fast -- the diploid route from Anchor_hits to the levelized DP graph in one fused, threaded
-// construction.  It produces exactly what the literal route of pipeline.cpp produces by running, one after the other,
+// construction.  It produces exactly what the literal route of solve.cpp produces by running, one after the other,
 //   Approximator::solve's graph construction           /root/reference/src/approximator.cpp:1017-1246
 //   ExpandedGraph::topologically_reorder                /root/reference/src/ExpandedGraph.hpp:29-102
 //   ExpandedGraph::strict_bfs_levelize_and_reorder      /root/reference/src/ExpandedGraph.hpp:269-409
@@ -28,7 +28,7 @@
 #include <stdexcept>
 #include <thread>
 
-#include "pipeline.hpp"
+#include "stage_util.hpp"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -37,17 +37,11 @@
 namespace dg {
 
 namespace {
-struct Lap {
-    bool on;
-    double t;
-    Lap() : on(getenv("DG_DEBUG") != nullptr), t(now_s()) {}
-    void operator()(const char *w) { if (on) { const double n = now_s(); fprintf(stderr, "[dg::fast] %-20s %.3f s\n", w, n - t); t = n; } }
-};
 struct Proxy { int32_t startExp, endExp, idx; };             // what the (startExp, endExp) sort of approximator.cpp:1203 looks at
 }  // namespace
 
 bool Pipeline::build_levelized_fast(ExpandedGraph &g, std::vector<std::vector<AnchorRec>> &anchorsByHap, std::vector<uint8_t> &color_homo_bv) {
-    Lap lap;
+    Lap lap("fast", 20);
     const int H = (int)paths.size();
     const int NT = std::max(1, std::min(opt.threads, 64));
     if (H == 0) return false;

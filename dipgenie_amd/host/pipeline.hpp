@@ -1,14 +1,17 @@
 // Host-side mirror of the reference's Solver / Approximator objects for the diploid hot path.
 //
 // Everything that is NOT one of the two device loops stays here, restated so that vertex numbering,
-// adjacency order and every tie-break match the reference exactly:
-//   Solver::read_gfa                       /root/reference/src/solver.cpp:27-227
-//   Solver::compute_and_classify_anchors   /root/reference/src/solver.cpp:449-887
-//   Approximator::solve                    /root/reference/src/approximator.cpp:1014-1331
-//   ExpandedGraph::topologically_reorder   /root/reference/src/ExpandedGraph.hpp:29-102
-//   ExpandedGraph::strict_bfs_levelize_and_reorder   /root/reference/src/ExpandedGraph.hpp:269-409
-//   haploid dp_approximation_solver        /root/reference/src/approximator.cpp:44-168 (CPU by design)
-//   traceback -> sequences, certificate    /root/reference/src/approximator.cpp:720-1004
+// adjacency order and every tie-break match the reference exactly.  One translation unit per stage:
+//   pipeline.cpp        driver (main.cpp:117-165) and
+//                       Solver::read_gfa                       /root/reference/src/solver.cpp:27-227
+//   anchors.cpp         Solver::compute_and_classify_anchors   /root/reference/src/solver.cpp:449-887
+//   expanded_graph.cpp  ExpandedGraph::topologically_reorder   /root/reference/src/ExpandedGraph.hpp:29-102
+//                       ExpandedGraph::strict_bfs_levelize_and_reorder   /root/reference/src/ExpandedGraph.hpp:269-409
+//                       (and DpGraphStorage, the .dpg file)
+//   haploid_dp.cpp      haploid dp_approximation_solver        /root/reference/src/approximator.cpp:44-168 (host twin of the device loop)
+//   solve.cpp           Approximator::solve                    /root/reference/src/approximator.cpp:1014-1331 (literal graph construction)
+//   fast_graph.cpp      the fused route to the same levelized graph
+//   diploid.cpp         DP prologue; traceback -> sequences, certificate   /root/reference/src/approximator.cpp:362-453, 720-1011
 // The two device loops are reached only through the Backend table (= include/dipgenie_hip.h).
 #pragma once
 #include <cstdint>
@@ -16,7 +19,6 @@
 #include <memory>
 #include <string>
 #include <thread>
-#include <utility>
 #include <initializer_list>
 #include <utility>
 #include <vector>
@@ -142,7 +144,7 @@ struct DpGraphStorage {
     uvec<int64_t> out_off, hom_off, het_off;
     uvec<uint8_t> out_w;
     dg_dp_graph view(int R) const;
-    bool save(const std::string &path, int R) const;   // little-endian binary, see pipeline.cpp
+    bool save(const std::string &path, int R) const;   // little-endian binary, see expanded_graph.cpp
     bool load(const std::string &path, int &R);
 };
 
@@ -167,8 +169,17 @@ struct Summary {              // what tests and the CLI report
 // One anchor occurrence: vertex list vpool[off, off+len) of read-minimizer id `a` on haplotype `h`.
 struct Occ { int32_t a, h; uint32_t off, len; };
 
+// One haplotype laid out along its walk: start offset of every step (one more entry: the total length) and, on request,
+// node_seq concatenated along paths[h] (solver.cpp:283-288).
+struct HapAssembly {
+    std::vector<int64_t> step_start;
+    size_t total = 0;
+    std::string seq;
+};
+
 class Pipeline {
   public:
+    ~Pipeline() { if (fit_thread.joinable()) fit_thread.join(); }
     Options opt;
     Backend be;
     Summary sum;
@@ -198,6 +209,7 @@ class Pipeline {
     struct HapSketch { std::vector<uint64_t> hash; std::vector<int64_t> pos; bool set = false; };
     std::vector<HapSketch> inj_hap;
     std::string haplotype_sequence(uint32_t h) const;   // node_seq concatenated along paths[h] (solver.cpp:283-288)
+    HapAssembly assemble_haplotype(uint32_t h, bool with_sequence) const;
 
     int load_graph(std::string &err);      // gfa_read + Solver::read_gfa
     int run_loaded(std::string &err);      // everything after load_graph (main.cpp:163-165)
@@ -218,6 +230,7 @@ class Pipeline {
     // fused + threaded route from Anchor_hits to the levelized graph (fast_graph.cpp); false: take the literal route
     bool build_levelized_fast(ExpandedGraph &g, std::vector<std::vector<AnchorRec>> &anchorsByHap, std::vector<uint8_t> &color_homo_bv);
     void stamp(const char *name, double t0);
+    void clamp_threads();                  // -t0 / negative: every num_threads clause sees a valid count
     double t_run0 = 0;
     bool reads_loaded = false;
     // fit + classify on its own thread (compute_and_classify_anchors starts it, wait_fit joins it)
@@ -226,10 +239,11 @@ class Pipeline {
     double fit_t0 = 0;
     int64_t fit_n_hom = 0;
     std::vector<int32_t> fit_sp_count;
+    std::string start_fit(std::vector<int32_t> &sp_count);   // "" or the error; takes the counts
+    void fit_and_classify(const std::vector<HistBin> &hist, int max_mult, int threads);
     void wait_fit();
-  public:
-    ~Pipeline() { if (fit_thread.joinable()) fit_thread.join(); }
-  private:
+    int solve_fused(double t0, bool &declined, std::string &err);   // fast_graph.cpp's route; declined: take the literal one
+    int solve_literal(double t0, std::string &err);
 };
 
 double now_s();

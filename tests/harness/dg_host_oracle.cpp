@@ -69,6 +69,16 @@ static int o_dp(void *, const dg_dp_graph *g, dg_dp_result *r) {
 }
 static const char *o_err() { return "oracle"; }
 
+// DG_HARNESS_UNSTABLE_ANCHORS: a device anchor path that always declines -- every haplotype "adds" 0 minimizers and the
+// finish reports one unstable group with an empty result, so the pipeline must redo the whole stage on the host
+static int s_anchor_begin(void *, int32_t, int32_t, const int32_t *, int, int) { return 0; }
+static int s_anchor_add(void *, int32_t, const char *, int64_t, const int32_t *, const int64_t *, int64_t, int64_t *n) { *n = 0; return 0; }
+static int s_anchor_finish(void *, const uint64_t *, int64_t, float, dg_anchor_result *out) {
+    memset(out, 0, sizeof(*out));
+    out->n_unstable_groups = 1;
+    return 0;
+}
+
 // --fit: read "multiplicity freq" lines, print the host fitter's result in ref_harness's format
 static int fit_mode() {
     std::vector<dg::HistBin> H;
@@ -112,6 +122,11 @@ int main(int argc, char **argv) {
     p.be.dp_solve_diploid = o_dp;
     p.be.free_buf = orc_free;
     p.be.last_error = o_err;
+    if (getenv("DG_HARNESS_UNSTABLE_ANCHORS")) {
+        p.be.anchor_begin = s_anchor_begin;
+        p.be.anchor_add_haplotype = s_anchor_add;
+        p.be.anchor_finish = s_anchor_finish;
+    }
     std::string err;
     if (p.run(err) != 0) { if (err == "dump_only") return 0; fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
     if (!json.empty()) {
