@@ -356,6 +356,54 @@ class Context:
         _check(lib.dg_hash_kmers(self.h, kmers, n, k, out.ctypes.data), "dg_hash_kmers")
         return out
 
+    # ---- anchors ----
+    def anchor_begin(self, n_haps, n_vertices, top_order_map, k, w):
+        top = np.ascontiguousarray(top_order_map, np.int32)
+        _check(lib.dg_anchor_begin(self.h, n_haps, n_vertices, top.ctypes.data if top.size else None, k, w), "dg_anchor_begin")
+
+    @staticmethod
+    def _steps(step_vtx, step_start):
+        sv = np.ascontiguousarray(step_vtx, np.int32)
+        ss = np.ascontiguousarray(step_start, np.int64)
+        if ss.size != sv.size + 1:
+            raise ValueError("step_start needs one entry more than step_vtx")
+        return sv if sv.size else np.zeros(1, np.int32), ss, sv.size      # (a non-NULL pointer for a haplotype of zero steps)
+
+    def anchor_add_haplotype(self, h, seq, step_vtx, step_start):
+        """haplotype h (bytes) with its walk: step s is vertex step_vtx[s] over bases [step_start[s], step_start[s + 1]).
+        Returns the minimizer count."""
+        sv, ss, n_steps = self._steps(step_vtx, step_start)
+        n = C.c_int64()
+        _check(lib.dg_anchor_add_haplotype(self.h, h, seq, len(seq), sv.ctypes.data, ss.ctypes.data, n_steps, C.byref(n)), "dg_anchor_add_haplotype")
+        return n.value
+
+    def anchor_add_haplotype_sketched(self, h, length, hash, pos, step_vtx, step_start):
+        """the same for a minimizer list computed elsewhere (sketch_haplotype's output)"""
+        sv, ss, n_steps = self._steps(step_vtx, step_start)
+        hs = np.ascontiguousarray(hash, np.uint64)
+        ps = np.ascontiguousarray(pos, np.int64)
+        if hs.size != ps.size:
+            raise ValueError("hash and pos differ in length")
+        _check(lib.dg_anchor_add_haplotype_sketched(self.h, h, length, hs.ctypes.data if hs.size else None, ps.ctypes.data if ps.size else None, hs.size,
+                                                    sv.ctypes.data, ss.ctypes.data, n_steps), "dg_anchor_add_haplotype_sketched")
+
+    def anchor_finish(self, sp_hash, min_shared):
+        """join with the sorted read spectrum, filter, sort: dict of occ_id, occ_hap int32[n_occ], occ_off, occ_len uint32[n_occ],
+        vpool int32[n_vtx] (Anchor_hits order) and the counters n_candidates, n_unstable_groups"""
+        sp = np.ascontiguousarray(sp_hash, np.uint64)
+        res = AnchorResult()
+        try:
+            _check(lib.dg_anchor_finish(self.h, sp.ctypes.data if sp.size else None, sp.size, float(min_shared), C.byref(res)), "dg_anchor_finish")
+            def arr(p, ct, dt, n):
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (n,)).astype(dt, copy=True) if n and p else np.zeros(0, dt)
+            return dict(occ_id=arr(res.occ_id, C.c_int32, np.int32, res.n_occ), occ_hap=arr(res.occ_hap, C.c_int32, np.int32, res.n_occ),
+                        occ_off=arr(res.occ_off, C.c_uint32, np.uint32, res.n_occ), occ_len=arr(res.occ_len, C.c_uint32, np.uint32, res.n_occ),
+                        vpool=arr(res.vpool, C.c_int32, np.int32, res.n_vtx), n_candidates=res.n_candidates, n_unstable_groups=res.n_unstable_groups)
+        finally:
+            for p in (res.occ_id, res.occ_hap, res.occ_off, res.occ_len, res.vpool):
+                if p:
+                    lib.dg_free(p)
+
     def sketch_set_option(self, name, value):
         _check(lib.dg_sketch_set_option(self.h, name.encode(), int(value)), "dg_sketch_set_option")
 

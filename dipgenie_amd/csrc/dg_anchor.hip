@@ -16,7 +16,7 @@
 //     elements, so for such groups the result is the order by (front, back, key, push order): one device sort with that
 //     comparator.  A larger group that holds two DIFFERENT lists with equal (front, back) would expose introsort's
 //     unstable partitioning; such groups are counted (n_unstable_groups) and the caller re-does the stage on the host
-//     (none exists in any test input or synthetic panel; identical lists tie harmlessly).
+//     (no GFA input or synthetic panel has one -- tests/test_gpu_anchor_kernels.py builds them; identical lists tie harmlessly).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -192,13 +192,13 @@ __global__ void iota_kernel(uint32_t *p, int64_t n) {
 __device__ __forceinline__ uint64_t mix64(uint64_t k) {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33; return k;
 }
-__global__ void fingerprint_kernel(Occs O, Lists L, int64_t n, uint64_t *__restrict__ fp, uint32_t *__restrict__ idx) {
+__global__ void fingerprint_kernel(Occs O, Lists L, int64_t n, uint64_t fp_mask, uint64_t *__restrict__ fp, uint32_t *__restrict__ idx) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const uint32_t g = O.g[j], a = L.voff[g], b = L.voff[g + 1];
     uint64_t h = mix64((uint64_t)(b - a) + 0x9E3779B97F4A7C15ULL);
     for (uint32_t q = a; q < b; ++q) h = mix64(h ^ ((uint64_t)(uint32_t)L.v[q] + 0x9E3779B97F4A7C15ULL + (h << 6) + (h >> 2)));
-    fp[j] = h;
+    fp[j] = h & fp_mask;
     idx[j] = (uint32_t)j;
 }
 __global__ void gather_id_kernel(const uint32_t *__restrict__ order, const int32_t *__restrict__ oid, int64_t n, uint32_t *__restrict__ key) {
@@ -325,7 +325,7 @@ static int check_haplotype_args(dg_ctx *c, int32_t h, int64_t len, const int32_t
     if (!c->an) { set_error("dg_anchor_add_haplotype: dg_anchor_begin first"); return DG_ERR_STATE; }
     AnchorState &A = *c->an;
     if (h != A.next_h || h >= A.n_haps) { set_error("dg_anchor_add_haplotype: haplotypes must be added in order (got %d, expected %d)", h, A.next_h); return DG_ERR_ARG; }
-    if (!step_vtx || !step_start || n_steps < 0 || step_start[0] != 0 || (n_steps > 0 && step_start[n_steps] != len)) {
+    if (!step_vtx || !step_start || n_steps < 0 || step_start[0] != 0 || step_start[n_steps] != len) {   // (zero steps: length zero, solver.cpp:598)
         set_error("dg_anchor_add_haplotype: step_start must run from 0 to the haplotype length"); return DG_ERR_ARG;
     }
     for (int64_t q = 0; q < n_steps; ++q)
@@ -405,6 +405,15 @@ extern "C" int dg_anchor_finish(dg_ctx *c, const uint64_t *sp_hash, int64_t n_sp
     memset(out, 0, sizeof *out);
     hipStream_t s = c->stream;
     const bool dbg = getenv("DG_DEBUG") != nullptr;
+    // DG_ANCHOR_FP_BITS (0..64, default 64): keep only that many low bits of every list fingerprint, so that a test can force
+    // the collisions that send the filter through its exact order
+    uint64_t fp_mask = ~0ULL;
+    if (const char *e = getenv("DG_ANCHOR_FP_BITS")) {
+        char *end = nullptr;
+        const long bits = strtol(e, &end, 10);
+        if (end == e || *end || bits < 0 || bits > 64) { set_error("dg_anchor_finish: DG_ANCHOR_FP_BITS must be 0..64 (got \"%s\")", e); return DG_ERR_ARG; }
+        fp_mask = bits == 64 ? ~0ULL : ((1ULL << bits) - 1);
+    }
     struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
     double tl = ts0.tv_sec + 1e-9 * ts0.tv_nsec;
     auto lap = [&](const char *what) {
@@ -482,7 +491,7 @@ extern "C" int dg_anchor_finish(dg_ctx *c, const uint64_t *sp_hash, int64_t n_sp
     if (int rc = d_key2.ensure(4 * (size_t)n_occ)) return rc;
     if (int rc = d_coll.ensure(8)) return rc;
     DG_HIP(hipMemsetAsync(d_coll.p, 0, 8, s));
-    hipLaunchKernelGGL(fingerprint_kernel, dim3(blocks(n_occ)), dim3(256), 0, s, O, L, (int64_t)n_occ, d_fp.as<uint64_t>(), d_idx.as<uint32_t>());
+    hipLaunchKernelGGL(fingerprint_kernel, dim3(blocks(n_occ)), dim3(256), 0, s, O, L, (int64_t)n_occ, fp_mask, d_fp.as<uint64_t>(), d_idx.as<uint32_t>());
     if (int rc = radix_pairs<uint64_t>(d_tmp, d_fp.as<uint64_t>(), d_fp2.as<uint64_t>(), d_idx.as<uint32_t>(), d_ord.as<uint32_t>(), n_occ, 64, s)) return rc;
     hipLaunchKernelGGL(gather_id_kernel, dim3(blocks(n_occ)), dim3(256), 0, s, d_ord.as<uint32_t>(), d_oid.as<int32_t>(), (int64_t)n_occ, d_key.as<uint32_t>());
     int id_bits = 1;
@@ -495,7 +504,8 @@ extern "C" int dg_anchor_finish(dg_ctx *c, const uint64_t *sp_hash, int64_t n_sp
     unsigned long long collisions = 0;
     DG_HIP(hipMemcpyAsync(&collisions, d_coll.p, 8, hipMemcpyDeviceToHost, s));
     DG_HIP(hipStreamSynchronize(s));
-    if (collisions) {                   // exact order instead (never seen: 64-bit fingerprints of <= 10^8 lists)
+    if (dbg) fprintf(stderr, "[dipgenie_hip] anchors: %llu fingerprint collisions\n", collisions);
+    if (collisions) {                   // exact order instead (64-bit fingerprints of <= 10^8 lists: only DG_ANCHOR_FP_BITS gets here)
         hipLaunchKernelGGL(iota_kernel, dim3(blocks(n_occ)), dim3(256), 0, s, d_ord.as<uint32_t>(), (int64_t)n_occ);
         if (int rc = sort_indices(d_tmp, d_ord.as<uint32_t>(), d_idx.as<uint32_t>(), n_occ, CmpFilter{O, L}, s)) return rc;
         hipLaunchKernelGGL(exact_head_kernel, dim3(blocks(n_occ)), dim3(256), 0, s, filter_order, (int64_t)n_occ, O, L, d_head.as<uint32_t>());
@@ -510,6 +520,7 @@ extern "C" int dg_anchor_finish(dg_ctx *c, const uint64_t *sp_hash, int64_t n_sp
     uint32_t n_keep = 0;
     DG_HIP(hipMemcpyAsync(&n_keep, d_slot.as<uint32_t>() + n_occ, 4, hipMemcpyDeviceToHost, s));
     DG_HIP(hipStreamSynchronize(s));
+    out->n_candidates = n_occ;
     if (n_keep == 0) return DG_OK;
     if (int rc = d_kept.ensure(4 * (size_t)n_keep)) return rc;
     hipLaunchKernelGGL(keep_scatter_kernel, dim3(blocks(n_occ)), dim3(256), 0, s, d_head.as<uint32_t>(), d_slot.as<uint32_t>(), (int64_t)n_occ, d_kept.as<uint32_t>());

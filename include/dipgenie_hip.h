@@ -244,7 +244,8 @@ int       dg_shard_score_reads(dg_shard *, const char *bases, const int64_t *rea
 int dg_anchor_begin(dg_ctx *, int32_t n_haps, int32_t n_vertices, const int32_t *top_order_map /* [n_vertices], solver.cpp:174-199 */,
                     int k, int w);
 /* seq = the haplotype's bases (node_seq concatenated along paths[h], :283-288); step_vtx[n_steps] = paths[h];
- * step_start[n_steps + 1] = base offset of every step (step_start[n_steps] = len).  *n_minimizers = |index_kmers(h)|. */
+ * step_start[n_steps + 1] = base offset of every step (step_start[n_steps] = len, so a walk of zero steps has len = 0; anything
+ * else is DG_ERR_ARG).  *n_minimizers = |index_kmers(h)|. */
 int dg_anchor_add_haplotype(dg_ctx *, int32_t h, const char *seq, int64_t len, const int32_t *step_vtx, const int64_t *step_start,
                             int64_t n_steps, int64_t *n_minimizers);
 /* the same for a haplotype whose minimizer list (hash / pos = the output of dg_sketch_haplotype on its sequence, host memory) was
@@ -261,7 +262,9 @@ typedef struct dg_anchor_result {     /* Anchor_hits flattened: occurrence i = (
     int64_t n_unstable_groups;        /* (id, haplotype) groups of > 16 occurrences holding different vertex lists with equal (front,  */
 } dg_anchor_result;                   /* back): their order would depend on std::sort's unstable partitioning -- redo the stage on the host */
 /* sp_hash[n_sp] = sorted distinct read-minimizer hashes (Sp_R keys, the output of dg_sketch_reads); min_shared =
- * threshold * num_walks as float (:618).  Consumes the index built since dg_anchor_begin. */
+ * threshold * num_walks as float (:618).  Consumes the index built since dg_anchor_begin.  Environment, read at call time:
+ * DG_DEBUG (stage timings and counts on stderr), DG_ANCHOR_FP_BITS = 0..64 (tests: keep that many bits of the filter's list
+ * fingerprints, to force the collisions that take its exact order). */
 int dg_anchor_finish(dg_ctx *, const uint64_t *sp_hash, int64_t n_sp, float min_shared, dg_anchor_result *out);
 
 #ifdef __cplusplus

@@ -258,6 +258,70 @@ def e2e_kw(cases):
     return [name for name, _, _ in specs]
 
 
+def e2e_anchor_reach(cases):
+    """inputs for what the anchor stage can meet in a GFA but the bubble chains above never give it (appended to e2e.json; the
+    returned names get anchor goldens, whose dumps anchor_reach_check then holds to their purpose):
+    * anc_tiny_segs: 400 bubbles of 1..3-base backbone segments at k = 31 -- one k-mer lies over far more than 8 vertices, and the
+      1,200+ segment ids cross 9/10, 99/100 and 999/1000 (the decimal-string key order);
+    * anc_tandem: a 7-base unit as 45 consecutive two-allele segments (both alleles spell the unit) between random flanks, k = 9,
+      w = 4: one minimizer hash comes back at every unit, more than 16 times per haplotype, each time with another front vertex;
+      the walks keep every list below the filter (walks 0 and 1 share no allele, 2 and 3 alternate);
+    * anc_thresholds: one 4-walk graph at -T0.5 (threshold * num_walks = 2.0 exactly) and -T0.26 (1.04f)."""
+    ed = os.path.join(HERE, "e2e")
+    def put(name, segs, links, walks, rd):
+        gfa, reads = os.path.join(ed, name + ".gfa"), os.path.join(ed, name + ".fa")
+        if not os.path.exists(gfa):
+            synth.write_gfa(gfa, segs, links, walks)
+            synth.write_fasta(reads, rd)
+        return gfa, reads
+    def tandem():
+        rng = np.random.default_rng(77)
+        rnd = lambda n: bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n).tobytes())
+        unit = b"ACGGTCA"
+        segs, layers = [rnd(40)], [[0]]
+        for _ in range(45):
+            layers.append([len(segs), len(segs) + 1])
+            segs += [unit, unit]
+        layers.append([len(segs)])
+        segs.append(rnd(40))
+        links = [(a, b) for x, y in zip(layers[:-1], layers[1:]) for a in x for b in y]
+        pick = [lambda q: 0, lambda q: 1, lambda q: q % 2, lambda q: (q + 1) % 2]
+        walks = [("hap%d" % h, h, [layer[pick[h](q) % len(layer)] for q, layer in enumerate(layers)]) for h in range(4)]
+        haps = [b"".join(segs[v] for v in walks[h][2]) for h in (0, 1)]
+        return segs, links, walks, synth.simulate_reads(rng, haps, 50, 80, 0.0)
+    specs = [
+        ("anc_tiny_segs", "anc_tiny_segs", lambda: synth.random_bubble_graph(seed=131, n_bubbles=400, n_haps=4, seg_len=(1, 3), coverage=4.0, read_len=100),
+         ["-p2", "-R4", "-k31", "-w5"]),
+        ("anc_tandem", "anc_tandem", tandem, ["-p2", "-R2", "-k9", "-w4"]),
+        ("anc_thresholds_T0.5", "anc_thresholds", lambda: synth.random_bubble_graph(seed=132, n_bubbles=20, n_haps=4, coverage=8.0), ["-p2", "-R3", "-k11", "-w5", "-T0.5"]),
+        ("anc_thresholds_T0.26", "anc_thresholds", lambda: synth.random_bubble_graph(seed=132, n_bubbles=20, n_haps=4, coverage=8.0), ["-p2", "-R3", "-k11", "-w5", "-T0.26"]),
+    ]
+    for name, base, make, args in specs:
+        gfa, reads = put(base, *make()) if not os.path.exists(os.path.join(ed, base + ".gfa")) else (os.path.join(ed, base + ".gfa"), os.path.join(ed, base + ".fa"))
+        assert sum(1 for l in open(gfa) if l.startswith("S\t")) >= 1200 or name != "anc_tiny_segs"
+        cases[name] = dict(gfa=f"tests/golden/e2e/{base}.gfa", reads=f"tests/golden/e2e/{base}.fa", **run_ref(gfa, reads, args))
+        print(name, cases[name].get("dp_value"), cases[name].get("r1"), cases[name].get("r2"), cases[name]["fasta_md5"], flush=True)
+    return [name for name, _, _, _ in specs]
+
+
+def anchor_reach_check(cases, anch):
+    """the e2e_anchor_reach inputs must have met their purpose in the reference's own Anchor_hits (re-dumped in full here)"""
+    full = anchors({n: cases[n] for n in ("anc_tiny_segs", "anc_tandem")}, max_dump=1 << 40)
+    occ = lambda n: [l.split() for l in full[n]["dump"] if not l.startswith("homo")]
+    longest = max(len(o[2].split(",")) for o in occ("anc_tiny_segs"))
+    assert longest > 8, f"anc_tiny_segs: no list above 8 vertices (longest {longest})"
+    groups = {}
+    for o in occ("anc_tandem"):
+        groups[(o[0], o[1])] = groups.get((o[0], o[1]), 0) + 1
+    assert max(groups.values()) > 16, f"anc_tandem: largest (id, haplotype) group is {max(groups.values())}"
+    # -T0.5 and -T0.26 give 2.0 and 1.04f with 4 walks: an integer count reaches either exactly from 2 on, so the two runs must
+    # AGREE (a '>' in place of '>=' at 2.0, or a bound rounded down to 1, would part them); both must drop ids that -T1.0 keeps
+    a, b = anch["anc_thresholds_T0.5"], anch["anc_thresholds_T0.26"]
+    base = anchors({"t1": dict(cases["anc_thresholds_T0.5"], args=[x for x in cases["anc_thresholds_T0.5"]["args"] if not x.startswith("-T")])}, max_dump=0)["t1"]
+    assert a["sha256"] == b["sha256"] and a["n_ids"] < base["n_ids"], (a["n_ids"], b["n_ids"], base["n_ids"])
+    print("anchor reach: longest list", longest, "largest group", max(groups.values()), "ids at T0.5 / T0.26 / T1.0", a["n_ids"], b["n_ids"], base["n_ids"], flush=True)
+
+
 def anchors(cases, max_dump=65536):
     """Anchor_hits + homo_bv of the REAL reference (ref_harness anchors = Solver::read_gfa + read_ip_reads +
     compute_and_classify_anchors, solver.cpp:27-245, 449-887) for every e2e case with inputs on disk: the text dump
@@ -385,6 +449,14 @@ if __name__ == "__main__":
         json.dump(cases, open(os.path.join(HERE, "e2e.json"), "w"), indent=1)
         anch = json.load(open(os.path.join(HERE, "anchors.json")))
         anch.update(anchors({n: cases[n] for n in names}, max_dump=0))   # (counts + sha256, no verbatim dump)
+        json.dump(anch, open(os.path.join(HERE, "anchors.json"), "w"), indent=0)
+    if "anc" in what:                                             # adds the anchor-reach cases to e2e.json and their anchors to anchors.json
+        cases = json.load(open(os.path.join(HERE, "e2e.json")))
+        names = e2e_anchor_reach(cases)
+        anch = json.load(open(os.path.join(HERE, "anchors.json")))
+        anch.update(anchors({n: cases[n] for n in names}))
+        anchor_reach_check(cases, anch)
+        json.dump(cases, open(os.path.join(HERE, "e2e.json"), "w"), indent=1)
         json.dump(anch, open(os.path.join(HERE, "anchors.json"), "w"), indent=0)
     if "anchors" in what:
         json.dump(anchors(json.load(open(os.path.join(HERE, "e2e.json")))), open(os.path.join(HERE, "anchors.json"), "w"), indent=0)
