@@ -48,6 +48,10 @@ class DpTiming(C.Structure):
     ]
 
 
+# dg_dp_pair_score as a numpy record: what Context.dp_score_paths returns
+PAIR_SCORE = np.dtype([("value", np.int32), ("s_het", np.int32), ("r1", np.int32), ("r2", np.int32)])
+
+
 class SketchTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("sort_ms", C.c_float), ("total_ms", C.c_float), ("n_emitted", C.c_int64)]
 
@@ -62,7 +66,7 @@ SYMBOLS = [
     "dg_anchor_begin", "dg_anchor_add_haplotype", "dg_anchor_finish", "dg_dp_solve_haploid", "dg_dp_get_table_digest", "dg_hip_versions", "dg_anchor_add_haplotype_sketched",
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
-    "dg_dp_run_budgets", "dg_dp_get_budget_values",
+    "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -78,6 +82,7 @@ lib.dg_dp_load_graph.argtypes = [C.c_void_p, C.POINTER(DpGraph)]
 lib.dg_dp_run.argtypes = [C.c_void_p, C.POINTER(DpResult)]
 lib.dg_dp_run_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DpResult)]
 lib.dg_dp_get_budget_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+lib.dg_dp_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -282,6 +287,18 @@ class Context:
         """the sink's value on planes 0..R of the last dp_run / dp_run_budgets (int32[R + 1], NEG_INF where unreachable)"""
         out = np.zeros(self._g.R + 1, np.int32)
         _check(lib.dg_dp_get_budget_values(self.h, out.ctypes.data, out.size), "dg_dp_get_budget_values")
+        return out
+
+    def dp_score_paths(self, paths):
+        """paths: int32 [n, 2, n_levels], the vertex id of both paths of n pairs at every level of the loaded graph (source first,
+        sink last).  Returns a PAIR_SCORE record array of n entries (fields value, s_het, r1, r2); a vertex outside its level or a
+        hop without an edge raises DgError naming the first offending pair, path and level.  Leaves the last run's answers alone."""
+        p = np.ascontiguousarray(paths, np.int32)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+            raise ValueError(f"paths must have shape [n, 2, n_levels], got {p.shape}")
+        out = np.zeros(p.shape[0], PAIR_SCORE)
+        _check(lib.dg_dp_score_paths(self.h, p.ctypes.data if p.size else None, p.shape[0], out.ctypes.data if out.size else None), "dg_dp_score_paths")
         return out
 
     def dp_solve(self, g):

@@ -1,5 +1,5 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
-// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip).
+// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -215,6 +215,9 @@ struct DpState {
     std::vector<BudgetSlot> tab_host;          // host copy of d_ch_tab (the run at hand)
     int n_groups = 0;                          // walker groups of the run at hand (chains of neighbouring budgets share an XCD and its helpers)
     mutable int walk_seq = 0;                  // per-launch number of the chain walk (ChainSync; counted from 0 in every run)
+    // ---- dg_dp_score_paths (dg_dp_score.hip): staging of one slab of caller paths, its result words, the first-bad-hop word ----
+    int64_t score_slab_bytes = (int64_t)256 << 20;   // score_slab_bytes: bound of the path staging buffer (a slab holds at least one pair)
+    DevBuf d_sc_paths, d_sc_out, d_sc_err;
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -272,5 +275,8 @@ void budgets_launch_sink_copy(const DpState &S, const int32_t *sink_state, hipSt
 int budgets_reserve(DpState &S, int n);                                                      // buffers of n chains (grow-only)
 int budgets_prepare(DpState &S, const int32_t *budgets, int n, hipStream_t s);                // buffers of n chains + walker placement
 void budgets_launch_finish(const DpState &S, int n, hipStream_t s);                           // the finish kernel once per chain
+
+// ---- caller-supplied pairs of paths scored on the resident graph (dg_dp_score.hip) ----
+int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out);
 
 }  // namespace dgi

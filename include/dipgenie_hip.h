@@ -105,6 +105,25 @@ int dg_dp_run_budgets(dg_ctx *, const int32_t *budgets, int32_t n_budgets, dg_dp
 /* the sink's value on planes 0..R (NEG_INF where unreachable) of the last dg_dp_run / dg_dp_run_budgets on the loaded graph;
  * out has n >= R + 1 entries */
 int dg_dp_get_budget_values(dg_ctx *, int32_t *out, int32_t n);
+/* What a pair of source -> sink paths is worth on the loaded graph (the question the sweep answers with a maximum: plane r of the
+ * sink is the best `value` over all pairs with r1 + r2 <= r).  For the transition into level l the ordered pair (path 1, path 2)
+ * contributes what the sweep adds to cell (i, j) for the in-edge pair (p1[l-1] -> p1[l], p2[l-1] -> p2[l]): |(Hom u Hom) n (Hom u Hom)|
+ * + |(Het u Het) /\ (Het u Het)| of the two sources' against the two destinations' colour lists (approximator.cpp:604-624); a
+ * transition without colours contributes 0.  Parallel edges between the same two vertices carry equal weights (checked at load) and
+ * are one edge to the score. */
+typedef struct dg_dp_pair_score {
+    int32_t value;                    /* sum of the transitions' score deltas, as the sweep adds them */
+    int32_t s_het;                    /* sum of their Het terms (approximator.cpp:662): dg_dp_result::s_het of a walked pair */
+    int32_t r1, r2;                   /* weight-1 edges on path 1 / path 2; no budget applies, the caller compares r1 + r2 with one */
+} dg_dp_pair_score;
+/* paths (host) = [n_pairs][2][n_levels] vertex ids, one per level of the loaded graph: entry 0 the source, the last one the sink;
+ * out (host) has n_pairs entries.  Needs dg_dp_load_graph only, and leaves the answers of an earlier run (dg_dp_get_budget_values,
+ * dg_dp_get_level_digest, dg_dp_get_timing) as they were.  Validation and scoring run on the device, one lane per transition, the
+ * paths going up in slabs of at most 256 MB (option score_slab_bytes).  DG_ERR_STATE: no graph loaded.  DG_ERR_ARG: a null
+ * argument, n_pairs < 0, or a vertex that is not in its level / two consecutive vertices that no edge joins -- the message names
+ * the first such (pair, path 0|1, level), in that order of significance (the level of a missing edge is its destination's), and
+ * out is not written.  n_pairs = 0 is DG_OK.  Synchronises. */
+int dg_dp_score_paths(dg_ctx *, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out);
 /* debug/parity: copy the per-level digest (same definition as the oracle's level_digest) of the
  * last run; out has n_levels entries, entry 0 unused. Requires dg_dp_set_option("digest",1). */
 int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
@@ -123,6 +142,7 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   sync_every n          drain the stream every n level launches (rocprofv3 --pmc)
  *   side_stream -1|0|1    L2 prefetcher + score deltas beside the sweep: -1 (default) while this is the only DP state on its device, 0 never, 1 always
  *   test_poison_level l, test_poison_byte b   tests: fill level l of the back-pointer lattice with byte b between sweep and walk (dg_dp_run must answer DG_ERR_STATE)
+ *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning */
 int dg_dp_set_option(dg_ctx *, const char *key, int64_t value);
