@@ -51,6 +51,9 @@ class DpTiming(C.Structure):
 # dg_dp_pair_score as a numpy record: what Context.dp_score_paths returns
 PAIR_SCORE = np.dtype([("value", np.int32), ("s_het", np.int32), ("r1", np.int32), ("r2", np.int32)])
 
+# dg_dp_partner as a numpy record: what Context.dp_best_partners returns
+PARTNER = np.dtype([("value", np.int32), ("s_het", np.int32), ("r1", np.int32), ("r2", np.int32)])
+
 
 class SketchTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("sort_ms", C.c_float), ("total_ms", C.c_float), ("n_emitted", C.c_int64)]
@@ -66,7 +69,7 @@ SYMBOLS = [
     "dg_anchor_begin", "dg_anchor_add_haplotype", "dg_anchor_finish", "dg_dp_solve_haploid", "dg_dp_get_table_digest", "dg_hip_versions", "dg_anchor_add_haplotype_sketched",
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
-    "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths",
+    "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -83,6 +86,7 @@ lib.dg_dp_run.argtypes = [C.c_void_p, C.POINTER(DpResult)]
 lib.dg_dp_run_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DpResult)]
 lib.dg_dp_get_budget_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 lib.dg_dp_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+lib.dg_dp_best_partners.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -300,6 +304,24 @@ class Context:
         out = np.zeros(p.shape[0], PAIR_SCORE)
         _check(lib.dg_dp_score_paths(self.h, p.ctypes.data if p.size else None, p.shape[0], out.ctypes.data if out.size else None), "dg_dp_score_paths")
         return out
+
+    def dp_best_partners(self, given, budgets, want_paths=True):
+        """given: int32 [n, n_levels], one source -> sink path of the loaded graph per query; budgets: int [n], each >= 0.  Returns
+        (records, partners): a PARTNER record array of n entries (value, s_het, r1, r2) and the best partner of every given path
+        within its budget, int32 [n, n_levels] (None with want_paths=False).  value = NEG_INF: no path fits the budget, the row is
+        all -1.  A bad given path raises DgError naming the first (query, level).  Leaves the last run's answers alone."""
+        p = np.ascontiguousarray(given, np.int32)
+        b = np.ascontiguousarray(budgets, np.int32)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 2 or (g is not None and p.shape[1] != g.n_levels):
+            raise ValueError(f"given must have shape [n, n_levels], got {p.shape}")
+        if b.shape != (p.shape[0],):
+            raise ValueError(f"budgets must have shape [{p.shape[0]}], got {b.shape}")
+        out = np.zeros(p.shape[0], PARTNER)
+        partners = np.zeros(p.shape, np.int32) if want_paths else None
+        _check(lib.dg_dp_best_partners(self.h, p.ctypes.data if p.size else None, p.shape[0], b.ctypes.data if b.size else None,
+                                       partners.ctypes.data if want_paths and partners.size else None, out.ctypes.data if out.size else None), "dg_dp_best_partners")
+        return out, partners
 
     def dp_solve(self, g):
         self.dp_load_graph(g)

@@ -1,5 +1,5 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
-// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip).
+// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -218,6 +218,10 @@ struct DpState {
     // ---- dg_dp_score_paths (dg_dp_score.hip): staging of one slab of caller paths, its result words, the first-bad-hop word ----
     int64_t score_slab_bytes = (int64_t)256 << 20;   // score_slab_bytes: bound of the path staging buffer (a slab holds at least one pair)
     DevBuf d_sc_paths, d_sc_out, d_sc_err;
+    // ---- dg_dp_best_partners (dg_dp_partner.hip): one slab of queries -- (given, partner) pairs, budgets, sink cells, the re-scoring
+    // pass's records, the two first-bad-hop words; back-pointers and edge scores (released when the call returns) ----
+    int64_t partner_slab_bytes = (int64_t)4 << 30;   // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab (a slab holds at least one query)
+    DevBuf d_pt_pairs, d_pt_bud, d_pt_val, d_pt_out, d_pt_err, d_pt_bp, d_pt_scores;
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -278,5 +282,11 @@ void budgets_launch_finish(const DpState &S, int n, hipStream_t s);             
 
 // ---- caller-supplied pairs of paths scored on the resident graph (dg_dp_score.hip) ----
 int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out);
+int score_pair_blocks(const DpState &S);                                                     // workgroups per pair of the scoring kernel
+// the scoring kernel on n pairs [n][2][L] resident on the device; out (4 words per pair) zeroed and *err all ones beforehand
+void score_launch_pairs(const DpState &S, const int32_t *pairs, int64_t n, int32_t *out, unsigned long long *err, hipStream_t s);
+
+// ---- the best partner of a given path: the DP with one haplotype fixed (dg_dp_partner.hip) ----
+int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out);
 
 }  // namespace dgi

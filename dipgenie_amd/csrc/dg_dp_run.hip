@@ -494,7 +494,7 @@ extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
     return DG_OK;
 }
 // Options: parity / test knobs (digest, fast, adaptive_rc, coop, rowx, lean_chain, segment_cells, delta_cap_entries, lattice_chunk_cells,
-// graph_batch, warm_ahead, score_slab_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
+// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
 extern "C" int dg_dp_set_option(dg_ctx *c, const char *key, int64_t v) {
     if (!c || !key) { dgi::set_error("dg_dp_set_option: null"); return DG_ERR_ARG; }
     if (!c->dp) c->dp = new dgi::DpState(c->device);
@@ -514,6 +514,7 @@ extern "C" int dg_dp_set_option(dg_ctx *c, const char *key, int64_t v) {
     else if (!strcmp(key, "rc_cap")) S.rc_cap = v > 0 ? v : 65536;
     else if (!strcmp(key, "max_blocks")) S.max_blocks = v > 0 ? v : 1024;
     else if (!strcmp(key, "score_slab_bytes")) S.score_slab_bytes = v > 0 ? v : (int64_t)256 << 20;   // staging bound of dg_dp_score_paths (a slab holds at least one pair)
+    else if (!strcmp(key, "partner_slab_bytes")) S.partner_slab_bytes = v > 0 ? v : (int64_t)4 << 30;   // device memory of one slab of dg_dp_best_partners (a slab holds at least one query)
     else if (!strcmp(key, "lattice_chunk_cells")) {          // size of one lattice chunk (in 16-bit back-pointer units = cells on ordinary levels; default 2^32 = 8 GB)
         if (v < 1) { dgi::set_error("lattice_chunk_cells must be positive"); return DG_ERR_ARG; }
         dgi::pool_clear(S);

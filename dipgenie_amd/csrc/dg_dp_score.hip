@@ -29,20 +29,6 @@ __device__ __forceinline__ unsigned long long score_err_key(int64_t pair, int pa
     return ((unsigned long long)pair << 33) | ((unsigned long long)path << 32) | ((unsigned long long)(uint32_t)level << 1) | (unsigned long long)kind;
 }
 
-// weight of an edge (source position `pos` of the previous level) -> dst, -1 if there is none; dst is a checked vertex id
-__device__ __forceinline__ int score_edge_weight(const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge, int dst, uint32_t pos) {
-    uint32_t lo = in_off[dst];
-    const uint32_t end = in_off[dst + 1];
-    uint32_t hi = end;
-    while (lo < hi) {                                               // first in-edge whose source position is >= pos
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((in_edge[mid] & 0x7FFFFFFFu) < pos) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= end) return -1;
-    const uint32_t w = in_edge[lo];
-    return (w & 0x7FFFFFFFu) == pos ? (int)(w >> 31) : -1;
-}
-
 // grid: n_pairs * nblk workgroups of 64 or 256 lanes; out (4 words per pair: value, s_het, r1, r2) and *err are set by the host before the launch
 __global__ __launch_bounds__(SCORE_BLOCK) void dp_score_paths_kernel(const LevelDesc *__restrict__ descs, int L, int nblk,
                                                                      const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge, ColourCsr col,
@@ -90,7 +76,17 @@ __global__ __launch_bounds__(SCORE_BLOCK) void dp_score_paths_kernel(const Level
     }
 }
 
+inline int score_threads(int L) { return L - 1 <= 64 ? 64 : SCORE_BLOCK; }
+
 }  // namespace
+
+int score_pair_blocks(const DpState &S) { return (S.L - 1 + score_threads(S.L) - 1) / score_threads(S.L); }
+
+void score_launch_pairs(const DpState &S, const int32_t *pairs, int64_t n, int32_t *out, unsigned long long *err, hipStream_t s) {
+    const int nblk = score_pair_blocks(S);
+    hipLaunchKernelGGL(dp_score_paths_kernel, dim3((unsigned)(n * nblk)), dim3((unsigned)score_threads(S.L)), 0, s, S.d_descs.as<LevelDesc>(), S.L, nblk,
+                       S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), colour_csr(S), pairs, out, err);
+}
 
 int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out) {
     DpState *Sp = c->dp;
@@ -101,8 +97,7 @@ int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_
     DpState &S = *Sp;
     hipStream_t s = c->stream;
     const int L = S.L;
-    const int threads = L - 1 <= 64 ? 64 : SCORE_BLOCK;
-    const int nblk = (L - 1 + threads - 1) / threads;
+    const int nblk = score_pair_blocks(S);
     const int64_t pair_words = 2 * (int64_t)L;
     // pairs per slab: what the staging bound holds (at least one), a grid of at most 2^30 workgroups, a pair index of 31 bits
     int64_t per_slab = std::max<int64_t>(1, S.score_slab_bytes / (4 * pair_words));
@@ -120,9 +115,7 @@ int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_
         DG_HIP(hipMemcpyAsync(S.d_sc_paths.p, src, (size_t)(n * pair_words) * 4, hipMemcpyHostToDevice, s));
         DG_HIP(hipMemsetAsync(S.d_sc_out.p, 0, (size_t)n * sizeof(dg_dp_pair_score), s));
         DG_HIP(hipMemsetAsync(S.d_sc_err.p, 0xFF, sizeof err, s));
-        hipLaunchKernelGGL(dp_score_paths_kernel, dim3((unsigned)(n * nblk)), dim3((unsigned)threads), 0, s, S.d_descs.as<LevelDesc>(), L, nblk,
-                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), colour_csr(S), S.d_sc_paths.as<int32_t>(), S.d_sc_out.as<int32_t>(),
-                           S.d_sc_err.as<unsigned long long>());
+        score_launch_pairs(S, S.d_sc_paths.as<int32_t>(), n, S.d_sc_out.as<int32_t>(), S.d_sc_err.as<unsigned long long>(), s);
         DG_HIP(hipGetLastError());
         DG_HIP(hipMemcpyAsync(res.data() + first, S.d_sc_out.p, (size_t)n * sizeof(dg_dp_pair_score), hipMemcpyDeviceToHost, s));
         DG_HIP(hipMemcpyAsync(&err, S.d_sc_err.p, sizeof err, hipMemcpyDeviceToHost, s));

@@ -39,4 +39,18 @@ __device__ __forceinline__ int score_symd(const ColourCsr &c, int u1, int v1, in
                           c.het_col + d, (int)(c.het_off[u2 + 1] - d), c.het_col + e, (int)(c.het_off[v2 + 1] - e));
 }
 
+// weight of an edge (source position `pos` of the previous level) -> dst, -1 if there is none; dst is a checked vertex id
+__device__ __forceinline__ int score_edge_weight(const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge, int dst, uint32_t pos) {
+    uint32_t lo = in_off[dst];
+    const uint32_t end = in_off[dst + 1];
+    uint32_t hi = end;
+    while (lo < hi) {                                               // first in-edge whose source position is >= pos
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((in_edge[mid] & 0x7FFFFFFFu) < pos) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= end) return -1;
+    const uint32_t w = in_edge[lo];
+    return (w & 0x7FFFFFFFu) == pos ? (int)(w >> 31) : -1;
+}
+
 }  // namespace dgi

@@ -124,6 +124,30 @@ typedef struct dg_dp_pair_score {
  * the first such (pair, path 0|1, level), in that order of significance (the level of a missing edge is its destination's), and
  * out is not written.  n_pairs = 0 is DG_OK.  Synchronises. */
 int dg_dp_score_paths(dg_ctx *, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out);
+/* The best partner of a path that is already known: the DP with one haplotype fixed.  `given` is a source -> sink path, one vertex
+ * per level; with it fixed, the in-edge (u -> v, w) into level l is worth what dg_dp_score_paths adds there for the ordered pair
+ * (given, partner): inter + symd of the sources (given[l-1], u) against the destinations (given[l], v); parallel edges are one edge.
+ * S_0[source][r] = 0 for r = 0..budget ("at most", as in the sweep); S_l[v][r] = max over the in-edges of v with r - w >= 0 and a
+ * reachable source cell of S_{l-1}[u][r - w] + that score, the smallest source position winning among equals; NEG_INF = INT32_MIN / 4
+ * where nothing arrives.  The answer is the sink's cell on plane `budget` and the path its winners lead back along. */
+typedef struct dg_dp_partner {
+    int32_t value;                    /* S[sink][budget]; NEG_INF: no path fits the budget (not an error: s_het = r2 = 0, the partner row is all -1) */
+    int32_t s_het;                    /* sum of the symd terms of (given, partner) */
+    int32_t r1, r2;                   /* weight-1 edges on the given path / on the partner (r2 <= budget) */
+} dg_dp_partner;
+/* given (host) = [n][n_levels] vertex ids; budgets (host) = [n], each >= 0 (independent of the graph's R); partners (host) =
+ * [n][n_levels], may be NULL (values only); out (host) = [n].  Needs dg_dp_load_graph only and leaves the answers of an earlier run
+ * (dg_dp_get_budget_values, dg_dp_get_level_digest, dg_dp_get_timing) as they were.  One workgroup per query keeps the
+ * widest level x (budget + 1) cells of state in LDS and streams one 16-bit back-pointer per cell; every answered query is then
+ * re-scored as the pair (given, partner) by the kernel of dg_dp_score_paths, which yields s_het, r1 and r2 and must reproduce
+ * `value` with r2 <= budget (DG_ERR_STATE naming the query otherwise).  Queries go up in slabs, in order; option partner_slab_bytes
+ * bounds the device memory of a slab, every query counting 2 * n_vertices * (bmax + 1) + 2 * n_edges + 8 * n_levels bytes, bmax the
+ * largest budget of the call.  DG_ERR_STATE: no graph loaded.  DG_ERR_ARG: a null given, budgets or out, n < 0, a negative budget
+ * (the message names the query), a given path with a vertex outside its level or a hop without an edge (the message names the first
+ * such (query, level), in that order of significance; the level of a missing edge is its destination's).  DG_ERR_UNSUPPORTED: widest
+ * level x (budget + 1) > 16384 cells for some query (the message names both numbers).  A failed call writes neither partners nor out.
+ * n = 0 is DG_OK.  Synchronises. */
+int dg_dp_best_partners(dg_ctx *, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out);
 /* debug/parity: copy the per-level digest (same definition as the oracle's level_digest) of the
  * last run; out has n_levels entries, entry 0 unused. Requires dg_dp_set_option("digest",1). */
 int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
@@ -143,6 +167,7 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   side_stream -1|0|1    L2 prefetcher + score deltas beside the sweep: -1 (default) while this is the only DP state on its device, 0 never, 1 always
  *   test_poison_level l, test_poison_byte b   tests: fill level l of the back-pointer lattice with byte b between sweep and walk (dg_dp_run must answer DG_ERR_STATE)
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
+ *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning */
 int dg_dp_set_option(dg_ctx *, const char *key, int64_t value);
