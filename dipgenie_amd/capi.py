@@ -1,4 +1,5 @@
 """ctypes bindings of include/dipgenie_hip.h (libdipgenie_hip.so).  No fallbacks, no oracle imports."""
+import contextlib
 import ctypes as C
 import os
 import struct
@@ -70,6 +71,7 @@ SYMBOLS = [
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners",
+    "dg_dp_get_option", "dg_sketch_get_option",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -91,6 +93,7 @@ lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 lib.dg_dp_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+lib.dg_dp_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
 lib.dg_dp_get_launch_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
 lib.dg_dp_get_table_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_sketch_reads.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
@@ -111,6 +114,7 @@ lib.dg_sketch_rank_dictionary_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64,
 lib.dg_sketch_histogram_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
 lib.dg_sketch_count_rank_dictionary_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
 lib.dg_sketch_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+lib.dg_sketch_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
 lib.dg_sketch_get_stat.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
 
 
@@ -227,6 +231,20 @@ def outcome_from(res, bufs):
     return DpOutcome(res, p1, p2)
 
 
+@contextlib.contextmanager
+def _options(get, set_, kv):
+    saved = []
+    try:
+        for key, value in kv.items():
+            old = get(key)
+            set_(key, value)
+            saved.append((key, old))
+        yield
+    finally:
+        for key, old in reversed(saved):
+            set_(key, old)
+
+
 class Context:
     """One dg_ctx (one HIP device + stream)."""
 
@@ -258,6 +276,15 @@ class Context:
     # ---- DP ----
     def dp_set_option(self, key, value):
         _check(lib.dg_dp_set_option(self.h, key.encode(), int(value)), "dg_dp_set_option")
+
+    def dp_get_option(self, key):
+        v = C.c_int64(0)
+        _check(lib.dg_dp_get_option(self.h, key.encode(), C.byref(v)), "dg_dp_get_option")
+        return v.value
+
+    def dp_options(self, **kv):
+        """with ctx.dp_options(fast=0, ...): the given DP options for the body, then the values they had before"""
+        return _options(self.dp_get_option, self.dp_set_option, kv)
 
     def dp_prealloc(self, nbytes=0):
         """start reserving back-pointer lattice chunks in the background (nbytes <= 0: 60 % of the free HBM)"""
@@ -445,6 +472,15 @@ class Context:
 
     def sketch_set_option(self, name, value):
         _check(lib.dg_sketch_set_option(self.h, name.encode(), int(value)), "dg_sketch_set_option")
+
+    def sketch_get_option(self, name):
+        v = C.c_int64(0)
+        _check(lib.dg_sketch_get_option(self.h, name.encode(), C.byref(v)), "dg_sketch_get_option")
+        return v.value
+
+    def sketch_options(self, **kv):
+        """with ctx.sketch_options(spectrum_mode=1, ...): the given sketch options for the body, then the values they had before"""
+        return _options(self.sketch_get_option, self.sketch_set_option, kv)
 
     def sketch_stat(self, name):
         v = C.c_int64(0)

@@ -112,19 +112,10 @@ struct FastArgs {                                       // fast sweep kernel
 // sit in front of the other's sweep.  States on other devices do not matter.
 inline std::atomic<int> &dp_states_on_device(int device) { static std::atomic<int> n[64]; return n[device & 63]; }
 
-struct DpState {
-    explicit DpState(int dev) : device(dev) { ++dp_states_on_device(device); }
-    ~DpState() { --dp_states_on_device(device); }
-    const int device;
+// Every option of dg_dp_set_option / dg_dp_get_option (key table: dg_dp_run.hip).  These initialisers are the defaults, written nowhere else.
+struct DpOptions {
     int64_t side_stream = -1;                           // side_stream: -1 = on while this is the device's only DP state (and the concurrency probe agrees), 0 = off, 1 = on
-    bool side_stream_ok() const { return side_stream < 0 ? dp_states_on_device(device).load() <= 1 : side_stream != 0; }
-    DpState(const DpState &) = delete;
-    DpState &operator=(const DpState &) = delete;
-    int32_t nV = 0, L = 0, R = 0, RP = 0, cap = 0;
-    int32_t rp_active = 0;                              // planes [0, rp_active) are swept by the fast kernels (= RP except while a segment is re-swept below its path's plane)
     int64_t plane_limit = 1;                            // plane_limit: beyond HBM, re-sweep every segment only up to the plane its path leaves it on (0: all planes)
-    bool loaded = false;
-    // ---- options (dg_dp_set_option) ----
     int64_t want_digest = 0;                            // digest: accumulate per-level digests (values + back-pointers)
     int64_t use_fast = 1;                               // fast: 0 forces the generic kernel
     int64_t adaptive_rc = 1;                            // adaptive_rc: 0 = one chunk of all recombination counts per task
@@ -140,22 +131,37 @@ struct DpState {
     int64_t sync_every = 0;                             // sync_every: drain the stream every N level launches (profiler aid)
     int64_t l2_prefetch = 6;                            // l2_prefetch: levels the per-XCD table prefetcher runs ahead of the sweep (0: off)
     int64_t use_lean_chain = 1;                         // lean_chain: 1 the lean walk where the lattice allows it, 0 always the general one; next load
+    int64_t delta_overlap = 1;                          // delta_overlap: 0 = the whole window before the sweep
+    int64_t pf_far = 128;                               // pf_far: > 0 = prefetcher blocks also pull the tables pf_far levels ahead into the Infinity Cache (then no periodic look-ahead launches)
+    int64_t use_rowx = 1;                               // rowx: row in-edge matrices (0: every fan-in row fetches its list from in_edge[])
+    int64_t delta_cap_entries = (int64_t)4 << 30;       // delta_cap_entries: budget of resident score-delta entries
+    int64_t rc_cap = 65536, rc_t0_ns = 3000, rc_tg_ps = 20000, rc_tw_ps = 50;   // rc_*: cost model of the per-level RC choice
+    int64_t chunk_units_cfg = (int64_t)4 << 30;         // lattice_chunk_cells: size of one lattice chunk (16-bit units, even: 8 GB)
+    int64_t score_slab_bytes = (int64_t)256 << 20;      // score_slab_bytes: bound of the path staging buffer of dg_dp_score_paths (a slab holds at least one pair)
+    int64_t partner_slab_bytes = (int64_t)4 << 30;      // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners (a slab holds at least one query)
+};
+
+struct DpState {
+    explicit DpState(int dev) : device(dev) { ++dp_states_on_device(device); }
+    ~DpState() { --dp_states_on_device(device); }
+    const int device;
+    DpOptions opt;
+    bool side_stream_ok() const { return opt.side_stream < 0 ? dp_states_on_device(device).load() <= 1 : opt.side_stream != 0; }
+    DpState(const DpState &) = delete;
+    DpState &operator=(const DpState &) = delete;
+    int32_t nV = 0, L = 0, R = 0, RP = 0, cap = 0;
+    int32_t rp_active = 0;                              // planes [0, rp_active) are swept by the fast kernels (= RP except while a segment is re-swept below its path's plane)
+    bool loaded = false;
     bool lean_chain = false;
     // single-window score deltas computed beside the sweep: piece k (transitions of levels >= delta_piece_level[k]) signals delta_piece_ev[k]
     std::vector<hipEvent_t> delta_piece_ev;
     std::vector<int32_t> delta_piece_level;
     int delta_piece_next = 0;                           // first piece the sweep has not waited for yet
-    int64_t delta_overlap = 1;                          // delta_overlap: 0 = the whole window before the sweep (option)
     hipStream_t pf_stream = nullptr;                    // the ONE side stream: score-delta pieces, then the L2 table prefetcher (dg_dp_sweep.hip)
     hipEvent_t pf_ev = nullptr;
     int pf_seq = 0;
     bool pf_active = false;                             // a prefetcher accompanies the sweep range being issued
-    int64_t pf_far = 128;                               // pf_far: > 0 = prefetcher blocks also pull the tables pf_far levels ahead into the Infinity Cache (then no periodic look-ahead launches)
     int pf_tested = 0;                                  // 0: the side stream's concurrency with the sweep's stream not yet probed, 1: probed
-    int64_t use_rowx = 1;                               // rowx: row in-edge matrices (0: every fan-in row fetches its list from in_edge[])
-    int64_t delta_cap_entries = (int64_t)4 << 30;       // delta_cap_entries: budget of resident score-delta entries
-    int64_t rc_cap = 65536, rc_t0_ns = 3000, rc_tg_ps = 20000, rc_tw_ps = 50;   // rc_*: cost model of the per-level RC choice
-    size_t chunk_units_cfg = (size_t)4 << 30;           // lattice_chunk_cells: size of one lattice chunk (16-bit units)
     // ---- lattice segments: destination levels [seg_begin[s], seg_begin[s+1]); one segment = whole lattice resident.
     // More than one = checkpoint + recompute (value-only pass, then each segment re-swept with back-pointers, last first).
     std::vector<int> seg_begin;
@@ -198,7 +204,7 @@ struct DpState {
         std::mutex mu;
         std::condition_variable cv;
         std::vector<void *> chunks;           // each chunk_units * 2 bytes
-        size_t chunk_units = (size_t)4 << 30;  // 8 GB
+        size_t chunk_units = (size_t)DpOptions().chunk_units_cfg;
         size_t target = 0;                     // chunks wanted
         size_t cap_chunks = 0;                 // upper bound for reservations made before the graph is known
         bool running = false, failed = false, paused = false;
@@ -216,11 +222,9 @@ struct DpState {
     int n_groups = 0;                          // walker groups of the run at hand (chains of neighbouring budgets share an XCD and its helpers)
     mutable int walk_seq = 0;                  // per-launch number of the chain walk (ChainSync; counted from 0 in every run)
     // ---- dg_dp_score_paths (dg_dp_score.hip): staging of one slab of caller paths, its result words, the first-bad-hop word ----
-    int64_t score_slab_bytes = (int64_t)256 << 20;   // score_slab_bytes: bound of the path staging buffer (a slab holds at least one pair)
     DevBuf d_sc_paths, d_sc_out, d_sc_err;
     // ---- dg_dp_best_partners (dg_dp_partner.hip): one slab of queries -- (given, partner) pairs, budgets, sink cells, the re-scoring
     // pass's records, the two first-bad-hop words; back-pointers and edge scores (released when the call returns) ----
-    int64_t partner_slab_bytes = (int64_t)4 << 30;   // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab (a slab holds at least one query)
     DevBuf d_pt_pairs, d_pt_bud, d_pt_val, d_pt_out, d_pt_err, d_pt_bp, d_pt_scores;
 };
 

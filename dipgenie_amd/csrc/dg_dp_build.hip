@@ -407,7 +407,7 @@ int dp_build_tables_device(dg_ctx *c, const dg_dp_graph *g, DpState &S, std::vec
     const size_t LS = (size_t)L + 1;
     if (int rc = t_cnt.ensure(8 * LS * NQ)) return rc;
     if (int rc = t_pre.ensure(8 * LS * NQ)) return rc;
-    hipLaunchKernelGGL(bt_level_count_kernel, dim3(nblk((int64_t)L + 1, 128)), dim3(128), 0, s, L, S.RP, (int)(S.use_rowx != 0), level_off, in_off, t_hascol.as<uint8_t>(),
+    hipLaunchKernelGGL(bt_level_count_kernel, dim3(nblk((int64_t)L + 1, 128)), dim3(128), 0, s, L, S.RP, (int)(S.opt.use_rowx != 0), level_off, in_off, t_hascol.as<uint8_t>(),
                        t_cnt.as<int64_t>(), st);
     for (int q = 0; q < NQ; ++q) {
         size_t tb = 0;
@@ -444,7 +444,7 @@ int dp_build_tables_device(dg_ctx *c, const dg_dp_graph *g, DpState &S, std::vec
     S.max_level_cells = std::max<int64_t>(S.RP, (int64_t)hs.max_level_cells);
     S.delta_entries = DELTA_PAD + tot[Q_DELTA];
     S.n_delta_blocks = tot[Q_DBLK];
-    S.lean_chain = S.use_lean_chain && !hs.any_wide && S.max_level_cells < ((int64_t)1 << 30) && (int64_t)S.RP * max_k < ((int64_t)1 << 24) && nV < (1 << 27);
+    S.lean_chain = S.opt.use_lean_chain && !hs.any_wide && S.max_level_cells < ((int64_t)1 << 30) && (int64_t)S.RP * max_k < ((int64_t)1 << 24) && nV < (1 << 27);
     const int64_t rowx_words = std::min(tot[Q_ROWX], ROWX_BUDGET_WORDS);
     S.n_grp = tot[Q_GRP]; S.n_dead = tot[Q_DEAD]; S.n_heavy_rows = tot[Q_HEAVY]; S.n_slot_records = tot[Q_BLOCKS] * 64; S.n_rowx_words = rowx_words;
     // ---- level pass 2: fill
@@ -463,7 +463,7 @@ int dp_build_tables_device(dg_ctx *c, const dg_dp_graph *g, DpState &S, std::vec
     DG_HIP(hipMemsetAsync(S.d_heavy.p, 0, 4 * ((size_t)tot[Q_HEAVY] + 1), s));
     FillOut O{S.d_descs.as<LevelDesc>(), S.d_grp.as<uint32_t>(), S.d_dead.as<int32_t>(), S.d_heavy.as<int32_t>(), S.d_dtrans.as<int32_t>(), S.d_dblk_first.as<int64_t>(),
               t_heads.as<uint4>(), t_head_b0.as<int32_t>(), rowx_words};
-    hipLaunchKernelGGL(bt_level_fill_kernel, dim3(nblk(L, 128)), dim3(128), 0, s, L, S.RP, (int)(S.use_rowx != 0), level_off, in_off, t_hascol.as<uint8_t>(),
+    hipLaunchKernelGGL(bt_level_fill_kernel, dim3(nblk(L, 128)), dim3(128), 0, s, L, S.RP, (int)(S.opt.use_rowx != 0), level_off, in_off, t_hascol.as<uint8_t>(),
                        t_pre.as<int64_t>(), O);
     hipLaunchKernelGGL(bt_slots_kernel, dim3(nblk(n_blocks, 4)), dim3(256), 0, s, n_blocks, t_heads.as<uint4>(), t_head_b0.as<int32_t>(), in_edge, in_dst, in_off,
                        S.d_slots.as<uint2>());

@@ -142,19 +142,19 @@ constexpr int DELTA_PIECES = 8, DELTA_HEAD = 250;
 
 const uint16_t *delta_launch_overlapped(DpState &S, hipStream_t s) {
     const int nt = (int)S.dtrans_host.size();
-    const bool forced = S.delta_overlap == 2;                          // (tests: small graphs too)
+    const bool forced = S.opt.delta_overlap == 2;                          // (tests: small graphs too)
     // (one DP state per device unless option side_stream says otherwise: with several, a side stream may share a hardware queue with
     // another state's sweep and its pieces would queue behind whole batches of that sweep)
-    if (!S.delta_overlap || nt < 2 * DELTA_PIECES || (!forced && (S.L < 32000 || !S.side_stream_ok()))) return delta_launch_window(S, 0, s);
+    if (!S.opt.delta_overlap || nt < 2 * DELTA_PIECES || (!forced && (S.L < 32000 || !S.side_stream_ok()))) return delta_launch_window(S, 0, s);
     const int head = forced ? std::max(2, S.L / 256) : DELTA_HEAD;
     // ONE side stream for these pieces and for the L2 table prefetcher (dg_dp_sweep.hip).  With a stream each, the prefetcher -- a kernel
     // that lives as long as its range's sweep -- and the pieces could meet in one hardware queue (HIP maps streams onto a few of them):
     // the sweep then waited for a piece that waited behind a prefetcher that waited for the sweep.  Seen with GPU_MAX_HW_QUEUES=8: 4.1 s
     // per sweep.  In one stream the pieces always precede the prefetcher.
-    if (!S.pf_stream && hipStreamCreateWithFlags(&S.pf_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); S.pf_stream = nullptr; S.delta_overlap = 0; return delta_launch_window(S, 0, s); }
+    if (!S.pf_stream && hipStreamCreateWithFlags(&S.pf_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); S.pf_stream = nullptr; S.opt.delta_overlap = 0; return delta_launch_window(S, 0, s); }
     if (S.delta_piece_ev.empty()) {
         S.delta_piece_ev.assign(DELTA_PIECES, nullptr);
-        for (auto &e : S.delta_piece_ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); S.delta_overlap = 0; return delta_launch_window(S, 0, s); }
+        for (auto &e : S.delta_piece_ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); S.opt.delta_overlap = 0; return delta_launch_window(S, 0, s); }
     }
     hipStream_t side = S.pf_stream;
     // piece boundaries in transitions: pieces that grow fourfold from the head on (a piece must be finished before the sweep reaches

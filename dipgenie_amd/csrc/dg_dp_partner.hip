@@ -251,7 +251,7 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
     const int64_t pair_words = 2 * (int64_t)L;
     const int64_t query_bytes = 2 * bp_stride + 2 * E + 4 * pair_words;
     const int nblk_sc = (L - 1 + PT_SCORE_LEVELS - 1) / PT_SCORE_LEVELS;
-    int64_t per_slab = std::max<int64_t>(1, S.partner_slab_bytes / query_bytes);
+    int64_t per_slab = std::max<int64_t>(1, S.opt.partner_slab_bytes / query_bytes);
     per_slab = std::min(per_slab, std::max<int64_t>(1, ((int64_t)1 << 30) / std::max(nblk_sc, score_pair_blocks(S))));
     per_slab = std::min(per_slab, n);
     if (int rc = S.d_pt_pairs.ensure((size_t)(per_slab * pair_words) * 4)) return rc;

@@ -118,16 +118,16 @@ struct Run {
     int issue_levels(int l0, int l1, int lb, int le) {
         for (int l = l0; l < l1; ++l) {
             if (S.level_win[l] >= 0 && S.level_win[l] != S.cur_win) load_window(S.level_win[l]);
-            if (S.warm_ahead > 0 && l >= next_warm && (l == lb || !(S.pf_active && S.pf_far > 0))) {
+            if (S.opt.warm_ahead > 0 && l >= next_warm && (l == lb || !(S.pf_active && S.opt.pf_far > 0))) {
                 // tables of the batch after this one (and, at the start of a range, of this one too)
-                const int q0 = l == lb ? l : (int)std::min<int64_t>(l + S.warm_ahead, le), q1 = (int)std::min<int64_t>(l + 2 * S.warm_ahead, le);
+                const int q0 = l == lb ? l : (int)std::min<int64_t>(l + S.opt.warm_ahead, le), q1 = (int)std::min<int64_t>(l + 2 * S.opt.warm_ahead, le);
                 if (q1 > q0) sweep_warm_tables(S, X, q0, q1, s);
             }
-            if (l >= next_warm) next_warm = l + (int)std::max<int64_t>(S.warm_ahead, 1);
+            if (l >= next_warm) next_warm = l + (int)std::max<int64_t>(S.opt.warm_ahead, 1);
             sweep_launch_level(S, X, l, s);
             ++n_launch;
             // profiling aid: rocprofv3 --pmc crashes when ~10^5 dispatches are queued without a drain
-            if (S.sync_every > 0 && n_launch % S.sync_every == 0) DG_HIP(hipStreamSynchronize(s));
+            if (S.opt.sync_every > 0 && n_launch % S.opt.sync_every == 0) DG_HIP(hipStreamSynchronize(s));
         }
         return DG_OK;
     }
@@ -145,12 +145,12 @@ struct Run {
         X.A.bp = bp_biased; X.F.bp = bp_biased;
         next_warm = lb;
         if (int rc = sweep_prefetch_begin(S, X, lb, le, n_win() == 1, s)) return rc;
-        const int64_t gb = S.graph_batch >= 0 ? S.graph_batch : 1000;
+        const int64_t gb = S.opt.graph_batch >= 0 ? S.opt.graph_batch : 1000;
         // what issue_levels bakes into a captured batch besides the levels: whether the periodic look-ahead launches are left to the
         // prefetcher's far blocks -- part of the cache key (a second DP state on the device switches the prefetcher off)
-        const int pf_key = ((S.pf_active && S.pf_far > 0) ? 1 : 0) | (S.rp_active << 1);
+        const int pf_key = ((S.pf_active && S.opt.pf_far > 0) ? 1 : 0) | (S.rp_active << 1);
         for (int l0 = lb; l0 < le;) {
-            const bool use_graph = gb > 0 && n_win() == 1 && S.sync_every == 0 && !S.graph_failed;
+            const bool use_graph = gb > 0 && n_win() == 1 && S.opt.sync_every == 0 && !S.graph_failed;
             const int l1 = use_graph ? (int)std::min<int64_t>((int64_t)l0 + gb, le) : le;
             // score deltas computed beside the sweep (delta_launch_overlapped): the stream waits for the pieces that hold a level below l1
             while (S.delta_piece_next < (int)S.delta_piece_level.size() && S.delta_piece_level[S.delta_piece_next] < l1) {
@@ -231,10 +231,10 @@ struct Run {
             host_enqueue_s += wall_s() - th0;
         }
         if (mark_forward_end) { DG_HIP(hipEventRecord(S.ev[2], s)); budgets_launch_sink_copy(S, state_ptr(S.L - 1), s); }
-        if (S.test_poison_level > 0 && S.test_poison_level < S.L)        // tests: a level nobody swept / a damaged lattice
+        if (S.opt.test_poison_level > 0 && S.opt.test_poison_level < S.L)        // tests: a level nobody swept / a damaged lattice
             for (int ch = c0; ch < c1; ++ch) {
-                const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1], lp = (int)S.test_poison_level;
-                if (lp >= lb && lp < le) DG_HIP(hipMemsetAsync(biased[ch - c0] + S.descs[lp].bp_off, (int)S.test_poison_byte, 2 * (size_t)S.level_units[lp], s));
+                const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1], lp = (int)S.opt.test_poison_level;
+                if (lp >= lb && lp < le) DG_HIP(hipMemsetAsync(biased[ch - c0] + S.descs[lp].bp_off, (int)S.opt.test_poison_byte, 2 * (size_t)S.level_units[lp], s));
             }
         for (int ch = c1 - 1; ch >= c0; --ch) {
             const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1];
@@ -252,7 +252,7 @@ struct Run {
         S.delta_piece_next = DELTA_NO_PIECES;
         if (n_win() == 1 && S.n_delta_blocks > 0) X.A.delta = X.F.delta = delta_launch_overlapped(S, s);   // everything fits: the head up front (delta_ms), the rest beside the sweep
         DG_HIP(hipEventRecord(S.ev[1], s));
-        if (S.want_digest) DG_HIP(hipMemsetAsync(S.d_digest.p, 0, 8 * (size_t)S.L, s));
+        if (S.opt.want_digest) DG_HIP(hipMemsetAsync(S.d_digest.p, 0, 8 * (size_t)S.L, s));
 #ifdef DG_SWEEP_PROBE
         {   // slot 0 of every level takes an atomicMin: start from all ones
             std::vector<unsigned long long> init((size_t)S.L * 8, 0ULL);
@@ -266,7 +266,7 @@ struct Run {
             if (int rc = sweep_and_walk(0, S.d_bp.p ? 1 : n_chunks_all, true, true)) return rc;
         } else {
             // pass 1: values only, keeping the state in front of every segment
-            const int64_t dig = S.want_digest;
+            const int64_t dig = S.opt.want_digest;
             int64_t planes_swept = 0;
             S.rp_active = S.RP;
             for (int sg = 0; sg < n_seg; ++sg) {
@@ -278,7 +278,7 @@ struct Run {
             DG_HIP(hipEventRecord(S.ev[2], s));                 // (the re-sweeps below are booked under traceback_ms)
             budgets_launch_sink_copy(S, state_ptr(S.L - 1), s);  // the second pass overwrites the state ring
             // pass 2: last segment first -- restore its input state, re-sweep its chunks with back-pointers, walk them
-            S.want_digest = 0;                                  // digests were accumulated in pass 1
+            S.opt.want_digest = 0;                                  // digests were accumulated in pass 1
             // Along a path the recombination count only grows, and a cell of plane r gathers from planes r, r - 1, r - 2 of the level
             // before: once the walk has left segment sg on plane r*, the cells it can meet in the segments before lie on planes
             // <= r*, and those depend on planes <= r* only.  Every earlier segment is therefore re-swept up to the plane its
@@ -292,10 +292,10 @@ struct Run {
                 else
                     sweep_init_state(S, s);
                 const int c0 = sg * S.seg_chunks, c1 = std::min(n_chunks_all, c0 + S.seg_chunks);
-                if (int rc = sweep_and_walk(c0, c1, sg == n_seg - 1, false)) { S.want_digest = dig; S.rp_active = S.RP; return rc; }
-                if (S.plane_limit && sg > 0) {
+                if (int rc = sweep_and_walk(c0, c1, sg == n_seg - 1, false)) { S.opt.want_digest = dig; S.rp_active = S.RP; return rc; }
+                if (S.opt.plane_limit && sg > 0) {
                     std::vector<ChainState> cs((size_t)n_chains);
-                    if (hipMemcpyAsync(cs.data(), S.d_ch_state.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
+                    if (hipMemcpyAsync(cs.data(), S.d_ch_state.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.opt.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
                     int planes = 1;
                     for (const ChainState &q : cs) {
                         if (q.value == NEG_INF) continue;
@@ -306,8 +306,8 @@ struct Run {
                 }
             }
             S.rp_active = S.RP;
-            S.want_digest = dig;
-            if (getenv("DG_DEBUG") && S.plane_limit) fprintf(stderr, "[dipgenie_hip] run: second pass swept %.1f %% of the (level, plane) pairs before the last segment\n",
+            S.opt.want_digest = dig;
+            if (getenv("DG_DEBUG") && S.opt.plane_limit) fprintf(stderr, "[dipgenie_hip] run: second pass swept %.1f %% of the (level, plane) pairs before the last segment\n",
                                                               100.0 * (double)planes_swept / std::max(1.0, (double)S.RP * (S.seg_begin[n_seg - 1] - 1)));
         }
         budgets_launch_finish(S, n_chains, s);
@@ -363,7 +363,7 @@ static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result
     DG_HIP(hipMemcpyAsync(edges.data(), S.d_ch_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
     std::vector<int32_t> sink((size_t)S.RP);
     DG_HIP(hipMemcpyAsync(sink.data(), S.d_sink.p, 4 * sink.size(), hipMemcpyDeviceToHost, s));
-    if (S.want_digest) {
+    if (S.opt.want_digest) {
         S.digest_host.assign(S.L, 0);
         DG_HIP(hipMemcpyAsync(S.digest_host.data(), S.d_digest.p, 8 * (size_t)S.L, hipMemcpyDeviceToHost, s));
     }
@@ -451,7 +451,7 @@ extern "C" int dg_dp_prealloc(dg_ctx *c, int64_t bytes) {
     if (int rc = dgi::bind(c)) return rc;
     if (!c->dp) c->dp = new dgi::DpState(c->device);
     dgi::DpState &S = *c->dp;
-    if (S.pool.chunk_units != S.chunk_units_cfg) { dgi::pool_clear(S); S.pool.chunk_units = S.chunk_units_cfg; }
+    if (S.pool.chunk_units != (size_t)S.opt.chunk_units_cfg) { dgi::pool_clear(S); S.pool.chunk_units = (size_t)S.opt.chunk_units_cfg; }
     const size_t chunk_bytes = S.pool.chunk_units * 2;
     if (S.pool.cap_chunks == 0) {          // first call only: later ones may arrive while chunks are being mapped
         size_t free_b = 0, total_b = 0;
@@ -495,31 +495,40 @@ extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
 }
 // Options: parity / test knobs (digest, fast, adaptive_rc, coop, rowx, lean_chain, segment_cells, delta_cap_entries, lattice_chunk_cells,
 // graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
-extern "C" int dg_dp_set_option(dg_ctx *c, const char *key, int64_t v) {
-    if (!c || !key) { dgi::set_error("dg_dp_set_option: null"); return DG_ERR_ARG; }
+// One row per key: its DpOptions field, the lower clamp, whether v <= 0 asks for the default (that of a fresh DpOptions).
+typedef dgi::DpOptions DpO;
+static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t lo; bool nonpos_is_default; } dp_option_keys[] = {
+    // read by every run or call: in effect at once
+    {"digest", &DpO::want_digest, 0, false}, {"fast", &DpO::use_fast, 0, false}, {"adaptive_rc", &DpO::adaptive_rc, 0, false}, {"coop", &DpO::use_coop, 0, false},
+    {"sync_every", &DpO::sync_every, 0, false}, {"rc_t0_ns", &DpO::rc_t0_ns, 0, false}, {"rc_tg_ps", &DpO::rc_tg_ps, 0, false}, {"rc_tw_ps", &DpO::rc_tw_ps, 0, false},
+    {"rc_cap", &DpO::rc_cap, 0, true}, {"max_blocks", &DpO::max_blocks, 0, true}, {"bp_nt_min_cells", &DpO::bp_nt_min_cells, 0, false}, {"warm_ahead", &DpO::warm_ahead, 0, false},
+    {"graph_batch", &DpO::graph_batch, -1, false}, {"l2_prefetch", &DpO::l2_prefetch, 0, false}, {"delta_overlap", &DpO::delta_overlap, 0, false}, {"pf_far", &DpO::pf_far, 0, false},
+    {"side_stream", &DpO::side_stream, -1, false}, {"plane_limit", &DpO::plane_limit, 0, false}, {"test_poison_level", &DpO::test_poison_level, 0, false},
+    {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
+    // read by dg_dp_load_graph: in effect at the next load
+    {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},
+    {"host_threads", &DpO::host_threads, 1, false}, {"host_tables", &DpO::host_tables, 0, false}, {"delta_cap_entries", &DpO::delta_cap_entries, 0, true},
+    {"lattice_chunk_cells", &DpO::chunk_units_cfg, 1, false},   // 16-bit back-pointer units; below 1 is an error, else rounded up to even; empties the chunk pool at once
+};
+static int dp_option(dg_ctx *c, const char *what, const char *key, const int64_t *set, int64_t *get) {   // set or get, the other is null
+    if (!c || !key || (!set && !get)) { dgi::set_error("%s: null", what); return DG_ERR_ARG; }
     if (!c->dp) c->dp = new dgi::DpState(c->device);
     dgi::DpState &S = *c->dp;
-    dgi::graphs_clear(S);
-    struct { const char *name; int64_t *field; int64_t lo; } plain[] = {
-        {"digest", &S.want_digest, 0}, {"fast", &S.use_fast, 0}, {"adaptive_rc", &S.adaptive_rc, 0}, {"coop", &S.use_coop, 0},
-        {"rowx", &S.use_rowx, 0}, {"lean_chain", &S.use_lean_chain, 0},   // take effect at the next load
-        {"segment_cells", &S.segment_cells, 0}, {"sync_every", &S.sync_every, 0}, {"rc_t0_ns", &S.rc_t0_ns, 0}, {"rc_tg_ps", &S.rc_tg_ps, 0},
-        {"rc_tw_ps", &S.rc_tw_ps, 0}, {"bp_nt_min_cells", &S.bp_nt_min_cells, 0}, {"warm_ahead", &S.warm_ahead, 0}, {"graph_batch", &S.graph_batch, -1}, {"l2_prefetch", &S.l2_prefetch, 0}, {"delta_overlap", &S.delta_overlap, 0}, {"pf_far", &S.pf_far, 0},
-        {"host_threads", &S.host_threads, 1}, {"host_tables", &S.host_tables, 0}, {"side_stream", &S.side_stream, -1}, {"plane_limit", &S.plane_limit, 0},
-        {"test_poison_level", &S.test_poison_level, 0}, {"test_poison_byte", &S.test_poison_byte, 0},
-    };
-    for (auto &o : plain)
-        if (!strcmp(key, o.name)) { *o.field = v < o.lo ? o.lo : v; return DG_OK; }
-    if (!strcmp(key, "delta_cap_entries")) S.delta_cap_entries = v > 0 ? v : (int64_t)4 << 30;   // takes effect at the next load
-    else if (!strcmp(key, "rc_cap")) S.rc_cap = v > 0 ? v : 65536;
-    else if (!strcmp(key, "max_blocks")) S.max_blocks = v > 0 ? v : 1024;
-    else if (!strcmp(key, "score_slab_bytes")) S.score_slab_bytes = v > 0 ? v : (int64_t)256 << 20;   // staging bound of dg_dp_score_paths (a slab holds at least one pair)
-    else if (!strcmp(key, "partner_slab_bytes")) S.partner_slab_bytes = v > 0 ? v : (int64_t)4 << 30;   // device memory of one slab of dg_dp_best_partners (a slab holds at least one query)
-    else if (!strcmp(key, "lattice_chunk_cells")) {          // size of one lattice chunk (in 16-bit back-pointer units = cells on ordinary levels; default 2^32 = 8 GB)
-        if (v < 1) { dgi::set_error("lattice_chunk_cells must be positive"); return DG_ERR_ARG; }
-        dgi::pool_clear(S);
-        S.chunk_units_cfg = S.pool.chunk_units = ((size_t)v + 1) & ~(size_t)1;
+    if (set) dgi::graphs_clear(S);
+    for (const DpOptionKey &o : dp_option_keys) {
+        if (strcmp(key, o.key)) continue;
+        if (!set) { *get = S.opt.*o.field; return DG_OK; }
+        int64_t v = *set;
+        if (o.field == &DpO::chunk_units_cfg) {
+            if (v < o.lo) { dgi::set_error("lattice_chunk_cells must be positive"); return DG_ERR_ARG; }
+            dgi::pool_clear(S);
+            v = (int64_t)(S.pool.chunk_units = ((size_t)v + 1) & ~(size_t)1);
+        }
+        S.opt.*o.field = o.nonpos_is_default && v <= 0 ? DpO().*o.field : v < o.lo ? o.lo : v;
+        return DG_OK;
     }
-    else { dgi::set_error("unknown option %s", key); return DG_ERR_ARG; }
-    return DG_OK;
+    dgi::set_error("unknown option %s", key);
+    return DG_ERR_ARG;
 }
+extern "C" int dg_dp_set_option(dg_ctx *c, const char *key, int64_t v) { return dp_option(c, "dg_dp_set_option", key, &v, nullptr); }
+extern "C" int dg_dp_get_option(dg_ctx *c, const char *key, int64_t *value) { return dp_option(c, "dg_dp_get_option", key, nullptr, value); }

@@ -100,7 +100,7 @@ int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_
     const int nblk = score_pair_blocks(S);
     const int64_t pair_words = 2 * (int64_t)L;
     // pairs per slab: what the staging bound holds (at least one), a grid of at most 2^30 workgroups, a pair index of 31 bits
-    int64_t per_slab = std::max<int64_t>(1, S.score_slab_bytes / (4 * pair_words));
+    int64_t per_slab = std::max<int64_t>(1, S.opt.score_slab_bytes / (4 * pair_words));
     per_slab = std::min(per_slab, std::max<int64_t>(1, SCORE_MAX_GRID / nblk));
     per_slab = std::min(per_slab, n_pairs);
     if (int rc = S.d_sc_paths.ensure((size_t)(per_slab * pair_words) * 4)) return rc;

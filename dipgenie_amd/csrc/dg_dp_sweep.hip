@@ -18,7 +18,7 @@
 namespace dgi {
 
 // state slot of a level: the two slots are ping-pong buffers
-#define DG_SLOT(ARGS, LEVEL) ((LEVEL) & 1)
+#define DG_SLOT(LEVEL) ((LEVEL) & 1)
 
 constexpr unsigned long long DIGEST_PRED_MUL = 0x9E3779B97F4A7C15ULL;   // oracle_dp.cpp: weight of the predecessor term
 
@@ -80,8 +80,8 @@ template <int RC, bool DIGEST>
 __device__ __forceinline__ void sweep_level_pairs(const SweepArgs &A, int lvl, int wave_id, int n_waves) {
     const LevelDesc d = A.descs[lvl];
     const int RP = A.RP;
-    const int32_t *__restrict__ cur = (const int32_t *)(A.ring + (size_t)DG_SLOT(A, lvl - 1) * A.slot_bytes + A.pad_bytes);
-    int32_t *__restrict__ nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(A, lvl) * A.slot_bytes + A.pad_bytes);
+    const int32_t *__restrict__ cur = (const int32_t *)(A.ring + (size_t)DG_SLOT(lvl - 1) * A.slot_bytes + A.pad_bytes);
+    int32_t *__restrict__ nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(lvl) * A.slot_bytes + A.pad_bytes);
     const int lane = threadIdx.x & 63;
     const int nchunk = (RP + RC - 1) / RC;
     const int64_t ntask = (int64_t)d.k2 * d.ngroups * nchunk;
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(DG_PLAIN_WG) void dp_sweep_fast_kernel(const uint4 
     const int g = (int)blockIdx.x * DG_PLAIN_GW + (wv % DG_PLAIN_GW);    // always launched with DG_PLAIN_WG threads (reading blockDim would be a kernel-argument load)
     const int r0 = ((int)blockIdx.y * DG_PLAIN_CH + wv / DG_PLAIN_GW) * RC;
     if (g >= nblocks || r0 >= (rp_k & 0x1FFF)) return;                  // wave-uniform; no block barrier below
-    int32_t *nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(A, lvl) * A.slot_bytes + A.pad_bytes);
+    int32_t *nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(lvl) * A.slot_bytes + A.pad_bytes);
     sweep_task<RC, DIGEST, GENERAL, 0>(H, A, d, state_rsrc(cur, buf_bytes), nxt, (int)blockIdx.z, g, r0, lvl);
 }
 
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256) void dp_sweep_coop_kernel(const uint4 *rowrec_
                                                             FastArgs A, LevelDesc d, int lvl, const uint16_t *dm, int dT, const int32_t *__restrict__ heavy_rows) {
     const LevelHead H{rowrec_l, slots_l, rowx_l, cur, dm, rowx_stride, rp_k & 0x1FFF, rp_k >> 13, A.pad_bytes, dT, A.buf_bytes};
     publish_level(A.progress, lvl);
-    int32_t *nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(A, lvl) * A.slot_bytes + A.pad_bytes);
+    int32_t *nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(lvl) * A.slot_bytes + A.pad_bytes);
     const int r0 = (int)blockIdx.y * RC;                                // chunks of a row are neighbours in dispatch order: they share its delta row
     const int zc = 4 * n_heavy;
     if ((int)blockIdx.z < zc) {
@@ -590,7 +590,6 @@ __global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__r
         ++lp; ++done;
     }
     if (lane == 0 && blockIdx.x == 0) atomicAdd(&ctl->levels_done, done);
-    (void)far_role;
 #undef DG_DROP_LOAD
 }
 
@@ -633,19 +632,19 @@ void sweep_init_state(const DpState &S, hipStream_t s) {
 static void choose_rc(const DpState &S, const LevelDesc &d, int l, int rc_sel, int &rc, bool &coop) {
     rc = rc_sel;
     coop = false;
-    if (S.adaptive_rc == 0) return;
+    if (S.opt.adaptive_rc == 0) return;
     const int cand[11] = {1, 2, 3, 4, 5, 6, 8, 10, 11, 16, rc_sel};
-    const bool coop_ok = S.use_coop && d.n_heavy > 0 && d.k2 + 4 * d.n_heavy <= 65535;
+    const bool coop_ok = S.opt.use_coop && d.n_heavy > 0 && d.k2 + 4 * d.n_heavy <= 65535;
     const double dmax = (double)std::max(1, S.level_dmax[l]);
     double best = 1e300;
-    for (int pass = (coop_ok && S.use_coop == 2) ? 1 : 0; pass < (coop_ok ? 2 : 1); ++pass) {     // coop = 2 (tests): whenever possible
+    for (int pass = (coop_ok && S.opt.use_coop == 2) ? 1 : 0; pass < (coop_ok ? 2 : 1); ++pass) {     // coop = 2 (tests): whenever possible
         for (int q = 0; q < 11; ++q) {
             if (cand[q] > rc_sel || (q < 10 && cand[q] == rc_sel)) continue;
             if (pass == 1 && cand[q] > 4) continue;
             const double rows = pass ? (double)d.k2 + 4.0 * d.n_heavy : (double)d.k2;
             const double chain = pass ? std::max((double)COOP_MIN, std::ceil(dmax / 4.0)) + 1.0 : dmax;
             const double W = rows * d.nblocks * ((S.rp_active + cand[q] - 1) / cand[q]);
-            const double T = std::max(1.0, W / (double)S.rc_cap) * ((double)S.rc_t0_ns + chain * cand[q] * (double)S.rc_tg_ps * 1e-3) + W * (double)S.rc_tw_ps * 1e-3;
+            const double T = std::max(1.0, W / (double)S.opt.rc_cap) * ((double)S.opt.rc_t0_ns + chain * cand[q] * (double)S.opt.rc_tg_ps * 1e-3) + W * (double)S.opt.rc_tw_ps * 1e-3;
             if (T <= best) { best = T; rc = cand[q]; coop = pass == 1; }   // ties: the larger RC (fewer waves)
         }
     }
@@ -656,8 +655,8 @@ void sweep_launch_level(DpState &S, SweepLaunch &X, int l, hipStream_t s) {
     // small and mid-sized levels end sooner with write-back back-pointer stores (3.6 vs 4.2 us per level on MHC_4; threshold
     // 16 K / 64 K / 256 K / 1 M / 4 M cells: MHC-24 sweep 580 / 575 / 574 / 579 / 586 ms), big ones with non-temporal ones that
     // keep the once-written lattice out of the L2
-    d.bp_nt = (int64_t)d.k2 * d.k2 * S.RP >= S.bp_nt_min_cells ? 1 : 0;
-    if (d.fast_ok && X.small_state && S.RP <= 65535 && S.use_fast) {
+    d.bp_nt = (int64_t)d.k2 * d.k2 * S.RP >= S.opt.bp_nt_min_cells ? 1 : 0;
+    if (d.fast_ok && X.small_state && S.RP <= 65535 && S.opt.use_fast) {
         int rc;
         bool coop;
         choose_rc(S, d, l, X.rc_sel, rc, coop);
@@ -670,7 +669,7 @@ void sweep_launch_level(DpState &S, SweepLaunch &X, int l, hipStream_t s) {
         const uint4 *rowrec_l = F.rowrec + d.b0;
         const uint2 *slots_l = F.slots + d.slot_first;
         const uint32_t *rowx_l = F.rowx + d.rowx_off;
-        const int32_t *cur = (const int32_t *)(F.ring + (size_t)DG_SLOT(F, l - 1) * F.slot_bytes);
+        const int32_t *cur = (const int32_t *)(F.ring + (size_t)DG_SLOT(l - 1) * F.slot_bytes);
         const int dT = d.delta_off >= 0 ? d.T : 0;
         const uint16_t *dm = dT ? F.delta + d.delta_off - (int64_t)d.in_base * dT : F.delta_zero;   // (F.delta is biased by the resident delta window)
         const int rp_k = S.RP | (d.k << 13);
@@ -687,18 +686,18 @@ void sweep_launch_level(DpState &S, SweepLaunch &X, int l, hipStream_t s) {
                                         case 8: DG_FAST(8, DG); break; case 10: DG_FAST(10, DG); break; case 11: DG_FAST(11, DG); break; \
                                         case 16: DG_FAST(16, DG); break; case 19: DG_FAST(19, DG); break; \
                                         default: DG_FAST(33, DG); break; } } while (0)
-        if (S.want_digest) DG_FAST_RC(true); else DG_FAST_RC(false);
+        if (S.opt.want_digest) DG_FAST_RC(true); else DG_FAST_RC(false);
 #undef DG_COOP
 #undef DG_FAST_RC
 #undef DG_FAST
     } else {
         const int nchunk = (S.RP + X.rc_sel - 1) / X.rc_sel;
         const int64_t ntask = (int64_t)d.k2 * d.ngroups * nchunk;
-        const unsigned grid = (unsigned)std::min<int64_t>((ntask + 3) / 4, S.max_blocks);
+        const unsigned grid = (unsigned)std::min<int64_t>((ntask + 3) / 4, S.opt.max_blocks);
         const SweepArgs &A = X.A;
         S.launch_hist[0]++;
 #define DG_SWEEP(RCV, DG) hipLaunchKernelGGL((dp_sweep_kernel<RCV, DG>), dim3(grid), dim3(256), 0, s, A, l)
-        if (S.want_digest) { if (X.rc_sel == 8) DG_SWEEP(8, true); else if (X.rc_sel == 19) DG_SWEEP(19, true); else DG_SWEEP(33, true); }
+        if (S.opt.want_digest) { if (X.rc_sel == 8) DG_SWEEP(8, true); else if (X.rc_sel == 19) DG_SWEEP(19, true); else DG_SWEEP(33, true); }
         else { if (X.rc_sel == 8) DG_SWEEP(8, false); else if (X.rc_sel == 19) DG_SWEEP(19, false); else DG_SWEEP(33, false); }
 #undef DG_SWEEP
     }
@@ -739,9 +738,9 @@ void sweep_warm_tables(const DpState &S, const SweepLaunch &X, int q0, int q1, h
 // L2 prefetcher of the sweep range [lb, le): control words set in stream order on s, the prefetcher itself on the side stream
 int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool delta_resident, hipStream_t s) {
     S.pf_active = false;
-    if (S.l2_prefetch <= 0 || !X.small_state || !S.use_fast || le - lb < 64) return DG_OK;
-    if (!S.pf_stream && hipStreamCreateWithFlags(&S.pf_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); S.pf_stream = nullptr; S.l2_prefetch = 0; return DG_OK; }
-    if (!S.pf_ev && hipEventCreateWithFlags(&S.pf_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); S.pf_ev = nullptr; S.l2_prefetch = 0; return DG_OK; }
+    if (S.opt.l2_prefetch <= 0 || !X.small_state || !S.opt.use_fast || le - lb < 64) return DG_OK;
+    if (!S.pf_stream && hipStreamCreateWithFlags(&S.pf_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); S.pf_stream = nullptr; S.opt.l2_prefetch = 0; return DG_OK; }
+    if (!S.pf_ev && hipEventCreateWithFlags(&S.pf_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); S.pf_ev = nullptr; S.opt.l2_prefetch = 0; return DG_OK; }
     // One DP state per DEVICE (option side_stream: -1 = this rule, 0 / 1 = the caller decides): a second instance's sweep could share a
     // hardware queue with THIS state's prefetcher and would then wait behind it for a whole range (three concurrent instances on
     // one GPU: 78 -> 52 G cells/s before this rule).
@@ -756,7 +755,7 @@ int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool 
             hipMemcpy(&h, S.d_pfctl.p, sizeof h, hipMemcpyDeviceToHost) != hipSuccess || !h.probe_ok) {
             (void)hipGetLastError();
             if (getenv("DG_DEBUG")) fprintf(stderr, "[dipgenie_hip] L2 prefetcher off: its stream does not run beside the sweep's\n");
-            S.l2_prefetch = 0;
+            S.opt.l2_prefetch = 0;
             return DG_OK;
         }
     }
@@ -764,14 +763,14 @@ int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool 
     hipLaunchKernelGGL(dp_pf_ctl_kernel, dim3(1), dim3(1), 0, s, S.d_pfctl.as<PfCtl>(), seq, lb - 1, 0);
     DG_HIP(hipEventRecord(S.pf_ev, s));
     DG_HIP(hipStreamWaitEvent(S.pf_stream, S.pf_ev, 0));
-    const int far = (int)S.pf_far;
+    const int far = (int)S.opt.pf_far;
     hipLaunchKernelGGL(dp_l2_prefetch_kernel, dim3(PF_WORKGROUPS + (far > 0 ? PF_FAR_WORKGROUPS : 0)), dim3(64), 0, S.pf_stream, S.d_descs.as<LevelDesc>(), X.F,
-                       S.d_pfctl.as<PfCtl>(), seq, lb, le, (int)S.l2_prefetch, delta_resident ? 1 : 0, far);
+                       S.d_pfctl.as<PfCtl>(), seq, lb, le, (int)S.opt.l2_prefetch, delta_resident ? 1 : 0, far);
     S.pf_active = true;
     return DG_OK;
 }
 void sweep_prefetch_end(DpState &S, int le, hipStream_t s) {
-    if (S.pf_stream && S.l2_prefetch > 0) hipLaunchKernelGGL(dp_pf_ctl_kernel, dim3(1), dim3(1), 0, s, S.d_pfctl.as<PfCtl>(), S.pf_seq, le, 1);
+    if (S.pf_stream && S.opt.l2_prefetch > 0) hipLaunchKernelGGL(dp_pf_ctl_kernel, dim3(1), dim3(1), 0, s, S.d_pfctl.as<PfCtl>(), S.pf_seq, le, 1);
 }
 void sweep_prefetch_free(DpState &S) {
     if (S.pf_stream) { (void)hipStreamSynchronize(S.pf_stream); (void)hipStreamDestroy(S.pf_stream); S.pf_stream = nullptr; }

@@ -54,7 +54,7 @@ struct Builder {
     std::vector<int64_t> dblk_first;
 
     Builder(const dg_dp_graph *g_, DpState &S_) : g(g_), S(S_), nV(g_->n_vertices), L(g_->n_levels) {
-        NT = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)S.host_threads, (int64_t)std::thread::hardware_concurrency(), (int64_t)L / 64 + 1}));
+        NT = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)S.opt.host_threads, (int64_t)std::thread::hardware_concurrency(), (int64_t)L / 64 + 1}));
         lcut.assign(NT + 1, L);
         lcut[0] = 0;
         for (int t = 1; t < NT; ++t) {
@@ -289,7 +289,7 @@ int Builder::build_level_tables() {
             // row in-edge matrix (LevelDesc::rowx_*): fan-in rows on latency-bound levels of the lean variant
             d.rowx_off = (int64_t)P.rowx.size();
             d.rowx_stride = 0;
-            if (S.use_rowx && d.fast_ok == 1 && max_indeg > 2 && max_indeg <= (uint32_t)ROWX_MAX && ncell <= ROWX_MAX_LEVEL_CELLS) {
+            if (S.opt.use_rowx && d.fast_ok == 1 && max_indeg > 2 && max_indeg <= (uint32_t)ROWX_MAX && ncell <= ROWX_MAX_LEVEL_CELLS) {
                 d.rowx_stride = (int32_t)max_indeg;
                 P.rowx.resize(P.rowx.size() + (size_t)d.k2 * max_indeg, 0u);
                 uint32_t *rx = P.rowx.data() + d.rowx_off;
@@ -347,7 +347,7 @@ int Builder::build_level_tables() {
         int kmax = 1;
         bool wide = false;
         for (int l = 1; l < L; ++l) { kmax = std::max(kmax, S.descs[l].k2); wide |= S.descs[l].bp_wide != 0; }
-        S.lean_chain = S.use_lean_chain && !wide && S.max_level_cells < ((int64_t)1 << 30) && (int64_t)S.RP * kmax < ((int64_t)1 << 24) && nV < (1 << 27);
+        S.lean_chain = S.opt.use_lean_chain && !wide && S.max_level_cells < ((int64_t)1 << 30) && (int64_t)S.RP * kmax < ((int64_t)1 << 24) && nV < (1 << 27);
     }
     S.cells = (uint64_t)b_cells[NT];
     S.delta_entries = b_delta[NT];
@@ -397,7 +397,7 @@ void plan_delta_windows(DpState &S, const std::vector<int32_t> &dtrans, const st
     int64_t acc = 0, max_win = 0;
     for (size_t t = 0; t < dtrans.size(); ++t) {
         const int64_t n = (int64_t)S.descs[dtrans[t]].T * S.descs[dtrans[t]].T;
-        if (acc > 0 && acc + n > S.delta_cap_entries) { S.dwin_t.push_back((int32_t)t); max_win = std::max(max_win, acc); acc = 0; }
+        if (acc > 0 && acc + n > S.opt.delta_cap_entries) { S.dwin_t.push_back((int32_t)t); max_win = std::max(max_win, acc); acc = 0; }
         acc += n;
         S.level_win[dtrans[t]] = (int32_t)S.dwin_t.size() - 1;
     }
@@ -422,8 +422,8 @@ int plan_lattice(dg_ctx *c, DpState &S, size_t st_bytes, size_t dl_bytes, size_t
         set_error("graph needs %.1f GB of HBM for state/delta/tables but only %.1f GB is free", fixed / 1e9, have / 1e9);
         return DG_ERR_OOM;
     }
-    size_t chunk_units = S.chunk_units_cfg;
-    if (S.segment_cells > 0) chunk_units = std::min(chunk_units, ((size_t)S.segment_cells + 1) & ~(size_t)1);
+    size_t chunk_units = (size_t)S.opt.chunk_units_cfg;
+    if (S.opt.segment_cells > 0) chunk_units = std::min(chunk_units, ((size_t)S.opt.segment_cells + 1) & ~(size_t)1);
     if ((size_t)S.max_level_units > chunk_units) chunk_units = (size_t)S.max_level_units;
     S.chunk_begin.assign(1, 1);
     {
@@ -436,10 +436,10 @@ int plan_lattice(dg_ctx *c, DpState &S, size_t st_bytes, size_t dl_bytes, size_t
         S.chunk_begin.push_back(L);
     }
     const size_t n_chunks = S.chunk_begin.size() - 1;
-    const bool tiny = n_chunks == 1 && (size_t)S.total_units < S.chunk_units_cfg / 8 && S.segment_cells == 0;   // one exact allocation
+    const bool tiny = n_chunks == 1 && S.total_units < S.opt.chunk_units_cfg / 8 && S.opt.segment_cells == 0;   // one exact allocation
     const size_t chunk_bytes = chunk_units * 2;
     const size_t resident_bytes = tiny ? (size_t)S.total_units * 2 : n_chunks * chunk_bytes;
-    const bool segmented = (resident_bytes + fixed > have || S.segment_cells > 0) && n_chunks > 1;
+    const bool segmented = (resident_bytes + fixed > have || S.opt.segment_cells > 0) && n_chunks > 1;
     if (!segmented && resident_bytes + fixed > have) {
         set_error("back-pointer lattice of %.1f GB (one level alone needs %.1f GB) does not fit the %.1f GB of free HBM", resident_bytes / 1e9,
                   S.max_level_units * 2 / 1e9, (have - fixed) / 1e9);
@@ -451,11 +451,11 @@ int plan_lattice(dg_ctx *c, DpState &S, size_t st_bytes, size_t dl_bytes, size_t
     S.ckpt_off.assign(1, 0);
     int64_t ckpt_cells = 0;
     if (segmented) {
-        group = S.segment_cells > 0 ? 1 : std::max<size_t>(1, std::min(n_chunks - 1, (have - fixed) / chunk_bytes));
+        group = S.opt.segment_cells > 0 ? 1 : std::max<size_t>(1, std::min(n_chunks - 1, (have - fixed) / chunk_bytes));
         // Beyond HBM every level is swept twice whatever the segment size, but a segment's chunks must be mapped before its re-sweep
         // starts and mapping runs at ~85 GB/s (the 5 Mbp x 100-walk panel waited 3.5 s for 33 chunks = all of HBM): stay near what
         // the background thread has mapped by now -- more, smaller segments cost one tiny checkpoint each
-        if (S.segment_cells == 0) group = std::min(group, std::max<size_t>(8, pool_bytes / chunk_bytes + 2));
+        if (S.opt.segment_cells == 0) group = std::min(group, std::max<size_t>(8, pool_bytes / chunk_bytes + 2));
         for (;; --group) {
             S.seg_begin.assign(1, 1);
             S.ckpt_off.assign(1, 0);
@@ -525,7 +525,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     std::vector<int32_t> dtrans;
     std::vector<int64_t> dblk_first;
     int max_k = 1;
-    if (!S.host_tables) {
+    if (!S.opt.host_tables) {
         if (int rc = dp_build_tables_device(c, g, S, dtrans, dblk_first, max_k)) return rc;
     } else {
         Builder B(g, S);

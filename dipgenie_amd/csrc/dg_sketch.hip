@@ -804,7 +804,7 @@ static int sketch_reads_device(dg_ctx *c, const char *bases_dev, const int64_t *
     BucketPlan plan;
     bucket_plan(S, n_reads, nt, n_win, n_multi, w, &plan);
     bool done = nt == 0, ev1 = false;
-    if (!done && plan.ok && S.opt_mode == 0 && !S.sticky_exact) {
+    if (!done && plan.ok && S.opt.mode == 0 && !S.sticky_exact) {
         BucketEmit be;
         if (int rc = bucket_fast_begin(c, S, plan, &be)) return rc;
         if (int rc = launch_tiles_buckets(c, bases_dev, nt, k, w, be)) return rc;
@@ -815,7 +815,7 @@ static int sketch_reads_device(dg_ctx *c, const char *bases_dev, const int64_t *
         else if (outcome == 1) S.sticky_exact = true;                  // this ctx's read sets have hashes too frequent for the stride
         else plan.ok = false;
     }
-    if (!done && plan.ok && S.opt_mode != 1) {
+    if (!done && plan.ok && S.opt.mode != 1) {
         if (int rc = launch_tiles_sparse<false>(c, bases_dev, nt, n_win, k, w, 1)) return rc;
         if (!ev1) { DG_HIP(hipEventRecord(S.ev[1], s)); ev1 = true; }
         if (int rc = bucket_exact_scatter(c, S, plan, nt)) return rc;
@@ -886,20 +886,33 @@ extern "C" int dg_sketch_reads_dev(dg_ctx *c, const char *bases_dev, const int64
     return DG_OK;
 }
 
-extern "C" int dg_sketch_set_option(dg_ctx *c, const char *name, int64_t value) {
+// One row per option: its SketchOptions field, its range and the message for a value outside it, and whether a new value lets this
+// ctx try the tile kernel's buckets again (sticky_exact).
+static const struct SketchOptionName { const char *name; int64_t SketchOptions::*field; int64_t lo, hi; const char *range; bool clears_sticky_exact; } sketch_option_names[] = {
+    {"spectrum_mode", &SketchOptions::mode, 0, 2, "spectrum_mode must be 0, 1 or 2", true},
+    {"bucket_bits", &SketchOptions::bucket_bits, 0, 15, "bucket_bits must be 0 (automatic) .. 15", false},
+    {"bucket_stride", &SketchOptions::stride, 0, 1 << 20, "bucket_stride out of range", true},
+    {"host_buckets", &SketchOptions::host_buckets, 0, 256, "host_buckets must be 0 (default 256) .. 256", false},
+    {"spill_cap", &SketchOptions::spill_cap, -1, (int64_t)1 << 28, "spill_cap must be -1 (none) .. 2^28, 0 = default", true},
+    {"residual_cap", &SketchOptions::residual_cap, -1, 1024, "residual_cap must be -1 (none) .. 1024, 0 = default", false},
+};
+static int sketch_option(dg_ctx *c, const char *what, const char *name, const int64_t *set, int64_t *get) {   // set or get, the other is null
     if (int rc = bind(c)) return rc;
-    if (!name) { set_error("dg_sketch_set_option: null name"); return DG_ERR_ARG; }
+    if (!name || (!set && !get)) { set_error("%s: null name", what); return DG_ERR_ARG; }
     SketchState &S = state(c);
-    const std::string n(name);
-    if (n == "spectrum_mode") { if (value < 0 || value > 2) { set_error("spectrum_mode must be 0, 1 or 2"); return DG_ERR_ARG; } S.opt_mode = (int)value; S.sticky_exact = false; }
-    else if (n == "bucket_bits") { if (value < 0 || value > 15) { set_error("bucket_bits must be 0 (automatic) .. 15"); return DG_ERR_ARG; } S.opt_bucket_bits = (int)value; }
-    else if (n == "bucket_stride") { if (value < 0 || value > (1 << 20)) { set_error("bucket_stride out of range"); return DG_ERR_ARG; } S.opt_stride = (int)value; S.sticky_exact = false; }
-    else if (n == "host_buckets") { if (value < 0 || value > 256) { set_error("host_buckets must be 0 (default 256) .. 256"); return DG_ERR_ARG; } S.opt_host_buckets = (int)value; }
-    else if (n == "spill_cap") { if (value < -1 || value > ((int64_t)1 << 28)) { set_error("spill_cap must be -1 (none) .. 2^28, 0 = default"); return DG_ERR_ARG; } S.opt_spill_cap = value; S.sticky_exact = false; }
-    else if (n == "residual_cap") { if (value < -1 || value > 1024) { set_error("residual_cap must be -1 (none) .. 1024, 0 = default"); return DG_ERR_ARG; } S.opt_residual_cap = (int)value; }
-    else { set_error("dg_sketch_set_option: unknown option '%s'", name); return DG_ERR_ARG; }
-    return DG_OK;
+    for (const SketchOptionName &o : sketch_option_names) {
+        if (strcmp(name, o.name)) continue;
+        if (!set) { *get = S.opt.*o.field; return DG_OK; }
+        if (*set < o.lo || *set > o.hi) { set_error("%s", o.range); return DG_ERR_ARG; }
+        S.opt.*o.field = *set;
+        if (o.clears_sticky_exact) S.sticky_exact = false;
+        return DG_OK;
+    }
+    set_error("%s: unknown option '%s'", what, name);
+    return DG_ERR_ARG;
 }
+extern "C" int dg_sketch_set_option(dg_ctx *c, const char *name, int64_t value) { return sketch_option(c, "dg_sketch_set_option", name, &value, nullptr); }
+extern "C" int dg_sketch_get_option(dg_ctx *c, const char *name, int64_t *value) { return sketch_option(c, "dg_sketch_get_option", name, nullptr, value); }
 
 extern "C" int dg_sketch_get_stat(dg_ctx *c, const char *name, int64_t *value) {
     if (!c || !c->sk || !name || !value) { set_error("dg_sketch_get_stat: no state"); return DG_ERR_STATE; }

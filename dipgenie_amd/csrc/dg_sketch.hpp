@@ -11,6 +11,8 @@ struct BucketEmit { uint32_t *fill = nullptr; uint64_t *bk_hash = nullptr; uint3
                     uint32_t *spill_n = nullptr; uint64_t *spill_hash = nullptr; uint32_t *spill_read = nullptr; uint32_t spill_cap = 0; };
 struct BucketPlan { bool ok = false, has_multi = false; int bbits = 0, sbits = 0, B = 0, G = 0; uint32_t stride = 0, residual_cap = 0, spill_cap = 0; };
 
+struct SketchOptions { int64_t mode = 0, bucket_bits = 0, stride = 0, residual_cap = 0, host_buckets = 0, spill_cap = 0; };   // dg_sketch_set_option / dg_sketch_get_option (names and ranges: dg_sketch.hip); 0 = each one's default
+
 struct SketchState {
     DevBuf d_bases, d_off, d_seq_tiles, d_seq_wins, d_seq_tile0, d_seq_win0, d_tiles, d_tile_cnt, d_tile_base, d_tile_sparse, d_hash, d_aux, d_hash2, d_aux2, d_tmp, d_flag, d_uniq, d_cnt, d_n, d_kmers, d_out;
     // bucketed spectrum (dg_sketch_spectrum.hip): bucket arrays, the (workgroup x bucket) count matrix, per-bucket tables
@@ -18,9 +20,8 @@ struct SketchState {
     bool attr_set = false;              // the kernels' dynamic-LDS limits are raised once per ctx
     bool sticky_exact = false;          // a bucket ran over its stride once: this ctx places buckets exactly from then on
     int64_t *h_status = nullptr;        // pinned: {pairs, distinct hashes, buckets left to the host, a bucket ran over its stride}
-    // options (dg_sketch_set_option) and what the last dg_sketch_reads* call did (dg_sketch_get_stat)
-    int opt_mode = 0, opt_bucket_bits = 0, opt_stride = 0, opt_residual_cap = 0, opt_host_buckets = 0;
-    int64_t opt_spill_cap = 0;
+    SketchOptions opt;
+    // what the last dg_sketch_reads* call did (dg_sketch_get_stat)
     int64_t stat_path = 0, stat_buckets = 0, stat_overflow = 0, stat_spilled = 0;
     dg_sketch_timing timing;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};

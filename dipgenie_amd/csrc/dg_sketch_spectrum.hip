@@ -387,17 +387,17 @@ int common_buffers(dg_ctx *c, SketchState &S, const BucketPlan &plan) {
 void bucket_plan(const SketchState &S, int64_t n_reads, int64_t nt, int64_t n_win, int64_t n_multi, int w, BucketPlan *plan) {
     *plan = BucketPlan{};
     plan->has_multi = n_multi > 0;
-    if (S.opt_mode == 1 || nt <= 0 || n_win >= ((int64_t)1 << 31) || n_reads >= ((int64_t)1 << 31)) return;
+    if (S.opt.mode == 1 || nt <= 0 || n_win >= ((int64_t)1 << 31) || n_reads >= ((int64_t)1 << 31)) return;
     // ~2.5 k pairs per bucket at the emission density of random sequence (2 / (w + 1) per window)
     const int64_t n_est = std::max<int64_t>(nt, 2 * n_win / (w + 1));
-    int bbits = S.opt_bucket_bits > 0 ? S.opt_bucket_bits : bits_for((uint64_t)((n_est + 2559) / 2560 - 1));
+    int bbits = S.opt.bucket_bits > 0 ? (int)S.opt.bucket_bits : bits_for((uint64_t)((n_est + 2559) / 2560 - 1));
     plan->bbits = std::max(1, std::min(15, bbits));
     plan->sbits = SBITS;
     plan->B = 1 << plan->bbits;
     plan->G = (int)std::min<int64_t>(G_MAX, (nt + 127) / 128);
-    plan->stride = S.opt_stride > 0 ? (uint32_t)S.opt_stride : (uint32_t)STRIDE;
-    plan->residual_cap = S.opt_residual_cap < 0 ? 0u : S.opt_residual_cap > 0 ? (uint32_t)S.opt_residual_cap : (uint32_t)RCAP;
-    plan->spill_cap = S.opt_spill_cap < 0 ? 0u : S.opt_spill_cap > 0 ? (uint32_t)S.opt_spill_cap : (uint32_t)SPILL_CAP;
+    plan->stride = S.opt.stride > 0 ? (uint32_t)S.opt.stride : (uint32_t)STRIDE;
+    plan->residual_cap = S.opt.residual_cap < 0 ? 0u : S.opt.residual_cap > 0 ? (uint32_t)S.opt.residual_cap : (uint32_t)RCAP;
+    plan->spill_cap = S.opt.spill_cap < 0 ? 0u : S.opt.spill_cap > 0 ? (uint32_t)S.opt.spill_cap : (uint32_t)SPILL_CAP;
     plan->ok = true;
 }
 
@@ -465,7 +465,7 @@ int bucket_finish(dg_ctx *c, SketchState &S, const BucketPlan &plan, bool fast, 
     if (S.h_status[3]) { *outcome = 1; return DG_OK; }                 // a bucket ran over its stride (pairs were dropped)
     const int64_t n_ovf = S.h_status[2];
     S.stat_overflow = n_ovf;
-    if (n_ovf > (S.opt_host_buckets > 0 ? std::min(S.opt_host_buckets, OVF_MAX) : OVF_MAX)) { *outcome = 2; return DG_OK; }
+    if (n_ovf > (S.opt.host_buckets > 0 ? std::min<int64_t>(S.opt.host_buckets, OVF_MAX) : OVF_MAX)) { *outcome = 2; return DG_OK; }
     if (n_ovf > 0) {
         std::vector<uint32_t> list((size_t)n_ovf), tab(fast ? (size_t)B * FILL_PAD : (size_t)B + 1);
         DG_HIP(hipMemcpyAsync(list.data(), ovf + 2, 4 * (size_t)n_ovf, hipMemcpyDeviceToHost, s));

@@ -169,8 +169,11 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
- *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning */
+ *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning
+ * This list is documentation: struct DpOptions (csrc/dg_dp.hpp) is authoritative for the defaults, the key table beside dg_dp_set_option for the clamps. */
 int dg_dp_set_option(dg_ctx *, const char *key, int64_t value);
+/* the stored value of a key (what a set clamped or rounded it to), so that set(key, get(key)) changes nothing; DG_ERR_ARG like the setter */
+int dg_dp_get_option(dg_ctx *, const char *key, int64_t *value);
 /* parity: FNV-1a digests of the 12 tables built by dg_dp_load_graph (level descriptors, in-CSR offsets / sources / destinations,
  * coloured transitions, their delta blocks, column groups, dead columns, heavy rows, row records, row in-edge matrices, slot
  * records): the device construction and the host construction (option host_tables) must agree.  out has n >= 12 words. */
@@ -221,8 +224,10 @@ int dg_sketch_get_timing(dg_ctx *, dg_sketch_timing *);
  *                          leave more buckets to the host's per-segment finish
  *   host_buckets n         0 (default): up to 256 buckets may be left to the host before the generic path takes over; 1..256
  * dg_sketch_get_stat names, about the last dg_sketch_reads / dg_sketch_reads_dev call: spectrum_path (0 buckets filled by the
- * tile kernel, 1 exact placement, 2 generic), buckets, overflow_buckets (finished by the host per segment), spilled_pairs */
+ * tile kernel, 1 exact placement, 2 generic), buckets, overflow_buckets (finished by the host per segment), spilled_pairs
+ * This list is documentation: the option table beside dg_sketch_set_option (csrc/dg_sketch.hip) is authoritative for names, ranges and defaults. */
 int dg_sketch_set_option(dg_ctx *, const char *name, int64_t value);
+int dg_sketch_get_option(dg_ctx *, const char *name, int64_t *value);   /* the stored value (0 = the default of every option) */
 int dg_sketch_get_stat(dg_ctx *, const char *name, int64_t *value);
 
 /* Device-resident variants for the read-sharded multi-GPU path (one rank per GPU; collectives are

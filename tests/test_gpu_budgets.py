@@ -81,18 +81,12 @@ def test_library_every_budget_equals_the_oracle(gpu_ctx):
 @pytest.mark.parametrize("plane_limit", [1, 0])
 @pytest.mark.parametrize("mode", ["chunked", "segmented"])
 def test_every_lattice_mode_every_walker(gpu_ctx, mode, plane_limit, lean):
-    defaults = {"lattice_chunk_cells": 1 << 32, "segment_cells": 0, "lean_chain": 1, "plane_limit": 1}
-    try:
-        gpu_ctx.dp_set_option("lean_chain", lean)
-        gpu_ctx.dp_set_option("plane_limit", plane_limit)
-        for q in (3, 8, 12):
-            g = graph(q)
-            want = oracle_per_budget(q)
-            cells = int(orc.dp_solve(g)["cells"])
-            if mode == "chunked":
-                gpu_ctx.dp_set_option("lattice_chunk_cells", max(2, cells // 5))
-            else:
-                gpu_ctx.dp_set_option("segment_cells", max(1, cells // 7))
+    for q in (3, 8, 12):
+        g = graph(q)
+        want = oracle_per_budget(q)
+        cells = int(orc.dp_solve(g)["cells"])
+        cut = {"lattice_chunk_cells": max(2, cells // 5)} if mode == "chunked" else {"segment_cells": max(1, cells // 7)}
+        with gpu_ctx.dp_options(lean_chain=lean, plane_limit=plane_limit, **cut):
             gpu_ctx.dp_load_graph(g)
             rnd = random.Random(q)
             full = list(range(g.R + 1))
@@ -107,9 +101,6 @@ def test_every_lattice_mode_every_walker(gpu_ctx, mode, plane_limit, lean):
                 for r, out in zip(subset, outs):
                     assert out.key() == want[r], (q, mode, plane_limit, lean, subset, r)
                 assert list(gpu_ctx.dp_budget_values()) == [w[0] for w in want], (q, mode)
-    finally:
-        for k, v in defaults.items():
-            gpu_ctx.dp_set_option(k, v)
 
 
 def test_errors_leave_the_context_usable(gpu_ctx):
@@ -134,17 +125,12 @@ def test_errors_leave_the_context_usable(gpu_ctx):
     assert gpu_ctx.dp_run().key() == want[g.R]
     assert [o.key() for o in gpu_ctx.dp_run_budgets([2, g.R])] == [want[2], want[g.R]]
     # a damaged lattice: dg_dp_run_budgets fails as dg_dp_run does
-    try:
-        gpu_ctx.dp_set_option("test_poison_level", g.n_levels - 1)
-        gpu_ctx.dp_set_option("test_poison_byte", 0xFF)
+    with gpu_ctx.dp_options(test_poison_level=g.n_levels - 1, test_poison_byte=0xFF):
         gpu_ctx.dp_load_graph(g)
         with pytest.raises(capi.DgError, match="corrupt|disagree"):
             gpu_ctx.dp_run()
         with pytest.raises(capi.DgError, match="(corrupt|disagree).*budget"):
             gpu_ctx.dp_run_budgets(range(g.R + 1))
-    finally:
-        gpu_ctx.dp_set_option("test_poison_level", 0)
-        gpu_ctx.dp_set_option("test_poison_byte", 0xFF)
     gpu_ctx.dp_load_graph(g)
     assert gpu_ctx.dp_run().key() == want[g.R]
 

@@ -40,19 +40,11 @@ def test_config5_panel_one_answer_in_every_execution_mode(c5_panel, gpu_ctx):
     assert ref["value"] == summ["dp_value"]
     modes = [{}, {"segment_cells": max(1, int(ref["cells"]) // 7)}, {"segment_cells": max(1, int(ref["cells"]) // 23), "plane_limit": 0},
              {"segment_cells": max(1, int(ref["cells"]) // 23), "graph_batch": 0}, {"graph_batch": 0}, {"lattice_chunk_cells": max(2, int(ref["cells"]) // 5)}, {"fast": 0}]
-    try:
-        gpu_ctx.dp_set_option("digest", 1)
-        for m in modes:
-            for k, v in m.items():
-                gpu_ctx.dp_set_option(k, v)
+    for m in modes:
+        with gpu_ctx.dp_options(digest=1, **m):
             out = gpu_ctx.dp_solve(g)
             assert (out.value, out.s_het, out.p1, out.p2) == (ref["value"], ref["s_het"], ref["p1"], ref["p2"]), m
             assert np.array_equal(gpu_ctx.dp_level_digest(g.n_levels)[1:], ref["digest"][1:]), m
-            for k in m:
-                gpu_ctx.dp_set_option(k, {"segment_cells": 0, "graph_batch": -1, "lattice_chunk_cells": 1 << 32, "fast": 1, "plane_limit": 1}[k])
-    finally:
-        for k, v in {"digest": 0, "segment_cells": 0, "graph_batch": -1, "lattice_chunk_cells": 1 << 32, "fast": 1, "plane_limit": 1}.items():
-            gpu_ctx.dp_set_option(k, v)
 
 
 def test_config5_5mbp_tier_naturally_segmented(built_hip, tmp_path_factory):

@@ -90,11 +90,6 @@ def _spectrum_reads(rng):
     return reads
 
 
-def _reset_spectrum_options(ctx):
-    for key in ("spectrum_mode", "bucket_bits", "bucket_stride", "residual_cap", "host_buckets", "spill_cap"):
-        ctx.sketch_set_option(key, 0)
-
-
 @pytest.mark.parametrize("mode", list(SPECTRUM_MODES))
 def test_sketch_spectrum_paths_agree(gpu_ctx, mode):
     """Sp_R from hash-range buckets resolved in LDS tables == the stable radix sort of all pairs == the oracle, in every
@@ -103,13 +98,9 @@ def test_sketch_spectrum_paths_agree(gpu_ctx, mode):
     reads = _spectrum_reads(rng)
     ho, co = orc.sketch_reads(reads, 21, 11)
     opts, want_path = SPECTRUM_MODES[mode]
-    try:
-        for key, v in opts.items():
-            gpu_ctx.sketch_set_option(key, v)
+    with gpu_ctx.sketch_options(**opts):
         hg, cg = gpu_ctx.sketch_reads(reads, 21, 11)
         path, ovf, spilled = gpu_ctx.sketch_stat("spectrum_path"), gpu_ctx.sketch_stat("overflow_buckets"), gpu_ctx.sketch_stat("spilled_pairs")
-    finally:
-        _reset_spectrum_options(gpu_ctx)
     assert np.array_equal(hg, ho) and np.array_equal(cg, co)
     assert path == want_path
     if mode.startswith("host_segments"):
@@ -129,14 +120,13 @@ def test_sketch_spectrum_heavy_hitters(gpu_ctx):
     ctx = capi.Context(0)
     hg, cg = ctx.sketch_reads(reads, 31, 25)
     assert ctx.sketch_stat("spectrum_path") == 0 and ctx.sketch_stat("spilled_pairs") > 0 and ctx.sketch_stat("overflow_buckets") == 0
-    ctx.sketch_set_option("spill_cap", 100)
-    hx, cx = ctx.sketch_reads(reads, 31, 25)
-    assert ctx.sketch_stat("spectrum_path") == 1
-    ctx.sketch_reads(reads[:5000], 31, 25)
-    assert ctx.sketch_stat("spectrum_path") == 1                        # sticky
-    ctx.sketch_set_option("spill_cap", 0)
-    ctx.sketch_set_option("spectrum_mode", 1)
-    h2, c2 = ctx.sketch_reads(reads, 31, 25)
+    with ctx.sketch_options(spill_cap=100):
+        hx, cx = ctx.sketch_reads(reads, 31, 25)
+        assert ctx.sketch_stat("spectrum_path") == 1
+        ctx.sketch_reads(reads[:5000], 31, 25)
+        assert ctx.sketch_stat("spectrum_path") == 1                    # sticky
+    with ctx.sketch_options(spectrum_mode=1):
+        h2, c2 = ctx.sketch_reads(reads, 31, 25)
     assert np.array_equal(hg, h2) and np.array_equal(cg, c2) and np.array_equal(hx, h2) and np.array_equal(cx, c2)
     ho, co = orc.sketch_reads(reads[:3000] + [one], 31, 25)
     h1, c1 = orc.sketch_reads([one], 31, 25)
@@ -159,13 +149,9 @@ def test_sketch_spectrum_multi_tile_reads(gpu_ctx, mode):
     reads += [_rnd(rng, 150) for _ in range(300)] + [reads[0]] * 50
     ho, co = orc.sketch_reads(reads, 21, 11)
     opts, want_path = SPECTRUM_MODES[mode]
-    try:
-        for key, v in opts.items():
-            gpu_ctx.sketch_set_option(key, v)
+    with gpu_ctx.sketch_options(**opts):
         hg, cg = gpu_ctx.sketch_reads(reads, 21, 11)
         assert gpu_ctx.sketch_stat("spectrum_path") == want_path
-    finally:
-        _reset_spectrum_options(gpu_ctx)
     assert np.array_equal(hg, ho) and np.array_equal(cg, co)
 
 
@@ -209,16 +195,15 @@ def test_sketch_full_size_properties(gpu_ctx):
 
 # ------------------------------------------------------------------------------------- DP
 def _dp_both(ctx, g, digest=True):
-    ctx.dp_set_option("digest", 1 if digest else 0)
-    out = ctx.dp_solve(g)
-    ref = orc.dp_solve(g, want_digest=digest)
-    assert (out.value, out.s_het) == (ref["value"], ref["s_het"])
-    assert out.p1 == ref["p1"] and out.p2 == ref["p2"]
-    assert (out.cells, out.relaxations) == (ref["cells"], ref["relaxations"])
-    if digest:
-        dg = ctx.dp_level_digest(g.n_levels)
-        assert np.array_equal(dg[1:], ref["digest"][1:])
-    ctx.dp_set_option("digest", 0)
+    with ctx.dp_options(digest=1 if digest else 0):
+        out = ctx.dp_solve(g)
+        ref = orc.dp_solve(g, want_digest=digest)
+        assert (out.value, out.s_het) == (ref["value"], ref["s_het"])
+        assert out.p1 == ref["p1"] and out.p2 == ref["p2"]
+        assert (out.cells, out.relaxations) == (ref["cells"], ref["relaxations"])
+        if digest:
+            dg = ctx.dp_level_digest(g.n_levels)
+            assert np.array_equal(dg[1:], ref["digest"][1:])
     return out
 
 
@@ -280,23 +265,18 @@ def test_dp_device_tables_equal_host_tables(gpu_ctx):
              dict(max_width=3, n_levels=6, R=1, extra_edges=300.0, dup_edges=False), dict(min_width=20, max_width=24, n_levels=8, R=2, extra_edges=70.0)]
     graphs = [graphgen.random_levelized(9100 + q, **kw) for q, kw in enumerate(cases)]
     graphs += [capi.DpGraphArrays.load(os.path.join(HERE, "golden", n)) for n in ("toy2_R2.dpg", "toy1_k5w3_R2.dpg")]
-    try:
-        for rowx in (1, 0):
-            gpu_ctx.dp_set_option("rowx", rowx)
-            for q, g in enumerate(graphs):
-                gpu_ctx.dp_set_option("host_tables", 1)
+    for rowx in (1, 0):
+        for q, g in enumerate(graphs):
+            with gpu_ctx.dp_options(rowx=rowx, host_tables=1):
                 gpu_ctx.dp_load_graph(g)
                 want = gpu_ctx.dp_table_digest()
-                gpu_ctx.dp_set_option("host_tables", 0)
+            with gpu_ctx.dp_options(rowx=rowx, host_tables=0):
                 gpu_ctx.dp_load_graph(g)
                 got = gpu_ctx.dp_table_digest()
                 assert got == want, (rowx, q, [t for t in got if got[t] != want[t]])
                 out = gpu_ctx.dp_run()
                 ref = orc.dp_solve(g)
                 assert (out.value, out.s_het, out.p1, out.p2, out.cells, out.relaxations) == (ref["value"], ref["s_het"], ref["p1"], ref["p2"], ref["cells"], ref["relaxations"]), q
-    finally:
-        gpu_ctx.dp_set_option("rowx", 1)
-        gpu_ctx.dp_set_option("host_tables", 0)
 
 
 @pytest.mark.parametrize("mode", ["generic", "no_adaptive", "no_coop", "force_coop", "no_rowx", "general_chain", "no_l2_prefetch", "no_delta_overlap", "forced_delta_overlap", "no_far_prefetch", "host_tables"])
@@ -305,9 +285,7 @@ def test_dp_alternative_kernels(gpu_ctx, mode):
     matrices and the general chain walk (in place of the lean one) must all give the oracle's answer"""
     opts = {"generic": {"fast": 0}, "no_adaptive": {"adaptive_rc": 0}, "no_coop": {"coop": 0}, "force_coop": {"coop": 2}, "no_rowx": {"rowx": 0},
             "general_chain": {"lean_chain": 0}, "no_l2_prefetch": {"l2_prefetch": 0}, "no_delta_overlap": {"delta_overlap": 0}, "forced_delta_overlap": {"delta_overlap": 2}, "no_far_prefetch": {"pf_far": 0}, "host_tables": {"host_tables": 1}}[mode]
-    try:
-        for k, v in opts.items():
-            gpu_ctx.dp_set_option(k, v)
+    with gpu_ctx.dp_options(**opts):
         for seed, kw in [(1, dict(max_width=12, n_levels=300, R=5)), (2, dict(max_width=40, n_levels=60, R=18, p_w1=0.5)),
                          (3, dict(max_width=6, n_levels=2000, R=3, p_colour=0.2)), (4, dict(R=33, max_width=20, n_levels=50))]:
             g = graphgen.random_levelized(7000 + seed, **kw)
@@ -318,9 +296,6 @@ def test_dp_alternative_kernels(gpu_ctx, mode):
         for seed, kw in [(5, dict(max_width=30, n_levels=120, R=18, p_w1=0.3, p_colour=0.5)), (6, dict(max_width=60, n_levels=40, R=32, p_w1=0.6)),
                          (7, dict(max_width=64, n_levels=30, R=3, p_w1=0.5, p_colour=0.8)), (8, dict(max_width=70, n_levels=12, R=4, extra_edges=3.0))]:
             _dp_both(gpu_ctx, graphgen.random_levelized(7100 + seed, **kw))
-    finally:
-        for k, v in {"fast": 1, "adaptive_rc": 1, "coop": 1, "rowx": 1, "lean_chain": 1, "l2_prefetch": 6, "delta_overlap": 1, "pf_far": 128, "host_tables": 0}.items():
-            gpu_ctx.dp_set_option(k, v)
 
 
 DP_SHAPES = [dict(), dict(max_width=30, n_levels=40, R=6), dict(max_width=3, n_levels=200, R=2), dict(R=0), dict(p_w1=0.9, R=18),
@@ -342,16 +317,11 @@ def test_dp_shapes_every_level_digest(gpu_ctx, mode):
     opts = {"default": {}, "no_coop": {"coop": 0}, "plain_launches": {"graph_batch": 0}, "host_tables": {"host_tables": 1}, "no_rowx": {"rowx": 0}}[mode]
     with pytest.raises(capi.DgError):
         gpu_ctx.dp_set_option("sym", 1)      # the symmetric form of the sweep was removed
-    try:
-        for k, v in opts.items():
-            gpu_ctx.dp_set_option(k, v)
+    with gpu_ctx.dp_options(**opts):
         for q, kw in enumerate(DP_SHAPES):
             _dp_both(gpu_ctx, graphgen.random_levelized(9700 + q, **kw))
         for k in (90, 200):
             _dp_both(gpu_ctx, _fan_in_graph(k))
-    finally:
-        for k, v in {"coop": 1, "graph_batch": -1, "host_tables": 0, "rowx": 1}.items():
-            gpu_ctx.dp_set_option(k, v)
 
 
 @pytest.mark.parametrize("lean", [1, 0])
@@ -361,31 +331,24 @@ def test_dp_corrupt_lattice_is_an_error_not_a_fault(gpu_ctx, lean):
     (a vertex with one in-edge then yields the all-ones guard word, whose ids lie outside every level), 0x30 = ranks beyond any list"""
     g = graphgen.random_levelized(9300, max_width=12, n_levels=120, R=4, p_colour=0.5)
     ref = orc.dp_solve(g)
-    try:
-        gpu_ctx.dp_set_option("lean_chain", lean)
+    with gpu_ctx.dp_options(lean_chain=lean):
         for level in (119, 60, 7, 1):
             for byte in (0xFF, 0x01, 0x30):
-                gpu_ctx.dp_set_option("test_poison_level", level)
-                gpu_ctx.dp_set_option("test_poison_byte", byte)
-                gpu_ctx.dp_load_graph(g)
-                try:
-                    out = gpu_ctx.dp_run()
-                except capi.DgError as e:
-                    assert "corrupt" in str(e) or "disagree" in str(e), (level, byte, str(e))
-                else:
-                    # a poisoned level the answer path happens to cross with an in-range word may still decode: the run then ends
-                    # normally only if the walked path is a path of the graph that re-scores to the DP value (dg_dp_run checks both),
-                    # so the value is the sweep's; level 119 / byte 0xFF can never pass
-                    assert byte != 0xFF, (level, byte)
-                    assert out.value == ref["value"], (level, byte)
-        gpu_ctx.dp_set_option("test_poison_level", 0)
-        gpu_ctx.dp_load_graph(g)
+                with gpu_ctx.dp_options(test_poison_level=level, test_poison_byte=byte):
+                    gpu_ctx.dp_load_graph(g)
+                    try:
+                        out = gpu_ctx.dp_run()
+                    except capi.DgError as e:
+                        assert "corrupt" in str(e) or "disagree" in str(e), (level, byte, str(e))
+                    else:
+                        # a poisoned level the answer path happens to cross with an in-range word may still decode: the run then ends
+                        # normally only if the walked path is a path of the graph that re-scores to the DP value (dg_dp_run checks both),
+                        # so the value is the sweep's; level 119 / byte 0xFF can never pass
+                        assert byte != 0xFF, (level, byte)
+                        assert out.value == ref["value"], (level, byte)
+        gpu_ctx.dp_load_graph(g)                              # (no level poisoned any more)
         out = gpu_ctx.dp_run()
         assert (out.value, out.s_het, out.p1, out.p2) == (ref["value"], ref["s_het"], ref["p1"], ref["p2"])
-    finally:
-        gpu_ctx.dp_set_option("test_poison_level", 0)
-        gpu_ctx.dp_set_option("test_poison_byte", 0xFF)
-        gpu_ctx.dp_set_option("lean_chain", 1)
 
 
 def test_dp_launch_profile_counts_every_level(gpu_ctx):
@@ -398,12 +361,9 @@ def test_dp_launch_profile_counts_every_level(gpu_ctx):
         gpu_ctx.dp_run()
         profiles.append(gpu_ctx.dp_launch_profile())
     assert sum(profiles[0].values()) == g.n_levels - 1 and profiles[0] == profiles[1] == profiles[2], profiles
-    try:
-        gpu_ctx.dp_set_option("graph_batch", 0)
+    with gpu_ctx.dp_options(graph_batch=0):
         gpu_ctx.dp_run()
         assert gpu_ctx.dp_launch_profile() == profiles[0]
-    finally:
-        gpu_ctx.dp_set_option("graph_batch", -1)
 
 
 def test_dp_large_recombination_budget(gpu_ctx):
@@ -416,14 +376,11 @@ def test_dp_large_recombination_budget(gpu_ctx):
 def test_dp_segmented_lattice(gpu_ctx, seg_cells):
     """checkpoint + recompute (lattices beyond HBM, BASELINE config 5): forced here with tiny segments; value, s_het,
     edge lists and every level digest must not change"""
-    try:
-        gpu_ctx.dp_set_option("segment_cells", seg_cells)
+    with gpu_ctx.dp_options(segment_cells=seg_cells):
         for seed, kw in [(11, dict(max_width=14, n_levels=400, R=6)), (12, dict(max_width=45, n_levels=70, R=18, p_w1=0.5)),
                          (13, dict(n_levels=2, R=2)), (14, dict(max_width=8, n_levels=3000, R=3, p_colour=0.3)), (15, dict(R=33, max_width=25, n_levels=90))]:
             _dp_both(gpu_ctx, graphgen.random_levelized(8000 + seed, **kw))
         _dp_both(gpu_ctx, capi.DpGraphArrays.load(os.path.join(HERE, "golden", "toy1_k5w3_R2.dpg")))
-    finally:
-        gpu_ctx.dp_set_option("segment_cells", 0)
 
 
 @pytest.mark.parametrize("cap,seg", [(1, 0), (400, 0), (20000, 0), (400, 5000), (1, 1)])
@@ -431,34 +388,22 @@ def test_dp_delta_windows(gpu_ctx, cap, seg):
     """score-delta matrices that outgrow their budget are recomputed window by window right before the levels that read
     them (chr22-scale panels: hundreds of GB otherwise) -- forced here with tiny budgets, alone and together with a
     segmented lattice (whose second pass re-enters windows half way)"""
-    try:
-        gpu_ctx.dp_set_option("delta_cap_entries", cap)
-        gpu_ctx.dp_set_option("segment_cells", seg)
+    with gpu_ctx.dp_options(delta_cap_entries=cap, segment_cells=seg):
         for seed, kw in [(31, dict(max_width=14, n_levels=300, R=6, p_colour=0.6)), (32, dict(max_width=45, n_levels=60, R=18, p_w1=0.5, p_colour=0.9)),
                          (33, dict(n_levels=2, R=2)), (34, dict(max_width=8, n_levels=2000, R=3, p_colour=0.3)), (35, dict(R=33, max_width=25, n_levels=90, p_colour=0.1))]:
             _dp_both(gpu_ctx, graphgen.random_levelized(8200 + seed, **kw))
         _dp_both(gpu_ctx, capi.DpGraphArrays.load(os.path.join(HERE, "golden", "toy1_k5w3_R2.dpg")))
-    finally:
-        gpu_ctx.dp_set_option("delta_cap_entries", 0)
-        gpu_ctx.dp_set_option("segment_cells", 0)
 
 
 @pytest.mark.parametrize("ahead,cap,seg", [(0, 0, 0), (1, 0, 0), (7, 0, 0), (7, 400, 0), (3, 400, 5000), (1000, 0, 5000)])
 def test_dp_sweep_lookahead(gpu_ctx, ahead, cap, seg):
     """the sweep streams the graph tables of the next batch of levels through the Infinity Cache (reads only): any batch
     size, with delta windows and lattice segments cutting the ranges, leaves every result and level digest unchanged"""
-    try:
-        gpu_ctx.dp_set_option("warm_ahead", ahead)
-        gpu_ctx.dp_set_option("delta_cap_entries", cap)
-        gpu_ctx.dp_set_option("segment_cells", seg)
+    with gpu_ctx.dp_options(warm_ahead=ahead, delta_cap_entries=cap, segment_cells=seg):
         for seed, kw in [(41, dict(max_width=14, n_levels=300, R=6, p_colour=0.6)), (42, dict(max_width=45, n_levels=60, R=18, p_w1=0.5, p_colour=0.9)),
                          (43, dict(n_levels=2, R=2)), (44, dict(max_width=8, n_levels=2000, R=3, p_colour=0.3))]:
             _dp_both(gpu_ctx, graphgen.random_levelized(8300 + seed, **kw))
         _dp_both(gpu_ctx, capi.DpGraphArrays.load(os.path.join(HERE, "golden", "toy1_k5w3_R2.dpg")))
-    finally:
-        gpu_ctx.dp_set_option("warm_ahead", 128)
-        gpu_ctx.dp_set_option("delta_cap_entries", 0)
-        gpu_ctx.dp_set_option("segment_cells", 0)
 
 
 @pytest.mark.parametrize("batch,seg,chunk", [(0, 0, 0), (1, 0, 0), (7, 0, 0), (1000, 0, 0), (7, 5000, 0), (5, 0, 3000)])
@@ -466,11 +411,7 @@ def test_dp_graph_batches(gpu_ctx, batch, seg, chunk):
     """level launches captured into hipGraphs and replayed: the capturing pass and the replaying passes give the oracle's
     answer and level digests, also with lattice segments / pool chunks cutting the batches, and after another graph was
     loaded into the same context (stale batches must not survive)"""
-    try:
-        gpu_ctx.dp_set_option("segment_cells", seg)
-        if chunk:
-            gpu_ctx.dp_set_option("lattice_chunk_cells", chunk)
-        gpu_ctx.dp_set_option("graph_batch", batch)
+    with gpu_ctx.dp_options(segment_cells=seg, **({"lattice_chunk_cells": chunk} if chunk else {}), graph_batch=batch):
         for seed, kw in [(51, dict(max_width=14, n_levels=300, R=6, p_colour=0.6)), (52, dict(max_width=45, n_levels=60, R=18, p_w1=0.5, p_colour=0.9)),
                          (53, dict(n_levels=2, R=2)), (54, dict(max_width=8, n_levels=2000, R=3, p_colour=0.3))]:
             g = graphgen.random_levelized(8400 + seed, **kw)
@@ -478,11 +419,6 @@ def test_dp_graph_batches(gpu_ctx, batch, seg, chunk):
             first = gpu_ctx.dp_run()
             for _ in range(2):                                  # replays of the cached batches
                 assert gpu_ctx.dp_run().key() == first.key()
-    finally:
-        gpu_ctx.dp_set_option("graph_batch", -1)
-        gpu_ctx.dp_set_option("segment_cells", 0)
-        if chunk:
-            gpu_ctx.dp_set_option("lattice_chunk_cells", 1 << 31)
 
 
 def test_dp_graph_batches_fall_back_on_uncapturable_stream(gpu_ctx):
@@ -536,16 +472,13 @@ def test_dp_chunked_lattice(gpu_ctx, chunk_cells):
     """the resident back-pointer lattice is a pool of chunks mapped by a background thread while the sweep runs;
     forced here with tiny chunks (one level per chunk at 1): results and level digests must not change, also when
     the same context is reused for graphs that need more / fewer chunks, and with a reservation made up front"""
-    try:
-        gpu_ctx.dp_set_option("lattice_chunk_cells", chunk_cells)
+    with gpu_ctx.dp_options(lattice_chunk_cells=chunk_cells):
         gpu_ctx.dp_prealloc(chunk_cells * 4 * 3)
         for seed, kw in [(21, dict(max_width=14, n_levels=400, R=6)), (22, dict(max_width=45, n_levels=70, R=18, p_w1=0.5)),
                          (23, dict(n_levels=2, R=2)), (24, dict(max_width=8, n_levels=3000, R=3, p_colour=0.3)), (25, dict(R=33, max_width=25, n_levels=90)),
                          (26, dict(max_width=6, n_levels=40, R=4))]:
             _dp_both(gpu_ctx, graphgen.random_levelized(8100 + seed, **kw))
         _dp_both(gpu_ctx, capi.DpGraphArrays.load(os.path.join(HERE, "golden", "toy1_k5w3_R2.dpg")))
-    finally:
-        gpu_ctx.dp_set_option("lattice_chunk_cells", 1 << 31)
 
 
 @pytest.mark.parametrize("k", [90, 255, 256, 300])

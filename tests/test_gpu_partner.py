@@ -96,13 +96,10 @@ def test_device_equals_model(gpu_ctx, name):
     gpu_ctx.dp_load_graph(g)                             # no run before the call
     for per_slab in (None, 7, 1):
         sub = slice(None) if per_slab != 1 else slice(0, 9)
-        try:
-            if per_slab:                                 # 7: the last slab is short; a query is sized for the call's largest budget
-                gpu_ctx.dp_set_option("partner_slab_bytes", per_slab * _footprint(g, int(budgets[sub].max())))
+        opts = {"partner_slab_bytes": per_slab * _footprint(g, int(budgets[sub].max()))} if per_slab else {}   # 7: the last slab is short; a query is sized for the call's largest budget
+        with gpu_ctx.dp_options(**opts):
             rec, rows = gpu_ctx.dp_best_partners(given[sub], budgets[sub])
             rec2, none = gpu_ctx.dp_best_partners(given[sub], budgets[sub], want_paths=False)     # partners = NULL
-        finally:
-            gpu_ctx.dp_set_option("partner_slab_bytes", 0)
         assert n % 7 != 0
         bad = np.flatnonzero((_rows(rec) != want[sub]).any(axis=1))
         assert bad.size == 0, (name, per_slab, bad[:5], _rows(rec)[bad[:5]], want[sub][bad[:5]])
@@ -225,8 +222,7 @@ def test_errors(gpu_ctx):
         assert untouched()
 
     assert untouched()
-    try:
-        gpu_ctx.dp_set_option("partner_slab_bytes", 7 * _footprint(g, int(budgets.max())))       # 29 slabs
+    with gpu_ctx.dp_options(partner_slab_bytes=7 * _footprint(g, int(budgets.max()))):           # 29 slabs
         neg = budgets.copy()
         neg[123] = -1
         neg[150] = -3
@@ -248,8 +244,6 @@ def test_errors(gpu_ctx):
         # and the same call with valid paths succeeds
         rec, rows = gpu_ctx.dp_best_partners(given, budgets)
         assert np.array_equal(rec["value"], values) and np.array_equal(rows, partners)
-    finally:
-        gpu_ctx.dp_set_option("partner_slab_bytes", 0)
     with pytest.raises(ValueError):
         gpu_ctx.dp_best_partners(given[:, :-1], budgets)
     with pytest.raises(ValueError):
@@ -275,8 +269,7 @@ def test_errors(gpu_ctx):
 
 def test_a_partner_call_leaves_the_last_run_alone(gpu_ctx):
     g, m, given, budgets, values, partners = _case("levels65")
-    try:
-        gpu_ctx.dp_set_option("digest", 1)
+    with gpu_ctx.dp_options(digest=1):
         gpu_ctx.dp_load_graph(g)
         outs = [o.key() for o in gpu_ctx.dp_run_budgets(range(g.R + 1))]
         planes = gpu_ctx.dp_budget_values().copy()
@@ -296,8 +289,6 @@ def test_a_partner_call_leaves_the_last_run_alone(gpu_ctx):
         assert np.array_equal(gpu_ctx.dp_level_digest(g.n_levels), digest)
         again = gpu_ctx.dp_best_partners(given, budgets)
         assert np.array_equal(again[0], got[0]) and np.array_equal(again[1], got[1])
-    finally:
-        gpu_ctx.dp_set_option("digest", 0)
 
 
 def test_capi_layout(gpu_ctx):

@@ -75,23 +75,16 @@ def test_device_equals_model(gpu_ctx, name):
     want = m.score_many(paths)
     assert np.array_equal(want[:, 2:], rec)
     gpu_ctx.dp_load_graph(g)                             # no run before the scoring call
-    try:
-        if name in ("wide40", "fat_column", "levels600"):
-            gpu_ctx.dp_set_option("score_slab_bytes", 64 * 2 * g.n_levels * 4)      # 64 pairs per slab: 8 slabs, the last one short
+    with gpu_ctx.dp_options(**({"score_slab_bytes": 64 * 2 * g.n_levels * 4} if name in ("wide40", "fat_column", "levels600") else {})):   # 64 pairs per slab: 8 slabs, the last one short
         got = _as_rows(gpu_ctx.dp_score_paths(paths))
-    finally:
-        gpu_ctx.dp_set_option("score_slab_bytes", 0)
     bad = np.flatnonzero((got != want).any(axis=1))
     assert bad.size == 0, (name, bad[:5], got[bad[:5]], want[bad[:5]])
     assert want[:, 0].max() > 0 or name == "two_levels"
     # one pair, and the same pairs one per slab
     one = _as_rows(gpu_ctx.dp_score_paths(paths[7:8]))
     assert np.array_equal(one, want[7:8])
-    try:
-        gpu_ctx.dp_set_option("score_slab_bytes", 1)
+    with gpu_ctx.dp_options(score_slab_bytes=1):
         assert np.array_equal(_as_rows(gpu_ctx.dp_score_paths(paths[:5])), want[:5])
-    finally:
-        gpu_ctx.dp_set_option("score_slab_bytes", 0)
 
 
 ENUMERABLE = [(7115, 10, 0.5, 0.25, 0.3), (7101, 9, 0.6, 0.4, 0.2), (7129, 6, 1.0, 0.3, 0.4), (7126, 9, 0.6, 0.4, 0.2), (7100, 6, 1.0, 0.3, 0.4)]
@@ -199,8 +192,7 @@ def test_errors(gpu_ctx):
     out = np.zeros(4, capi.PAIR_SCORE)
     assert capi.lib.dg_dp_score_paths(gpu_ctx.h, None, 4, out.ctypes.data) == -1 and capi.lib.dg_dp_score_paths(gpu_ctx.h, paths.ctypes.data, 4, None) == -1
     assert capi.lib.dg_dp_score_paths(gpu_ctx.h, paths.ctypes.data, -1, out.ctypes.data) == -1
-    try:
-        gpu_ctx.dp_set_option("score_slab_bytes", 64 * 2 * L * 4)                     # 5 slabs
+    with gpu_ctx.dp_options(score_slab_bytes=64 * 2 * L * 4):                         # 5 slabs
         # the sink of path 1 of the last pair replaced by a vertex of another level: the last level of the last pair of the last slab
         bad = paths.copy()
         bad[299, 1, L - 1] = g.level_off[L - 2]
@@ -239,8 +231,6 @@ def test_errors(gpu_ctx):
         assert (out.view(np.int32) == -7).all()
         # and the same call with valid paths succeeds
         assert np.array_equal(_as_rows(gpu_ctx.dp_score_paths(paths)), want)
-    finally:
-        gpu_ctx.dp_set_option("score_slab_bytes", 0)
     with pytest.raises(ValueError):
         gpu_ctx.dp_score_paths(paths[:, :, :-1])
 
@@ -249,8 +239,7 @@ def test_a_scoring_call_leaves_the_last_run_alone(gpu_ctx):
     g = DEVICE_MODEL["levels65"]()
     m = PathModel(g)
     paths, _ = _pairs(m, 5, 200)
-    try:
-        gpu_ctx.dp_set_option("digest", 1)
+    with gpu_ctx.dp_options(digest=1):
         gpu_ctx.dp_load_graph(g)
         outs = [o.key() for o in gpu_ctx.dp_run_budgets(range(g.R + 1))]
         values = gpu_ctx.dp_budget_values().copy()
@@ -268,5 +257,3 @@ def test_a_scoring_call_leaves_the_last_run_alone(gpu_ctx):
         assert [o.key() for o in gpu_ctx.dp_run_budgets(range(g.R + 1))] == outs           # and the next run answers as before
         assert np.array_equal(gpu_ctx.dp_level_digest(g.n_levels), digest)
         assert np.array_equal(gpu_ctx.dp_score_paths(paths), got)
-    finally:
-        gpu_ctx.dp_set_option("digest", 0)

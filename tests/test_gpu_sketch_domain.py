@@ -96,12 +96,8 @@ def test_sketch_reads_kw_domain(gpu_ctx, k, w):
     assert ho.size > 0
     if w >= 128 or k > 32:
         for mode, opts in SPECTRUM_MODES.items():
-            try:
-                for key, v in opts.items():
-                    gpu_ctx.sketch_set_option(key, v)
+            with gpu_ctx.sketch_options(**opts):
                 hm, cm = gpu_ctx.sketch_reads(reads, k, w)
-            finally:
-                gpu_ctx.sketch_set_option("spectrum_mode", 0)
             assert np.array_equal(hm, hg) and np.array_equal(cm, cg), mode
 
 

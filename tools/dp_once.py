@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT)
 from dipgenie_amd import capi
 ctx = capi.Context(0)
 g = capi.DpGraphArrays.load(sys.argv[1])
-ctx.dp_set_option("fast", int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+if len(sys.argv) > 2: ctx.dp_set_option("fast", int(sys.argv[2]))
 if os.environ.get("DG_SYNC_EVERY"): ctx.dp_set_option("sync_every", int(os.environ["DG_SYNC_EVERY"]))
 if os.environ.get("DG_OPTS"):
     for kv in os.environ["DG_OPTS"].split(","):

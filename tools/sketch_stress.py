@@ -25,10 +25,10 @@ for t in range(n):
     # strides and residual lists (host-finished buckets, the give-up route)
     opts = {"spectrum_mode": int(rng.choice([0, 0, 0, 2])), "bucket_bits": int(rng.choice([0, 0, 1, 3, 6])), "bucket_stride": int(rng.choice([0, 0, 0, 64, 1024])),
             "residual_cap": int(rng.choice([0, 0, 0, 4, -1])), "host_buckets": int(rng.choice([0, 0, 3])), "spill_cap": int(rng.choice([0, 0, 0, 50, -1]))}
-    for key, v in opts.items(): ctx.sketch_set_option(key, v)
-    hg, cg = ctx.sketch_reads(reads, k, w)
-    paths[ctx.sketch_stat("spectrum_path")] += 1
-    hosted += ctx.sketch_stat("overflow_buckets") > 0
+    with ctx.sketch_options(**opts):
+        hg, cg = ctx.sketch_reads(reads, k, w)
+        paths[ctx.sketch_stat("spectrum_path")] += 1
+        hosted += ctx.sketch_stat("overflow_buckets") > 0
     ho, co = orc.sketch_reads(reads, k, w)
     ok = np.array_equal(hg, ho) and np.array_equal(cg, co)
     hap = rnd(int(rng.integers(0, 60000)), a) + rnd(int(rng.integers(0, 200)), b"ACGTN") + rnd(int(rng.integers(0, 20000)), b"ACGT")
