@@ -112,6 +112,21 @@ struct FastArgs {                                       // fast sweep kernel
 // sit in front of the other's sweep.  States on other devices do not matter.
 inline std::atomic<int> &dp_states_on_device(int device) { static std::atomic<int> n[64]; return n[device & 63]; }
 
+// One instantiated sweep kernel: rc = its chunk of recombination counts, 0 for the generic kernel (one name for all its chunks).  Defined
+// in dg_dp_sweep.hip beside the RC table and the dispatch: index() is dense (0 .. count() - 1, the order the launch profile prints).
+struct SweepVariant {
+    int rc;
+    bool general, coop;
+    int index() const;
+    std::string name() const;                           // as rocprof prints the kernel, without its DIGEST argument
+    static int count();
+    static SweepVariant at(int index);
+};
+struct SweepHist {                                      // launches per variant, by SweepVariant::index()
+    std::vector<int64_t> n = std::vector<int64_t>((size_t)SweepVariant::count(), 0);
+    void add(const SweepHist &o, int64_t sign = 1) { for (size_t q = 0; q < n.size(); ++q) n[q] += sign * o.n[q]; }
+};
+
 // Every option of dg_dp_set_option / dg_dp_get_option (key table: dg_dp_run.hip).  These initialisers are the defaults, written nowhere else.
 struct DpOptions {
     int64_t side_stream = -1;                           // side_stream: -1 = on while this is the device's only DP state (and the concurrency probe agrees), 0 = off, 1 = on
@@ -150,7 +165,6 @@ struct DpState {
     DpState(const DpState &) = delete;
     DpState &operator=(const DpState &) = delete;
     int32_t nV = 0, L = 0, R = 0, RP = 0, cap = 0;
-    int32_t rp_active = 0;                              // planes [0, rp_active) are swept by the fast kernels (= RP except while a segment is re-swept below its path's plane)
     bool loaded = false;
     bool lean_chain = false;
     // single-window score deltas computed beside the sweep: piece k (transitions of levels >= delta_piece_level[k]) signals delta_piece_ev[k]
@@ -168,8 +182,8 @@ struct DpState {
     std::vector<int64_t> ckpt_off;                     // element offset of checkpoint s (state of level seg_begin[s]-1)
     bool graph_failed = false;                          // capture or instantiation failed once: plain launches from then on
     typedef std::tuple<int, int, const void *, int> GraphKey;     // (first level, end level, biased lattice pointer, look-ahead launches left to the prefetcher | planes swept << 1)
-    std::map<GraphKey, hipGraphExec_t> graphs;                    // -> replayable batch
-    std::map<GraphKey, std::vector<int64_t>> graph_hist;          // -> its launches by kernel variant (launch_hist)
+    struct Batch { hipGraphExec_t exec = nullptr; SweepHist hist; };
+    std::map<GraphKey, Batch> graphs;                             // -> replayable batch and its launches by kernel variant
     bool all_fast = false;
     size_t state_alloc_bytes = 0;
     std::vector<LevelDesc> descs;
@@ -192,8 +206,7 @@ struct DpState {
     DevBuf d_probe;
 #endif
     std::vector<uint64_t> digest_host;
-    // launches of the last run per sweep kernel variant: index = rc * 4 + general * 2 + coop (rc 0 = generic kernel)
-    int64_t launch_hist[64 * 4] = {};
+    SweepHist launch_hist;                              // launches of the last run per sweep kernel variant (dg_dp_get_launch_profile)
     dg_dp_timing timing;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // The resident back-pointer lattice lives in a pool of equal chunks that a background thread allocates one by
@@ -262,11 +275,14 @@ struct SweepLaunch {                     // per-run launch context
     SweepArgs A;
     FastArgs F;
     bool small_state = true;
-    int rc_sel = 19;                     // chunk of "all recombination counts" (8 / 19 / 33 instantiations)
+    int rc_sel = 0;                      // chunk of "all recombination counts": the table's first all-planes entry that holds R + 1
+    bool digest = false;                 // this pass accumulates the level digests (the re-sweeps of a segmented run do not: pass 1 did)
+    int rp_active = 0;                   // planes [0, rp_active) are swept by the fast kernels (= RP except while a segment is re-swept below its path's plane)
+    SweepHist hist;                      // launches of this run by kernel variant
 };
 void sweep_prepare(const DpState &S, SweepLaunch &X);
 void sweep_init_state(const DpState &S, hipStream_t s);                  // level 0: every r starts at 0 (:534-535)
-void sweep_launch_level(DpState &S, SweepLaunch &X, int l, hipStream_t s);
+int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s);
 void sweep_warm_tables(const DpState &S, const SweepLaunch &X, int q0, int q1, hipStream_t s);
 int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool delta_resident, hipStream_t s);
 void sweep_prefetch_end(DpState &S, int le, hipStream_t s);

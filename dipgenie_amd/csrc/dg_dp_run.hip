@@ -15,9 +15,8 @@ constexpr int DELTA_NO_PIECES = 1 << 30;
 double wall_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
 void graphs_clear(DpState &S) {                 // captured level batches: stale as soon as the graph, the lattice or an option changes
-    for (auto &kv : S.graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
+    for (auto &kv : S.graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     S.graphs.clear();
-    S.graph_hist.clear();
 }
 
 void dp_state_free(DpState *s) {
@@ -124,7 +123,7 @@ struct Run {
                 if (q1 > q0) sweep_warm_tables(S, X, q0, q1, s);
             }
             if (l >= next_warm) next_warm = l + (int)std::max<int64_t>(S.opt.warm_ahead, 1);
-            sweep_launch_level(S, X, l, s);
+            if (int rc = sweep_launch_level(S, X, l, s)) return rc;
             ++n_launch;
             // profiling aid: rocprofv3 --pmc crashes when ~10^5 dispatches are queued without a drain
             if (S.opt.sync_every > 0 && n_launch % S.opt.sync_every == 0) DG_HIP(hipStreamSynchronize(s));
@@ -148,7 +147,7 @@ struct Run {
         const int64_t gb = S.opt.graph_batch >= 0 ? S.opt.graph_batch : 1000;
         // what issue_levels bakes into a captured batch besides the levels: whether the periodic look-ahead launches are left to the
         // prefetcher's far blocks -- part of the cache key (a second DP state on the device switches the prefetcher off)
-        const int pf_key = ((S.pf_active && S.opt.pf_far > 0) ? 1 : 0) | (S.rp_active << 1);
+        const int pf_key = ((S.pf_active && S.opt.pf_far > 0) ? 1 : 0) | (X.rp_active << 1);
         for (int l0 = lb; l0 < le;) {
             const bool use_graph = gb > 0 && n_win() == 1 && S.opt.sync_every == 0 && !S.graph_failed;
             const int l1 = use_graph ? (int)std::min<int64_t>((int64_t)l0 + gb, le) : le;
@@ -157,15 +156,14 @@ struct Run {
                 DG_HIP(hipStreamWaitEvent(s, S.delta_piece_ev[S.delta_piece_next], 0));
                 ++S.delta_piece_next;
             }
-            hipGraphExec_t *slot = nullptr;
+            const DpState::GraphKey key(l0, l1, (const void *)bp_biased, pf_key);
+            DpState::Batch *slot = nullptr;
             bool capturing = false;
             if (use_graph) {
-                const auto key = std::make_tuple(l0, l1, (const void *)bp_biased, pf_key);
                 slot = &S.graphs[key];
-                if (*slot) {
-                    DG_HIP(hipGraphLaunch(*slot, s));
-                    const std::vector<int64_t> &h = S.graph_hist[key];
-                    for (size_t q = 0; q < h.size(); ++q) S.launch_hist[q] += h[q];
+                if (slot->exec) {
+                    DG_HIP(hipGraphLaunch(slot->exec, s));
+                    X.hist.add(slot->hist);
                     n_launch += l1 - l0; l0 = l1;
                     continue;
                 }
@@ -173,31 +171,29 @@ struct Run {
                 else { (void)hipGetLastError(); S.graph_failed = true; continue; }
             }
             const int64_t n_launch_before = n_launch;
-            std::vector<int64_t> hist_before(S.launch_hist, S.launch_hist + 64 * 4);
+            const SweepHist hist_before = X.hist;
             if (int rc = issue_levels(l0, l1, lb, le)) {
                 if (capturing) {                                    // leave the stream usable: end the capture, drop the half-built graph
                     hipGraph_t cg = nullptr;
                     (void)hipStreamEndCapture(s, &cg);
                     if (cg) (void)hipGraphDestroy(cg);
                     (void)hipGetLastError();
-                    S.graphs.erase(std::make_tuple(l0, l1, (const void *)bp_biased, pf_key));
+                    S.graphs.erase(key);
                 }
                 return rc;
             }
             if (capturing) {
                 hipGraph_t cg = nullptr;
-                const bool ok = hipStreamEndCapture(s, &cg) == hipSuccess && cg && hipGraphInstantiate(slot, cg, nullptr, nullptr, 0) == hipSuccess;
+                const bool ok = hipStreamEndCapture(s, &cg) == hipSuccess && cg && hipGraphInstantiate(&slot->exec, cg, nullptr, nullptr, 0) == hipSuccess;
                 if (cg) (void)hipGraphDestroy(cg);
                 if (!ok) {                                          // nothing of this batch has run: issue it again without a graph
                     (void)hipGetLastError();
-                    *slot = nullptr; S.graph_failed = true; n_launch = n_launch_before;
-                    std::copy(hist_before.begin(), hist_before.end(), S.launch_hist);
+                    slot->exec = nullptr; S.graph_failed = true; n_launch = n_launch_before; X.hist = hist_before;
                     continue;
                 }
-                std::vector<int64_t> &h = S.graph_hist[std::make_tuple(l0, l1, (const void *)bp_biased, pf_key)];
-                h.resize(64 * 4);
-                for (size_t q = 0; q < h.size(); ++q) h[q] = S.launch_hist[q] - hist_before[q];
-                DG_HIP(hipGraphLaunch(*slot, s));
+                slot->hist = X.hist;
+                slot->hist.add(hist_before, -1);
+                DG_HIP(hipGraphLaunch(slot->exec, s));
             }
             l0 = l1;
         }
@@ -218,29 +214,34 @@ struct Run {
         return DG_OK;
     }
 
+    // lattice chunk ch of a run of chunks that begins with c0: its destination levels [lb, le) and its back-pointers (pool chunk ch - c0, or
+    // the one exact buffer) biased as sweep_range takes them
+    std::tuple<int, int, uint16_t *> chunk(int ch, int c0) const {
+        const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1];
+        return {lb, le, (S.d_bp.p ? S.d_bp.as<uint16_t>() : pool_base[ch - c0]) - S.descs[lb].bp_off};
+    }
+
     // Sweeps the chunks [c0, c1) with back-pointers into pool chunks 0 .. c1-c0-1 (or the one exact buffer), then walks
     // them last first; from_sink = this is the walk that starts at the sink.
     int sweep_and_walk(int c0, int c1, bool from_sink, bool mark_forward_end) {
-        std::vector<uint16_t *> biased(c1 - c0);
         for (int ch = c0; ch < c1; ++ch) {
-            const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1];
-            uint16_t *base = S.d_bp.p ? S.d_bp.as<uint16_t>() : pool_base[ch - c0];
-            biased[ch - c0] = base - S.descs[lb].bp_off;
+            const auto [lb, le, bp] = chunk(ch, c0);
             const double th0 = wall_s();
-            if (int rc = sweep_range(lb, le, biased[ch - c0])) return rc;
+            if (int rc = sweep_range(lb, le, bp)) return rc;
             host_enqueue_s += wall_s() - th0;
         }
         if (mark_forward_end) { DG_HIP(hipEventRecord(S.ev[2], s)); budgets_launch_sink_copy(S, state_ptr(S.L - 1), s); }
         if (S.opt.test_poison_level > 0 && S.opt.test_poison_level < S.L)        // tests: a level nobody swept / a damaged lattice
             for (int ch = c0; ch < c1; ++ch) {
-                const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1], lp = (int)S.opt.test_poison_level;
-                if (lp >= lb && lp < le) DG_HIP(hipMemsetAsync(biased[ch - c0] + S.descs[lp].bp_off, (int)S.opt.test_poison_byte, 2 * (size_t)S.level_units[lp], s));
+                const auto [lb, le, bp] = chunk(ch, c0);
+                const int lp = (int)S.opt.test_poison_level;
+                if (lp >= lb && lp < le) DG_HIP(hipMemsetAsync(bp + S.descs[lp].bp_off, (int)S.opt.test_poison_byte, 2 * (size_t)S.level_units[lp], s));
             }
         for (int ch = c1 - 1; ch >= c0; --ch) {
-            const int lb = S.d_bp.p ? 1 : S.chunk_begin[ch], le = S.d_bp.p ? S.L : S.chunk_begin[ch + 1];
+            const auto [lb, le, bp] = chunk(ch, c0);
             trace_launch_warm_rows(S, lb, le, s);
             const int32_t *final_val = from_sink && ch == c1 - 1 ? state_ptr(S.L - 1) : (const int32_t *)nullptr;
-            trace_launch_chains(S, n_chains, le - 1, lb, biased[ch - c0], final_val, s);
+            trace_launch_chains(S, n_chains, le - 1, lb, bp, final_val, s);
         }
         return DG_OK;
     }
@@ -266,9 +267,7 @@ struct Run {
             if (int rc = sweep_and_walk(0, S.d_bp.p ? 1 : n_chunks_all, true, true)) return rc;
         } else {
             // pass 1: values only, keeping the state in front of every segment
-            const int64_t dig = S.opt.want_digest;
             int64_t planes_swept = 0;
-            S.rp_active = S.RP;
             for (int sg = 0; sg < n_seg; ++sg) {
                 if (sg > 0)
                     DG_HIP(hipMemcpyAsync(S.d_ckpt.as<int32_t>() + S.ckpt_off[sg], state_ptr(S.seg_begin[sg] - 1),
@@ -278,7 +277,7 @@ struct Run {
             DG_HIP(hipEventRecord(S.ev[2], s));                 // (the re-sweeps below are booked under traceback_ms)
             budgets_launch_sink_copy(S, state_ptr(S.L - 1), s);  // the second pass overwrites the state ring
             // pass 2: last segment first -- restore its input state, re-sweep its chunks with back-pointers, walk them
-            S.opt.want_digest = 0;                                  // digests were accumulated in pass 1
+            X.digest = false;                                       // digests were accumulated in pass 1
             // Along a path the recombination count only grows, and a cell of plane r gathers from planes r, r - 1, r - 2 of the level
             // before: once the walk has left segment sg on plane r*, the cells it can meet in the segments before lie on planes
             // <= r*, and those depend on planes <= r* only.  Every earlier segment is therefore re-swept up to the plane its
@@ -292,21 +291,20 @@ struct Run {
                 else
                     sweep_init_state(S, s);
                 const int c0 = sg * S.seg_chunks, c1 = std::min(n_chunks_all, c0 + S.seg_chunks);
-                if (int rc = sweep_and_walk(c0, c1, sg == n_seg - 1, false)) { S.opt.want_digest = dig; S.rp_active = S.RP; return rc; }
+                if (int rc = sweep_and_walk(c0, c1, sg == n_seg - 1, false)) return rc;
                 if (S.opt.plane_limit && sg > 0) {
                     std::vector<ChainState> cs((size_t)n_chains);
-                    if (hipMemcpyAsync(cs.data(), S.d_ch_state.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S.opt.want_digest = dig; S.rp_active = S.RP; DG_HIP(hipGetLastError()); return DG_ERR_HIP; }
+                    DG_HIP(hipMemcpyAsync(cs.data(), S.d_ch_state.p, sizeof(ChainState) * cs.size(), hipMemcpyDeviceToHost, s));
+                    DG_HIP(hipStreamSynchronize(s));
                     int planes = 1;
                     for (const ChainState &q : cs) {
                         if (q.value == NEG_INF) continue;
                         planes = std::max(planes, (q.value != CHAIN_CORRUPT && q.r >= 0 && q.r < S.RP) ? q.r + 1 : S.RP);
                     }
-                    S.rp_active = planes;
-                    planes_swept += (int64_t)S.rp_active * (S.seg_begin[sg] - S.seg_begin[sg - 1]);
+                    X.rp_active = planes;
+                    planes_swept += (int64_t)planes * (S.seg_begin[sg] - S.seg_begin[sg - 1]);
                 }
             }
-            S.rp_active = S.RP;
-            S.opt.want_digest = dig;
             if (getenv("DG_DEBUG") && S.opt.plane_limit) fprintf(stderr, "[dipgenie_hip] run: second pass swept %.1f %% of the (level, plane) pairs before the last segment\n",
                                                               100.0 * (double)planes_swept / std::max(1.0, (double)S.RP * (S.seg_begin[n_seg - 1] - 1)));
         }
@@ -355,10 +353,10 @@ static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result
     std::vector<int32_t> edges(4 * (size_t)S.cap * (size_t)n_budgets);
     if (int rc = budgets_prepare(S, budgets, n_budgets, s)) return rc;
     run.n_chains = n_budgets;
-    memset(S.launch_hist, 0, sizeof S.launch_hist);
-    run.n_launch = 0;
     S.sink_host.clear();
-    if (int rc = run.forward_and_trace()) return rc;
+    const int rc_run = run.forward_and_trace();
+    S.launch_hist = run.X.hist;
+    if (rc_run) return rc_run;
     DG_HIP(hipMemcpyAsync(to.data(), S.d_ch_trace.p, sizeof(TraceOut) * to.size(), hipMemcpyDeviceToHost, s));
     DG_HIP(hipMemcpyAsync(edges.data(), S.d_ch_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
     std::vector<int32_t> sink((size_t)S.RP);
@@ -480,15 +478,8 @@ extern "C" int dg_dp_get_table_digest(dg_ctx *c, uint64_t *out, int n) {
 extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
     if (!c || !c->dp || !buf || cap < 2) { dgi::set_error("dg_dp_get_launch_profile: no state"); return DG_ERR_STATE; }
     std::string out;
-    for (int q = 0; q < 64 * 4; ++q) {
-        const int64_t n = c->dp->launch_hist[q];
-        if (!n) continue;
-        char item[96];
-        if (q == 0) snprintf(item, sizeof item, "dp_sweep_kernel:%lld", (long long)n);
-        else snprintf(item, sizeof item, "dp_sweep_%s_kernel<%d,%s>:%lld", (q & 1) ? "coop" : "fast", q / 4, (q & 2) ? "general" : "lean", (long long)n);
-        if (!out.empty()) out += ' ';
-        out += item;
-    }
+    for (int q = 0; q < dgi::SweepVariant::count(); ++q)
+        if (const int64_t n = c->dp->launch_hist.n[(size_t)q]) out += (out.empty() ? "" : " ") + dgi::SweepVariant::at(q).name() + ':' + std::to_string(n);
     if ((int)out.size() + 1 > cap) { dgi::set_error("dg_dp_get_launch_profile: buffer too small (%zu needed)", out.size() + 1); return DG_ERR_ARG; }
     memcpy(buf, out.c_str(), out.size() + 1);
     return DG_OK;

@@ -12,6 +12,7 @@
 // segment head stores the value and the back-pointer.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "dg_dp.hpp"
 
@@ -596,8 +597,48 @@ __global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__r
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// THE table of recombination-chunk sizes (RC), ascending; dispatch (launch_variant), per-level choice (choose_rc), the run's all-planes chunk
+// (sweep_prepare) and the variants' indices and names (SweepVariant) walk it, and no RC is written anywhere else.  Every entry is an instantiation of
+// the fast kernel.  RC_COOP: of the cooperative kernel too, and a candidate of choose_rc's cooperative pass; RC_PART: a candidate of choose_rc while
+// below the run's all-planes chunk; RC_ALL: an all-planes chunk (the first that holds R + 1 planes is the run's rc_sel), instantiated for the generic kernel too.
+enum : unsigned { RC_COOP = 1, RC_PART = 2, RC_ALL = 4, RC_ANY = 7 };
+constexpr struct SweepRc { int rc; unsigned is; } SWEEP_RCS[] = {
+    {1, RC_COOP | RC_PART}, {2, RC_COOP | RC_PART}, {3, RC_COOP | RC_PART}, {4, RC_COOP | RC_PART}, {5, RC_PART}, {6, RC_PART},
+    {8, RC_PART | RC_ALL}, {10, RC_PART}, {11, RC_PART}, {16, RC_PART}, {19, RC_ALL}, {33, RC_ALL}};
+constexpr int N_SWEEP_RCS = (int)(sizeof SWEEP_RCS / sizeof SWEEP_RCS[0]);
+constexpr bool sweep_rcs_ascend(int q = 1) { return q >= N_SWEEP_RCS || (SWEEP_RCS[q - 1].rc < SWEEP_RCS[q].rc && sweep_rcs_ascend(q + 1)); }
+static_assert(SWEEP_RCS[0].rc >= 1 && sweep_rcs_ascend() && (SWEEP_RCS[N_SWEEP_RCS - 1].is & RC_ALL), "ascending (choose_rc's ties go to the larger RC), and the largest chunk is an all-planes one");
+
+// variants in the launch profile's order: the generic kernel, then per table entry lean, lean cooperative, general, general cooperative
+int SweepVariant::count() { return 1 + 4 * N_SWEEP_RCS; }
+SweepVariant SweepVariant::at(int index) { return index == 0 ? SweepVariant{0, false, false} : SweepVariant{SWEEP_RCS[(index - 1) / 4].rc, ((index - 1) & 2) != 0, ((index - 1) & 1) != 0}; }
+int SweepVariant::index() const {
+    for (int q = 0; q < N_SWEEP_RCS; ++q) if (SWEEP_RCS[q].rc == rc) return 1 + 4 * q + (general ? 2 : 0) + (coop ? 1 : 0);
+    return 0;
+}
+std::string SweepVariant::name() const {
+    return rc == 0 ? "dp_sweep_kernel" : std::string("dp_sweep_") + (coop ? "coop" : "fast") + "_kernel<" + std::to_string(rc) + (general ? ",general>" : ",lean>");
+}
+
+// The run-time (rc, digest, general) as template arguments: calls f(RC, DIGEST, GENERAL), each a std::integral_constant, for the table entry rc if it
+// carries a mark of WANT (f is instantiated for those entries only).  A chunk size that is not among them cannot be launched: false, nothing called.
+template <unsigned WANT, int Q = 0, class F>
+static bool launch_variant(int rc, bool digest, bool general, F &f) {
+    if constexpr (Q < N_SWEEP_RCS) {
+        if constexpr ((SWEEP_RCS[Q].is & WANT) != 0) if (rc == SWEEP_RCS[Q].rc) {
+            constexpr std::integral_constant<int, SWEEP_RCS[Q].rc> RC{};
+            if (digest) { if (general) f(RC, std::true_type{}, std::true_type{}); else f(RC, std::true_type{}, std::false_type{}); }
+            else { if (general) f(RC, std::false_type{}, std::true_type{}); else f(RC, std::false_type{}, std::false_type{}); }
+            return true;
+        }
+        return launch_variant<WANT, Q + 1>(rc, digest, general, f);
+    }
+    return false;
+}
+
 void sweep_prepare(const DpState &S, SweepLaunch &X) {
-    X.rc_sel = S.RP <= 8 ? 8 : (S.RP <= 19 ? 19 : 33);
+    for (const SweepRc &e : SWEEP_RCS) if ((e.is & RC_ALL) && (X.rc_sel = e.rc) >= S.RP) break;
+    X.digest = S.opt.want_digest != 0; X.rp_active = S.RP;
     X.small_state = S.state_alloc_bytes < ((size_t)1 << 31);            // 32-bit buffer offsets inside a slot
     SweepArgs &A = X.A;
     A.descs = S.d_descs.as<LevelDesc>(); A.in_off = S.d_in_off.as<uint32_t>(); A.in_edge = S.d_in_edge.as<uint32_t>();
@@ -629,40 +670,39 @@ void sweep_init_state(const DpState &S, hipStream_t s) {
 // dmax in-edges with RC gathers each); last: per-wave issue overhead.  Cooperative variant (RC <= 4): rows above
 // COOP_MIN in-edges are walked by four waves, so the chain is a quarter (at least COOP_MIN) while four extra
 // workgroup slots per heavy row are launched.
-static void choose_rc(const DpState &S, const LevelDesc &d, int l, int rc_sel, int &rc, bool &coop) {
-    rc = rc_sel;
+static void choose_rc(const DpState &S, const SweepLaunch &X, const LevelDesc &d, int l, int &rc, bool &coop) {
+    const int rc_sel = rc = X.rc_sel;
     coop = false;
     if (S.opt.adaptive_rc == 0) return;
-    const int cand[11] = {1, 2, 3, 4, 5, 6, 8, 10, 11, 16, rc_sel};
     const bool coop_ok = S.opt.use_coop && d.n_heavy > 0 && d.k2 + 4 * d.n_heavy <= 65535;
     const double dmax = (double)std::max(1, S.level_dmax[l]);
     double best = 1e300;
     for (int pass = (coop_ok && S.opt.use_coop == 2) ? 1 : 0; pass < (coop_ok ? 2 : 1); ++pass) {     // coop = 2 (tests): whenever possible
-        for (int q = 0; q < 11; ++q) {
-            if (cand[q] > rc_sel || (q < 10 && cand[q] == rc_sel)) continue;
-            if (pass == 1 && cand[q] > 4) continue;
+        for (const SweepRc &e : SWEEP_RCS) {                                   // the partial chunks below rc_sel, then rc_sel itself
+            if (e.rc != rc_sel && !((e.is & RC_PART) && e.rc < rc_sel)) continue;
+            if (pass == 1 && !(e.is & RC_COOP)) continue;
             const double rows = pass ? (double)d.k2 + 4.0 * d.n_heavy : (double)d.k2;
             const double chain = pass ? std::max((double)COOP_MIN, std::ceil(dmax / 4.0)) + 1.0 : dmax;
-            const double W = rows * d.nblocks * ((S.rp_active + cand[q] - 1) / cand[q]);
-            const double T = std::max(1.0, W / (double)S.opt.rc_cap) * ((double)S.opt.rc_t0_ns + chain * cand[q] * (double)S.opt.rc_tg_ps * 1e-3) + W * (double)S.opt.rc_tw_ps * 1e-3;
-            if (T <= best) { best = T; rc = cand[q]; coop = pass == 1; }   // ties: the larger RC (fewer waves)
+            const double W = rows * d.nblocks * ((X.rp_active + e.rc - 1) / e.rc);
+            const double T = std::max(1.0, W / (double)S.opt.rc_cap) * ((double)S.opt.rc_t0_ns + chain * e.rc * (double)S.opt.rc_tg_ps * 1e-3) + W * (double)S.opt.rc_tw_ps * 1e-3;
+            if (T <= best) { best = T; rc = e.rc; coop = pass == 1; }      // ties: the larger RC (fewer waves)
         }
     }
 }
 
-void sweep_launch_level(DpState &S, SweepLaunch &X, int l, hipStream_t s) {
-    LevelDesc &d = S.descs[l];
+int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
+    LevelDesc d = S.descs[l];                                           // the copy that goes to the kernel
     // small and mid-sized levels end sooner with write-back back-pointer stores (3.6 vs 4.2 us per level on MHC_4; threshold
     // 16 K / 64 K / 256 K / 1 M / 4 M cells: MHC-24 sweep 580 / 575 / 574 / 579 / 586 ms), big ones with non-temporal ones that
     // keep the once-written lattice out of the L2
     d.bp_nt = (int64_t)d.k2 * d.k2 * S.RP >= S.opt.bp_nt_min_cells ? 1 : 0;
+    SweepVariant v{0, false, false};
+    bool launched;                                                      // false: the table holds no such kernel, nothing was launched
     if (d.fast_ok && X.small_state && S.RP <= 65535 && S.opt.use_fast) {
-        int rc;
-        bool coop;
-        choose_rc(S, d, l, X.rc_sel, rc, coop);
-        S.launch_hist[(rc & 63) * 4 + (d.fast_ok == 2 ? 2 : 0) + (coop ? 1 : 0)]++;
-        const int nch = (S.rp_active + rc - 1) / rc;              // (rp_active < RP: re-sweep of a segment whose path stays below that plane, dg_dp_run.hip)
-        const dim3 grid((unsigned)((d.nblocks + 3) / 4), (unsigned)nch, (unsigned)(d.k2 + (coop ? 4 * d.n_heavy : 0)));
+        choose_rc(S, X, d, l, v.rc, v.coop);
+        v.general = d.fast_ok == 2;
+        const int nch = (X.rp_active + v.rc - 1) / v.rc;          // (rp_active < RP: re-sweep of a segment whose path stays below that plane, dg_dp_run.hip)
+        const dim3 grid((unsigned)((d.nblocks + 3) / 4), (unsigned)nch, (unsigned)(d.k2 + (v.coop ? 4 * d.n_heavy : 0)));
         const dim3 pgrid((unsigned)((d.nblocks + DG_PLAIN_GW - 1) / DG_PLAIN_GW), (unsigned)((nch + DG_PLAIN_CH - 1) / DG_PLAIN_CH), grid.z);
         const int32_t *hv = S.d_heavy.as<int32_t>();
         const FastArgs &F = X.F;
@@ -675,32 +715,20 @@ void sweep_launch_level(DpState &S, SweepLaunch &X, int l, hipStream_t s) {
         const int rp_k = S.RP | (d.k << 13);
         unsigned long long hlo = 0, hhi = 0;
         for (int q = 0; q < 4; ++q) { hlo |= (unsigned long long)(uint16_t)d.heavy_in[q] << (16 * q); hhi |= (unsigned long long)(uint16_t)d.heavy_in[4 + q] << (16 * q); }
-#define DG_FAST(RCV, DG) do { if (d.fast_ok == 2) hipLaunchKernelGGL((dp_sweep_fast_kernel<RCV, DG, true>), pgrid, dim3(DG_PLAIN_WG), 0, s, rowrec_l, slots_l, rowx_l, cur, dm, d.rowx_stride, d.nblocks, rp_k, F.pad_bytes, dT, F.buf_bytes, F, d, l); \
-                              else hipLaunchKernelGGL((dp_sweep_fast_kernel<RCV, DG, false>), pgrid, dim3(DG_PLAIN_WG), 0, s, rowrec_l, slots_l, rowx_l, cur, dm, d.rowx_stride, d.nblocks, rp_k, F.pad_bytes, dT, F.buf_bytes, F, d, l); } while (0)
-#define DG_COOP(RCV, DG) do { if (d.fast_ok == 2) hipLaunchKernelGGL((dp_sweep_coop_kernel<RCV, DG, true>), grid, dim3(256), 0, s, rowrec_l, slots_l, rowx_l, cur, d.rowx_stride, d.nblocks, d.n_heavy, rp_k, hlo, hhi, F, d, l, dm, dT, hv); \
-                              else hipLaunchKernelGGL((dp_sweep_coop_kernel<RCV, DG, false>), grid, dim3(256), 0, s, rowrec_l, slots_l, rowx_l, cur, d.rowx_stride, d.nblocks, d.n_heavy, rp_k, hlo, hhi, F, d, l, dm, dT, hv); } while (0)
-#define DG_FAST_RC(DG) do { if (coop) { switch (rc) { case 1: DG_COOP(1, DG); break; case 2: DG_COOP(2, DG); break; case 3: DG_COOP(3, DG); break; \
-                                                    default: DG_COOP(4, DG); break; } break; } \
-                            switch (rc) { case 1: DG_FAST(1, DG); break; case 2: DG_FAST(2, DG); break; case 3: DG_FAST(3, DG); break; \
-                                        case 4: DG_FAST(4, DG); break; case 5: DG_FAST(5, DG); break; case 6: DG_FAST(6, DG); break; \
-                                        case 8: DG_FAST(8, DG); break; case 10: DG_FAST(10, DG); break; case 11: DG_FAST(11, DG); break; \
-                                        case 16: DG_FAST(16, DG); break; case 19: DG_FAST(19, DG); break; \
-                                        default: DG_FAST(33, DG); break; } } while (0)
-        if (S.opt.want_digest) DG_FAST_RC(true); else DG_FAST_RC(false);
-#undef DG_COOP
-#undef DG_FAST_RC
-#undef DG_FAST
+        auto fast = [&](auto RC, auto DG, auto GEN) { hipLaunchKernelGGL((dp_sweep_fast_kernel<RC.value, DG.value, GEN.value>), pgrid, dim3(DG_PLAIN_WG), 0, s, rowrec_l, slots_l, rowx_l, cur, dm, d.rowx_stride, d.nblocks, rp_k, F.pad_bytes, dT, F.buf_bytes, F, d, l); };
+        auto cooperative = [&](auto RC, auto DG, auto GEN) { hipLaunchKernelGGL((dp_sweep_coop_kernel<RC.value, DG.value, GEN.value>), grid, dim3(256), 0, s, rowrec_l, slots_l, rowx_l, cur, d.rowx_stride, d.nblocks, d.n_heavy, rp_k, hlo, hhi, F, d, l, dm, dT, hv); };
+        launched = v.coop ? launch_variant<RC_COOP>(v.rc, X.digest, v.general, cooperative) : launch_variant<RC_ANY>(v.rc, X.digest, v.general, fast);
     } else {
         const int nchunk = (S.RP + X.rc_sel - 1) / X.rc_sel;
         const int64_t ntask = (int64_t)d.k2 * d.ngroups * nchunk;
         const unsigned grid = (unsigned)std::min<int64_t>((ntask + 3) / 4, S.opt.max_blocks);
         const SweepArgs &A = X.A;
-        S.launch_hist[0]++;
-#define DG_SWEEP(RCV, DG) hipLaunchKernelGGL((dp_sweep_kernel<RCV, DG>), dim3(grid), dim3(256), 0, s, A, l)
-        if (S.opt.want_digest) { if (X.rc_sel == 8) DG_SWEEP(8, true); else if (X.rc_sel == 19) DG_SWEEP(19, true); else DG_SWEEP(33, true); }
-        else { if (X.rc_sel == 8) DG_SWEEP(8, false); else if (X.rc_sel == 19) DG_SWEEP(19, false); else DG_SWEEP(33, false); }
-#undef DG_SWEEP
+        auto generic = [&](auto RC, auto DG, auto) { hipLaunchKernelGGL((dp_sweep_kernel<RC.value, DG.value>), dim3(grid), dim3(256), 0, s, A, l); };
+        launched = launch_variant<RC_ALL>(X.rc_sel, X.digest, false, generic);
     }
+    if (!launched) { set_error("sweep of level %d: no %s kernel is instantiated for chunks of %d recombination counts", l, v.coop ? "cooperative" : v.rc ? "fast" : "generic", v.rc ? v.rc : X.rc_sel); return DG_ERR_STATE; }
+    X.hist.n[(size_t)v.index()]++;
+    return DG_OK;
 }
 
 void sweep_warm_tables(const DpState &S, const SweepLaunch &X, int q0, int q1, hipStream_t s) {   // graph tables of destination levels [q0, q1) -> Infinity Cache

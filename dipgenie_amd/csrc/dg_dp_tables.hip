@@ -519,7 +519,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     DpState &S = *c->dp;
     graphs_clear(S);
     S.loaded = false;
-    S.nV = nV; S.L = L; S.R = R; S.RP = R + 1; S.rp_active = S.RP;
+    S.nV = nV; S.L = L; S.R = R; S.RP = R + 1;
     hipStream_t s = c->stream;
     PoolPause pause(S);                                         // the pool thread maps no chunk while this function allocates
     std::vector<int32_t> dtrans;
@@ -599,7 +599,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     return DG_OK;
 }
 
-// FNV-1a over every table of the resident graph (bp_nt is a launch-time field): the device and the host construction must agree
+// FNV-1a over every table of the resident graph (LevelDesc::bp_nt is set at launch time, on the kernel's copy only): the device and the host construction must agree
 int dp_table_digest(dg_ctx *c, uint64_t *out, int n) {
     DpState *Sp = c->dp;
     if (!Sp || !Sp->loaded) { set_error("dg_dp_get_table_digest: no graph loaded"); return DG_ERR_STATE; }
@@ -615,13 +615,7 @@ int dp_table_digest(dg_ctx *c, uint64_t *out, int n) {
         dst = x;
         return DG_OK;
     };
-    {
-        std::vector<LevelDesc> d(S.L);
-        DG_HIP(hipMemcpy(d.data(), S.d_descs.p, sizeof(LevelDesc) * (size_t)S.L, hipMemcpyDeviceToHost));
-        uint64_t x = 1469598103934665603ULL;
-        for (auto &q : d) { q.bp_nt = 0; const unsigned char *p = (const unsigned char *)&q; for (size_t i = 0; i < sizeof q; ++i) { x ^= p[i]; x *= 1099511628211ULL; } }
-        out[0] = x;
-    }
+    if (int rc = fnv(S.d_descs, sizeof(LevelDesc) * (size_t)S.L, out[0])) return rc;
     if (int rc = fnv(S.d_in_off, 4 * ((size_t)S.nV + 1), out[1])) return rc;
     if (int rc = fnv(S.d_in_edge, 4 * (size_t)S.n_edges, out[2])) return rc;
     if (int rc = fnv(S.d_in_dst, 4 * (size_t)S.n_edges, out[3])) return rc;

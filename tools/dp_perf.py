@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Perf probe: load .dpg graphs, run the HIP DP in its modes, print timings.
-usage: python tools/dp_perf.py [--check] [--modes=fast,norowx,generic] graph.dpg ... """
+usage: python tools/dp_perf.py [--check] [--modes=fast,norowx,generic,plain] graph.dpg ...
+(plain = no hipGraph batches: with DG_DEBUG=1 the library's "host issued N sweep launches" line is then the cost of issuing one launch)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -13,7 +14,7 @@ for a in sys.argv[1:]:
     if a.startswith("--modes="): modes = a.split("=")[1]
 paths = [a for a in sys.argv[1:] if not a.startswith("--")]
 ctx = capi.Context(0)
-OPT = {"fast": {}, "norowx": {"rowx": 0}, "generic": {"fast": 0}}     # what each mode changes
+OPT = {"fast": {}, "norowx": {"rowx": 0}, "generic": {"fast": 0}, "plain": {"graph_batch": 0}}     # what each mode changes
 for p in paths:
     g = capi.DpGraphArrays.load(p)
     t0 = time.time(); ctx.dp_load_graph(g); t1 = time.time()
