@@ -71,7 +71,7 @@ SYMBOLS = [
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners",
-    "dg_dp_get_option", "dg_sketch_get_option",
+    "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -95,6 +95,7 @@ lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 lib.dg_dp_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
 lib.dg_dp_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
 lib.dg_dp_get_launch_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+lib.dg_dp_list_sweep_variants.argtypes = [C.c_char_p, C.c_int]
 lib.dg_dp_get_table_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_sketch_reads.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
@@ -374,6 +375,13 @@ class Context:
         buf = C.create_string_buffer(8192)
         _check(lib.dg_dp_get_launch_profile(self.h, buf, 8192), "dg_dp_get_launch_profile")
         return {k: int(v) for k, v in (item.rsplit(":", 1) for item in buf.value.decode().split())}
+
+    @staticmethod
+    def dp_sweep_variants():
+        """the names of every sweep kernel variant the library can launch, in dp_launch_profile's order (needs no device)"""
+        buf = C.create_string_buffer(8192)
+        _check(lib.dg_dp_list_sweep_variants(buf, 8192), "dg_dp_list_sweep_variants")
+        return buf.value.decode().split()
 
     TABLES = ["descs", "in_off", "in_edge", "in_dst", "dtrans", "dblk_first", "grp_begin", "dead_cols", "heavy_rows", "rowrec", "rowx", "slots"]
 

@@ -119,6 +119,7 @@ struct SweepVariant {
     bool general, coop;
     int index() const;
     std::string name() const;                           // as rocprof prints the kernel, without its DIGEST argument
+    bool exists() const;                                // the dispatch instantiates it (cooperative: the RC_COOP entries only)
     static int count();
     static SweepVariant at(int index);
 };
@@ -139,6 +140,7 @@ struct DpOptions {
     int64_t segment_cells = 0;                          // segment_cells: force lattice segments of at most this many cells (tests)
     int64_t host_threads = 16;                          // host_threads: threads of dg_dp_load_graph's host table construction
     int64_t test_poison_level = 0, test_poison_byte = 0xFF;   // test_poison_*: overwrite one level of the lattice between sweep and walk (tests of the corrupt-lattice path)
+    int64_t test_force_rc = 0;                          // test_force_rc: n != 0 = the per-level RC choice considers the table entry of n recombination counts only (tests: one variant per run)
     int64_t host_tables = 0;                            // host_tables: 1 = build the tables on the host and upload them (dg_dp_tables.hip; parity twin of dg_dp_build.hip)
     int64_t bp_nt_min_cells = 262144;                   // bp_nt_min_cells: levels this big stream their back-pointers non-temporally
     int64_t graph_batch = -1;                           // graph_batch: levels per captured hipGraph (0 = plain launches, -1 = the default of 1,000)

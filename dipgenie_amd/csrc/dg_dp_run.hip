@@ -484,6 +484,14 @@ extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
     memcpy(buf, out.c_str(), out.size() + 1);
     return DG_OK;
 }
+extern "C" int dg_dp_list_sweep_variants(char *buf, int cap) {
+    std::string out;
+    for (int q = 0; q < dgi::SweepVariant::count(); ++q)
+        if (dgi::SweepVariant::at(q).exists()) out += (out.empty() ? "" : " ") + dgi::SweepVariant::at(q).name();
+    if (!buf || (int)out.size() + 1 > cap) { dgi::set_error("dg_dp_list_sweep_variants: buffer too small (%zu needed)", out.size() + 1); return DG_ERR_ARG; }
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return DG_OK;
+}
 // Options: parity / test knobs (digest, fast, adaptive_rc, coop, rowx, lean_chain, segment_cells, delta_cap_entries, lattice_chunk_cells,
 // graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
 // One row per key: its DpOptions field, the lower clamp, whether v <= 0 asks for the default (that of a fresh DpOptions).
@@ -495,7 +503,7 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"rc_cap", &DpO::rc_cap, 0, true}, {"max_blocks", &DpO::max_blocks, 0, true}, {"bp_nt_min_cells", &DpO::bp_nt_min_cells, 0, false}, {"warm_ahead", &DpO::warm_ahead, 0, false},
     {"graph_batch", &DpO::graph_batch, -1, false}, {"l2_prefetch", &DpO::l2_prefetch, 0, false}, {"delta_overlap", &DpO::delta_overlap, 0, false}, {"pf_far", &DpO::pf_far, 0, false},
     {"side_stream", &DpO::side_stream, -1, false}, {"plane_limit", &DpO::plane_limit, 0, false}, {"test_poison_level", &DpO::test_poison_level, 0, false},
-    {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
+    {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"test_force_rc", &DpO::test_force_rc, 0, false}, {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
     // read by dg_dp_load_graph: in effect at the next load
     {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},
     {"host_threads", &DpO::host_threads, 1, false}, {"host_tables", &DpO::host_tables, 0, false}, {"delta_cap_entries", &DpO::delta_cap_entries, 0, true},

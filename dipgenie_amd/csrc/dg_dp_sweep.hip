@@ -616,6 +616,11 @@ int SweepVariant::index() const {
     for (int q = 0; q < N_SWEEP_RCS; ++q) if (SWEEP_RCS[q].rc == rc) return 1 + 4 * q + (general ? 2 : 0) + (coop ? 1 : 0);
     return 0;
 }
+bool SweepVariant::exists() const {
+    if (rc == 0) return !general && !coop;
+    for (const SweepRc &e : SWEEP_RCS) if (e.rc == rc) return !coop || (e.is & RC_COOP);
+    return false;
+}
 std::string SweepVariant::name() const {
     return rc == 0 ? "dp_sweep_kernel" : std::string("dp_sweep_") + (coop ? "coop" : "fast") + "_kernel<" + std::to_string(rc) + (general ? ",general>" : ",lean>");
 }
@@ -681,6 +686,7 @@ static void choose_rc(const DpState &S, const SweepLaunch &X, const LevelDesc &d
         for (const SweepRc &e : SWEEP_RCS) {                                   // the partial chunks below rc_sel, then rc_sel itself
             if (e.rc != rc_sel && !((e.is & RC_PART) && e.rc < rc_sel)) continue;
             if (pass == 1 && !(e.is & RC_COOP)) continue;
+            if (S.opt.test_force_rc && e.rc != S.opt.test_force_rc) continue;  // tests: this entry or, where it is no candidate, plain rc_sel
             const double rows = pass ? (double)d.k2 + 4.0 * d.n_heavy : (double)d.k2;
             const double chain = pass ? std::max((double)COOP_MIN, std::ceil(dmax / 4.0)) + 1.0 : dmax;
             const double W = rows * d.nblocks * ((X.rp_active + e.rc - 1) / e.rc);

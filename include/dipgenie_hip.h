@@ -166,6 +166,8 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   sync_every n          drain the stream every n level launches (rocprofv3 --pmc)
  *   side_stream -1|0|1    L2 prefetcher + score deltas beside the sweep: -1 (default) while this is the only DP state on its device, 0 never, 1 always
  *   test_poison_level l, test_poison_byte b   tests: fill level l of the back-pointer lattice with byte b between sweep and walk (dg_dp_run must answer DG_ERR_STATE)
+ *   test_force_rc n       tests: n != 0 = every level's chunk-size choice considers the chunk of n recombination counts only (with coop 0|2: one kernel variant per run);
+ *                         a level on which n is no candidate (not instantiated, above the run's all-planes chunk, no cooperative form) runs the all-planes chunk as with adaptive_rc 0
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
@@ -181,6 +183,10 @@ int dg_dp_get_table_digest(dg_ctx *, uint64_t *out, int n);
 /* measurement: which sweep kernel variants the last dg_dp_run launched, as "name:count name:count ..." (the names
  * rocprofv3 reports, abbreviated); lets a profile taken in another process be matched against this run. */
 int dg_dp_get_launch_profile(dg_ctx *, char *buf, int cap);
+/* parity: the names of every sweep kernel variant the dispatch can launch, space-separated, in the order the launch profile prints
+ * them: the generic kernel, then per chunk size fast<rc,lean>, coop<rc,lean>, fast<rc,general>, coop<rc,general> (the cooperative
+ * ones for the chunk sizes that have them).  Needs no context.  DG_ERR_ARG: buf is null or too small. */
+int dg_dp_list_sweep_variants(char *buf, int cap);
 
 /* ---- haploid (vertex, r) DP ---- */
 typedef struct dg_hap_graph {         /* expanded graph after topologically_reorder: every edge u -> v has u < v */

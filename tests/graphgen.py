@@ -5,11 +5,18 @@ from dipgenie_amd.capi import DpGraphArrays
 
 
 def random_levelized(seed, n_levels=12, max_width=9, R=3, p_w1=0.3, p_colour=0.4, n_colours=12, max_list=4,
-                     extra_edges=1.5, dup_edges=True, min_width=1):
+                     extra_edges=1.5, dup_edges=True, min_width=1, widths=None):
     """Level 0 = {source}, last level = {sink}. Every vertex gets >=1 out-edge (except sink) and edges only
-    go to the next level. Parallel edges carry equal weights (the product's documented precondition)."""
+    go to the next level. Parallel edges carry equal weights (the product's documented precondition).
+    widths=[1, ..., 1] prescribes every level's width (n_levels, min_width and max_width are then unused) in place of the random
+    draw; without it every seeded call gives the arrays it always gave (tests/test_graphgen.py pins three of them)."""
     rng = np.random.default_rng(seed)
-    widths = [1] + [int(rng.integers(min_width, max_width + 1)) for _ in range(n_levels - 2)] + [1]
+    if widths is None:
+        widths = [1] + [int(rng.integers(min_width, max_width + 1)) for _ in range(n_levels - 2)] + [1]
+    else:
+        widths = [int(w) for w in widths]
+        n_levels = len(widths)
+        assert n_levels >= 2 and widths[0] == 1 and widths[-1] == 1 and min(widths) >= 1, widths
     level_off = np.zeros(n_levels + 1, np.int32)
     level_off[1:] = np.cumsum(widths)
     nV = int(level_off[-1])

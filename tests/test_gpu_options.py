@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 DP_DEFAULTS = {
     "digest": 0, "fast": 1, "adaptive_rc": 1, "coop": 1, "rowx": 1, "lean_chain": 1, "graph_batch": -1, "l2_prefetch": 6, "pf_far": 128,
     "delta_overlap": 1, "warm_ahead": 128, "segment_cells": 0, "lattice_chunk_cells": 4 << 30, "delta_cap_entries": 4 << 30, "plane_limit": 1,
-    "sync_every": 0, "side_stream": -1, "test_poison_level": 0, "test_poison_byte": 0xFF, "score_slab_bytes": 256 << 20,
+    "sync_every": 0, "side_stream": -1, "test_poison_level": 0, "test_poison_byte": 0xFF, "test_force_rc": 0, "score_slab_bytes": 256 << 20,
     "partner_slab_bytes": 4 << 30, "host_tables": 0, "rc_t0_ns": 3000, "rc_tg_ps": 20000, "rc_tw_ps": 50, "rc_cap": 65536,
     "bp_nt_min_cells": 262144, "max_blocks": 1024, "host_threads": 16,
 }
@@ -62,7 +62,7 @@ def test_defaults_are_pinned_once(ctx):
 def test_options_are_restored_on_error(ctx):
     g = capi.DpGraphArrays.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "toy1_k5w3_R2.dpg"))
     ref = orc.dp_solve(g)
-    changed = dict(fast=0, graph_batch=0, lattice_chunk_cells=3000, score_slab_bytes=1)
+    changed = dict(fast=0, graph_batch=0, lattice_chunk_cells=3000, score_slab_bytes=1, test_force_rc=4)
     with pytest.raises(RuntimeError, match="boom"):
         with ctx.dp_options(**changed):
             assert _dp(ctx) == {**DP_DEFAULTS, **changed}
@@ -88,13 +88,36 @@ def test_options_are_restored_on_error(ctx):
 
 
 def test_nested_managers_restore_the_outer_value(ctx):
-    with ctx.dp_options(graph_batch=7, segment_cells=5000):
-        with ctx.dp_options(graph_batch=0, lattice_chunk_cells=3000):
-            assert _dp(ctx) == {**DP_DEFAULTS, "graph_batch": 0, "segment_cells": 5000, "lattice_chunk_cells": 3000}
-        assert _dp(ctx) == {**DP_DEFAULTS, "graph_batch": 7, "segment_cells": 5000}
+    with ctx.dp_options(graph_batch=7, segment_cells=5000, test_force_rc=3):
+        with ctx.dp_options(graph_batch=0, lattice_chunk_cells=3000, test_force_rc=16):
+            assert _dp(ctx) == {**DP_DEFAULTS, "graph_batch": 0, "segment_cells": 5000, "lattice_chunk_cells": 3000, "test_force_rc": 16}
+        assert _dp(ctx) == {**DP_DEFAULTS, "graph_batch": 7, "segment_cells": 5000, "test_force_rc": 3}
     assert _dp(ctx) == DP_DEFAULTS
     with ctx.sketch_options(bucket_bits=9, bucket_stride=256):
         with ctx.sketch_options(bucket_bits=3, spill_cap=-1):
             assert _sketch(ctx) == {**SKETCH_DEFAULTS, "bucket_bits": 3, "bucket_stride": 256, "spill_cap": -1}
         assert _sketch(ctx) == {**SKETCH_DEFAULTS, "bucket_bits": 9, "bucket_stride": 256}
     assert _sketch(ctx) == SKETCH_DEFAULTS
+
+
+def test_force_rc_zero_changes_no_launch(ctx):
+    """test_force_rc = 0, set explicitly and after a forced run: the recorded launch profiles (golden/launch_profiles.json) of the eight
+    graphs under default options; a forced chunk size in between does change them, and one that is no candidate runs the all-planes chunk"""
+    import json
+    import test_gpu_sweep_variants as sw
+    want = json.load(open(sw.GOLDEN))
+    for q, make in enumerate(sw.GRAPHS):
+        g = make()
+        with ctx.dp_options(test_force_rc=0):
+            ctx.dp_solve(g)
+            assert sw._profile_text(ctx) == want[f"graph{q}"], q
+        if q in (0, 2):                                                     # R + 1 = 19 and 8: all-planes chunks 19 and 8
+            with ctx.dp_options(test_force_rc=2, coop=0):
+                ctx.dp_solve(g)
+                assert set(ctx.dp_launch_profile()) <= {"dp_sweep_fast_kernel<2,lean>", "dp_sweep_fast_kernel<2,general>"}, q
+            for n in (7, 33, 1000):                                         # not in the table / above the run's all-planes chunk
+                with ctx.dp_options(test_force_rc=n):
+                    ctx.dp_solve(g)
+                    assert sw._profile_text(ctx) == want[f"graph{q} adaptive_rc=0"], (q, n)
+            ctx.dp_solve(g)
+            assert sw._profile_text(ctx) == want[f"graph{q}"], q

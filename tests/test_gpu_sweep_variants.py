@@ -45,11 +45,13 @@ def _profile_text(ctx):
 
 def test_launch_profiles_equal_the_recorded_ones(gpu_ctx):
     graphs = [make() for make in GRAPHS]
+    refs = [orc.dp_solve(g) for g in graphs]                                # whatever was launched, the answer is the oracle's
     got, all_planes = {}, {}
     for q, opts in CASES:
         with gpu_ctx.dp_options(**opts):
-            gpu_ctx.dp_solve(graphs[q])
+            out = gpu_ctx.dp_solve(graphs[q])
             got[_case_name(q, opts)] = _profile_text(gpu_ctx)
+        assert (out.value, out.s_het, out.p1, out.p2) == (refs[q]["value"], refs[q]["s_het"], refs[q]["p1"], refs[q]["p2"]), _case_name(q, opts)
         all_planes[_case_name(q, opts)] = 8 if graphs[q].R + 1 <= 8 else 19 if graphs[q].R + 1 <= 19 else 33
     if RECORD_TO:
         with open(RECORD_TO, "w") as f:
