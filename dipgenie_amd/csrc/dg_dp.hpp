@@ -43,6 +43,13 @@ constexpr int ROWX_MAX = 64;                            // widest row in-edge ma
 constexpr int DELTA_PER_BLOCK = 256 * 16;
 constexpr int DELTA_PAD = 8;                            // delta[0..8) stays zero: the colourless transitions' slot
 constexpr int32_t CHAIN_CORRUPT = INT32_MIN;            // ChainState::value after a hop left its level
+// Score deltas are stored as uint16.  A delta is |(Hom u1 u Hom v1) n (Hom u2 u Hom v2)| + |(Het u1 u Het v1) /\ (Het u2 u Het v2)|:
+// the intersection has at most as many ids as one of its sides, 2 * max_hom, the symmetric difference at most as many as the four
+// het lists together, 4 * max_het.  Hom and het are separate lists, so the two terms add up.  (A single list stays below 16,384 ids.)
+constexpr int64_t DELTA_MAX = 65535, COLOUR_LIST_MAX = 16383;
+inline bool colour_lists_fit_delta(int64_t max_hom, int64_t max_het) {
+    return max_hom <= COLOUR_LIST_MAX && max_het <= COLOUR_LIST_MAX && 2 * max_hom + 4 * max_het <= DELTA_MAX;
+}
 
 struct LevelDesc {                                      // transition (l-1) -> l, indexed by l; passed BY VALUE to the sweep
     int32_t a0, k;                                      // source level: first vertex id, width

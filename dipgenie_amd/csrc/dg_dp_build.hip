@@ -31,7 +31,7 @@ constexpr int64_t ROWX_BUDGET_WORDS = (int64_t)1 << 30;
 enum BuildErrCode { BE_OK = 0, BE_OUT_OFF, BE_EDGE_LEVEL, BE_WEIGHT, BE_PARALLEL, BE_COL_OFF, BE_COL_SORT };
 struct BuildStat {                                           // one per build, zeroed before the first kernel
     int err, err_a, err_b, pad_;
-    unsigned long long max_list, edge_pairs, colour_entries, max_level_cells, max_level_units;
+    unsigned long long max_hom, max_het, edge_pairs, colour_entries, max_level_cells, max_level_units;
     int max_k2, any_wide;
 };
 
@@ -112,12 +112,13 @@ __global__ __launch_bounds__(256) void bt_rowrec_kernel(int nV, const uint32_t *
     rowrec[v] = make_uint4(e0, dv, word[0], word[1]);
 }
 
-// colour lists must be sorted-unique (the merges rely on it) and short enough for uint16 score deltas
+// colour lists must be sorted-unique (the merges rely on it) and short enough for uint16 score deltas: the longest hom list and the
+// longest het list are tracked separately (colour_lists_fit_delta, dg_dp.hpp)
 __global__ __launch_bounds__(256) void bt_colours_kernel(int nV, ColourCsr col, int64_t n_hom, int64_t n_het, const int32_t *__restrict__ level_of,
                                                          uint8_t *__restrict__ has_col, BuildStat *st) {
     const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (v >= nV) return;
-    unsigned long long longest = 0;
+    unsigned long long longest[2] = {0, 0};
     bool any = false;
     for (int pass = 0; pass < 2; ++pass) {
         const int64_t *off = pass ? col.het_off : col.hom_off;
@@ -125,13 +126,14 @@ __global__ __launch_bounds__(256) void bt_colours_kernel(int nV, ColourCsr col, 
         const int64_t n = pass ? n_het : n_hom;
         int64_t a = off[v], b = off[v + 1];
         if (a < 0 || b < a || b > n) { build_fail(st, BE_COL_OFF, v, 0); a = b = 0; }
-        longest = max(longest, (unsigned long long)(b - a));
+        longest[pass] = (unsigned long long)(b - a);
         any |= b > a;
         for (int64_t q = a + 1; q < b; ++q)
             if (cv[q] <= cv[q - 1]) { build_fail(st, BE_COL_SORT, v, 0); break; }
     }
     if (any) has_col[level_of[v]] = 1;
-    if (longest) atomicMax(&st->max_list, longest);
+    if (longest[0]) atomicMax(&st->max_hom, longest[0]);
+    if (longest[1]) atomicMax(&st->max_het, longest[1]);
 }
 
 // ---- per-level passes -------------------------------------------------------------------------------------------
@@ -431,7 +433,10 @@ int dp_build_tables_device(dg_ctx *c, const dg_dp_graph *g, DpState &S, std::vec
         default: set_error("colour list of vertex %d is not sorted-unique", hs.err_a); return DG_ERR_ARG;
         }
     }
-    if ((int64_t)hs.max_list * 4 > 65535) { set_error("colour lists too long for uint16 score deltas (%lld)", (long long)hs.max_list); return DG_ERR_UNSUPPORTED; }
+    if (!colour_lists_fit_delta((int64_t)hs.max_hom, (int64_t)hs.max_het)) {
+        set_error("colour lists too long for uint16 score deltas (longest hom list %lld, longest het list %lld: 2 hom + 4 het must not exceed 65535)", (long long)hs.max_hom, (long long)hs.max_het);
+        return DG_ERR_UNSUPPORTED;
+    }
     max_k = std::max(hs.max_k2, 1);
     if (max_k > MAX_K) { set_error("level width %d exceeds the supported %d", max_k, MAX_K); return DG_ERR_UNSUPPORTED; }
     if (tot[Q_GRP] >= (int64_t)1 << 31 || tot[Q_DEAD] >= (int64_t)1 << 31) { set_error("group tables too large"); return DG_ERR_UNSUPPORTED; }

@@ -6,8 +6,8 @@
 // is k x (budget + 1) cells, so a query is one workgroup and thousands of them run side by side.  Three kernels per slab of queries:
 //   * dp_partner_scores_kernel: one workgroup per (query, 64 destination levels).  One lane per level checks given[l-1], given[l]
 //     against the level descriptor and looks the hop up (first bad (query, level) by atomicMin, as dg_dp_score.hip does); then one
-//     lane per in-edge of those levels runs the two 4-way merges and stores d as 16 bits (load rejects colour lists whose four-fold
-//     length exceeds that).  All merges are done here, off the serial path.
+//     lane per in-edge of those levels runs the two 4-way merges and stores d as 16 bits (load rejects graphs whose longest
+//     hom and het lists allow more: 2 max_hom + 4 max_het > 65535, colour_lists_fit_delta).  All merges are done here, off the serial path.
 //   * dp_partner_sweep_kernel: one persistent workgroup per query, no synchronisation between workgroups.  Two copies of the state
 //     in LDS ([vertex][r], r fastest: the lanes of a vertex read consecutive words of a source row and share the in-edge records);
 //     the in-edge words, their scores and the in-edge offsets of level l + 1 are loaded into registers before the cells of level l

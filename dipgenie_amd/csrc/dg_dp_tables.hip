@@ -153,9 +153,9 @@ int Builder::build_in_csr() {
     return first_error();
 }
 
-int Builder::check_colours() {   // colour lists must be sorted (the merges rely on it) and fit the uint16 delta
+int Builder::check_colours() {   // colour lists must be sorted (the merges rely on it) and fit the uint16 delta (colour_lists_fit_delta, dg_dp.hpp)
     if (g->hom_off[0] != 0 || g->het_off[0] != 0) { set_error("colour offsets must start at 0"); return DG_ERR_ARG; }
-    std::vector<int64_t> tmax_list(NT, 0);
+    std::vector<int64_t> tmax_list(2 * (size_t)NT, 0);      // per thread: longest hom list, longest het list
     has_col.assign(L, 0);
     run_threads([&](int t) {
         for (int v = range_v0(t); v < range_v1(t); ++v) {
@@ -163,7 +163,7 @@ int Builder::check_colours() {   // colour lists must be sorted (the merges rely
                 const int64_t *off = pass ? g->het_off : g->hom_off;
                 const int32_t *colv = pass ? g->het_col : g->hom_col;
                 if (off[v + 1] < off[v]) { tfail(t, DG_ERR_ARG, "colour offsets not monotone at %d", v); return; }
-                tmax_list[t] = std::max(tmax_list[t], off[v + 1] - off[v]);
+                tmax_list[2 * t + pass] = std::max(tmax_list[2 * t + pass], off[v + 1] - off[v]);
                 if (off[v + 1] > off[v]) has_col[level_of[v]] = 1;
                 for (int64_t q = off[v] + 1; q < off[v + 1]; ++q)
                     if (colv[q] <= colv[q - 1]) { tfail(t, DG_ERR_ARG, "colour list of vertex %d is not sorted-unique", v); return; }
@@ -171,9 +171,12 @@ int Builder::check_colours() {   // colour lists must be sorted (the merges rely
         }
     });
     if (int rc = first_error()) return rc;
-    int64_t max_list = 0;
-    for (int t = 0; t < NT; ++t) max_list = std::max(max_list, tmax_list[t]);
-    if (max_list * 4 > 65535) { set_error("colour lists too long for uint16 score deltas (%lld)", (long long)max_list); return DG_ERR_UNSUPPORTED; }
+    int64_t max_hom = 0, max_het = 0;
+    for (int t = 0; t < NT; ++t) { max_hom = std::max(max_hom, tmax_list[2 * t]); max_het = std::max(max_het, tmax_list[2 * t + 1]); }
+    if (!colour_lists_fit_delta(max_hom, max_het)) {
+        set_error("colour lists too long for uint16 score deltas (longest hom list %lld, longest het list %lld: 2 hom + 4 het must not exceed 65535)", (long long)max_hom, (long long)max_het);
+        return DG_ERR_UNSUPPORTED;
+    }
     return DG_OK;
 }
 

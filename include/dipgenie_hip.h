@@ -58,7 +58,8 @@ typedef struct dg_dp_graph {          /* levelized expanded graph, vertex ids al
     const int32_t *out_dst;           /* every edge goes from level l to level l+1 */
     const uint8_t *out_w;             /* recombination weight 0/1 */
     const int64_t *hom_off, *het_off; /* [n_vertices+1] sorted-unique colour CSR (HOM / HET colours) */
-    const int32_t *hom_col, *het_col;
+    const int32_t *hom_col, *het_col; /* score deltas are 16 bits wide: 2 * (longest HOM list) + 4 * (longest HET list) must not exceed
+                                         65535 and no list may hold more than 16383 ids, or the load fails with DG_ERR_UNSUPPORTED */
 } dg_dp_graph;
 
 typedef struct dg_dp_result {         /* sink state at r = R (approximator.cpp:774-785) */

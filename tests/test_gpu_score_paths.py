@@ -97,6 +97,31 @@ def _consistent(m, path, edges):
     return mine == list(edges)
 
 
+def walked_pairs_score_their_plane(ctx, g, m, what):
+    """the check of test_walked_paths_score_their_plane on one enumerable graph (m = PathModel(g)); returns, per reachable budget,
+    (budget, the candidate pairs [n, 2, L], the device's records of them, the index of one that is worth the plane)"""
+    all_paths = m.all_paths()
+    ctx.dp_load_graph(g)
+    outs = ctx.dp_run_budgets(range(g.R + 1))
+    values = ctx.dp_budget_values()
+    checked = []
+    for b, out in enumerate(outs):
+        assert out.value == values[b]
+        if out.value == NEG_INF:
+            continue
+        c1 = [p for p in all_paths if _consistent(m, p, out.p1)]
+        c2 = [p for p in all_paths if _consistent(m, p, out.p2)]
+        assert c1 and c2, (what, b)
+        cand = np.array([[p, q] for p in c1 for q in c2], np.int32)
+        got = ctx.dp_score_paths(cand)
+        assert (got["r1"] == len(out.p1) - 1).all() and (got["r2"] == len(out.p2) - 1).all()
+        assert (got["r1"] + got["r2"] <= b).all() and (got["value"] <= out.value).all(), (what, b)
+        hit = (got["value"] == out.value) & (got["s_het"] == out.s_het)
+        assert hit.any(), (what, b, out.key(), got)
+        checked.append((b, cand, got, int(np.argmax(hit))))
+    return checked
+
+
 def test_walked_paths_score_their_plane(gpu_ctx):
     """every reachable budget's two paths, rebuilt from the returned edge lists plus the graph (all paths that spend exactly those
     weight-1 edges; stretches of weight-0 edges may leave a choice), scored by the device: r1 / r2 are the lists' lengths, none
@@ -104,24 +129,7 @@ def test_walked_paths_score_their_plane(gpu_ctx):
     n_checked = 0
     for seed, n_levels, extra, p_w1, p_colour in ENUMERABLE:
         g = graphgen.random_levelized(seed, n_levels=n_levels, max_width=4, R=3, extra_edges=extra, p_w1=p_w1, p_colour=p_colour)
-        m = PathModel(g)
-        all_paths = m.all_paths()
-        gpu_ctx.dp_load_graph(g)
-        outs = gpu_ctx.dp_run_budgets(range(g.R + 1))
-        values = gpu_ctx.dp_budget_values()
-        for b, out in enumerate(outs):
-            assert out.value == values[b]
-            if out.value == NEG_INF:
-                continue
-            c1 = [p for p in all_paths if _consistent(m, p, out.p1)]
-            c2 = [p for p in all_paths if _consistent(m, p, out.p2)]
-            assert c1 and c2, (seed, b)
-            cand = np.array([[p, q] for p in c1 for q in c2], np.int32)
-            got = gpu_ctx.dp_score_paths(cand)
-            assert (got["r1"] == len(out.p1) - 1).all() and (got["r2"] == len(out.p2) - 1).all()
-            assert (got["r1"] + got["r2"] <= b).all() and (got["value"] <= out.value).all(), (seed, b)
-            assert ((got["value"] == out.value) & (got["s_het"] == out.s_het)).any(), (seed, b, out.key(), got)
-            n_checked += 1
+        n_checked += len(walked_pairs_score_their_plane(gpu_ctx, g, PathModel(g), seed))
     assert n_checked >= 12, n_checked
 
 

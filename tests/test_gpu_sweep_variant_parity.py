@@ -92,23 +92,26 @@ def test_the_variant_list_is_the_table(gpu_ctx):
     assert capi.lib.dg_dp_list_sweep_variants(None, 8192) != 0
 
 
-@pytest.mark.parametrize("digest", [1, 0])
-@pytest.mark.parametrize("case", list(sv.GRAPHS))
-def test_every_variant_equals_the_oracle(gpu_ctx, case, digest):
-    g = sv.graph(case)
-    ref = sv.oracle(case)
-    planes = [r["value"] for r in sv.oracle_per_budget(case)]
+def every_variant_equals_the_oracle(ctx, g, ref, planes, digest, case):
+    """the variant loop: g under every (kernel, RC) that is a candidate at its R + 1, against the oracle's answer ref (with digests)
+    and the oracle's sink value per budget 0..R (planes); tests/test_gpu_colour_lists.py runs its graphs through it as well"""
     n_run = 0
     for kernel, rc in TARGETS:
         if kernel != "generic" and not _eligible(rc, g.R):
             continue
-        with gpu_ctx.dp_options(digest=digest, **_options(kernel, rc)):
-            out = gpu_ctx.dp_solve(g)
-            _equals_the_oracle(gpu_ctx, g, out, ref, digest, (case, kernel, rc))
-            assert [int(v) for v in gpu_ctx.dp_budget_values()] == planes, (case, kernel, rc)
-            _check_profile(gpu_ctx, g, kernel, rc)
+        with ctx.dp_options(digest=digest, **_options(kernel, rc)):
+            out = ctx.dp_solve(g)
+            _equals_the_oracle(ctx, g, out, ref, digest, (case, kernel, rc))
+            assert [int(v) for v in ctx.dp_budget_values()] == planes, (case, kernel, rc)
+            _check_profile(ctx, g, kernel, rc)
         n_run += 1
     assert n_run >= 12, n_run                               # generic + at least RC 1..6, 8 fast + RC 1..4 cooperative
+
+
+@pytest.mark.parametrize("digest", [1, 0])
+@pytest.mark.parametrize("case", list(sv.GRAPHS))
+def test_every_variant_equals_the_oracle(gpu_ctx, case, digest):
+    every_variant_equals_the_oracle(gpu_ctx, sv.graph(case), sv.oracle(case), [r["value"] for r in sv.oracle_per_budget(case)], digest, case)
 
 
 @pytest.mark.parametrize("case", ["lean-R18", "general-R18"])
