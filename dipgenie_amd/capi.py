@@ -55,6 +55,9 @@ PAIR_SCORE = np.dtype([("value", np.int32), ("s_het", np.int32), ("r1", np.int32
 # dg_dp_partner as a numpy record: what Context.dp_best_partners returns
 PARTNER = np.dtype([("value", np.int32), ("s_het", np.int32), ("r1", np.int32), ("r2", np.int32)])
 
+# dg_dp_level_margin as a numpy record: one per (query, level) of Context.dp_partner_marginals
+LEVEL_MARGIN = np.dtype([("best_vertex", np.int32), ("best_value", np.int32), ("second_vertex", np.int32), ("second_value", np.int32)])
+
 
 class SketchTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("sort_ms", C.c_float), ("total_ms", C.c_float), ("n_emitted", C.c_int64)]
@@ -70,7 +73,7 @@ SYMBOLS = [
     "dg_anchor_begin", "dg_anchor_add_haplotype", "dg_anchor_finish", "dg_dp_solve_haploid", "dg_dp_get_table_digest", "dg_hip_versions", "dg_anchor_add_haplotype_sketched",
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
-    "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners",
+    "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants",
 ]
 
@@ -89,6 +92,7 @@ lib.dg_dp_run_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(D
 lib.dg_dp_get_budget_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 lib.dg_dp_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_best_partners.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_partner_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -350,6 +354,28 @@ class Context:
         _check(lib.dg_dp_best_partners(self.h, p.ctypes.data if p.size else None, p.shape[0], b.ctypes.data if b.size else None,
                                        partners.ctypes.data if want_paths and partners.size else None, out.ctypes.data if out.size else None), "dg_dp_best_partners")
         return out, partners
+
+    def dp_partner_marginals(self, given, budgets, want_vertices=False):
+        """given, budgets: as for dp_best_partners.  Returns (levels, vertex_values): a LEVEL_MARGIN record array [n, n_levels]
+        (best_vertex, best_value, second_vertex, second_value: the vertex of the level that the best partner within the budget
+        passes through -- the smallest id among equals --, what that partner is worth, and the same for the best partner that goes
+        through another vertex of the level; -1 and NEG_INF where there is none) and, with want_vertices=True, int32
+        [n, n_vertices]: the value of the best partner through every vertex, NEG_INF where no path within the budget passes
+        (None otherwise).  best_value - second_value is the margin of the call at that level.  A query whose budget nothing fits
+        is all -1 / NEG_INF.  A bad given path raises DgError naming the first (query, level).  Leaves the last run's answers alone."""
+        p = np.ascontiguousarray(given, np.int32)
+        b = np.ascontiguousarray(budgets, np.int32)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 2 or (g is not None and p.shape[1] != g.n_levels):
+            raise ValueError(f"given must have shape [n, n_levels], got {p.shape}")
+        if b.shape != (p.shape[0],):
+            raise ValueError(f"budgets must have shape [{p.shape[0]}], got {b.shape}")
+        levels = np.zeros(p.shape, LEVEL_MARGIN)
+        values = np.zeros((p.shape[0], g.n_vertices if g is not None else 0), np.int32) if want_vertices else None
+        _check(lib.dg_dp_partner_marginals(self.h, p.ctypes.data if p.size else None, p.shape[0], b.ctypes.data if b.size else None,
+                                           levels.ctypes.data if levels.size else None, values.ctypes.data if want_vertices and values.size else None),
+               "dg_dp_partner_marginals")
+        return levels, values
 
     def dp_solve(self, g):
         self.dp_load_graph(g)

@@ -1,5 +1,5 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
-// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip).
+// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -162,7 +162,7 @@ struct DpOptions {
     int64_t rc_cap = 65536, rc_t0_ns = 3000, rc_tg_ps = 20000, rc_tw_ps = 50;   // rc_*: cost model of the per-level RC choice
     int64_t chunk_units_cfg = (int64_t)4 << 30;         // lattice_chunk_cells: size of one lattice chunk (16-bit units, even: 8 GB)
     int64_t score_slab_bytes = (int64_t)256 << 20;      // score_slab_bytes: bound of the path staging buffer of dg_dp_score_paths (a slab holds at least one pair)
-    int64_t partner_slab_bytes = (int64_t)4 << 30;      // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners (a slab holds at least one query)
+    int64_t partner_slab_bytes = (int64_t)4 << 30;      // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, of the forward values, edge scores, marginals and records of one slab of dg_dp_partner_marginals (a slab holds at least one query)
 };
 
 struct DpState {
@@ -248,6 +248,9 @@ struct DpState {
     // ---- dg_dp_best_partners (dg_dp_partner.hip): one slab of queries -- (given, partner) pairs, budgets, sink cells, the re-scoring
     // pass's records, the two first-bad-hop words; back-pointers and edge scores (released when the call returns) ----
     DevBuf d_pt_pairs, d_pt_bud, d_pt_val, d_pt_out, d_pt_err, d_pt_bp, d_pt_scores;
+    // ---- dg_dp_partner_marginals (dg_dp_marginals.hip): the level records and the marginals of one slab; the given paths, budgets, sink
+    // cells, first-bad-hop word, forward values (in d_pt_bp) and edge scores live in the buffers above ----
+    DevBuf d_mg_levels, d_mg_vertex;
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -317,5 +320,8 @@ void score_launch_pairs(const DpState &S, const int32_t *pairs, int64_t n, int32
 
 // ---- the best partner of a given path: the DP with one haplotype fixed (dg_dp_partner.hip) ----
 int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out);
+
+// ---- partner marginals: that DP forward and backward, combined per vertex (dg_dp_marginals.hip; shares dg_dp_partner.hpp with the above) ----
+int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
 
 }  // namespace dgi

@@ -19,39 +19,32 @@
 //     DP's cell and r2 must fit the budget, or the call fails with DG_ERR_STATE.
 // Nothing of a run is read or written.  Per query a slab holds 2 * n_vertices * (bmax + 1) bytes of back-pointers (bmax: the largest
 // budget of the call), 2 bytes per in-edge of scores and 8 * n_levels bytes of paths; partner_slab_bytes bounds their sum.
+// dg_dp_partner_marginals (dg_dp_marginals.hip) runs the first two kernels as well, the second one storing every cell's int32 value
+// in place of the back-pointer (VALUES): what the two files share is declared in dg_dp_partner.hpp.
 #include <algorithm>
 #include <cstring>
 
+#include "dg_dp_partner.hpp"
 #include "dg_dp_setops.hpp"
 
 namespace dgi {
 
 namespace {
 
-constexpr unsigned long long PT_NO_ERROR = ~0ull;
-constexpr int PT_THREADS = 256;
-constexpr int PT_SCORE_LEVELS = 64;                     // destination levels per workgroup of the score kernel
-constexpr int PT_PF = 4;                                // staged in-edges per lane
-constexpr int PT_STAGE = PT_THREADS * PT_PF;            // in-edges (and vertices) of a level that the LDS stage holds
-constexpr int PT_MAX_CELLS = 16384;                     // kmax * (budget + 1): two int32 copies = 128 KiB of the CU's 160 KiB
 constexpr uint32_t PT_BP_NONE = 0xFFFFu;
-constexpr size_t PT_STAGE_BYTES = 2 * ((size_t)PT_STAGE * 4 + ((size_t)PT_STAGE + 4) * 4 + (size_t)PT_STAGE * 2);
+constexpr size_t PT_STAGE_BYTES = 2 * PT_STAGE_BUF_BYTES;
 
-__device__ __forceinline__ unsigned long long partner_err_key(int64_t query, int level, int kind) {
-    return ((unsigned long long)query << 33) | ((unsigned long long)(uint32_t)level << 1) | (unsigned long long)kind;
-}
-
-// grid: n * nblk workgroups; pairs = [n][2][L], row 0 the given path; scores = [n][E]
+// grid: n * nblk workgroups; query q's given path = given_all + q * given_stride ([n][2][L], row 0, for dg_dp_best_partners); scores = [n][E]
 __global__ __launch_bounds__(PT_THREADS) void dp_partner_scores_kernel(const LevelDesc *__restrict__ descs, int L, int nblk,
                                                                        const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
-                                                                       const int32_t *__restrict__ in_dst, ColourCsr col, const int32_t *__restrict__ pairs,
-                                                                       uint16_t *__restrict__ scores, int64_t E, unsigned long long *__restrict__ err) {
+                                                                       const int32_t *__restrict__ in_dst, ColourCsr col, const int32_t *__restrict__ given_all,
+                                                                       int64_t given_stride, uint16_t *__restrict__ scores, int64_t E, unsigned long long *__restrict__ err) {
     __shared__ uint32_t s_base[PT_SCORE_LEVELS + 1];
     __shared__ int32_t s_a0[PT_SCORE_LEVELS], s_gu[PT_SCORE_LEVELS], s_gv[PT_SCORE_LEVELS], s_ok[PT_SCORE_LEVELS];
     const int64_t q = (int64_t)(blockIdx.x / (unsigned)nblk);
     const int l0 = 1 + (int)(blockIdx.x % (unsigned)nblk) * PT_SCORE_LEVELS;
     const int nl = min(PT_SCORE_LEVELS, L - l0);
-    const int32_t *given = pairs + q * 2 * (int64_t)L;
+    const int32_t *given = given_all + q * given_stride;
     const int t = (int)threadIdx.x;
     if (t < nl) {
         const int l = l0 + t;
@@ -84,18 +77,15 @@ __global__ __launch_bounds__(PT_THREADS) void dp_partner_scores_kernel(const Lev
     }
 }
 
-struct PtLevel { int b0, k2; uint32_t in_base; int T; };
-__device__ __forceinline__ PtLevel pt_level(const LevelDesc *__restrict__ descs, int l) {
-    const LevelDesc &d = descs[l];
-    return PtLevel{d.b0, d.k2, d.in_base, d.T};
-}
-__device__ __forceinline__ bool pt_staged(const PtLevel &v) { return v.T <= PT_STAGE && v.k2 <= PT_STAGE; }
+// What a cell leaves in global memory: its 16-bit back-pointer (dg_dp_best_partners) or its int32 value (VALUES: dg_dp_partner_marginals)
+template <bool VALUES> struct PtStore { typedef uint16_t type; };
+template <> struct PtStore<true> { typedef int32_t type; };
 
 // The cells of one level.  STAGED: edge / sc / off are the LDS stage (indices relative to the level's first in-edge / vertex);
 // otherwise the global arrays (off = in_off + b0, absolute in-edge indices).
-template <bool STAGED>
+template <bool STAGED, bool VALUES>
 __device__ __forceinline__ void pt_cells(const PtLevel &lv, int B1, int vrow, int rows, int r0, int rstep, const int32_t *prev, int32_t *cur,
-                                         const uint32_t *edge, const uint16_t *sc, const uint32_t *off, uint16_t *__restrict__ bp) {
+                                         const uint32_t *edge, const uint16_t *sc, const uint32_t *off, typename PtStore<VALUES>::type *__restrict__ bp) {
     for (int v = vrow; v < lv.k2; v += rows) {
         const uint32_t e0 = off[v], e1 = off[v + 1];
         for (int r = r0; r < B1; r += rstep) {
@@ -111,22 +101,24 @@ __device__ __forceinline__ void pt_cells(const PtLevel &lv, int B1, int vrow, in
                 if (cand > best) { best = cand; word = (uint32_t)pos | ((uint32_t)w << 15); }
             }
             cur[v * B1 + r] = best;
-            bp[((int64_t)lv.b0 + v) * B1 + r] = (uint16_t)word;
+            if constexpr (VALUES) bp[((int64_t)lv.b0 + v) * B1 + r] = best;
+            else bp[((int64_t)lv.b0 + v) * B1 + r] = (uint16_t)word;
         }
     }
 }
 
 // grid: n workgroups of PT_THREADS; dynamic LDS = two states of `cells` int32 each, then the two stage buffers
+template <bool VALUES>
 __global__ __launch_bounds__(PT_THREADS) void dp_partner_sweep_kernel(const LevelDesc *__restrict__ descs, int L, int nV, int cells,
                                                                       const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
                                                                       const uint16_t *__restrict__ scores, int64_t E, const int32_t *__restrict__ budgets,
-                                                                      uint16_t *__restrict__ bp_all, int64_t bp_stride, int32_t *__restrict__ value) {
+                                                                      typename PtStore<VALUES>::type *__restrict__ bp_all, int64_t bp_stride, int32_t *__restrict__ value) {
     extern __shared__ int32_t pt_lds[];
     const int64_t q = blockIdx.x;
     const int t = (int)threadIdx.x;
     const int B1 = budgets[q] + 1;
     const uint16_t *__restrict__ sc_g = scores + q * E;
-    uint16_t *__restrict__ bp = bp_all + q * bp_stride;
+    typename PtStore<VALUES>::type *__restrict__ bp = bp_all + q * bp_stride;
     int32_t *const state0 = pt_lds, *const state1 = pt_lds + cells;     // level l lives in state (l & 1)
     // stage buffer b: PT_STAGE in-edge words, PT_STAGE + 4 in-edge offsets, PT_STAGE scores
     uint32_t *const st_edge0 = (uint32_t *)(pt_lds + 2 * (size_t)cells), *const st_off0 = st_edge0 + 2 * PT_STAGE;
@@ -139,7 +131,10 @@ __global__ __launch_bounds__(PT_THREADS) void dp_partner_sweep_kernel(const Leve
     if (B1 <= PT_THREADS) { rows = PT_THREADS / B1; vrow = t / B1; r0 = t - vrow * B1; rstep = B1; if (vrow >= rows) vrow = 1 << 30; }
     else { rows = 1; vrow = 0; r0 = t; rstep = PT_THREADS; }
 
-    for (int r = t; r < B1; r += PT_THREADS) state0[r] = 0;           // level 0 is the source alone
+    for (int r = t; r < B1; r += PT_THREADS) {                        // level 0 is the source alone
+        state0[r] = 0;
+        if constexpr (VALUES) bp[(int64_t)descs[1].a0 * B1 + r] = 0;
+    }
     PtLevel lv = pt_level(descs, 1);
     PtLevel ln = L > 2 ? pt_level(descs, 2) : lv;
     if (pt_staged(lv)) {
@@ -166,8 +161,8 @@ __global__ __launch_bounds__(PT_THREADS) void dp_partner_sweep_kernel(const Leve
         }
         const int32_t *prev = (l & 1) ? state0 : state1;
         int32_t *cur = (l & 1) ? state1 : state0;
-        if (pt_staged(lv)) pt_cells<true>(lv, B1, vrow, rows, r0, rstep, prev, cur, PT_EDGE(l & 1), PT_SC(l & 1), PT_OFF(l & 1), bp);
-        else pt_cells<false>(lv, B1, vrow, rows, r0, rstep, prev, cur, in_edge, sc_g, in_off + lv.b0, bp);
+        if (pt_staged(lv)) pt_cells<true, VALUES>(lv, B1, vrow, rows, r0, rstep, prev, cur, PT_EDGE(l & 1), PT_SC(l & 1), PT_OFF(l & 1), bp);
+        else pt_cells<false, VALUES>(lv, B1, vrow, rows, r0, rstep, prev, cur, in_edge, sc_g, in_off + lv.b0, bp);
         if (stage_next) {
             const int nb = (l + 1) & 1;
 #pragma unroll
@@ -222,6 +217,57 @@ __global__ __launch_bounds__(64) void dp_partner_walk_kernel(const LevelDesc *__
 
 }  // namespace
 
+int partner_check_budgets(const char *fn, const DpState &S, int64_t n, const int32_t *budgets, int &kmax, int &bmax) {
+    kmax = 1;
+    for (int l = 1; l < S.L; ++l) kmax = std::max(kmax, S.descs[l].k2);
+    bmax = 0;
+    for (int64_t q = 0; q < n; ++q) {
+        if (budgets[q] < 0) { set_error("%s: query %lld: budget %d is negative", fn, (long long)q, budgets[q]); return DG_ERR_ARG; }
+        if ((int64_t)kmax * ((int64_t)budgets[q] + 1) > PT_MAX_CELLS) {
+            set_error("%s: query %lld: widest level %d x (budget + 1) %lld exceeds %d cells", fn, (long long)q, kmax, (long long)budgets[q] + 1, PT_MAX_CELLS);
+            return DG_ERR_UNSUPPORTED;
+        }
+        bmax = std::max(bmax, budgets[q]);
+    }
+    return DG_OK;
+}
+
+static int partner_score_blocks(const DpState &S) { return (S.L - 1 + PT_SCORE_LEVELS - 1) / PT_SCORE_LEVELS; }
+
+int64_t partner_slab_limit(const DpState &S) { return std::max<int64_t>(1, ((int64_t)1 << 30) / std::max(partner_score_blocks(S), score_pair_blocks(S))); }
+
+int partner_bad_hop(const char *fn, unsigned long long key, int64_t first, const int32_t *given, int L) {
+    const int64_t q = first + (int64_t)(key >> 33);
+    const int level = (int)((uint32_t)key >> 1), kind = (int)(key & 1u);
+    const int32_t *pp = given + q * L;
+    if (kind == 0) set_error("%s: query %lld level %d: vertex %d is not in that level", fn, (long long)q, level, pp[level]);
+    else set_error("%s: query %lld level %d: no edge %d -> %d", fn, (long long)q, level, pp[level - 1], pp[level]);
+    return DG_ERR_ARG;
+}
+
+void partner_launch_scores(const DpState &S, const int32_t *given, int64_t given_stride, int64_t m, uint16_t *scores, unsigned long long *err, hipStream_t s) {
+    const int nblk = partner_score_blocks(S);
+    hipLaunchKernelGGL(dp_partner_scores_kernel, dim3((unsigned)(m * nblk)), dim3(PT_THREADS), 0, s, S.d_descs.as<LevelDesc>(), S.L, nblk,
+                       S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_in_dst.as<int32_t>(), colour_csr(S), given, given_stride, scores, S.n_edges, err);
+}
+
+// the recurrence on m queries; store = back-pointers (16 bits per cell) or values (32 bits), stride in those units
+template <bool VALUES>
+static int partner_launch_sweep(const DpState &S, int cells, int64_t m, const uint16_t *scores, const int32_t *budgets, typename PtStore<VALUES>::type *store,
+                                int64_t stride, int32_t *value, hipStream_t s) {
+    const size_t lds_bytes = 2 * (size_t)cells * 4 + PT_STAGE_BYTES;
+    if (lds_bytes > 65536) DG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dp_partner_sweep_kernel<VALUES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(dp_partner_sweep_kernel<VALUES>, dim3((unsigned)m), dim3(PT_THREADS), lds_bytes, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, cells,
+                       S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), scores, S.n_edges, budgets, store, stride, value);
+    DG_HIP(hipGetLastError());
+    return DG_OK;
+}
+
+int partner_launch_forward_values(const DpState &S, int cells, int64_t m, const uint16_t *scores, const int32_t *budgets, int32_t *values, int64_t stride,
+                                  int32_t *value, hipStream_t s) {
+    return partner_launch_sweep<true>(S, cells, m, scores, budgets, values, stride, value, s);
+}
+
 int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out) {
     DpState *Sp = c->dp;
     if (!Sp || !Sp->loaded) { set_error("dg_dp_best_partners: no graph loaded"); return DG_ERR_STATE; }
@@ -232,27 +278,15 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
     hipStream_t s = c->stream;
     const int L = S.L, nV = S.nV;
     const int64_t E = S.n_edges;
-    int kmax = 1;
-    for (int l = 1; l < L; ++l) kmax = std::max(kmax, S.descs[l].k2);
-    int bmax = 0;
-    for (int64_t q = 0; q < n; ++q) {
-        if (budgets[q] < 0) { set_error("dg_dp_best_partners: query %lld: budget %d is negative", (long long)q, budgets[q]); return DG_ERR_ARG; }
-        if ((int64_t)kmax * ((int64_t)budgets[q] + 1) > PT_MAX_CELLS) {
-            set_error("dg_dp_best_partners: query %lld: widest level %d x (budget + 1) %lld exceeds %d cells", (long long)q, kmax, (long long)budgets[q] + 1, PT_MAX_CELLS);
-            return DG_ERR_UNSUPPORTED;
-        }
-        bmax = std::max(bmax, budgets[q]);
-    }
+    int kmax, bmax;
+    if (int rc = partner_check_budgets("dg_dp_best_partners", S, n, budgets, kmax, bmax)) return rc;
     const int cells = kmax * (bmax + 1);
-    const size_t lds_bytes = 2 * (size_t)cells * 4 + PT_STAGE_BYTES;
-    if (lds_bytes > 65536) DG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dp_partner_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     // queries per slab: what partner_slab_bytes holds (at least one), every query sized for the call's largest budget
     const int64_t bp_stride = (int64_t)nV * (bmax + 1);                 // 16-bit units
     const int64_t pair_words = 2 * (int64_t)L;
     const int64_t query_bytes = 2 * bp_stride + 2 * E + 4 * pair_words;
-    const int nblk_sc = (L - 1 + PT_SCORE_LEVELS - 1) / PT_SCORE_LEVELS;
     int64_t per_slab = std::max<int64_t>(1, S.opt.partner_slab_bytes / query_bytes);
-    per_slab = std::min(per_slab, std::max<int64_t>(1, ((int64_t)1 << 30) / std::max(nblk_sc, score_pair_blocks(S))));
+    per_slab = std::min(per_slab, partner_slab_limit(S));
     per_slab = std::min(per_slab, n);
     if (int rc = S.d_pt_pairs.ensure((size_t)(per_slab * pair_words) * 4)) return rc;
     if (int rc = S.d_pt_bud.ensure((size_t)per_slab * 4)) return rc;
@@ -277,13 +311,9 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
         DG_HIP(hipMemcpyAsync(S.d_pt_bud.p, budgets + first, (size_t)m * 4, hipMemcpyHostToDevice, s));
         DG_HIP(hipMemsetAsync(S.d_pt_out.p, 0, (size_t)m * sizeof(dg_dp_pair_score), s));
         DG_HIP(hipMemsetAsync(d_err, 0xFF, sizeof err, s));
-        hipLaunchKernelGGL(dp_partner_scores_kernel, dim3((unsigned)(m * nblk_sc)), dim3(PT_THREADS), 0, s, S.d_descs.as<LevelDesc>(), L, nblk_sc,
-                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_in_dst.as<int32_t>(), colour_csr(S), pairs, S.d_pt_scores.as<uint16_t>(), E, d_err);
+        partner_launch_scores(S, pairs, pair_words, m, S.d_pt_scores.as<uint16_t>(), d_err, s);
         DG_HIP(hipGetLastError());
-        hipLaunchKernelGGL(dp_partner_sweep_kernel, dim3((unsigned)m), dim3(PT_THREADS), lds_bytes, s, S.d_descs.as<LevelDesc>(), L, nV, cells,
-                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_pt_scores.as<uint16_t>(), E, S.d_pt_bud.as<int32_t>(),
-                           S.d_pt_bp.as<uint16_t>(), bp_stride, S.d_pt_val.as<int32_t>());
-        DG_HIP(hipGetLastError());
+        if (int rc = partner_launch_sweep<false>(S, cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_bp.as<uint16_t>(), bp_stride, S.d_pt_val.as<int32_t>(), s)) return rc;
         hipLaunchKernelGGL(dp_partner_walk_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), L, nV, m, S.d_pt_bud.as<int32_t>(),
                            S.d_pt_bp.as<uint16_t>(), bp_stride, S.d_pt_val.as<int32_t>(), pairs);
         DG_HIP(hipGetLastError());
@@ -295,14 +325,7 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
         if (partners)
             DG_HIP(hipMemcpy2DAsync(rows.data() + first * L, (size_t)L * 4, pairs + L, (size_t)pair_words * 4, (size_t)L * 4, (size_t)m, hipMemcpyDeviceToHost, s));
         DG_HIP(hipStreamSynchronize(s));
-        if (err[0] != PT_NO_ERROR) {                                    // slabs go up in order: the first slab with a bad hop holds the first bad hop
-            const int64_t q = first + (int64_t)(err[0] >> 33);
-            const int level = (int)((uint32_t)err[0] >> 1), kind = (int)(err[0] & 1u);
-            const int32_t *pp = given + q * L;
-            if (kind == 0) set_error("dg_dp_best_partners: query %lld level %d: vertex %d is not in that level", (long long)q, level, pp[level]);
-            else set_error("dg_dp_best_partners: query %lld level %d: no edge %d -> %d", (long long)q, level, pp[level - 1], pp[level]);
-            return DG_ERR_ARG;
-        }
+        if (err[0] != PT_NO_ERROR) return partner_bad_hop("dg_dp_best_partners", err[0], first, given, L);   // slabs go up in order: the first slab with a bad hop holds the first bad hop
         if (err[1] != PT_NO_ERROR) {
             set_error("dg_dp_best_partners: query %lld: the walked partner is not a path (level %d)", (long long)(first + (int64_t)(err[1] >> 33)), (int)((uint32_t)err[1] >> 1));
             return DG_ERR_STATE;

@@ -149,6 +149,34 @@ typedef struct dg_dp_partner {
  * level x (budget + 1) > 16384 cells for some query (the message names both numbers).  A failed call writes neither partners nor out.
  * n = 0 is DG_OK.  Synchronises. */
 int dg_dp_best_partners(dg_ctx *, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out);
+/* Partner marginals: for a given path and a budget b, what the best partner through every vertex is worth, and per level the best
+ * vertex, the best of the others and so the margin between them.  Notation of dg_dp_best_partners: d_l(u, v) is the score of the
+ * in-edge u -> v into level l with `given` fixed, parallel edges are one edge.  Forward: F = the S of dg_dp_best_partners.  Backward:
+ * B_{L-1}[sink][r] = 0 for r = 0..b; B_{l-1}[u][r] = max over the out-edges (u -> v, w) with r - w >= 0 and a reachable destination
+ * cell of d_l(u, v) + B_l[v][r - w], NEG_INF where there is none.  M[v] = max over r = 0..b with both cells reachable of
+ * F[v][r] + B[v][b - r], NEG_INF if there is no such r: the maximum of dg_dp_score_paths' value of (given, q) over all source -> sink
+ * paths q through v with r(q) <= b (both tables mean "at most r", so the split over r loses nothing). */
+typedef struct dg_dp_level_margin {
+    int32_t best_vertex, best_value;      /* the vertex of the level with the largest M (the smallest id among equals) and its M: dg_dp_best_partners' value at every level */
+    int32_t second_vertex, second_value;  /* the same choice among the level's other vertices; -1, NEG_INF if none of them has a reachable M */
+} dg_dp_level_margin;
+/* given, budgets (host): as for dg_dp_best_partners, one budget per query; levels (host) = [n][n_levels]; vertex_values (host) =
+ * [n][n_vertices] receives M, may be NULL.  second_value == best_value: the data cannot tell the two vertices apart at that level;
+ * best_value - second_value is the margin of the call there.  best_vertex[l] need not be dg_dp_best_partners' partner[l] where
+ * values tie: that walk breaks a tie by the smallest source position of the in-edge it came through, this record by the smallest
+ * vertex id among ALL vertices of the level that reach the value.  A query whose budget no path fits is an answer, not an error:
+ * -1, NEG_INF, -1, NEG_INF on every level and NEG_INF for every vertex.  Needs dg_dp_load_graph only and leaves the answers of an
+ * earlier run (dg_dp_get_budget_values, dg_dp_get_level_digest, dg_dp_get_timing) as they were.  Per query one workgroup runs the
+ * forward recurrence, keeping every cell's value, and a second one the backward recurrence with the combination, both with
+ * widest level x (budget + 1) cells of state in LDS.  Queries go up in slabs, in order; option partner_slab_bytes bounds the device
+ * memory of a slab, every query counting 4 * n_vertices * (bmax + 1) bytes of forward values, 2 * n_edges of scores, 4 * n_vertices
+ * of marginals and 20 * n_levels of path and level records, bmax the largest budget of the call.  Errors as for dg_dp_best_partners:
+ * DG_ERR_STATE: no graph loaded.  DG_ERR_ARG: a null given, budgets or levels, n < 0, a negative budget (the message names the
+ * query), a given path with a vertex outside its level or a hop without an edge (the message names the first such (query, level),
+ * in that order of significance; the level of a missing edge is its destination's).  DG_ERR_UNSUPPORTED: widest level x (budget + 1)
+ * > 16384 cells for some query (the message names both numbers).  A failed call writes neither levels nor vertex_values.  n = 0 is
+ * DG_OK.  Synchronises. */
+int dg_dp_partner_marginals(dg_ctx *, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
 /* debug/parity: copy the per-level digest (same definition as the oracle's level_digest) of the
  * last run; out has n_levels entries, entry 0 unused. Requires dg_dp_set_option("digest",1). */
 int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
@@ -170,7 +198,7 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   test_force_rc n       tests: n != 0 = every level's chunk-size choice considers the chunk of n recombination counts only (with coop 0|2: one kernel variant per run);
  *                         a level on which n is no candidate (not instantiated, above the run's all-planes chunk, no cooperative form) runs the all-planes chunk as with adaptive_rc 0
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
- *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners (default 4 GB, n <= 0 restores it; a slab holds at least one query)
+ *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, and of what a slab of dg_dp_partner_marginals holds (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning
  * This list is documentation: struct DpOptions (csrc/dg_dp.hpp) is authoritative for the defaults, the key table beside dg_dp_set_option for the clamps. */
