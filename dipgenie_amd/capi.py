@@ -58,6 +58,9 @@ PARTNER = np.dtype([("value", np.int32), ("s_het", np.int32), ("r1", np.int32), 
 # dg_dp_level_margin as a numpy record: one per (query, level) of Context.dp_partner_marginals
 LEVEL_MARGIN = np.dtype([("best_vertex", np.int32), ("best_value", np.int32), ("second_vertex", np.int32), ("second_value", np.int32)])
 
+# dg_dp_call_margin as a numpy record: one per (haplotype, level) of Context.dp_call_margins
+CALL_MARGIN = np.dtype([("vertex", np.int32), ("value", np.int32), ("alt_vertex", np.int32), ("alt_value", np.int32)])
+
 
 class SketchTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("sort_ms", C.c_float), ("total_ms", C.c_float), ("n_emitted", C.c_int64)]
@@ -74,7 +77,7 @@ SYMBOLS = [
     "dg_sketch_set_option", "dg_sketch_get_stat", "dg_sketch_count_rank_dictionary_dev",
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
-    "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants",
+    "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -93,6 +96,8 @@ lib.dg_dp_get_budget_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 lib.dg_dp_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_best_partners.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_partner_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_get_answer_paths.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+lib.dg_dp_call_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -376,6 +381,34 @@ class Context:
                                            levels.ctypes.data if levels.size else None, values.ctypes.data if want_vertices and values.size else None),
                "dg_dp_partner_marginals")
         return levels, values
+
+    def dp_answer_paths(self, budget):
+        """the pair of paths the last dp_run / dp_run_budgets walked for `budget` (one the run read out): int32 [2, n_levels], row 0
+        the path of DpOutcome.p1, row 1 that of p2 -- rows that dp_score_paths, dp_best_partners and dp_partner_marginals take.  Both
+        rows are all -1 where no pair fits the budget.  Leaves the run's answers alone."""
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        paths = np.zeros((2, g.n_levels if g is not None else 1), np.int32)
+        _check(lib.dg_dp_get_answer_paths(self.h, int(budget), paths.ctypes.data), "dg_dp_get_answer_paths")
+        return paths
+
+    def dp_call_margins(self, budget, vertex_class=None, want_paths=False):
+        """Per haplotype of the last run's answer at `budget` and per level: a CALL_MARGIN record array [2, n_levels] (vertex: the
+        called vertex; value: what the best partner through it is worth with the other haplotype fixed, the run's value at the
+        budget; alt_vertex, alt_value: the same for the best vertex of another class, -1 and NEG_INF where there is none) and, with
+        want_paths=True, what dp_answer_paths returns (None otherwise).  vertex_class: int32 [n_vertices], or None for "every vertex
+        is its own class".  value - alt_value is the margin of the call.  Leaves the run's answers alone."""
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        n_levels = g.n_levels if g is not None else 1
+        cls = None
+        if vertex_class is not None:
+            cls = np.ascontiguousarray(vertex_class, np.int32)
+            if g is not None and cls.shape != (g.n_vertices,):
+                raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
+        levels = np.zeros((2, n_levels), CALL_MARGIN)
+        paths = np.zeros((2, n_levels), np.int32) if want_paths else None
+        _check(lib.dg_dp_call_margins(self.h, int(budget), cls.ctypes.data if cls is not None else None, levels.ctypes.data,
+                                      paths.ctypes.data if want_paths else None), "dg_dp_call_margins")
+        return levels, paths
 
     def dp_solve(self, g):
         self.dp_load_graph(g)

@@ -251,6 +251,10 @@ struct DpState {
     // ---- dg_dp_partner_marginals (dg_dp_marginals.hip): the level records and the marginals of one slab; the given paths, budgets, sink
     // cells, first-bad-hop word, forward values (in d_pt_bp) and edge scores live in the buffers above ----
     DevBuf d_mg_levels, d_mg_vertex;
+    // ---- the answer of the last run as paths, and its call margins (dg_dp_budgets.hip, dg_dp_marginals.hip) ----
+    bool run_ok = false;                       // the last dg_dp_run / dg_dp_run_budgets on the loaded graph returned DG_OK: d_ch_path and d_ch_state hold its chains (sink_host is emptied by a load)
+    DevBuf d_ans_paths, d_ans_cnt;             // dg_dp_get_answer_paths: the [2][L] vertex ids and the two counts of weight-1 hops
+    DevBuf d_cm_class, d_cm_out;               // dg_dp_call_margins: the caller's classes (released when the call returns) and the [2][L] records
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -311,6 +315,13 @@ void budgets_launch_sink_copy(const DpState &S, const int32_t *sink_state, hipSt
 int budgets_reserve(DpState &S, int n);                                                      // buffers of n chains (grow-only)
 int budgets_prepare(DpState &S, const int32_t *budgets, int n, hipStream_t s);                // buffers of n chains + walker placement
 void budgets_launch_finish(const DpState &S, int n, hipStream_t s);                           // the finish kernel once per chain
+// the chain that the last run walked for `budget` (fn: the entry point's name, for the messages): DG_ERR_STATE without a graph, without a
+// run since the load, or for a budget that run did not read out
+int budgets_find_chain(const char *fn, const DpState *S, int32_t budget, int &chain);
+// the chain's path slice expanded into vertex ids: row h of the pair goes to out + (h ^ swap) * L (device), the weight-1 hops of row h
+// are added to cnt[h] (device, zeroed here).  A chain whose budget nothing fits writes -1 everywhere.
+void budgets_launch_expand(const DpState &S, int chain, int swap, int32_t *out, int32_t *cnt, hipStream_t s);
+int dp_get_answer_paths(dg_ctx *c, int32_t budget, int32_t *paths);
 
 // ---- caller-supplied pairs of paths scored on the resident graph (dg_dp_score.hip) ----
 int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out);
@@ -323,5 +334,6 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
 
 // ---- partner marginals: that DP forward and backward, combined per vertex (dg_dp_marginals.hip; shares dg_dp_partner.hpp with the above) ----
 int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
+int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
 
 }  // namespace dgi

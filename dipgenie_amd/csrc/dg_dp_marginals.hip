@@ -192,6 +192,89 @@ __global__ __launch_bounds__(PT_THREADS) void dp_marginals_back_kernel(const Lev
     }
 }
 
+// dg_dp_call_margins, after the backward kernel: one wave per (query, level).  Query q of the slab is row `first + q` of the call: its
+// marginals are those of the partners of the OTHER row's path, the called vertex is its own path's (given = the two paths in the
+// order of the queries, so the path of row r is given + (1 - r) * L).  The lanes stride over the level's vertices and keep the
+// largest key among those of another class than the called vertex's (cls null: every vertex is its own class).
+__global__ __launch_bounds__(PT_THREADS) void dp_call_margins_kernel(const LevelDesc *__restrict__ descs, int L, int nV, int m, int first,
+                                                                     const int32_t *__restrict__ given, const int32_t *__restrict__ vertex_values,
+                                                                     const int32_t *__restrict__ cls, dg_dp_call_margin *__restrict__ out) {
+    const int64_t wave = ((int64_t)blockIdx.x * PT_THREADS + threadIdx.x) >> 6;
+    const int lane = (int)(threadIdx.x & 63);
+    if (wave >= (int64_t)m * L) return;                                 // whole waves leave
+    const int q = (int)(wave / L), l = (int)(wave - (int64_t)q * L), row = first + q;
+    const PtLevel lv = mg_level(descs, l);
+    const int32_t *__restrict__ vv = vertex_values + (int64_t)q * nV;
+    const int called = given[(int64_t)(1 - row) * L + l];
+    dg_dp_call_margin rec{called, NEG_INF, -1, NEG_INF};
+    if ((uint32_t)called - (uint32_t)lv.b0 < (uint32_t)lv.k2) {         // (the expansion writes nothing else)
+        const int cc = cls ? cls[called] : called;
+        long long key = MG_NO_KEY;
+        for (int v = lane; v < lv.k2; v += 64) {
+            const int id = lv.b0 + v;
+            if ((cls ? cls[id] : id) == cc) continue;
+            const int mv = vv[id];
+            if (mv != NEG_INF) key = max(key, mg_key(mv, id));
+        }
+        for (int d = 32; d; d >>= 1) key = max(key, __shfl_xor(key, d));
+        rec.value = vv[called];
+        if (key != MG_NO_KEY) { rec.alt_vertex = INT32_MAX - (int)(uint32_t)key; rec.alt_value = (int)(key >> 32); }
+    }
+    if (lane == 0) out[(int64_t)row * L + l] = rec;
+}
+
+// What a call's slabs share: LDS sizes, strides, and the buffers of `per_slab` queries (grow-only but for the two large ones, which the
+// caller releases).  vertex: the marginals of every vertex are kept (on the device)
+struct MgPlan { int cells; size_t lds_bytes; int64_t fwd_stride, per_slab; };
+
+int mg_plan(DpState &S, int64_t n, int kmax, int bmax, bool vertex, MgPlan &P) {
+    const int L = S.L, nV = S.nV;
+    const int64_t E = S.n_edges;
+    P.cells = kmax * (bmax + 1);
+    P.lds_bytes = 2 * (size_t)P.cells * 4 + PT_STAGE_BUF_BYTES;
+    if (P.lds_bytes > 65536) DG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dp_marginals_back_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes));
+    // queries per slab: what partner_slab_bytes holds (at least one), every query sized for the call's largest budget
+    P.fwd_stride = (int64_t)nV * (bmax + 1);                            // int32 units
+    const int64_t query_bytes = 4 * P.fwd_stride + 2 * E + 4 * (int64_t)nV + 20 * (int64_t)L;
+    int64_t per_slab = std::max<int64_t>(1, S.opt.partner_slab_bytes / query_bytes);
+    per_slab = std::min(std::min(per_slab, partner_slab_limit(S)), n);
+    P.per_slab = per_slab;
+    if (int rc = S.d_pt_pairs.ensure((size_t)(per_slab * L) * 4)) return rc;
+    if (int rc = S.d_pt_bud.ensure((size_t)per_slab * 4)) return rc;
+    if (int rc = S.d_pt_val.ensure((size_t)per_slab * 4)) return rc;
+    if (int rc = S.d_pt_err.ensure(2 * sizeof(unsigned long long))) return rc;
+    if (int rc = S.d_mg_levels.ensure((size_t)(per_slab * L) * sizeof(dg_dp_level_margin))) return rc;
+    if (vertex)
+        if (int rc = S.d_mg_vertex.ensure((size_t)(per_slab * nV) * 4)) return rc;
+    return DG_OK;
+}
+
+// the two large buffers live for the call only: the lattice pool of a later run may need the memory
+struct MgRelease { DpState &S; ~MgRelease() { S.d_pt_bp.release(); S.d_pt_scores.release(); S.d_cm_class.release(); } };
+
+int mg_plan_large(DpState &S, const MgPlan &P) {
+    if (int rc = S.d_pt_bp.ensure((size_t)(P.per_slab * P.fwd_stride) * 4)) return rc;
+    return S.d_pt_scores.ensure((size_t)(P.per_slab * S.n_edges) * 2 + 16);
+}
+
+// The core: m queries of one slab whose given paths are on the device (query q's: given + q * L) and whose budgets are in d_pt_bud;
+// scores + validation, forward values, backward pass.  Leaves the level records in d_mg_levels, the marginals (vertex) in
+// d_mg_vertex and the first-bad-hop word in d_pt_err, all on the device; nothing is waited for.
+int mg_launch_slab(DpState &S, const MgPlan &P, const int32_t *d_given, int64_t m, bool vertex, hipStream_t s) {
+    unsigned long long *d_err = S.d_pt_err.as<unsigned long long>();
+    DG_HIP(hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), s));
+    partner_launch_scores(S, d_given, S.L, m, S.d_pt_scores.as<uint16_t>(), d_err, s);
+    DG_HIP(hipGetLastError());
+    if (int rc = partner_launch_forward_values(S, P.cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_bp.as<int32_t>(), P.fwd_stride,
+                                               S.d_pt_val.as<int32_t>(), s))
+        return rc;
+    hipLaunchKernelGGL(dp_marginals_back_kernel, dim3((unsigned)m), dim3(PT_THREADS), P.lds_bytes, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, P.cells,
+                       S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_pt_scores.as<uint16_t>(), S.n_edges, S.d_pt_bud.as<int32_t>(),
+                       S.d_pt_bp.as<int32_t>(), P.fwd_stride, S.d_mg_levels.as<dg_dp_level_margin>(), vertex ? S.d_mg_vertex.as<int32_t>() : nullptr);
+    DG_HIP(hipGetLastError());
+    return DG_OK;
+}
+
 }  // namespace
 
 int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values) {
@@ -204,52 +287,27 @@ int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32
     DpState &S = *Sp;
     hipStream_t s = c->stream;
     const int L = S.L, nV = S.nV;
-    const int64_t E = S.n_edges;
     int kmax, bmax;
     if (int rc = partner_check_budgets(FN, S, n, budgets, kmax, bmax)) return rc;
-    const int cells = kmax * (bmax + 1);
-    const size_t lds_bytes = 2 * (size_t)cells * 4 + PT_STAGE_BUF_BYTES;
-    if (lds_bytes > 65536) DG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dp_marginals_back_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    // queries per slab: what partner_slab_bytes holds (at least one), every query sized for the call's largest budget
-    const int64_t fwd_stride = (int64_t)nV * (bmax + 1);                // int32 units
-    const int64_t query_bytes = 4 * fwd_stride + 2 * E + 4 * (int64_t)nV + 20 * (int64_t)L;
-    int64_t per_slab = std::max<int64_t>(1, S.opt.partner_slab_bytes / query_bytes);
-    per_slab = std::min(std::min(per_slab, partner_slab_limit(S)), n);
-    if (int rc = S.d_pt_pairs.ensure((size_t)(per_slab * L) * 4)) return rc;
-    if (int rc = S.d_pt_bud.ensure((size_t)per_slab * 4)) return rc;
-    if (int rc = S.d_pt_val.ensure((size_t)per_slab * 4)) return rc;
-    if (int rc = S.d_pt_err.ensure(2 * sizeof(unsigned long long))) return rc;
-    if (int rc = S.d_mg_levels.ensure((size_t)(per_slab * L) * sizeof(dg_dp_level_margin))) return rc;
-    if (vertex_values)
-        if (int rc = S.d_mg_vertex.ensure((size_t)(per_slab * nV) * 4)) return rc;
-    // the two large buffers live for the call only: the lattice pool of a later run may need the memory
-    struct Release { DpState &S; ~Release() { S.d_pt_bp.release(); S.d_pt_scores.release(); } } release{S};
-    if (int rc = S.d_pt_bp.ensure((size_t)(per_slab * fwd_stride) * 4)) return rc;
-    if (int rc = S.d_pt_scores.ensure((size_t)(per_slab * E) * 2 + 16)) return rc;
+    MgPlan P;
+    if (int rc = mg_plan(S, n, kmax, bmax, vertex_values != nullptr, P)) return rc;
+    const int64_t per_slab = P.per_slab;
+    MgRelease release{S};
+    if (int rc = mg_plan_large(S, P)) return rc;
     // the caller's arrays are written only if every query is answered
     std::vector<dg_dp_level_margin> recs((size_t)(n * L));
     std::vector<int32_t> vals;
     if (vertex_values) vals.resize((size_t)(n * nV));
     int32_t *d_given = S.d_pt_pairs.as<int32_t>();
-    unsigned long long *d_err = S.d_pt_err.as<unsigned long long>();
     for (int64_t first = 0; first < n; first += per_slab) {
         const int64_t m = std::min(per_slab, n - first);
         unsigned long long err = PT_NO_ERROR;
         DG_HIP(hipMemcpyAsync(d_given, given + first * L, (size_t)(m * L) * 4, hipMemcpyHostToDevice, s));
         DG_HIP(hipMemcpyAsync(S.d_pt_bud.p, budgets + first, (size_t)m * 4, hipMemcpyHostToDevice, s));
-        DG_HIP(hipMemsetAsync(d_err, 0xFF, sizeof err, s));
-        partner_launch_scores(S, d_given, L, m, S.d_pt_scores.as<uint16_t>(), d_err, s);
-        DG_HIP(hipGetLastError());
-        if (int rc = partner_launch_forward_values(S, cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_bp.as<int32_t>(), fwd_stride,
-                                                   S.d_pt_val.as<int32_t>(), s))
-            return rc;
-        hipLaunchKernelGGL(dp_marginals_back_kernel, dim3((unsigned)m), dim3(PT_THREADS), lds_bytes, s, S.d_descs.as<LevelDesc>(), L, nV, cells,
-                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_pt_scores.as<uint16_t>(), E, S.d_pt_bud.as<int32_t>(),
-                           S.d_pt_bp.as<int32_t>(), fwd_stride, S.d_mg_levels.as<dg_dp_level_margin>(), vertex_values ? S.d_mg_vertex.as<int32_t>() : nullptr);
-        DG_HIP(hipGetLastError());
+        if (int rc = mg_launch_slab(S, P, d_given, m, vertex_values != nullptr, s)) return rc;
         DG_HIP(hipMemcpyAsync(recs.data() + first * L, S.d_mg_levels.p, (size_t)(m * L) * sizeof(dg_dp_level_margin), hipMemcpyDeviceToHost, s));
         if (vertex_values) DG_HIP(hipMemcpyAsync(vals.data() + first * nV, S.d_mg_vertex.p, (size_t)(m * nV) * 4, hipMemcpyDeviceToHost, s));
-        DG_HIP(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
+        DG_HIP(hipMemcpyAsync(&err, S.d_pt_err.p, sizeof err, hipMemcpyDeviceToHost, s));
         DG_HIP(hipStreamSynchronize(s));
         if (err != PT_NO_ERROR) return partner_bad_hop(FN, err, first, given, L);       // slabs go up in order: the first slab with a bad hop holds the first bad hop
     }
@@ -258,7 +316,96 @@ int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32
     return DG_OK;
 }
 
+// dg_dp_call_margins: both haplotypes of the last run's answer at `budget`, each against the best vertex of another class per level.
+// Row 0: haplotype 1 with haplotype 2 given and the budget that haplotype 2 leaves, row 1 the mirror image.  The two paths go from the
+// chain's hop words straight to where the score kernel reads them (budgets_launch_expand); back come the two hop counts, 16 bytes
+// per (row, level) and, if asked for, the paths.
+int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths) {
+    static const char *const FN = "dg_dp_call_margins";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
+    DpState &S = *Sp;
+    const int L = S.L, nV = S.nV;
+    int kmax = 1;
+    for (int l = 1; l < L; ++l) kmax = std::max(kmax, S.descs[l].k2);
+    if (budget >= 0 && (int64_t)kmax * ((int64_t)budget + 1) > PT_MAX_CELLS) {     // on the budget itself, not on what the other haplotype leaves: known before a run
+        set_error("%s: widest level %d x (budget + 1) %lld exceeds %d cells", FN, kmax, (long long)budget + 1, PT_MAX_CELLS);
+        return DG_ERR_UNSUPPORTED;
+    }
+    int chain = 0;
+    if (int rc = budgets_find_chain(FN, Sp, budget, chain)) return rc;
+    if (!levels) { set_error("%s: levels is required", FN); return DG_ERR_ARG; }
+    hipStream_t s = c->stream;
+    std::vector<dg_dp_call_margin> recs(2 * (size_t)L, dg_dp_call_margin{-1, NEG_INF, -1, NEG_INF});
+    std::vector<int32_t> rows(paths ? 2 * (size_t)L : 0, -1);
+    const int32_t V = S.sink_host[(size_t)budget];
+    if (V != NEG_INF) {
+        // the two queries, in order: given = haplotype 2 (row 0), given = haplotype 1 (row 1) -- the expansion writes them swapped
+        if (int rc = S.d_pt_pairs.ensure(2 * (size_t)L * 4)) return rc;
+        if (int rc = S.d_ans_cnt.ensure(8)) return rc;
+        int32_t *d_given = S.d_pt_pairs.as<int32_t>();
+        int32_t cnt[2] = {0, 0};
+        budgets_launch_expand(S, chain, 1, d_given, S.d_ans_cnt.as<int32_t>(), s);
+        DG_HIP(hipGetLastError());
+        DG_HIP(hipMemcpyAsync(cnt, S.d_ans_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+        DG_HIP(hipStreamSynchronize(s));
+        if (cnt[0] < 0 || cnt[1] < 0 || cnt[0] + cnt[1] > budget) {
+            set_error("%s: the answer at budget %d has %d + %d recombinations", FN, budget, cnt[0], cnt[1]);
+            return DG_ERR_STATE;
+        }
+        const int32_t budgets[2] = {budget - cnt[1], budget - cnt[0]};
+        MgPlan P;
+        if (int rc = mg_plan(S, 2, kmax, std::max(budgets[0], budgets[1]), true, P)) return rc;      // (d_pt_pairs holds both paths already: it only grows)
+        MgRelease release{S};
+        if (int rc = mg_plan_large(S, P)) return rc;
+        if (int rc = S.d_cm_out.ensure(2 * (size_t)L * sizeof(dg_dp_call_margin))) return rc;
+        if (vertex_class) {
+            if (int rc = S.d_cm_class.ensure((size_t)nV * 4)) return rc;
+            DG_HIP(hipMemcpyAsync(S.d_cm_class.p, vertex_class, (size_t)nV * 4, hipMemcpyHostToDevice, s));
+        }
+        for (int first = 0; first < 2; first += (int)P.per_slab) {
+            const int m = (int)std::min<int64_t>(P.per_slab, 2 - first);
+            unsigned long long err = PT_NO_ERROR;
+            DG_HIP(hipMemcpyAsync(S.d_pt_bud.p, budgets + first, (size_t)m * 4, hipMemcpyHostToDevice, s));
+            if (int rc = mg_launch_slab(S, P, d_given + (size_t)first * L, m, true, s)) return rc;
+            const int64_t waves = (int64_t)m * L;
+            hipLaunchKernelGGL(dp_call_margins_kernel, dim3((unsigned)((waves + PT_THREADS / 64 - 1) / (PT_THREADS / 64))), dim3(PT_THREADS), 0, s,
+                               S.d_descs.as<LevelDesc>(), L, nV, m, first, d_given, S.d_mg_vertex.as<int32_t>(),
+                               vertex_class ? S.d_cm_class.as<int32_t>() : nullptr, S.d_cm_out.as<dg_dp_call_margin>());
+            DG_HIP(hipGetLastError());
+            DG_HIP(hipMemcpyAsync(&err, S.d_pt_err.p, sizeof err, hipMemcpyDeviceToHost, s));
+            DG_HIP(hipStreamSynchronize(s));
+            if (err != PT_NO_ERROR) {
+                set_error("%s: row %d: the run's path is not a path of the graph (level %d)", FN, first + (int)(err >> 33), (int)((uint32_t)err >> 1));
+                return DG_ERR_STATE;
+            }
+        }
+        DG_HIP(hipMemcpyAsync(recs.data(), S.d_cm_out.p, recs.size() * sizeof(dg_dp_call_margin), hipMemcpyDeviceToHost, s));
+        if (paths) {                                                    // rows 0 and 1 of the caller are haplotypes 1 and 2: the second and the first given path
+            DG_HIP(hipMemcpyAsync(rows.data(), d_given + L, (size_t)L * 4, hipMemcpyDeviceToHost, s));
+            DG_HIP(hipMemcpyAsync(rows.data() + L, d_given, (size_t)L * 4, hipMemcpyDeviceToHost, s));
+        }
+        DG_HIP(hipStreamSynchronize(s));
+        // the closing check: the answer's own haplotype is a partner within the budget (M >= V), and no partner within it beats plane `budget` (M <= V)
+        for (int row = 0; row < 2; ++row)
+            for (int l = 0; l < L; ++l)
+                if (recs[(size_t)row * L + l].value != V) {
+                    set_error("%s: row %d level %d: the marginal of the called vertex %d is %d, the run's value at budget %d is %d", FN, row, l,
+                              recs[(size_t)row * L + l].vertex, recs[(size_t)row * L + l].value, budget, V);
+                    return DG_ERR_STATE;
+                }
+    }
+    memcpy(levels, recs.data(), recs.size() * sizeof(dg_dp_call_margin));
+    if (paths) memcpy(paths, rows.data(), rows.size() * 4);
+    return DG_OK;
+}
+
 }  // namespace dgi
+
+extern "C" int dg_dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_call_margins(c, budget, vertex_class, levels, paths);
+}
 
 extern "C" int dg_dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values) {
     if (int rc = dgi::bind(c)) return rc;

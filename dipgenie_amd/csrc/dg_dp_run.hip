@@ -351,6 +351,7 @@ static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result
     if (int rc = run.wait_for_chunks()) return rc;
     std::vector<TraceOut> to((size_t)n_budgets);
     std::vector<int32_t> edges(4 * (size_t)S.cap * (size_t)n_budgets);
+    S.run_ok = false;                                                   // the chains' buffers are about to be rewritten
     if (int rc = budgets_prepare(S, budgets, n_budgets, s)) return rc;
     run.n_chains = n_budgets;
     S.sink_host.clear();
@@ -392,6 +393,7 @@ static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result
     S.timing.n_chunks = (int32_t)S.chunk_begin.size() - 1;
     for (int q = 0; q < n_budgets; ++q)                                  // any corrupt or mis-scored chain fails the call
         if (int rc = emit_result(S, to[q], edges.data() + 4 * (size_t)S.cap * (size_t)q, res + q, name_budget ? budgets[q] : -1)) return rc;
+    S.run_ok = true;                                                    // every chain's path slice is a checked pair of paths (dg_dp_get_answer_paths)
     return DG_OK;
 }
 

@@ -96,10 +96,12 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
+    // --site-margins takes the same load-then-run route: the margins are read off the run that stays behind
+    if (!p.opt.site_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_call_margins)) return "--site-margins: this backend has no dp_call_margins";
     if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
     std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
     for (const ChainAnswer &a : answers) res.push_back(a.res);
@@ -260,6 +262,85 @@ std::string write_budget_table(const std::string &path, const std::vector<Budget
     return "";
 }
 
+// --site-margins: the allele class of every vertex.  Two vertices are the same class exactly when their original-vertex lists are
+// equal (a dummy shares its source's list; source and sink have an empty one): copies of one segment on several panel haplotypes
+// are one allele.
+std::vector<int32_t> allele_classes(const ExpandedGraph &g) {
+    std::vector<int32_t> cls((size_t)g.n);
+    // an empty list is class 0, a list of one original vertex x is class 1 + x (nearly every vertex); longer lists are numbered from
+    // `next` on, found by a hash of the list and compared in full with the lists that share it
+    int32_t next = 1;
+    for (int32_t x : g.orig_pool) next = std::max(next, x + 2);
+    std::unordered_map<uint64_t, std::vector<std::pair<int32_t, int32_t>>> seen;   // hash -> (a vertex with that list, its class)
+    for (int v = 0; v < g.n; ++v) {
+        const uint32_t off = g.orig_off[v], len = g.orig_len[v];
+        if (len == 0) { cls[v] = 0; continue; }
+        if (len == 1) { cls[v] = 1 + g.orig_pool[off]; continue; }
+        uint64_t h = 1469598103934665603ull;
+        for (uint32_t q = 0; q < len; ++q) h = (h ^ (uint32_t)g.orig_pool[off + q]) * 1099511628211ull;
+        auto &bucket = seen[h];
+        int32_t c = -1;
+        for (const auto &rep : bucket) {
+            const uint32_t roff = g.orig_off[rep.first];
+            if (g.orig_len[rep.first] == len && (roff == off || std::equal(g.orig_pool.begin() + off, g.orig_pool.begin() + off + len, g.orig_pool.begin() + roff))) { c = rep.second; break; }
+        }
+        if (c < 0) { c = next++; bucket.emplace_back(v, c); }
+        cls[v] = c;
+    }
+    return cls;
+}
+
+std::string write_raw_int32(const std::string &path, const std::vector<int32_t> &a) {
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open " + path;
+    f.write((const char *)a.data(), (std::streamsize)(a.size() * sizeof(int32_t)));
+    f.close();
+    return f.good() ? "" : "write to " + path + " failed";
+}
+
+// level  hap  vertex  panel_hap  segment  value  alt_vertex  alt_panel_hap  alt_segment  margin: levels 1 .. L - 2, haplotype 1 before
+// haplotype 2 within a level; '.' for what does not exist
+std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls) {
+    const double t0 = now_s();
+    const int L = (int)g.level_off.size() - 1;
+    std::vector<dg_dp_call_margin> rec(2 * (size_t)L);
+    if (p.be.dp_call_margins(p.be.ctx, p.opt.R, cls.data(), rec.data(), nullptr) != 0) return backend_error(p.be, "dp_call_margins");
+    auto panel = [&](int v) -> std::string {
+        const int h = v >= 0 ? g.haplotype.at(v) : -1;
+        return h >= 0 && h < (int)p.hap_id2name.size() ? p.hap_id2name[h] : ".";
+    };
+    auto segment = [&](int v) -> std::string {
+        if (v < 0 || g.orig_len.at(v) < 1) return ".";
+        const int32_t seg = g.orig_pool[g.orig_off[v]];
+        return seg >= 0 && seg < (int32_t)p.node_name.size() ? p.node_name[seg] : ".";
+    };
+    SiteMargins &sm = p.sum.site_margins;
+    sm = SiteMargins();
+    sm.set = true;
+    std::string text = "level\thap\tvertex\tpanel_hap\tsegment\tvalue\talt_vertex\talt_panel_hap\talt_segment\tmargin\n";
+    for (int l = 1; l < L - 1; ++l)
+        for (int h = 0; h < 2; ++h) {
+            const dg_dp_call_margin &r = rec[(size_t)h * L + l];
+            text += std::to_string(l) + '\t' + std::to_string(h + 1) + '\t' + std::to_string(r.vertex) + '\t' + panel(r.vertex) + '\t' + segment(r.vertex) + '\t' +
+                    std::to_string(r.value) + '\t' + std::to_string(r.alt_vertex) + '\t' + panel(r.alt_vertex) + '\t' + segment(r.alt_vertex) + '\t';
+            if (r.alt_vertex >= 0) {
+                const int32_t margin = r.value - r.alt_value;
+                text += std::to_string(margin);
+                sm.with_alternative[h]++;
+                if (margin == 0) sm.margin0[h]++;
+                else if (sm.min_positive_margin[h] < 0 || margin < sm.min_positive_margin[h]) sm.min_positive_margin[h] = margin;
+            } else text += '.';
+            text += '\n';
+        }
+    std::ofstream f(p.opt.site_margins, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open site margins file " + p.opt.site_margins;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + p.opt.site_margins + " failed";
+    sm.wall_s = now_s() - t0;
+    return "";
+}
+
 }  // namespace
 
 int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_bv,
@@ -279,6 +360,17 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     sum.n_levels = L;
     sum.n_vertices = g.n;
     stamp("dp_prologue_flatten", t0);
+    std::vector<int32_t> classes;
+    if (!opt.site_margins.empty()) {                                   // what dg_dp_call_margins can hold, known before the DP: no output of any kind otherwise
+        int64_t widest = 1;
+        for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
+        if (widest * ((int64_t)R + 1) > 16384) {
+            err = "--site-margins: widest level " + std::to_string(widest) + " x (R + 1) " + std::to_string(R + 1) + " exceeds 16384 cells";
+            return -1;
+        }
+        classes = allele_classes(g);
+        if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
+    }
     if (!opt.dump_prefix.empty()) dump_graph(dpg, g, opt.dump_prefix + ".dpg", R);
     if (opt.dump_only) { err = "dump_only"; return 1; }
 
@@ -311,6 +403,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     if (failed(write_budget_fastas(*this, g, anchorsByHap, answers), err)) return -1;
     if (!opt.budget_table.empty() && failed(write_budget_table(opt.budget_table, sum.budget_rows), err)) return -1;
     stamp("traceback+write", t0);
+    if (!opt.site_margins.empty()) {
+        t0 = now_s();
+        if (failed(write_site_margins(*this, g, classes), err)) return -1;
+        stamp("site_margins", t0);
+    }
     return 0;
 }
 

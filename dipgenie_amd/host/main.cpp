@@ -118,6 +118,10 @@ static int b_dp_budgets(void *c, const int32_t *budgets, int32_t n, dg_dp_result
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_run_budgets(x, budgets, n, r) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_call_margins(void *c, int32_t budget, const int32_t *cls, dg_dp_call_margin *levels, int32_t *paths) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_call_margins(x, budget, cls, levels, paths) : DG_ERR_NO_DEVICE;
+}
 static int b_hap(void *c, const dg_hap_graph *g, int32_t *dp, int32_t *bv, int32_t *br) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_solve_haploid(x, g, dp, bv, br) : DG_ERR_NO_DEVICE;
@@ -223,6 +227,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    -G INT       (MI355X build) HIP device ordinal [0]\n");
     fprintf(fp, "    --budgets all|a,b,c   (MI355X build, -p2) also answer these recombination limits below -R from the same DP pass: <haplotype.fasta>.R<r>\n");
     fprintf(fp, "    --budget-table FILE   (MI355X build) with --budgets: one line r, DP value, r1, r2, len1, len2 per listed limit\n");
+    fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
 
@@ -242,7 +247,7 @@ int main(int argc, char **argv) {
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
     std::string budgets_arg;
-    bool have_budgets = false;
+    bool have_budgets = false, have_site_margins = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -256,6 +261,12 @@ int main(int argc, char **argv) {
             if (!strncmp(argv[i], "--shard-transport", 17)) { const char *v = val("--shard-transport"); if (v) { shard_transport = !strcmp(v, "host") ? 1 : 0; continue; } }
             if (!strncmp(argv[i], "--shard-devices", 15)) { const char *v = val("--shard-devices"); if (v) { for (const char *q = v; *q;) { shard_devices.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; } continue; } }
             if (!strncmp(argv[i], "--budgets", 9) && (argv[i][9] == 0 || argv[i][9] == '=')) { const char *v = val("--budgets"); if (v) { budgets_arg = v; have_budgets = true; continue; } }
+            if (!strncmp(argv[i], "--site-margins", 14) && (argv[i][14] == 0 || argv[i][14] == '=')) {
+                have_site_margins = true;                              // (a missing value is an empty file name: refused below)
+                const char *v = val("--site-margins");
+                p.opt.site_margins = v ? v : "";
+                continue;
+            }
             if (!strncmp(argv[i], "--budget-table", 14)) { const char *v = val("--budget-table"); if (v) { p.opt.budget_table = v; continue; } }
             argv[w++] = argv[i];
         }
@@ -313,6 +324,11 @@ int main(int argc, char **argv) {
             }
         }
     }
+    // --site-margins FILE: checked here too, before any device is asked for
+    if (have_site_margins) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --site-margins describes the two haplotypes of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.site_margins.empty()) { fprintf(stderr, "[E::main] --site-margins needs a file name\n"); return 1; }
+    }
     if (!sharded) g_lazy.start(device, p.opt.k, p.opt.w);
     p.be.ctx = &g_lazy;
     p.be.sketch_reads = b_sketch_reads;
@@ -320,6 +336,7 @@ int main(int argc, char **argv) {
     p.be.dp_solve_diploid = b_dp;
     p.be.dp_load_graph = b_dp_load;
     p.be.dp_run_budgets = b_dp_budgets;
+    p.be.dp_call_margins = b_dp_call_margins;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -379,6 +396,15 @@ int main(int argc, char **argv) {
                     else fprintf(f, "%s{\"r\": %d, \"dp_value\": null, \"r1\": null, \"r2\": null, \"len1\": null, \"len2\": null}", i ? ", " : "", b.r);
                 }
                 fprintf(f, "]");
+            }
+            if (p.sum.site_margins.set) {                               // per haplotype, over the levels 1 .. L - 2; min_positive_margin null: none is positive
+                const dg::SiteMargins &sm = p.sum.site_margins;
+                fprintf(f, ", \"site_margins\": {\"haplotypes\": [");
+                for (int h = 0; h < 2; ++h) {
+                    fprintf(f, "%s{\"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", h ? ", " : "", (long long)sm.with_alternative[h], (long long)sm.margin0[h]);
+                    if (sm.min_positive_margin[h] >= 0) fprintf(f, "%d}", sm.min_positive_margin[h]); else fprintf(f, "null}");
+                }
+                fprintf(f, "], \"wall_s\": %.6f}", sm.wall_s);
             }
             fprintf(f, "}\n");
             fclose(f);

@@ -62,6 +62,9 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     int (*dp_run_budgets)(void *, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) = nullptr;
     void (*hint_dp_soon)(void *, int64_t est_cells) = nullptr;   // optional, may be called repeatedly (latest wins): the DP will run later with about est_cells cells
     const char *(*last_error)() = nullptr;
+    // optional (--site-margins): after dp_run_budgets, both haplotypes of the answer at a budget against the best vertex of another
+    // class per level (dg_dp_call_margins)
+    int (*dp_call_margins)(void *, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths) = nullptr;
 };
 
 struct Options {
@@ -81,6 +84,7 @@ struct Options {
     std::vector<int> budgets;    // (ours) --budgets: recombination budgets below -R answered from the same DP pass (diploid); -R itself is always solved
     std::string budget_table;    // (ours) --budget-table: TSV of the listed budgets
     bool host_anchors = false;   // (ours, tests) keep the anchor join / filter / sort on the host even if the backend offers it
+    std::string site_margins;    // (ours) --site-margins: TSV of the call margins of both haplotypes of the answer at -R, per level (diploid)
 };
 
 // ExpandedGraph.hpp:16-26, flattened: CSR adjacency (per-vertex order = the reference's push order),
@@ -155,6 +159,13 @@ struct BudgetRow {            // --budgets: one listed budget (reachable = the s
     int64_t len1 = 0, len2 = 0;
 };
 
+struct SiteMargins {          // --site-margins: per haplotype, over the levels 1 .. L - 2
+    bool set = false;
+    int64_t with_alternative[2] = {0, 0}, margin0[2] = {0, 0};
+    int32_t min_positive_margin[2] = {-1, -1};   // -1: no level with a positive margin
+    double wall_s = 0;
+};
+
 struct Summary {              // what tests and the CLI report
     int32_t dp_value = 0, s_het = 0, r1 = -1, r2 = -1, obj = 0, best_r_haploid = -1;
     int64_t len1 = 0, len2 = 0;
@@ -164,6 +175,7 @@ struct Summary {              // what tests and the CLI report
     KGFitResult fit;
     std::vector<std::pair<std::string, double>> stage_s;
     std::vector<BudgetRow> budget_rows;   // --budgets: in the order listed
+    SiteMargins site_margins;
 };
 
 // One anchor occurrence: vertex list vpool[off, off+len) of read-minimizer id `a` on haplotype `h`.
@@ -188,6 +200,7 @@ class Pipeline {
     uint32_t n_vtx = 0, num_walks = 0;
     std::vector<std::vector<uint32_t>> adj_list;
     std::vector<std::string> node_seq;
+    std::vector<std::string> node_name;    // GFA segment names (kept with --site-margins only)
     std::vector<std::vector<uint32_t>> paths;
     std::vector<int32_t> top_order_map;
     std::vector<std::string> hap_id2name;

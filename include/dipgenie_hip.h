@@ -177,6 +177,36 @@ typedef struct dg_dp_level_margin {
  * > 16384 cells for some query (the message names both numbers).  A failed call writes neither levels nor vertex_values.  n = 0 is
  * DG_OK.  Synchronises. */
 int dg_dp_partner_marginals(dg_ctx *, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
+/* The answer of the last dg_dp_run / dg_dp_run_budgets at `budget` as the pair of paths it walked: paths (host) = [2][n_levels]
+ * vertex ids, entry 0 the source, the last one the sink; row 0 is the path of dg_dp_result's p1 lists, row 1 that of p2 -- the rows
+ * dg_dp_score_paths, dg_dp_best_partners and dg_dp_partner_marginals take.  (The weight-1 edge lists of dg_dp_result do not fix the
+ * vertices in between on a general graph; the chain walk's hop words, which stay on the device, do: one kernel, one lane per level,
+ * expands them.)  `budget` must be one the last run read out (dg_dp_run: R).  A budget that no pair of paths fits is an answer, not
+ * an error: both rows are all -1, DG_OK.  DG_ERR_STATE: no graph loaded, no completed run since the last dg_dp_load_graph, or a budget
+ * the last run did not read out (the message names it).  DG_ERR_ARG: null paths.  paths is written only on success.  Leaves the
+ * run's answers (dg_dp_get_budget_values, dg_dp_get_level_digest, dg_dp_get_timing) as they were.  Synchronises. */
+int dg_dp_get_answer_paths(dg_ctx *, int32_t budget, int32_t *paths);
+/* Call margins: how sure each haplotype of the run's own answer is, per level.  With (p1, p2) the answer at `budget` b, r1 and r2 their
+ * weight-1 hops and V the sink's value on plane b: row 0 describes p1 with given = p2 and the partner budget b - r2, row 1 describes p2
+ * with given = p1 and b - r1; M is the quantity of dg_dp_partner_marginals for that given path and budget.  value == V on every level
+ * of both rows (p_h is itself a partner within the budget, so M >= V; every partner within it forms a pair of at most b
+ * recombinations, so M <= V; the score is symmetric in the two paths): the call checks it and answers DG_ERR_STATE naming the row
+ * and the level otherwise. */
+typedef struct dg_dp_call_margin {
+    int32_t vertex, value;            /* p_h[l] and M[p_h[l]] */
+    int32_t alt_vertex, alt_value;    /* the vertex of level l with the largest reachable M among those of another class than `vertex` (the smallest id among equals); -1, NEG_INF if there is none */
+} dg_dp_call_margin;
+/* levels (host) = [2][n_levels]; vertex_class (host) = [n_vertices], one int32 per vertex, or NULL: every vertex is its own class, so
+ * the alternative is the best other vertex; paths (host) = [2][n_levels] or NULL receives what dg_dp_get_answer_paths returns.
+ * value - alt_value is the margin of the call at that level; 0: the reads cannot tell the called allele from another one, given the
+ * other haplotype.  The two paths go from the chain's hop words to the score kernel on the device, the marginals of the vertices stay
+ * there too: after the backward pass one wave per (row, level) reduces the level's vertices of other classes to one record.  The two
+ * queries form one slab if option partner_slab_bytes holds both (a query counts as for dg_dp_partner_marginals), two otherwise.
+ * An unreachable budget is an answer: every record -1, NEG_INF, -1, NEG_INF, the paths all -1, DG_OK.  Errors as for
+ * dg_dp_get_answer_paths (DG_ERR_ARG: null levels), and DG_ERR_UNSUPPORTED: widest level x (budget + 1) > 16384 cells (the message
+ * names both numbers; on `budget` itself, not on what the other haplotype leaves of it, so that it is known before a run).  A failed
+ * call writes nothing.  Leaves the run's answers as they were.  Synchronises. */
+int dg_dp_call_margins(dg_ctx *, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
 /* debug/parity: copy the per-level digest (same definition as the oracle's level_digest) of the
  * last run; out has n_levels entries, entry 0 unused. Requires dg_dp_set_option("digest",1). */
 int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
