@@ -61,6 +61,9 @@ LEVEL_MARGIN = np.dtype([("best_vertex", np.int32), ("best_value", np.int32), ("
 # dg_dp_call_margin as a numpy record: one per (haplotype, level) of Context.dp_call_margins
 CALL_MARGIN = np.dtype([("vertex", np.int32), ("value", np.int32), ("alt_vertex", np.int32), ("alt_value", np.int32)])
 
+# dg_dp_pair_objective as a numpy record: what Context.dp_objective_paths and Context.dp_answer_objectives return
+PAIR_OBJECTIVE = np.dtype([("hom_shared", np.int32), ("hom_single", np.int32), ("het_single", np.int32), ("het_both", np.int32)])
+
 
 class SketchTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("sort_ms", C.c_float), ("total_ms", C.c_float), ("n_emitted", C.c_int64)]
@@ -78,6 +81,7 @@ SYMBOLS = [
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
+    "dg_dp_objective_paths", "dg_dp_answer_objectives",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -98,6 +102,8 @@ lib.dg_dp_best_partners.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_
 lib.dg_dp_partner_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_answer_paths.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_call_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
 lib.dg_dp_solve_diploid.argtypes = [C.c_void_p, C.POINTER(DpGraph), C.POINTER(DpResult)]
 lib.dg_dp_get_level_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -409,6 +415,29 @@ class Context:
         _check(lib.dg_dp_call_margins(self.h, int(budget), cls.ctypes.data if cls is not None else None, levels.ctypes.data,
                                       paths.ctypes.data if want_paths else None), "dg_dp_call_margins")
         return levels, paths
+
+    def dp_objective_paths(self, paths):
+        """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours
+        both paths cover (hom_shared) and exactly one covers (hom_single), the het colours exactly one covers (het_single) and both
+        cover (het_both), every colour counted once per path; the objective is hom_shared + het_single.  A vertex outside its
+        level or a hop without an edge raises DgError naming the first offending pair, path and level.  Leaves the last run's
+        answers alone."""
+        p = np.ascontiguousarray(paths, np.int32)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+            raise ValueError(f"paths must have shape [n, 2, n_levels], got {p.shape}")
+        out = np.zeros(p.shape[0], PAIR_OBJECTIVE)
+        _check(lib.dg_dp_objective_paths(self.h, p.ctypes.data if p.size else None, p.shape[0], out.ctypes.data if out.size else None), "dg_dp_objective_paths")
+        return out
+
+    def dp_answer_objectives(self, budgets):
+        """the PAIR_OBJECTIVE records of the pairs of paths the last dp_run / dp_run_budgets walked for `budgets` (each one the run
+        read out), without the paths leaving the device; all four fields are -1 where no pair fits the budget.  Leaves the run's
+        answers alone."""
+        b = np.ascontiguousarray(budgets, np.int32).reshape(-1)
+        out = np.zeros(b.size, PAIR_OBJECTIVE)
+        _check(lib.dg_dp_answer_objectives(self.h, b.ctypes.data if b.size else None, b.size, out.ctypes.data if out.size else None), "dg_dp_answer_objectives")
+        return out
 
     def dp_solve(self, g):
         self.dp_load_graph(g)

@@ -1,5 +1,6 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
-// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip).
+// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip,
+// dg_dp_objective.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -163,6 +164,7 @@ struct DpOptions {
     int64_t chunk_units_cfg = (int64_t)4 << 30;         // lattice_chunk_cells: size of one lattice chunk (16-bit units, even: 8 GB)
     int64_t score_slab_bytes = (int64_t)256 << 20;      // score_slab_bytes: bound of the path staging buffer of dg_dp_score_paths (a slab holds at least one pair)
     int64_t partner_slab_bytes = (int64_t)4 << 30;      // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, of the forward values, edge scores, marginals and records of one slab of dg_dp_partner_marginals (a slab holds at least one query)
+    int64_t objective_lds_bytes = 131072;               // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
 };
 
 struct DpState {
@@ -255,6 +257,13 @@ struct DpState {
     bool run_ok = false;                       // the last dg_dp_run / dg_dp_run_budgets on the loaded graph returned DG_OK: d_ch_path and d_ch_state hold its chains (sink_host is emptied by a load)
     DevBuf d_ans_paths, d_ans_cnt;             // dg_dp_get_answer_paths: the [2][L] vertex ids and the two counts of weight-1 hops
     DevBuf d_cm_class, d_cm_out;               // dg_dp_call_margins: the caller's classes (released when the call returns) and the [2][L] records
+    // ---- dg_dp_objective_paths / dg_dp_answer_objectives (dg_dp_objective.hip): the colour dictionary of the loaded graph -- per kind the
+    // number of distinct ids and one rank per colour-list entry, parallel to d_hom_col / d_het_col -- built by the first of these calls
+    // after a load (a load only clears ob_dict; a run neither reads nor writes any of this), and one slab's paths, records, first-bad-hop
+    // word and, on the global route, bitmaps ----
+    bool ob_dict = false;
+    int64_t ob_ch = 0, ob_ct = 0;              // distinct hom / het colours
+    DevBuf d_ob_hom_rank, d_ob_het_rank, d_ob_paths, d_ob_out, d_ob_err, d_ob_bits;
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -328,6 +337,11 @@ int dp_score_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_
 int score_pair_blocks(const DpState &S);                                                     // workgroups per pair of the scoring kernel
 // the scoring kernel on n pairs [n][2][L] resident on the device; out (4 words per pair) zeroed and *err all ones beforehand
 void score_launch_pairs(const DpState &S, const int32_t *pairs, int64_t n, int32_t *out, unsigned long long *err, hipStream_t s);
+
+// ---- pairs of paths by the distinct-colour objective (dg_dp_objective.hip) ----
+int dp_objective_paths(dg_ctx *c, const int32_t *paths, int64_t n_pairs, dg_dp_pair_objective *out);
+int dp_answer_objectives(dg_ctx *c, const int32_t *budgets, int32_t n_budgets, dg_dp_pair_objective *out);
+int64_t objective_lds_limit(const dg_ctx *c);                                                // the largest objective_lds_bytes the device allows
 
 // ---- the best partner of a given path: the DP with one haplotype fixed (dg_dp_partner.hip) ----
 int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out);

@@ -522,6 +522,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     DpState &S = *c->dp;
     graphs_clear(S);
     S.loaded = false;
+    S.ob_dict = false;                                          // the colour dictionary of dg_dp_objective_paths belongs to the graph that goes
     S.nV = nV; S.L = L; S.R = R; S.RP = R + 1;
     hipStream_t s = c->stream;
     PoolPause pause(S);                                         // the pool thread maps no chunk while this function allocates

@@ -96,12 +96,14 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty() && p.opt.site_margins.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
     // --site-margins takes the same load-then-run route: the margins are read off the run that stays behind
     if (!p.opt.site_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_call_margins)) return "--site-margins: this backend has no dp_call_margins";
+    // and so does --objective-table: the answers' paths stay on the device
+    if (!p.opt.objective_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_objectives)) return "--objective-table: this backend has no dp_answer_objectives";
     if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
     std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
     for (const ChainAnswer &a : answers) res.push_back(a.res);
@@ -262,6 +264,30 @@ std::string write_budget_table(const std::string &path, const std::vector<Budget
     return "";
 }
 
+// --objective-table: what the answer at every listed budget (without --budgets: at -R) is worth in the surrogate the DP maximises and
+// in the distinct-colour objective (dg_dp_answer_objectives).  budgets / answers: the run's, the listed budgets first.
+// r  dp_value  objective  hom_shared  hom_single  het_single  het_both under one header line; "." for an unreachable budget
+std::string write_objective_table(Pipeline &p, const std::vector<int32_t> &budgets, const std::vector<ChainAnswer> &answers) {
+    const size_t n = p.opt.budgets.empty() ? 1 : p.opt.budgets.size();  // (without --budgets the run's only budget is -R)
+    std::vector<dg_dp_pair_objective> rec(n);
+    if (p.be.dp_answer_objectives(p.be.ctx, budgets.data(), (int32_t)n, rec.data()) != 0) return backend_error(p.be, "dp_answer_objectives");
+    std::ofstream f(p.opt.objective_table, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open objective table " + p.opt.objective_table;
+    f << "r\tdp_value\tobjective\thom_shared\thom_single\thet_single\thet_both\n";
+    for (size_t q = 0; q < n; ++q) {
+        ObjectiveRow row;
+        row.r = budgets[q]; row.reachable = answers[q].reachable(); row.dp_value = answers[q].res.value; row.rec = rec[q];
+        if (row.reachable != (rec[q].hom_shared >= 0)) return "dp_answer_objectives and the run disagree on whether budget " + std::to_string(row.r) + " is reachable";
+        if (row.reachable) f << row.r << '\t' << row.dp_value << '\t' << rec[q].hom_shared + rec[q].het_single << '\t' << rec[q].hom_shared << '\t' << rec[q].hom_single << '\t'
+                             << rec[q].het_single << '\t' << rec[q].het_both << '\n';
+        else f << row.r << "\t.\t.\t.\t.\t.\t.\n";
+        p.sum.objective_rows.push_back(row);
+    }
+    f.close();
+    if (!f.good()) return "write to " + p.opt.objective_table + " failed";
+    return "";
+}
+
 // --site-margins: the allele class of every vertex.  Two vertices are the same class exactly when their original-vertex lists are
 // equal (a dummy shares its source's list; source and sink have an empty one): copies of one segment on several panel haplotypes
 // are one allele.
@@ -403,6 +429,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     if (failed(write_budget_fastas(*this, g, anchorsByHap, answers), err)) return -1;
     if (!opt.budget_table.empty() && failed(write_budget_table(opt.budget_table, sum.budget_rows), err)) return -1;
     stamp("traceback+write", t0);
+    if (!opt.objective_table.empty()) {
+        t0 = now_s();
+        if (failed(write_objective_table(*this, budgets, answers), err)) return -1;
+        stamp("objective_table", t0);
+    }
     if (!opt.site_margins.empty()) {
         t0 = now_s();
         if (failed(write_site_margins(*this, g, classes), err)) return -1;

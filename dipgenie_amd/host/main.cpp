@@ -122,6 +122,10 @@ static int b_dp_call_margins(void *c, int32_t budget, const int32_t *cls, dg_dp_
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_call_margins(x, budget, cls, levels, paths) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_answer_objectives(x, budgets, n, out) : DG_ERR_NO_DEVICE;
+}
 static int b_hap(void *c, const dg_hap_graph *g, int32_t *dp, int32_t *bv, int32_t *br) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_solve_haploid(x, g, dp, bv, br) : DG_ERR_NO_DEVICE;
@@ -228,6 +232,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --budgets all|a,b,c   (MI355X build, -p2) also answer these recombination limits below -R from the same DP pass: <haplotype.fasta>.R<r>\n");
     fprintf(fp, "    --budget-table FILE   (MI355X build) with --budgets: one line r, DP value, r1, r2, len1, len2 per listed limit\n");
     fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
+    fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
 
@@ -247,7 +252,7 @@ int main(int argc, char **argv) {
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
     std::string budgets_arg;
-    bool have_budgets = false, have_site_margins = false;
+    bool have_budgets = false, have_site_margins = false, have_objective_table = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -265,6 +270,12 @@ int main(int argc, char **argv) {
                 have_site_margins = true;                              // (a missing value is an empty file name: refused below)
                 const char *v = val("--site-margins");
                 p.opt.site_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--objective-table", 17) && (argv[i][17] == 0 || argv[i][17] == '=')) {
+                have_objective_table = true;                           // (a missing value is an empty file name: refused below)
+                const char *v = val("--objective-table");
+                p.opt.objective_table = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--budget-table", 14)) { const char *v = val("--budget-table"); if (v) { p.opt.budget_table = v; continue; } }
@@ -329,6 +340,11 @@ int main(int argc, char **argv) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --site-margins describes the two haplotypes of the diploid route (-p2)\n"); return 1; }
         if (p.opt.site_margins.empty()) { fprintf(stderr, "[E::main] --site-margins needs a file name\n"); return 1; }
     }
+    // --objective-table FILE: the same
+    if (have_objective_table) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.objective_table.empty()) { fprintf(stderr, "[E::main] --objective-table needs a file name\n"); return 1; }
+    }
     if (!sharded) g_lazy.start(device, p.opt.k, p.opt.w);
     p.be.ctx = &g_lazy;
     p.be.sketch_reads = b_sketch_reads;
@@ -337,6 +353,7 @@ int main(int argc, char **argv) {
     p.be.dp_load_graph = b_dp_load;
     p.be.dp_run_budgets = b_dp_budgets;
     p.be.dp_call_margins = b_dp_call_margins;
+    p.be.dp_answer_objectives = b_dp_answer_objectives;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -405,6 +422,16 @@ int main(int argc, char **argv) {
                     if (sm.min_positive_margin[h] >= 0) fprintf(f, "%d}", sm.min_positive_margin[h]); else fprintf(f, "null}");
                 }
                 fprintf(f, "], \"wall_s\": %.6f}", sm.wall_s);
+            }
+            if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
+                fprintf(f, ", \"objectives\": [");
+                for (size_t i = 0; i < p.sum.objective_rows.size(); ++i) {
+                    const dg::ObjectiveRow &o = p.sum.objective_rows[i];
+                    if (o.reachable) fprintf(f, "%s{\"r\": %d, \"dp_value\": %d, \"objective\": %d, \"hom_shared\": %d, \"hom_single\": %d, \"het_single\": %d, \"het_both\": %d}", i ? ", " : "", o.r, o.dp_value,
+                                         o.rec.hom_shared + o.rec.het_single, o.rec.hom_shared, o.rec.hom_single, o.rec.het_single, o.rec.het_both);
+                    else fprintf(f, "%s{\"r\": %d, \"dp_value\": null, \"objective\": null, \"hom_shared\": null, \"hom_single\": null, \"het_single\": null, \"het_both\": null}", i ? ", " : "", o.r);
+                }
+                fprintf(f, "]");
             }
             fprintf(f, "}\n");
             fclose(f);

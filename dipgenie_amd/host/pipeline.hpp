@@ -65,6 +65,9 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // optional (--site-margins): after dp_run_budgets, both haplotypes of the answer at a budget against the best vertex of another
     // class per level (dg_dp_call_margins)
     int (*dp_call_margins)(void *, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths) = nullptr;
+    // optional (--objective-table): after dp_run_budgets, the distinct-colour objective of the answers at the listed budgets
+    // (dg_dp_answer_objectives)
+    int (*dp_answer_objectives)(void *, const int32_t *budgets, int32_t n_budgets, dg_dp_pair_objective *out) = nullptr;
 };
 
 struct Options {
@@ -85,6 +88,7 @@ struct Options {
     std::string budget_table;    // (ours) --budget-table: TSV of the listed budgets
     bool host_anchors = false;   // (ours, tests) keep the anchor join / filter / sort on the host even if the backend offers it
     std::string site_margins;    // (ours) --site-margins: TSV of the call margins of both haplotypes of the answer at -R, per level (diploid)
+    std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
 };
 
 // ExpandedGraph.hpp:16-26, flattened: CSR adjacency (per-vertex order = the reference's push order),
@@ -159,6 +163,13 @@ struct BudgetRow {            // --budgets: one listed budget (reachable = the s
     int64_t len1 = 0, len2 = 0;
 };
 
+struct ObjectiveRow {         // --objective-table: one listed budget (reachable as in BudgetRow)
+    int32_t r = 0;
+    bool reachable = false;
+    int32_t dp_value = 0;
+    dg_dp_pair_objective rec = {-1, -1, -1, -1};
+};
+
 struct SiteMargins {          // --site-margins: per haplotype, over the levels 1 .. L - 2
     bool set = false;
     int64_t with_alternative[2] = {0, 0}, margin0[2] = {0, 0};
@@ -176,6 +187,7 @@ struct Summary {              // what tests and the CLI report
     std::vector<std::pair<std::string, double>> stage_s;
     std::vector<BudgetRow> budget_rows;   // --budgets: in the order listed
     SiteMargins site_margins;
+    std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
 };
 
 // One anchor occurrence: vertex list vpool[off, off+len) of read-minimizer id `a` on haplotype `h`.

@@ -207,6 +207,34 @@ typedef struct dg_dp_call_margin {
  * names both numbers; on `budget` itself, not on what the other haplotype leaves of it, so that it is known before a run).  A failed
  * call writes nothing.  Leaves the run's answers as they were.  Synchronises. */
 int dg_dp_call_margins(dg_ctx *, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
+/* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
+ * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
+ * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
+ * symmetric in the two paths; no budget applies.  objective = hom_shared + het_single: the hom colours both haplotypes cover plus
+ * the het colours exactly one covers; hom_single and het_both are reached but not credited. */
+typedef struct dg_dp_pair_objective {
+    int32_t hom_shared, hom_single;   /* |Hom(p1) n Hom(p2)|, |Hom(p1) /\ Hom(p2)| */
+    int32_t het_single, het_both;     /* |Het(p1) /\ Het(p2)|, |Het(p1) n Het(p2)| */
+} dg_dp_pair_objective;
+/* paths (host) = [n_pairs][2][n_levels] vertex ids and out (host) = [n_pairs], as for dg_dp_score_paths, whose guarantees and error
+ * contract this call shares: needs dg_dp_load_graph only, and leaves the answers of an earlier run (dg_dp_get_budget_values,
+ * dg_dp_get_level_digest, dg_dp_get_timing, dg_dp_get_answer_paths) as they were.  The first call after a load builds the graph's colour
+ * dictionary on the device (per kind the sorted distinct ids, and one rank per colour-list entry: colour ids are arbitrary int32
+ * values and never index anything); a run neither needs nor disturbs it.  One workgroup per pair validates the paths as
+ * dg_dp_score_paths does and ORs the ranks of their vertices' colours into four bitmaps, (distinct hom + distinct het colours) / 4
+ * bytes in all, which live in LDS up to option objective_lds_bytes and in device memory beyond.  The pairs go up in slabs bounded by
+ * option score_slab_bytes, a pair counting 8 * n_levels bytes of paths plus, on the device-memory route, its bitmaps.  DG_ERR_STATE:
+ * no graph loaded.  DG_ERR_ARG: a null argument, n_pairs < 0, or a vertex that is not in its level / two consecutive vertices that
+ * no edge joins -- the message names the first such (pair, path 0|1, level), in that order of significance (the level of a missing
+ * edge is its destination's), and out is not written.  n_pairs = 0 is DG_OK.  Synchronises. */
+int dg_dp_objective_paths(dg_ctx *, const int32_t *paths, int64_t n_pairs, dg_dp_pair_objective *out);
+/* The same record for the answers of the last dg_dp_run / dg_dp_run_budgets: out[q] describes the pair of paths the run walked for
+ * budgets[q] (dg_dp_get_answer_paths).  The paths never leave the device: the chains' hop words are expanded where the objective
+ * kernel reads them.  A budget that no pair of paths fits is an answer, not an error: -1 in all four fields, DG_OK.  Errors as for
+ * dg_dp_get_answer_paths: DG_ERR_STATE without a graph, without a completed run since the last dg_dp_load_graph, or for a budget the
+ * last run did not read out (the message names it); DG_ERR_ARG: a null argument or n_budgets <= 0.  out is written only on success.
+ * Leaves the run's answers as they were.  Synchronises. */
+int dg_dp_answer_objectives(dg_ctx *, const int32_t *budgets, int32_t n_budgets, dg_dp_pair_objective *out);
 /* debug/parity: copy the per-level digest (same definition as the oracle's level_digest) of the
  * last run; out has n_levels entries, entry 0 unused. Requires dg_dp_set_option("digest",1). */
 int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
@@ -229,6 +257,7 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *                         a level on which n is no candidate (not instantiated, above the run's all-planes chunk, no cooperative form) runs the all-planes chunk as with adaptive_rc 0
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, and of what a slab of dg_dp_partner_marginals holds (default 4 GB, n <= 0 restores it; a slab holds at least one query)
+ *   objective_lds_bytes n largest size of a pair's four colour bitmaps that dg_dp_objective_paths / dg_dp_answer_objectives keep in LDS; larger ones live in device memory (default 131072, n <= 0 restores it; clamped to the device's LDS per workgroup)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning
  * This list is documentation: struct DpOptions (csrc/dg_dp.hpp) is authoritative for the defaults, the key table beside dg_dp_set_option for the clamps. */
