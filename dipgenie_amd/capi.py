@@ -81,7 +81,7 @@ SYMBOLS = [
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
-    "dg_dp_objective_paths", "dg_dp_answer_objectives",
+    "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -102,6 +102,7 @@ lib.dg_dp_best_partners.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_
 lib.dg_dp_partner_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_answer_paths.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_call_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_get_partner_route.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
@@ -415,6 +416,14 @@ class Context:
         _check(lib.dg_dp_call_margins(self.h, int(budget), cls.ctypes.data if cls is not None else None, levels.ctypes.data,
                                       paths.ctypes.data if want_paths else None), "dg_dp_call_margins")
         return levels, paths
+
+    def dp_partner_route(self):
+        """(route, cells) of the last dp_best_partners / dp_partner_marginals / dp_call_margins on this context that got as far as
+        a launch: route 1 = level state in LDS, 2 = in device memory (option partner_wide), 0 = no such call yet; cells = that call's
+        widest level x (largest budget + 1)."""
+        route, cells = C.c_int32(0), C.c_int64(0)
+        _check(lib.dg_dp_get_partner_route(self.h, C.byref(route), C.byref(cells)), "dg_dp_get_partner_route")
+        return route.value, cells.value
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

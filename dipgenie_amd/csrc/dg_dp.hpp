@@ -164,7 +164,8 @@ struct DpOptions {
     int64_t chunk_units_cfg = (int64_t)4 << 30;         // lattice_chunk_cells: size of one lattice chunk (16-bit units, even: 8 GB)
     int64_t score_slab_bytes = (int64_t)256 << 20;      // score_slab_bytes: bound of the path staging buffer of dg_dp_score_paths (a slab holds at least one pair)
     int64_t partner_slab_bytes = (int64_t)4 << 30;      // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, of the forward values, edge scores, marginals and records of one slab of dg_dp_partner_marginals (a slab holds at least one query)
-    int64_t objective_lds_bytes = 131072;               // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
+    int64_t partner_wide = 0;                           // partner_wide: the level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 never (LDS only), 1 for a call beyond the LDS limit, 2 always
+    int64_t objective_lds_bytes = 131072;              // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
 };
 
 struct DpState {
@@ -250,6 +251,11 @@ struct DpState {
     // ---- dg_dp_best_partners (dg_dp_partner.hip): one slab of queries -- (given, partner) pairs, budgets, sink cells, the re-scoring
     // pass's records, the two first-bad-hop words; back-pointers and edge scores (released when the call returns) ----
     DevBuf d_pt_pairs, d_pt_bud, d_pt_val, d_pt_out, d_pt_err, d_pt_bp, d_pt_scores;
+    // the device-memory route (option partner_wide) of these calls and of the two below: per query two level states of kmax * (bmax + 1)
+    // int32 (released when the call returns); the route and the cells of the last call that chose one (dg_dp_get_partner_route)
+    DevBuf d_pt_state;
+    int32_t pt_route = 0;
+    int64_t pt_route_cells = 0;
     // ---- dg_dp_partner_marginals (dg_dp_marginals.hip): the level records and the marginals of one slab; the given paths, budgets, sink
     // cells, first-bad-hop word, forward values (in d_pt_bp) and edge scores live in the buffers above ----
     DevBuf d_mg_levels, d_mg_vertex;

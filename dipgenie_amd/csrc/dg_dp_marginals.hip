@@ -25,6 +25,9 @@
 // Nothing of a run is read or written.  Per query a slab holds 4 * n_vertices * (bmax + 1) bytes of forward values (bmax: the
 // largest budget of the call), 2 bytes per in-edge of scores, 4 * n_vertices bytes of marginals and 20 * n_levels bytes of path and
 // level records; partner_slab_bytes bounds their sum.
+// With option partner_wide (dg_dp_partner.hip) the forward kernel is dp_partner_sweep_wide_kernel<VALUES>, which reads level l - 1 back
+// from the forward values and needs no other state, and the backward kernel dp_marginals_back_wide_kernel, whose two level states live
+// in a per-query device buffer (8 * kmax * (bmax + 1) bytes more per query, released when the call returns).
 #include <algorithm>
 #include <cstring>
 
@@ -192,6 +195,154 @@ __global__ __launch_bounds__(PT_THREADS) void dp_marginals_back_kernel(const Lev
     }
 }
 
+// ---- the device-memory route (option partner_wide): the same backward pass with the two level states in device memory ----
+// The scatter's atomicMax is executed by the L2, past this CU's L1; a plain load of the same word may be served from an L1 line that
+// was filled before the atomics arrived (the combination of level l + 1 read the neighbouring words of the same state copy two levels
+// ago, the scatter itself reads rows next to the ones other lanes add to).  So every access to a backward state is an atomic one at
+// agent scope, which goes to the L2 as well: the NEG_INF fill and the sink's row are atomic stores, the reads atomic loads.  With the
+// barrier between the phases that orders fill, scatter and read of a word, whatever the L1 holds.  The forward values, written by
+// the kernel before this one, are read with plain loads as in the LDS kernel.  (What the L1 bypass costs against plain loads is not
+// measured: a plain load is not known to be correct here, so there is nothing to compare it with.)
+__device__ __forceinline__ int mgw_ld(int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void mgw_st(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Level l scattered into level l - 1, as mg_scatter
+template <bool STAGED>
+__device__ __forceinline__ void mgw_scatter(const PtLevel &lv, int B1, int vrow, int rows, int r0, int rstep, int32_t *src, int32_t *dst,
+                                            const uint32_t *edge, const uint16_t *sc, const uint32_t *off) {
+    for (int v = vrow; v < lv.k2; v += rows) {
+        const uint32_t e0 = off[v], e1 = off[v + 1];
+        for (int r = r0; r < B1; r += rstep) {
+            const int s0 = mgw_ld(src + v * B1 + r), s1 = r ? mgw_ld(src + v * B1 + r - 1) : NEG_INF;   // the destination cell an in-edge of weight 0 / 1 reads
+            for (uint32_t e = e0; e < e1; ++e) {
+                const uint32_t rec = edge[e];
+                const int pos = (int)(rec & 0x7FFFFFFFu);
+                const int s = (rec >> 31) ? s1 : s0;
+                if (s == NEG_INF) continue;
+                atomicMax(&dst[pos * B1 + r], s + (int)sc[e]);
+            }
+        }
+    }
+}
+
+// grid: n workgroups of PTW_THREADS; state_all = [n][2][cells] int32, level l in copy (l & 1); static LDS: one stage buffer and the
+// waves' top-two keys.  Phases, barriers and outputs are those of dp_marginals_back_kernel
+__global__ __launch_bounds__(PTW_THREADS) void dp_marginals_back_wide_kernel(const LevelDesc *__restrict__ descs, int L, int nV, int cells,
+                                                                             const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
+                                                                             const uint16_t *__restrict__ scores, int64_t E, const int32_t *__restrict__ budgets,
+                                                                             const int32_t *__restrict__ fwd_all, int64_t fwd_stride, int32_t *state_all,
+                                                                             dg_dp_level_margin *__restrict__ levels, int32_t *__restrict__ vertex_values) {
+    __shared__ uint32_t st_edge[PT_STAGE], st_off[PT_STAGE + 4];
+    __shared__ uint16_t st_sc[PT_STAGE];
+    __shared__ long long s_top[PTW_THREADS / 64][2];
+    const int64_t q = blockIdx.x;
+    const int t = (int)threadIdx.x;
+    const int B1 = budgets[q] + 1;
+    const uint16_t *__restrict__ sc_g = scores + q * E;
+    const int32_t *__restrict__ fwd = fwd_all + q * fwd_stride;
+    dg_dp_level_margin *__restrict__ out = levels + q * (int64_t)L;
+    int32_t *__restrict__ vv = vertex_values ? vertex_values + q * (int64_t)nV : nullptr;
+    int32_t *const state0 = state_all + q * 2 * (int64_t)cells, *const state1 = state0 + cells;
+    // scatter, lanes -> cells as in the forward recurrence
+    int rows, vrow, r0, rstep;
+    if (B1 <= PTW_THREADS) { rows = PTW_THREADS / B1; vrow = t / B1; r0 = t - vrow * B1; rstep = B1; if (vrow >= rows) vrow = 1 << 30; }
+    else { rows = 1; vrow = 0; r0 = t; rstep = PTW_THREADS; }
+    // combination: G lanes per vertex (a power of two, inside one wave), PTW_THREADS / G vertices per pass
+    int G = 1;
+    while (G < 64 && G < B1) G <<= 1;
+    const int gv = t / G, gj = t & (G - 1), gper = PTW_THREADS / G;
+
+    PtLevel lv = mg_level(descs, L - 1);                                // level l
+    PtLevel ln = mg_level(descs, L - 2);                                // level l - 1
+    {                                                                   // the sink's level: 0 on every plane of the sink, NEG_INF elsewhere; level L - 2: NEG_INF
+        int32_t *top = ((L - 1) & 1) ? state1 : state0, *below = ((L - 1) & 1) ? state0 : state1;
+        const int sink_lo = (nV - 1 - lv.b0) * B1;
+        for (int i = t; i < lv.k2 * B1; i += PTW_THREADS) mgw_st(top + i, (i >= sink_lo && i < sink_lo + B1) ? 0 : NEG_INF);
+        for (int i = t; i < ln.k2 * B1; i += PTW_THREADS) mgw_st(below + i, NEG_INF);
+        if (pt_staged(lv)) {
+            for (int i = t; i < lv.T; i += PTW_THREADS) { st_edge[i] = in_edge[lv.in_base + i]; st_sc[i] = sc_g[lv.in_base + i]; }
+            for (int i = t; i <= lv.k2; i += PTW_THREADS) st_off[i] = in_off[lv.b0 + i] - lv.in_base;
+        }
+    }
+    __syncthreads();
+    for (int l = L - 1; l >= 0; --l) {
+        const PtLevel lnn = mg_level(descs, l >= 2 ? l - 2 : 0);        // level l - 2 (its width: the fill below)
+        const bool stage_next = l >= 2 && pt_staged(ln);                // level l - 1 has in-edges to stage
+        // issued here, consumed after the scatter: the records of level l - 1 and the first forward value of this lane's group
+        uint32_t pf_edge[PTW_PF], pf_off[PTW_PF + 1], pf_sc[PTW_PF];
+        if (stage_next) {
+#pragma unroll
+            for (int j = 0; j < PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i < ln.T) { pf_edge[j] = in_edge[ln.in_base + i]; pf_sc[j] = sc_g[ln.in_base + i]; }
+            }
+#pragma unroll
+            for (int j = 0; j <= PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i <= ln.k2) pf_off[j] = in_off[ln.b0 + i];
+            }
+        }
+        int f_first = 0;                                                // F of level 0 is 0 on every plane and is not read
+        if (l >= 1 && gv < lv.k2 && gj < B1) f_first = fwd[((int64_t)lv.b0 + gv) * B1 + gj];
+        int32_t *cur = (l & 1) ? state1 : state0;
+        int32_t *below = (l & 1) ? state0 : state1;
+        if (l >= 1) {
+            if (pt_staged(lv)) mgw_scatter<true>(lv, B1, vrow, rows, r0, rstep, cur, below, st_edge, st_sc, st_off);
+            else mgw_scatter<false>(lv, B1, vrow, rows, r0, rstep, cur, below, in_edge, sc_g, in_off + lv.b0);
+        }
+        long long k1 = MG_NO_KEY, k2 = MG_NO_KEY;
+        for (int v0 = 0; v0 < lv.k2; v0 += gper) {                      // the same trips for every lane: the shuffles below find their group whole
+            const int v = v0 + gv;
+            int m = NEG_INF;
+            if (v < lv.k2) {
+                for (int r = gj; r < B1; r += G) {
+                    const int f = (v0 == 0 && r == gj) ? f_first : (l >= 1 ? fwd[((int64_t)lv.b0 + v) * B1 + r] : 0);
+                    const int b = mgw_ld(cur + v * B1 + (B1 - 1 - r));
+                    if (f != NEG_INF && b != NEG_INF) m = max(m, f + b);
+                }
+            }
+            for (int d = G >> 1; d; d >>= 1) m = max(m, __shfl_xor(m, d));
+            if (v < lv.k2 && gj == 0) {
+                if (vv) vv[lv.b0 + v] = m;
+                if (m != NEG_INF) mg_merge(k1, k2, mg_key(m, lv.b0 + v), MG_NO_KEY);
+            }
+        }
+        for (int d = 32; d; d >>= 1) {
+            const long long o1 = __shfl_xor(k1, d), o2 = __shfl_xor(k2, d);
+            mg_merge(k1, k2, o1, o2);
+        }
+        if ((t & 63) == 0) { s_top[t >> 6][0] = k1; s_top[t >> 6][1] = k2; }
+        __syncthreads();
+        if (t == 0) {
+            for (int w = 1; w < PTW_THREADS / 64; ++w) mg_merge(k1, k2, s_top[w][0], s_top[w][1]);
+            dg_dp_level_margin rec;
+            rec.best_vertex = k1 == MG_NO_KEY ? -1 : INT32_MAX - (int)(uint32_t)k1;
+            rec.best_value = k1 == MG_NO_KEY ? NEG_INF : (int)(k1 >> 32);
+            rec.second_vertex = k2 == MG_NO_KEY ? -1 : INT32_MAX - (int)(uint32_t)k2;
+            rec.second_value = k2 == MG_NO_KEY ? NEG_INF : (int)(k2 >> 32);
+            out[l] = rec;
+        }
+        if (l >= 2) {                                                   // level l's state has been read: it becomes level l - 2
+            int32_t *nxt = (l & 1) ? state1 : state0;
+            for (int i = t; i < lnn.k2 * B1; i += PTW_THREADS) mgw_st(nxt + i, NEG_INF);
+        }
+        if (stage_next) {
+#pragma unroll
+            for (int j = 0; j < PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i < ln.T) { st_edge[i] = pf_edge[j]; st_sc[i] = (uint16_t)pf_sc[j]; }
+            }
+#pragma unroll
+            for (int j = 0; j <= PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i <= ln.k2) st_off[i] = pf_off[j] - ln.in_base;
+            }
+        }
+        __syncthreads();
+        lv = ln; ln = lnn;
+    }
+}
+
 // dg_dp_call_margins, after the backward kernel: one wave per (query, level).  Query q of the slab is row `first + q` of the call: its
 // marginals are those of the partners of the OTHER row's path, the called vertex is its own path's (given = the two paths in the
 // order of the queries, so the path of row r is given + (1 - r) * L).  The lanes stride over the level's vertices and keep the
@@ -225,17 +376,19 @@ __global__ __launch_bounds__(PT_THREADS) void dp_call_margins_kernel(const Level
 
 // What a call's slabs share: LDS sizes, strides, and the buffers of `per_slab` queries (grow-only but for the two large ones, which the
 // caller releases).  vertex: the marginals of every vertex are kept (on the device)
-struct MgPlan { int cells; size_t lds_bytes; int64_t fwd_stride, per_slab; };
+struct MgPlan { int cells; bool wide; size_t lds_bytes; int64_t fwd_stride, per_slab; };
 
-int mg_plan(DpState &S, int64_t n, int kmax, int bmax, bool vertex, MgPlan &P) {
+// wide: the call takes the device-memory route (option partner_wide): no LDS to ask for, two backward states per query in d_pt_state
+int mg_plan(DpState &S, int64_t n, int kmax, int bmax, bool wide, bool vertex, MgPlan &P) {
     const int L = S.L, nV = S.nV;
     const int64_t E = S.n_edges;
     P.cells = kmax * (bmax + 1);
-    P.lds_bytes = 2 * (size_t)P.cells * 4 + PT_STAGE_BUF_BYTES;
+    P.wide = wide;
+    P.lds_bytes = wide ? 0 : 2 * (size_t)P.cells * 4 + PT_STAGE_BUF_BYTES;
     if (P.lds_bytes > 65536) DG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dp_marginals_back_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes));
     // queries per slab: what partner_slab_bytes holds (at least one), every query sized for the call's largest budget
     P.fwd_stride = (int64_t)nV * (bmax + 1);                            // int32 units
-    const int64_t query_bytes = 4 * P.fwd_stride + 2 * E + 4 * (int64_t)nV + 20 * (int64_t)L;
+    const int64_t query_bytes = 4 * P.fwd_stride + 2 * E + 4 * (int64_t)nV + 20 * (int64_t)L + (wide ? 8 * (int64_t)P.cells : 0);
     int64_t per_slab = std::max<int64_t>(1, S.opt.partner_slab_bytes / query_bytes);
     per_slab = std::min(std::min(per_slab, partner_slab_limit(S)), n);
     P.per_slab = per_slab;
@@ -246,14 +399,17 @@ int mg_plan(DpState &S, int64_t n, int kmax, int bmax, bool vertex, MgPlan &P) {
     if (int rc = S.d_mg_levels.ensure((size_t)(per_slab * L) * sizeof(dg_dp_level_margin))) return rc;
     if (vertex)
         if (int rc = S.d_mg_vertex.ensure((size_t)(per_slab * nV) * 4)) return rc;
+    partner_note_route(S, wide, P.cells);
     return DG_OK;
 }
 
-// the two large buffers live for the call only: the lattice pool of a later run may need the memory
-struct MgRelease { DpState &S; ~MgRelease() { S.d_pt_bp.release(); S.d_pt_scores.release(); S.d_cm_class.release(); } };
+// the large buffers live for the call only: the lattice pool of a later run may need the memory
+struct MgRelease { DpState &S; ~MgRelease() { S.d_pt_bp.release(); S.d_pt_scores.release(); S.d_pt_state.release(); S.d_cm_class.release(); } };
 
 int mg_plan_large(DpState &S, const MgPlan &P) {
     if (int rc = S.d_pt_bp.ensure((size_t)(P.per_slab * P.fwd_stride) * 4)) return rc;
+    if (P.wide)
+        if (int rc = S.d_pt_state.ensure((size_t)(P.per_slab * 2 * P.cells) * 4)) return rc;
     return S.d_pt_scores.ensure((size_t)(P.per_slab * S.n_edges) * 2 + 16);
 }
 
@@ -265,12 +421,19 @@ int mg_launch_slab(DpState &S, const MgPlan &P, const int32_t *d_given, int64_t 
     DG_HIP(hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), s));
     partner_launch_scores(S, d_given, S.L, m, S.d_pt_scores.as<uint16_t>(), d_err, s);
     DG_HIP(hipGetLastError());
-    if (int rc = partner_launch_forward_values(S, P.cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_bp.as<int32_t>(), P.fwd_stride,
+    if (int rc = partner_launch_forward_values(S, P.wide, P.cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_bp.as<int32_t>(), P.fwd_stride,
                                                S.d_pt_val.as<int32_t>(), s))
         return rc;
-    hipLaunchKernelGGL(dp_marginals_back_kernel, dim3((unsigned)m), dim3(PT_THREADS), P.lds_bytes, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, P.cells,
-                       S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_pt_scores.as<uint16_t>(), S.n_edges, S.d_pt_bud.as<int32_t>(),
-                       S.d_pt_bp.as<int32_t>(), P.fwd_stride, S.d_mg_levels.as<dg_dp_level_margin>(), vertex ? S.d_mg_vertex.as<int32_t>() : nullptr);
+    if (P.wide) {
+        hipLaunchKernelGGL(dp_marginals_back_wide_kernel, dim3((unsigned)m), dim3(PTW_THREADS), 0, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, P.cells,
+                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_pt_scores.as<uint16_t>(), S.n_edges, S.d_pt_bud.as<int32_t>(),
+                           S.d_pt_bp.as<int32_t>(), P.fwd_stride, S.d_pt_state.as<int32_t>(), S.d_mg_levels.as<dg_dp_level_margin>(),
+                           vertex ? S.d_mg_vertex.as<int32_t>() : nullptr);
+    } else {
+        hipLaunchKernelGGL(dp_marginals_back_kernel, dim3((unsigned)m), dim3(PT_THREADS), P.lds_bytes, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, P.cells,
+                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_pt_scores.as<uint16_t>(), S.n_edges, S.d_pt_bud.as<int32_t>(),
+                           S.d_pt_bp.as<int32_t>(), P.fwd_stride, S.d_mg_levels.as<dg_dp_level_margin>(), vertex ? S.d_mg_vertex.as<int32_t>() : nullptr);
+    }
     DG_HIP(hipGetLastError());
     return DG_OK;
 }
@@ -288,9 +451,10 @@ int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32
     hipStream_t s = c->stream;
     const int L = S.L, nV = S.nV;
     int kmax, bmax;
-    if (int rc = partner_check_budgets(FN, S, n, budgets, kmax, bmax)) return rc;
+    bool wide;
+    if (int rc = partner_check_budgets(FN, S, n, budgets, kmax, bmax, wide)) return rc;
     MgPlan P;
-    if (int rc = mg_plan(S, n, kmax, bmax, vertex_values != nullptr, P)) return rc;
+    if (int rc = mg_plan(S, n, kmax, bmax, wide, vertex_values != nullptr, P)) return rc;
     const int64_t per_slab = P.per_slab;
     MgRelease release{S};
     if (int rc = mg_plan_large(S, P)) return rc;
@@ -328,7 +492,10 @@ int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_d
     const int L = S.L, nV = S.nV;
     int kmax = 1;
     for (int l = 1; l < L; ++l) kmax = std::max(kmax, S.descs[l].k2);
-    if (budget >= 0 && (int64_t)kmax * ((int64_t)budget + 1) > PT_MAX_CELLS) {     // on the budget itself, not on what the other haplotype leaves: known before a run
+    // on the budget itself, not on what the other haplotype leaves: known before a run
+    if (budget >= 0 && S.opt.partner_wide >= 1) {
+        if (int rc = partner_check_wide(FN, "budget", budget, kmax, budget)) return rc;
+    } else if (budget >= 0 && (int64_t)kmax * ((int64_t)budget + 1) > PT_MAX_CELLS) {
         set_error("%s: widest level %d x (budget + 1) %lld exceeds %d cells", FN, kmax, (long long)budget + 1, PT_MAX_CELLS);
         return DG_ERR_UNSUPPORTED;
     }
@@ -355,7 +522,8 @@ int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_d
         }
         const int32_t budgets[2] = {budget - cnt[1], budget - cnt[0]};
         MgPlan P;
-        if (int rc = mg_plan(S, 2, kmax, std::max(budgets[0], budgets[1]), true, P)) return rc;      // (d_pt_pairs holds both paths already: it only grows)
+        const int bmax = std::max(budgets[0], budgets[1]);
+        if (int rc = mg_plan(S, 2, kmax, bmax, partner_route_wide(S, kmax, bmax), true, P)) return rc;      // (d_pt_pairs holds both paths already: it only grows)
         MgRelease release{S};
         if (int rc = mg_plan_large(S, P)) return rc;
         if (int rc = S.d_cm_out.ensure(2 * (size_t)L * sizeof(dg_dp_call_margin))) return rc;

@@ -19,6 +19,10 @@
 //     DP's cell and r2 must fit the budget, or the call fails with DG_ERR_STATE.
 // Nothing of a run is read or written.  Per query a slab holds 2 * n_vertices * (bmax + 1) bytes of back-pointers (bmax: the largest
 // budget of the call), 2 bytes per in-edge of scores and 8 * n_levels bytes of paths; partner_slab_bytes bounds their sum.
+// With option partner_wide a call whose kmax x (bmax + 1) cells exceed PT_MAX_CELLS (1), or every call (2), takes the device-memory
+// route: dp_partner_sweep_wide_kernel in place of the second kernel, one 1,024-lane workgroup per query, the two level states in a
+// per-query device buffer of 2 * kmax * (bmax + 1) int32 (8 bytes per cell more in the slab's sum; released when the call returns),
+// only the in-edge stage in LDS.  Same recurrence, ties, back-pointers and walk; kmax <= 32,767 and 2^24 cells per query.
 // dg_dp_partner_marginals (dg_dp_marginals.hip) runs the first two kernels as well, the second one storing every cell's int32 value
 // in place of the back-pointer (VALUES): what the two files share is declared in dg_dp_partner.hpp.
 #include <algorithm>
@@ -186,6 +190,118 @@ __global__ __launch_bounds__(PT_THREADS) void dp_partner_sweep_kernel(const Leve
 #undef PT_OFF
 #undef PT_SC
 
+// ---- the device-memory route (option partner_wide): the same recurrence with the level states in device memory ----
+// The cells of one level, as pt_cells.  prev / cur: the states of level l - 1 / l as [position][r] in device memory, written and read
+// by this workgroup alone.  They are plain pointers on purpose -- not const, not __restrict__, no non-temporal access: the loads of
+// level l must follow the barrier that ends level l - 1, and only a pointer the compiler has to assume written lets it neither hoist
+// such a load over the barrier nor turn it into a scalar (constant-cache) load.  All waves of a workgroup share one CU and its L1,
+// through which both the stores and the loads go, so the barrier is all the ordering they need.
+template <bool STAGED, bool VALUES>
+__device__ __forceinline__ void ptw_cells(const PtLevel &lv, int B1, int vrow, int rows, int r0, int rstep, int32_t *prev, int32_t *cur,
+                                          const uint32_t *edge, const uint16_t *sc, const uint32_t *off, uint16_t *bp) {
+    for (int v = vrow; v < lv.k2; v += rows) {
+        const uint32_t e0 = off[v], e1 = off[v + 1];
+        for (int r = r0; r < B1; r += rstep) {
+            int best = NEG_INF;
+            uint32_t word = PT_BP_NONE;
+            for (uint32_t e = e0; e < e1; ++e) {                        // sorted by source position: a strict > keeps the smallest among equals
+                const uint32_t rec = edge[e];
+                const int pos = (int)(rec & 0x7FFFFFFFu), w = (int)(rec >> 31);
+                if (r - w < 0) continue;
+                const int s = prev[pos * B1 + r - w];
+                if (s == NEG_INF) continue;
+                const int cand = s + (int)sc[e];
+                if (cand > best) { best = cand; word = (uint32_t)pos | ((uint32_t)w << 15); }
+            }
+            cur[v * B1 + r] = best;
+            if constexpr (!VALUES) bp[((int64_t)lv.b0 + v) * B1 + r] = (uint16_t)word;
+        }
+    }
+}
+
+// grid: n workgroups of PTW_THREADS; static LDS: the two stage buffers.  !VALUES: state_all = [n][2][cells] int32, level l in copy
+// (l & 1), store_all = the back-pointers.  VALUES: store_all = the values [vertex][r], which are the state as well (level l - 1 is
+// read back from where it was stored); state_all is not used
+template <bool VALUES>
+__global__ __launch_bounds__(PTW_THREADS) void dp_partner_sweep_wide_kernel(const LevelDesc *__restrict__ descs, int L, int nV, int cells,
+                                                                            const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
+                                                                            const uint16_t *__restrict__ scores, int64_t E, const int32_t *__restrict__ budgets,
+                                                                            int32_t *state_all, typename PtStore<VALUES>::type *store_all, int64_t stride,
+                                                                            int32_t *__restrict__ value) {
+    __shared__ uint32_t st_edge[2][PT_STAGE], st_off[2][PT_STAGE + 4];
+    __shared__ uint16_t st_sc[2][PT_STAGE];
+    const int64_t q = blockIdx.x;
+    const int t = (int)threadIdx.x;
+    const int B1 = budgets[q] + 1;
+    const uint16_t *__restrict__ sc_g = scores + q * E;
+    typename PtStore<VALUES>::type *store = store_all + q * stride;
+    int32_t *state0 = nullptr, *state1 = nullptr;
+    uint16_t *bp = nullptr;
+    if constexpr (!VALUES) { state0 = state_all + q * 2 * (int64_t)cells; state1 = state0 + cells; bp = store; }
+    // lanes -> cells as in dp_partner_sweep_kernel: whole rows of B1 planes per pass while a row fits the workgroup, else one row with the lanes striding over r
+    int rows, vrow, r0, rstep;
+    if (B1 <= PTW_THREADS) { rows = PTW_THREADS / B1; vrow = t / B1; r0 = t - vrow * B1; rstep = B1; if (vrow >= rows) vrow = 1 << 30; }
+    else { rows = 1; vrow = 0; r0 = t; rstep = PTW_THREADS; }
+
+    int prev_b0 = descs[1].a0;                                          // first vertex of level l - 1
+    {                                                                   // level 0 is the source alone
+        int32_t *lev0;
+        if constexpr (VALUES) lev0 = store + (int64_t)prev_b0 * B1; else lev0 = state0;
+        for (int r = t; r < B1; r += PTW_THREADS) lev0[r] = 0;
+    }
+    PtLevel lv = pt_level(descs, 1);
+    PtLevel ln = L > 2 ? pt_level(descs, 2) : lv;
+    if (pt_staged(lv)) {
+        for (int i = t; i < lv.T; i += PTW_THREADS) { st_edge[1][i] = in_edge[lv.in_base + i]; st_sc[1][i] = sc_g[lv.in_base + i]; }
+        for (int i = t; i <= lv.k2; i += PTW_THREADS) st_off[1][i] = in_off[lv.b0 + i] - lv.in_base;
+    }
+    __syncthreads();
+    for (int l = 1; l < L; ++l) {
+        const bool more = l + 1 < L, stage_next = more && pt_staged(ln);
+        const PtLevel lnn = l + 2 < L ? pt_level(descs, l + 2) : ln;
+        // level l + 1's records: issued here, consumed after this level's cells
+        uint32_t pf_edge[PTW_PF], pf_off[PTW_PF + 1], pf_sc[PTW_PF];
+        if (stage_next) {
+#pragma unroll
+            for (int j = 0; j < PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i < ln.T) { pf_edge[j] = in_edge[ln.in_base + i]; pf_sc[j] = sc_g[ln.in_base + i]; }
+            }
+#pragma unroll
+            for (int j = 0; j <= PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i <= ln.k2) pf_off[j] = in_off[ln.b0 + i];
+            }
+        }
+        int32_t *prev, *cur;
+        if constexpr (VALUES) { prev = store + (int64_t)prev_b0 * B1; cur = store + (int64_t)lv.b0 * B1; }
+        else { prev = (l & 1) ? state0 : state1; cur = (l & 1) ? state1 : state0; }
+        const int b = l & 1;
+        if (pt_staged(lv)) ptw_cells<true, VALUES>(lv, B1, vrow, rows, r0, rstep, prev, cur, st_edge[b], st_sc[b], st_off[b], bp);
+        else ptw_cells<false, VALUES>(lv, B1, vrow, rows, r0, rstep, prev, cur, in_edge, sc_g, in_off + lv.b0, bp);
+        if (stage_next) {
+            const int nb = (l + 1) & 1;
+#pragma unroll
+            for (int j = 0; j < PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i < ln.T) { st_edge[nb][i] = pf_edge[j]; st_sc[nb][i] = (uint16_t)pf_sc[j]; }
+            }
+#pragma unroll
+            for (int j = 0; j <= PTW_PF; ++j) {
+                const int i = t + j * PTW_THREADS;
+                if (i <= ln.k2) st_off[nb][i] = pf_off[j] - ln.in_base;
+            }
+        }
+        __syncthreads();                                                // level l's stores before level l + 1's loads
+        prev_b0 = lv.b0;
+        lv = ln; ln = lnn;
+    }
+    if (t == 0) {                                                       // lv: the sink's level
+        if constexpr (VALUES) value[q] = store[(int64_t)(nV - 1) * B1 + B1 - 1];
+        else value[q] = (((L - 1) & 1) ? state1 : state0)[(nV - 1 - lv.b0) * B1 + B1 - 1];
+    }
+}
+
 // one lane per query; pairs = [n][2][L]: row 1 receives the partner (the given path itself where the budget reaches nothing: the
 // re-scoring pass then still counts r1, and the host hands out a row of -1)
 __global__ __launch_bounds__(64) void dp_partner_walk_kernel(const LevelDesc *__restrict__ descs, int L, int nV, int64_t n, const int32_t *__restrict__ budgets,
@@ -217,18 +333,33 @@ __global__ __launch_bounds__(64) void dp_partner_walk_kernel(const LevelDesc *__
 
 }  // namespace
 
-int partner_check_budgets(const char *fn, const DpState &S, int64_t n, const int32_t *budgets, int &kmax, int &bmax) {
+int partner_check_wide(const char *fn, const char *who, long long which, int kmax, int64_t budget) {
+    if (kmax > PTW_MAX_K) {
+        set_error("%s: %s %lld: widest level %d exceeds the %d vertices of the device-memory route (budget + 1 = %lld)", fn, who, which, kmax, PTW_MAX_K, (long long)budget + 1);
+        return DG_ERR_UNSUPPORTED;
+    }
+    if ((int64_t)kmax * (budget + 1) > PTW_MAX_CELLS) {
+        set_error("%s: %s %lld: widest level %d x (budget + 1) %lld exceeds the %d cells of the device-memory route", fn, who, which, kmax, (long long)budget + 1, PTW_MAX_CELLS);
+        return DG_ERR_UNSUPPORTED;
+    }
+    return DG_OK;
+}
+
+int partner_check_budgets(const char *fn, const DpState &S, int64_t n, const int32_t *budgets, int &kmax, int &bmax, bool &wide) {
     kmax = 1;
     for (int l = 1; l < S.L; ++l) kmax = std::max(kmax, S.descs[l].k2);
     bmax = 0;
     for (int64_t q = 0; q < n; ++q) {
         if (budgets[q] < 0) { set_error("%s: query %lld: budget %d is negative", fn, (long long)q, budgets[q]); return DG_ERR_ARG; }
-        if ((int64_t)kmax * ((int64_t)budgets[q] + 1) > PT_MAX_CELLS) {
+        if (S.opt.partner_wide >= 1) {
+            if (int rc = partner_check_wide(fn, "query", (long long)q, kmax, budgets[q])) return rc;
+        } else if ((int64_t)kmax * ((int64_t)budgets[q] + 1) > PT_MAX_CELLS) {
             set_error("%s: query %lld: widest level %d x (budget + 1) %lld exceeds %d cells", fn, (long long)q, kmax, (long long)budgets[q] + 1, PT_MAX_CELLS);
             return DG_ERR_UNSUPPORTED;
         }
         bmax = std::max(bmax, budgets[q]);
     }
+    wide = partner_route_wide(S, kmax, bmax);                           // per call, not per query: one launch serves a slab
     return DG_OK;
 }
 
@@ -251,10 +382,17 @@ void partner_launch_scores(const DpState &S, const int32_t *given, int64_t given
                        S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), S.d_in_dst.as<int32_t>(), colour_csr(S), given, given_stride, scores, S.n_edges, err);
 }
 
-// the recurrence on m queries; store = back-pointers (16 bits per cell) or values (32 bits), stride in those units
+// the recurrence on m queries; store = back-pointers (16 bits per cell) or values (32 bits), stride in those units.  wide: the
+// device-memory route, state = [m][2][cells] int32 for the back-pointer form (the values form needs none)
 template <bool VALUES>
-static int partner_launch_sweep(const DpState &S, int cells, int64_t m, const uint16_t *scores, const int32_t *budgets, typename PtStore<VALUES>::type *store,
-                                int64_t stride, int32_t *value, hipStream_t s) {
+static int partner_launch_sweep(const DpState &S, bool wide, int cells, int64_t m, const uint16_t *scores, const int32_t *budgets, int32_t *state,
+                                typename PtStore<VALUES>::type *store, int64_t stride, int32_t *value, hipStream_t s) {
+    if (wide) {
+        hipLaunchKernelGGL(dp_partner_sweep_wide_kernel<VALUES>, dim3((unsigned)m), dim3(PTW_THREADS), 0, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, cells,
+                           S.d_in_off.as<uint32_t>(), S.d_in_edge.as<uint32_t>(), scores, S.n_edges, budgets, state, store, stride, value);
+        DG_HIP(hipGetLastError());
+        return DG_OK;
+    }
     const size_t lds_bytes = 2 * (size_t)cells * 4 + PT_STAGE_BYTES;
     if (lds_bytes > 65536) DG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dp_partner_sweep_kernel<VALUES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(dp_partner_sweep_kernel<VALUES>, dim3((unsigned)m), dim3(PT_THREADS), lds_bytes, s, S.d_descs.as<LevelDesc>(), S.L, S.nV, cells,
@@ -263,9 +401,9 @@ static int partner_launch_sweep(const DpState &S, int cells, int64_t m, const ui
     return DG_OK;
 }
 
-int partner_launch_forward_values(const DpState &S, int cells, int64_t m, const uint16_t *scores, const int32_t *budgets, int32_t *values, int64_t stride,
+int partner_launch_forward_values(const DpState &S, bool wide, int cells, int64_t m, const uint16_t *scores, const int32_t *budgets, int32_t *values, int64_t stride,
                                   int32_t *value, hipStream_t s) {
-    return partner_launch_sweep<true>(S, cells, m, scores, budgets, values, stride, value, s);
+    return partner_launch_sweep<true>(S, wide, cells, m, scores, budgets, nullptr, values, stride, value, s);
 }
 
 int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out) {
@@ -279,12 +417,15 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
     const int L = S.L, nV = S.nV;
     const int64_t E = S.n_edges;
     int kmax, bmax;
-    if (int rc = partner_check_budgets("dg_dp_best_partners", S, n, budgets, kmax, bmax)) return rc;
+    bool wide;
+    if (int rc = partner_check_budgets("dg_dp_best_partners", S, n, budgets, kmax, bmax, wide)) return rc;
     const int cells = kmax * (bmax + 1);
+    partner_note_route(S, wide, cells);
     // queries per slab: what partner_slab_bytes holds (at least one), every query sized for the call's largest budget
     const int64_t bp_stride = (int64_t)nV * (bmax + 1);                 // 16-bit units
     const int64_t pair_words = 2 * (int64_t)L;
-    const int64_t query_bytes = 2 * bp_stride + 2 * E + 4 * pair_words;
+    const int64_t state_words = wide ? 2 * (int64_t)cells : 0;         // the device-memory route: two level states per query
+    const int64_t query_bytes = 2 * bp_stride + 2 * E + 4 * pair_words + 4 * state_words;
     int64_t per_slab = std::max<int64_t>(1, S.opt.partner_slab_bytes / query_bytes);
     per_slab = std::min(per_slab, partner_slab_limit(S));
     per_slab = std::min(per_slab, n);
@@ -293,10 +434,12 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
     if (int rc = S.d_pt_val.ensure((size_t)per_slab * 4)) return rc;
     if (int rc = S.d_pt_out.ensure((size_t)per_slab * sizeof(dg_dp_pair_score))) return rc;
     if (int rc = S.d_pt_err.ensure(2 * sizeof(unsigned long long))) return rc;
-    // the two large buffers live for the call only: the lattice pool of a later run may need the memory
-    struct Release { DpState &S; ~Release() { S.d_pt_bp.release(); S.d_pt_scores.release(); } } release{S};
+    // the large buffers live for the call only: the lattice pool of a later run may need the memory
+    struct Release { DpState &S; ~Release() { S.d_pt_bp.release(); S.d_pt_scores.release(); S.d_pt_state.release(); } } release{S};
     if (int rc = S.d_pt_bp.ensure((size_t)(per_slab * bp_stride) * 2)) return rc;
     if (int rc = S.d_pt_scores.ensure((size_t)(per_slab * E) * 2 + 16)) return rc;
+    if (wide)
+        if (int rc = S.d_pt_state.ensure((size_t)(per_slab * state_words) * 4)) return rc;
     // the caller's arrays are written only if every query is answered
     std::vector<dg_dp_partner> res((size_t)n);
     std::vector<int32_t> val((size_t)per_slab), rows;
@@ -313,7 +456,7 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
         DG_HIP(hipMemsetAsync(d_err, 0xFF, sizeof err, s));
         partner_launch_scores(S, pairs, pair_words, m, S.d_pt_scores.as<uint16_t>(), d_err, s);
         DG_HIP(hipGetLastError());
-        if (int rc = partner_launch_sweep<false>(S, cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_bp.as<uint16_t>(), bp_stride, S.d_pt_val.as<int32_t>(), s)) return rc;
+        if (int rc = partner_launch_sweep<false>(S, wide, cells, m, S.d_pt_scores.as<uint16_t>(), S.d_pt_bud.as<int32_t>(), S.d_pt_state.as<int32_t>(), S.d_pt_bp.as<uint16_t>(), bp_stride, S.d_pt_val.as<int32_t>(), s)) return rc;
         hipLaunchKernelGGL(dp_partner_walk_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, S.d_descs.as<LevelDesc>(), L, nV, m, S.d_pt_bud.as<int32_t>(),
                            S.d_pt_bp.as<uint16_t>(), bp_stride, S.d_pt_val.as<int32_t>(), pairs);
         DG_HIP(hipGetLastError());
@@ -351,6 +494,13 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
 }
 
 }  // namespace dgi
+
+extern "C" int dg_dp_get_partner_route(dg_ctx *c, int32_t *route, int64_t *cells) {
+    if (!c || !route || !cells) { dgi::set_error("dg_dp_get_partner_route: null"); return DG_ERR_ARG; }
+    *route = c->dp ? c->dp->pt_route : 0;
+    *cells = c->dp ? c->dp->pt_route_cells : 0;
+    return DG_OK;
+}
 
 extern "C" int dg_dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out) {
     if (int rc = dgi::bind(c)) return rc;

@@ -495,7 +495,7 @@ extern "C" int dg_dp_list_sweep_variants(char *buf, int cap) {
     return DG_OK;
 }
 // Options: parity / test knobs (digest, fast, adaptive_rc, coop, rowx, lean_chain, segment_cells, delta_cap_entries, lattice_chunk_cells,
-// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes, objective_lds_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
+// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes, partner_wide, objective_lds_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
 // One row per key: its DpOptions field, the lower clamp, whether v <= 0 asks for the default (that of a fresh DpOptions).
 typedef dgi::DpOptions DpO;
 static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t lo; bool nonpos_is_default; } dp_option_keys[] = {
@@ -506,6 +506,7 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"graph_batch", &DpO::graph_batch, -1, false}, {"l2_prefetch", &DpO::l2_prefetch, 0, false}, {"delta_overlap", &DpO::delta_overlap, 0, false}, {"pf_far", &DpO::pf_far, 0, false},
     {"side_stream", &DpO::side_stream, -1, false}, {"plane_limit", &DpO::plane_limit, 0, false}, {"test_poison_level", &DpO::test_poison_level, 0, false},
     {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"test_force_rc", &DpO::test_force_rc, 0, false}, {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
+    {"partner_wide", &DpO::partner_wide, 0, false},                // 0..2: clamped from above below
     {"objective_lds_bytes", &DpO::objective_lds_bytes, 0, true},   // clamped from above to objective_lds_limit(): the device's LDS per workgroup
     // read by dg_dp_load_graph: in effect at the next load
     {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},
@@ -527,6 +528,7 @@ static int dp_option(dg_ctx *c, const char *what, const char *key, const int64_t
             v = (int64_t)(S.pool.chunk_units = ((size_t)v + 1) & ~(size_t)1);
         }
         if (o.field == &DpO::objective_lds_bytes) v = std::min(v, dgi::objective_lds_limit(c));
+        if (o.field == &DpO::partner_wide) v = std::min<int64_t>(v, 2);
         S.opt.*o.field = o.nonpos_is_default && v <= 0 ? DpO().*o.field : v < o.lo ? o.lo : v;
         return DG_OK;
     }

@@ -390,7 +390,12 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     if (!opt.site_margins.empty()) {                                   // what dg_dp_call_margins can hold, known before the DP: no output of any kind otherwise
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
-        if (widest * ((int64_t)R + 1) > 16384) {
+        if (opt.wide_levels) {                                          // the limits of the device-memory route of dg_dp_call_margins
+            if (widest > 32767 || widest * ((int64_t)R + 1) > ((int64_t)1 << 24)) {
+                err = "--site-margins --wide-levels: widest level " + std::to_string(widest) + " (at most 32767) x (R + 1) " + std::to_string(R + 1) + " exceeds 16777216 cells";
+                return -1;
+            }
+        } else if (widest * ((int64_t)R + 1) > 16384) {
             err = "--site-margins: widest level " + std::to_string(widest) + " x (R + 1) " + std::to_string(R + 1) + " exceeds 16384 cells";
             return -1;
         }

@@ -79,6 +79,7 @@ static int b_sketch_hap(void *c, const char *s, int64_t len, int k, int w, uint6
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_sketch_haplotype(x, s, len, k, w, h, p, n) : DG_ERR_NO_DEVICE;
 }
+static bool g_wide_levels = false;                          // --wide-levels
 static int apply_dp_options(dg_ctx *x) {
     // DG_DP_OPTIONS="key=value,key=value": dg_dp_set_option tuning knobs for profiling and for the segmented-lattice tests (none needed
     // in normal use).  Honoured with a notice on stderr; the fault-injection keys (test_*) are refused here -- they exist for the
@@ -112,6 +113,7 @@ static int b_dp_load(void *c, const dg_dp_graph *g) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     if (!x) return DG_ERR_NO_DEVICE;
     if (int rc = apply_dp_options(x)) return rc;
+    if (g_wide_levels && dg_dp_set_option(x, "partner_wide", 1) != DG_OK) return DG_ERR_ARG;   // --wide-levels (the --site-margins run goes through here)
     return dg_dp_load_graph(x, g);
 }
 static int b_dp_budgets(void *c, const int32_t *budgets, int32_t n, dg_dp_result *r) {
@@ -232,6 +234,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --budgets all|a,b,c   (MI355X build, -p2) also answer these recombination limits below -R from the same DP pass: <haplotype.fasta>.R<r>\n");
     fprintf(fp, "    --budget-table FILE   (MI355X build) with --budgets: one line r, DP value, r1, r2, len1, len2 per listed limit\n");
     fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
+    fprintf(fp, "    --wide-levels         (MI355X build) with --site-margins: lift its limit of 16384 cells (widest level x (R + 1)) by keeping the level state in device memory (then: widest level <= 32767, <= 16777216 cells)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
@@ -272,6 +275,7 @@ int main(int argc, char **argv) {
                 p.opt.site_margins = v ? v : "";
                 continue;
             }
+            if (!strcmp(argv[i], "--wide-levels")) { p.opt.wide_levels = true; continue; }
             if (!strncmp(argv[i], "--objective-table", 17) && (argv[i][17] == 0 || argv[i][17] == '=')) {
                 have_objective_table = true;                           // (a missing value is an empty file name: refused below)
                 const char *v = val("--objective-table");
@@ -340,11 +344,13 @@ int main(int argc, char **argv) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --site-margins describes the two haplotypes of the diploid route (-p2)\n"); return 1; }
         if (p.opt.site_margins.empty()) { fprintf(stderr, "[E::main] --site-margins needs a file name\n"); return 1; }
     }
+    if (p.opt.wide_levels && !have_site_margins) { fprintf(stderr, "[E::main] --wide-levels goes with --site-margins: it lifts the cell limit of that option alone\n"); return 1; }
     // --objective-table FILE: the same
     if (have_objective_table) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
         if (p.opt.objective_table.empty()) { fprintf(stderr, "[E::main] --objective-table needs a file name\n"); return 1; }
     }
+    g_wide_levels = p.opt.wide_levels;
     if (!sharded) g_lazy.start(device, p.opt.k, p.opt.w);
     p.be.ctx = &g_lazy;
     p.be.sketch_reads = b_sketch_reads;

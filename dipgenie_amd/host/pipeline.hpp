@@ -88,6 +88,7 @@ struct Options {
     std::string budget_table;    // (ours) --budget-table: TSV of the listed budgets
     bool host_anchors = false;   // (ours, tests) keep the anchor join / filter / sort on the host even if the backend offers it
     std::string site_margins;    // (ours) --site-margins: TSV of the call margins of both haplotypes of the answer at -R, per level (diploid)
+    bool wide_levels = false;    // (ours) --wide-levels, with --site-margins: the backend keeps the level state of dp_call_margins in device memory where LDS cannot hold it
     std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
 };
 

@@ -147,7 +147,13 @@ typedef struct dg_dp_partner {
  * (the message names the query), a given path with a vertex outside its level or a hop without an edge (the message names the first
  * such (query, level), in that order of significance; the level of a missing edge is its destination's).  DG_ERR_UNSUPPORTED: widest
  * level x (budget + 1) > 16384 cells for some query (the message names both numbers).  A failed call writes neither partners nor out.
- * n = 0 is DG_OK.  Synchronises. */
+ * n = 0 is DG_OK.  Synchronises.
+ * Option partner_wide (default 0: all of the above) opens a second route that keeps the two level states in device memory, one
+ * 1,024-lane workgroup per query: with 1 a call whose widest level x (bmax + 1) exceeds 16384 takes it as a whole, with 2 every call.
+ * Same recurrence, ties and outputs.  Its limits: widest level <= 32767 (the back-pointer holds the source position in 15 bits) and
+ * widest level x (budget + 1) <= 2^24 cells per query, DG_ERR_UNSUPPORTED beyond (the message names the query and both numbers).  On
+ * that route a query counts 8 * widest level * (bmax + 1) bytes of state on top of the bytes above; the state buffer is released
+ * when the call returns.  dg_dp_get_partner_route tells which route the last call took. */
 int dg_dp_best_partners(dg_ctx *, const int32_t *given, int64_t n, const int32_t *budgets, int32_t *partners, dg_dp_partner *out);
 /* Partner marginals: for a given path and a budget b, what the best partner through every vertex is worth, and per level the best
  * vertex, the best of the others and so the margin between them.  Notation of dg_dp_best_partners: d_l(u, v) is the score of the
@@ -175,7 +181,11 @@ typedef struct dg_dp_level_margin {
  * query), a given path with a vertex outside its level or a hop without an edge (the message names the first such (query, level),
  * in that order of significance; the level of a missing edge is its destination's).  DG_ERR_UNSUPPORTED: widest level x (budget + 1)
  * > 16384 cells for some query (the message names both numbers).  A failed call writes neither levels nor vertex_values.  n = 0 is
- * DG_OK.  Synchronises. */
+ * DG_OK.  Synchronises.
+ * Option partner_wide chooses the route as for dg_dp_best_partners, with the same limits.  On the device-memory route the forward
+ * kernel reads the previous level back from the forward values it stores anyway, and the backward kernel keeps its two level states
+ * in device memory: a query counts 8 * widest level * (bmax + 1) bytes of state on top of the bytes above, released when the call
+ * returns. */
 int dg_dp_partner_marginals(dg_ctx *, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
 /* The answer of the last dg_dp_run / dg_dp_run_budgets at `budget` as the pair of paths it walked: paths (host) = [2][n_levels]
  * vertex ids, entry 0 the source, the last one the sink; row 0 is the path of dg_dp_result's p1 lists, row 1 that of p2 -- the rows
@@ -205,8 +215,17 @@ typedef struct dg_dp_call_margin {
  * An unreachable budget is an answer: every record -1, NEG_INF, -1, NEG_INF, the paths all -1, DG_OK.  Errors as for
  * dg_dp_get_answer_paths (DG_ERR_ARG: null levels), and DG_ERR_UNSUPPORTED: widest level x (budget + 1) > 16384 cells (the message
  * names both numbers; on `budget` itself, not on what the other haplotype leaves of it, so that it is known before a run).  A failed
- * call writes nothing.  Leaves the run's answers as they were.  Synchronises. */
+ * call writes nothing.  Leaves the run's answers as they were.  Synchronises.
+ * With option partner_wide >= 1 the limits on `budget` are those of the device-memory route instead (widest level <= 32767, widest
+ * level x (budget + 1) <= 2^24; the message names the budget and both numbers), and the two queries take that route together if widest
+ * level x (the larger of their two budgets + 1) exceeds 16384 (with 2: always); a query then counts 8 * widest level * (that budget + 1)
+ * bytes of backward state more, released when the call returns. */
 int dg_dp_call_margins(dg_ctx *, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
+/* Which route the last dg_dp_best_partners, dg_dp_partner_marginals or dg_dp_call_margins on this context took: *route = 0: none of them
+ * has got as far as a launch since dg_create, 1: level state in LDS, 2: level state in device memory (option partner_wide); *cells =
+ * that call's widest level x (largest budget + 1).  A call that fails before the route is chosen, or has nothing to launch (n = 0, an
+ * unreachable budget of dg_dp_call_margins), leaves both as they were.  DG_ERR_ARG: a null argument. */
+int dg_dp_get_partner_route(dg_ctx *, int32_t *route, int64_t *cells);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
@@ -257,6 +276,7 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *                         a level on which n is no candidate (not instantiated, above the run's all-planes chunk, no cooperative form) runs the all-planes chunk as with adaptive_rc 0
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, and of what a slab of dg_dp_partner_marginals holds (default 4 GB, n <= 0 restores it; a slab holds at least one query)
+ *   partner_wide 0|1|2    level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 (default) never -- beyond 16384 cells the call is refused; 1 for a call beyond 16384 cells; 2 for every call (tests, A/B timing)
  *   objective_lds_bytes n largest size of a pair's four colour bitmaps that dg_dp_objective_paths / dg_dp_answer_objectives keep in LDS; larger ones live in device memory (default 131072, n <= 0 restores it; clamped to the device's LDS per workgroup)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning

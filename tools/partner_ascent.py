@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Coordinate ascent on a dumped graph with dp_best_partners: fix one path, take its best partner, swap, repeat.
 
-usage: partner_ascent.py GRAPH.dpg [--starts N] [--seed S] [--p-w0 P]
+usage: partner_ascent.py GRAPH.dpg [--starts N] [--seed S] [--p-w0 P] [--wide {0,1,2}]
 
 Runs dp_run_budgets(all budgets 0..R), samples N start paths p with r(p) <= R (a weight-0 out-edge with probability P wherever one
 exists, so that the starts fit the budget), then repeats q <- partner(p, R - r(p)), p <- partner(q, R - r(q)), ... for all starts at
 once, one dp_best_partners call per round, until no start's value rises any more.  Every round is exact, so the value of a start
 never falls, and a pair with r1 + r2 recombinations never beats that plane of the sweep: either is exit status 1.  Prints, per
-start, the rounds, the final value, r1, r2 and the gap to plane R."""
+start, the rounds, the final value, r1, r2 and the gap to plane R.  --wide w sets option partner_wide: 0 (default) the level state
+stays in LDS and a graph beyond 16,384 cells (widest level x (budget + 1)) is refused, 1 such a call keeps it in device memory, 2
+every call does (A/B timing)."""
 import argparse
 import os
 import sys
@@ -28,10 +30,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--p-w0", type=float, default=1.0)
     ap.add_argument("--max-rounds", type=int, default=64)
+    ap.add_argument("--wide", type=int, choices=(0, 1, 2), default=0, help="option partner_wide: level state in device memory never / beyond the LDS limit / always")
     a = ap.parse_args()
     g = capi.DpGraphArrays.load(a.graph)
     R = g.R
     ctx = capi.Context(0)
+    ctx.dp_set_option("partner_wide", a.wide)
     ctx.dp_load_graph(g)
     ctx.dp_run_budgets(range(R + 1))
     planes = ctx.dp_budget_values().astype(np.int64)

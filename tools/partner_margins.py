@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Per-level margins of the best partner on a dumped graph, with dp_partner_marginals.
 
-usage: partner_margins.py GRAPH.dpg [--starts N] [--seed S] [--p-w0 P]
+usage: partner_margins.py GRAPH.dpg [--starts N] [--seed S] [--p-w0 P] [--wide {0,1,2}]
 
 Samples N start paths p as partner_ascent.py does (a weight-0 out-edge with probability P wherever one exists, so that the starts
 fit the budget), takes each start's best partner within R - r(p) with dp_best_partners, and asks dp_partner_marginals for the same
 queries in one call: per level the vertex the best partner passes through, what the best partner through another vertex is worth,
 and so the margin of the call at that site.  Prints, per start, the value, the number of levels with margin 0 (the data cannot tell
 two vertices apart there), the smallest positive margin, the number of levels without any alternative, and the wall time of the one
-dp_partner_marginals call.  Exit status 1 if a level's best_value differs from the partner's value, or if the marginal of a vertex
+dp_partner_marginals call.  --wide w sets option partner_wide: 0 (default) the level state stays in LDS and a graph beyond 16,384 cells (widest level x
+(budget + 1)) is refused, 1 such a call keeps it in device memory, 2 every call does (A/B timing); the route taken is printed.  Exit status 1 if a level's best_value differs from the partner's value, or if the marginal of a vertex
 on the partner path differs from it."""
 import argparse
 import os
@@ -29,10 +30,12 @@ def main():
     ap.add_argument("--starts", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--p-w0", type=float, default=1.0)
+    ap.add_argument("--wide", type=int, choices=(0, 1, 2), default=0, help="option partner_wide: level state in device memory never / beyond the LDS limit / always")
     a = ap.parse_args()
     g = capi.DpGraphArrays.load(a.graph)
     R = g.R
     ctx = capi.Context(0)
+    ctx.dp_set_option("partner_wide", a.wide)
     ctx.dp_load_graph(g)
     print(f"{a.graph}: {g.n_levels} levels, {g.n_vertices} vertices, widest level {int(np.diff(g.level_off).max())}, R = {R}")
     rng = np.random.default_rng(a.seed)
@@ -49,6 +52,8 @@ def main():
     t0 = time.perf_counter()
     levels, values = ctx.dp_partner_marginals(cur, budgets, want_vertices=True)
     wall = time.perf_counter() - t0
+    route, cells = ctx.dp_partner_route()
+    print(f"partner_wide {a.wide}: {cells} cells per level state, in {'device memory' if route == 2 else 'LDS'}")
     ctx.close()
     n_bad = 0
     print("start\tbudget\tvalue\tmargin0_levels\tmin_positive_margin\tlevels_without_alternative")
