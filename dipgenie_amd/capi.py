@@ -81,7 +81,7 @@ SYMBOLS = [
     "dg_shard_create", "dg_shard_destroy", "dg_shard_n_ranks", "dg_shard_ctx", "dg_shard_score_reads",
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
-    "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route",
+    "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -112,6 +112,8 @@ lib.dg_dp_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
 lib.dg_dp_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
 lib.dg_dp_get_launch_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
 lib.dg_dp_list_sweep_variants.argtypes = [C.c_char_p, C.c_int]
+lib.dg_dp_get_pair_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+lib.dg_dp_list_pair_variants.argtypes = [C.c_char_p, C.c_int]
 lib.dg_dp_get_table_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_sketch_reads.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
@@ -472,6 +474,19 @@ class Context:
         buf = C.create_string_buffer(8192)
         _check(lib.dg_dp_get_launch_profile(self.h, buf, 8192), "dg_dp_get_launch_profile")
         return {k: int(v) for k, v in (item.rsplit(":", 1) for item in buf.value.decode().split())}
+
+    def dp_pair_profile(self):
+        """{pair kernel variant: launches} of the last dp_run: launches that swept two adjacent levels at once (not in dp_launch_profile)"""
+        buf = C.create_string_buffer(1024)
+        _check(lib.dg_dp_get_pair_profile(self.h, buf, 1024), "dg_dp_get_pair_profile")
+        return {k: int(v) for k, v in (item.rsplit(":", 1) for item in buf.value.decode().split())}
+
+    @staticmethod
+    def dp_pair_variants():
+        """the names of every pair kernel the library can launch, in dp_pair_profile's order (needs no device)"""
+        buf = C.create_string_buffer(1024)
+        _check(lib.dg_dp_list_pair_variants(buf, 1024), "dg_dp_list_pair_variants")
+        return buf.value.decode().split()
 
     @staticmethod
     def dp_sweep_variants():

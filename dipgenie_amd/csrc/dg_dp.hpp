@@ -1,5 +1,5 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
-// (dg_dp_tables.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip,
+// (dg_dp_tables.hip, dg_dp_pairs.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip,
 // dg_dp_objective.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
@@ -95,6 +95,7 @@ struct SweepArgs {                                      // generic sweep kernel
     unsigned long long *digest;
     int RP;
     int *progress;                                      // PfCtl::level: the level whose launch is running (dg_dp_sweep.hip: L2 prefetcher)
+    int flip;                                           // 1: an odd number of level pairs ran before this level, so level l lives in slot (l & 1) ^ 1 (SweepLaunch::flip)
 };
 
 struct FastArgs {                                       // fast sweep kernel
@@ -110,6 +111,7 @@ struct FastArgs {                                       // fast sweep kernel
     uint32_t buf_bytes;                                 // size of one padded state buffer (what a buffer resource covers)
     uint32_t slot_bytes;                                // distance between two state slots
     int *progress;                                      // PfCtl::level: the level whose launch is running (L2 prefetcher)
+    int flip;                                           // as SweepArgs::flip
 #ifdef DG_SWEEP_PROBE
     unsigned long long *probe;                          // measurement build: 8 words per level
 #endif
@@ -131,6 +133,26 @@ struct SweepVariant {
     static int count();
     static SweepVariant at(int index);
 };
+// ---- level pairs (dg_dp_pairs.hip: tables; dg_dp_sweep.hip: dp_sweep_pair_kernel) ----
+// Two adjacent low-fan-in levels (l - 1, l) composed into ONE transition from level l - 2: a cell of level l reduces over the composed
+// in-edges (eu2, eu1) x (ev2, ev1); the state of level l - 1 is never written, its back-pointers only where a cell of level l wins through it.
+constexpr int PAIR_MAX_INDEG = 8;                       // composed in-degree of a vertex (sum over its in-edges of their sources' in-degrees)
+constexpr int PAIR_MAX_WIDTH = 255;                     // widths of both levels of a pair (8-bit positions in the records)
+constexpr int PAIR_MAX_T = 2047;                        // in-edges into either level (11-bit score-delta rows)
+constexpr int PAIR_RCS[] = {1, 2, 4};                   // chunk sizes dp_sweep_pair_kernel is instantiated for
+constexpr int N_PAIR_RCS = (int)(sizeof PAIR_RCS / sizeof PAIR_RCS[0]);
+struct PairDesc {                                       // pair of destination levels (l - 1, l); on the host and on the device (L2 prefetcher)
+    int32_t l, nblocks;                                 // the later level; 64-slot blocks of composed column in-edges
+    int32_t k0, k1, k2;                                 // widths of levels l - 2, l - 1, l
+    int32_t dmax;                                       // largest composed in-degree among the vertices of level l
+    int64_t row_first;                                  // first composed row record (PAIR_MAX_INDEG per vertex of level l)
+    int64_t slot_first;                                 // first composed slot record
+};
+struct PairHist {                                       // pair launches per chunk size, by index into PAIR_RCS
+    int64_t n[N_PAIR_RCS] = {};
+    void add(const PairHist &o, int64_t sign = 1) { for (int q = 0; q < N_PAIR_RCS; ++q) n[q] += sign * o.n[q]; }
+};
+
 struct SweepHist {                                      // launches per variant, by SweepVariant::index()
     std::vector<int64_t> n = std::vector<int64_t>((size_t)SweepVariant::count(), 0);
     void add(const SweepHist &o, int64_t sign = 1) { for (size_t q = 0; q < n.size(); ++q) n[q] += sign * o.n[q]; }
@@ -165,6 +187,8 @@ struct DpOptions {
     int64_t score_slab_bytes = (int64_t)256 << 20;      // score_slab_bytes: bound of the path staging buffer of dg_dp_score_paths (a slab holds at least one pair)
     int64_t partner_slab_bytes = (int64_t)4 << 30;      // partner_slab_bytes: bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, of the forward values, edge scores, marginals and records of one slab of dg_dp_partner_marginals (a slab holds at least one query)
     int64_t partner_wide = 0;                           // partner_wide: the level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 never (LDS only), 1 for a call beyond the LDS limit, 2 always
+    int64_t pair_levels = 1;                            // pair_levels: adjacent low-fan-in levels run as one composed launch (dg_dp_pairs.hip); next load
+    int64_t pair_min = 4096;                            // pair_min: the composed tables are built and used only for a graph with at least this many pairs; next load
     int64_t objective_lds_bytes = 131072;              // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
 };
 
@@ -193,8 +217,8 @@ struct DpState {
     std::vector<int> seg_begin;
     std::vector<int64_t> ckpt_off;                     // element offset of checkpoint s (state of level seg_begin[s]-1)
     bool graph_failed = false;                          // capture or instantiation failed once: plain launches from then on
-    typedef std::tuple<int, int, const void *, int> GraphKey;     // (first level, end level, biased lattice pointer, look-ahead launches left to the prefetcher | planes swept << 1)
-    struct Batch { hipGraphExec_t exec = nullptr; SweepHist hist; };
+    typedef std::tuple<int, int, const void *, int> GraphKey;     // (first level, end level, biased lattice pointer, look-ahead launches left to the prefetcher | state-slot flip on entry << 1 | planes swept << 2)
+    struct Batch { hipGraphExec_t exec = nullptr; SweepHist hist; PairHist pair_hist; int64_t n_launch = 0; int flips = 0; };   // flips: parity of its pair launches
     std::map<GraphKey, Batch> graphs;                             // -> replayable batch and its launches by kernel variant
     bool all_fast = false;
     size_t state_alloc_bytes = 0;
@@ -213,6 +237,11 @@ struct DpState {
     std::vector<int32_t> level_dmax;                    // largest in-degree among the level's vertices
     int64_t n_grp = 0, n_dead = 0, n_heavy_rows = 0, n_slot_records = 0, n_rowx_words = 0, n_dtrans = 0, n_edges = 0;   // logical table sizes (dg_dp_get_table_digest)
     DevBuf d_descs, d_in_off, d_in_edge, d_in_dst, d_hom_off, d_het_off, d_hom_col, d_het_col, d_eflag, d_eself;
+    // level pairs: pair_at[l] = index of the pair whose later level is l, -2 for the earlier level of a pair, -1 otherwise (empty: no pairs)
+    std::vector<PairDesc> pairs;
+    std::vector<int32_t> pair_at;
+    DevBuf d_pairs, d_pair_at, d_prow, d_pslots;
+    PairHist pair_hist;                                 // pair launches of the last run (dg_dp_get_pair_profile)
     DevBuf d_delta, d_bp, d_ring, d_digest, d_dblk_first, d_dtrans, d_grp, d_dead, d_heavy, d_rowrec, d_rowx, d_slots, d_ckpt, d_pfctl;
 #ifdef DG_SWEEP_PROBE
     DevBuf d_probe;
@@ -293,6 +322,7 @@ double wall_s();
 int dp_load(dg_ctx *c, const dg_dp_graph *g);
 int dp_build_tables_device(dg_ctx *c, const dg_dp_graph *g, DpState &S, std::vector<int32_t> &dtrans, std::vector<int64_t> &dblk_first, int &max_k);
 int dp_table_digest(dg_ctx *c, uint64_t *out, int n);
+int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S);           // dg_dp_pairs.hip: chooses the level pairs and builds their tables (host)
 
 // ---- score deltas (dg_dp_delta.hip) ----
 void delta_launch_edge_flags(const DpState &S, hipStream_t s);
@@ -310,10 +340,15 @@ struct SweepLaunch {                     // per-run launch context
     bool digest = false;                 // this pass accumulates the level digests (the re-sweeps of a segmented run do not: pass 1 did)
     int rp_active = 0;                   // planes [0, rp_active) are swept by the fast kernels (= RP except while a segment is re-swept below its path's plane)
     SweepHist hist;                      // launches of this run by kernel variant
+    PairHist pair_hist;                  // its pair launches
+    bool pairs_ok = false;               // this pass may launch level pairs (dg_dp_run.hip decides)
+    int flip = 0;                        // parity of the pair launches so far: level l's state lives in slot (l & 1) ^ flip
 };
 void sweep_prepare(const DpState &S, SweepLaunch &X);
 void sweep_init_state(const DpState &S, hipStream_t s);                  // level 0: every r starts at 0 (:534-535)
 int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s);
+int sweep_launch_pair(const DpState &S, SweepLaunch &X, int l, hipStream_t s);   // levels l - 1 and l (S.pair_at[l] >= 0) in one launch
+std::string pair_variant_name(int q);                                      // of PAIR_RCS[q], as rocprof prints the kernel
 void sweep_warm_tables(const DpState &S, const SweepLaunch &X, int q0, int q1, hipStream_t s);
 int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool delta_resident, hipStream_t s);
 void sweep_prefetch_end(DpState &S, int le, hipStream_t s);

@@ -106,7 +106,7 @@ struct Run {
 
     Run(dg_ctx *c_, DpState &S_) : c(c_), S(S_), s(c_->stream) { sweep_prepare(S, X); }
     int n_win() const { return (int)S.dwin_t.size() - 1; }
-    int32_t *state_ptr(int level) const { return (int32_t *)(S.d_ring.as<char>() + (size_t)(level & 1) * S.state_alloc_bytes) + S.pad_front; }
+    int32_t *state_ptr(int level) const { return (int32_t *)(S.d_ring.as<char>() + (size_t)((level & 1) ^ X.flip) * S.state_alloc_bytes) + S.pad_front; }   // (the slot parity as the launches issued so far left it)
     size_t level_cells(int level) const {               // state size of a level (level 0: the source, k = 1)
         const int64_t k = level == 0 ? 1 : S.descs[level].k2;
         return (size_t)(k * k * S.RP);
@@ -123,7 +123,11 @@ struct Run {
                 if (q1 > q0) sweep_warm_tables(S, X, q0, q1, s);
             }
             if (l >= next_warm) next_warm = l + (int)std::max<int64_t>(S.opt.warm_ahead, 1);
-            if (int rc = sweep_launch_level(S, X, l, s)) return rc;
+            // a level pair (dg_dp_pairs.hip) runs as one launch where both of its levels lie inside this batch; else each level as ever
+            if (X.pairs_ok && l + 1 < l1 && S.pair_at[l + 1] >= 0) {
+                if (S.level_win[l + 1] >= 0 && S.level_win[l + 1] != S.cur_win) load_window(S.level_win[l + 1]);
+                if (int rc = sweep_launch_pair(S, X, ++l, s)) return rc;
+            } else if (int rc = sweep_launch_level(S, X, l, s)) return rc;
             ++n_launch;
             // profiling aid: rocprofv3 --pmc crashes when ~10^5 dispatches are queued without a drain
             if (S.opt.sync_every > 0 && n_launch % S.opt.sync_every == 0) DG_HIP(hipStreamSynchronize(s));
@@ -147,8 +151,8 @@ struct Run {
         const int64_t gb = S.opt.graph_batch >= 0 ? S.opt.graph_batch : 1000;
         // what issue_levels bakes into a captured batch besides the levels: whether the periodic look-ahead launches are left to the
         // prefetcher's far blocks -- part of the cache key (a second DP state on the device switches the prefetcher off)
-        const int pf_key = ((S.pf_active && S.opt.pf_far > 0) ? 1 : 0) | (X.rp_active << 1);
         for (int l0 = lb; l0 < le;) {
+            const int pf_key = ((S.pf_active && S.opt.pf_far > 0) ? 1 : 0) | (X.flip << 1) | (X.rp_active << 2);
             const bool use_graph = gb > 0 && n_win() == 1 && S.opt.sync_every == 0 && !S.graph_failed;
             const int l1 = use_graph ? (int)std::min<int64_t>((int64_t)l0 + gb, le) : le;
             // score deltas computed beside the sweep (delta_launch_overlapped): the stream waits for the pieces that hold a level below l1
@@ -163,8 +167,8 @@ struct Run {
                 slot = &S.graphs[key];
                 if (slot->exec) {
                     DG_HIP(hipGraphLaunch(slot->exec, s));
-                    X.hist.add(slot->hist);
-                    n_launch += l1 - l0; l0 = l1;
+                    X.hist.add(slot->hist); X.pair_hist.add(slot->pair_hist);
+                    n_launch += slot->n_launch; X.flip ^= slot->flips; l0 = l1;
                     continue;
                 }
                 if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) capturing = true;
@@ -172,6 +176,8 @@ struct Run {
             }
             const int64_t n_launch_before = n_launch;
             const SweepHist hist_before = X.hist;
+            const PairHist pair_hist_before = X.pair_hist;
+            const int flip_before = X.flip;
             if (int rc = issue_levels(l0, l1, lb, le)) {
                 if (capturing) {                                    // leave the stream usable: end the capture, drop the half-built graph
                     hipGraph_t cg = nullptr;
@@ -188,11 +194,14 @@ struct Run {
                 if (cg) (void)hipGraphDestroy(cg);
                 if (!ok) {                                          // nothing of this batch has run: issue it again without a graph
                     (void)hipGetLastError();
-                    slot->exec = nullptr; S.graph_failed = true; n_launch = n_launch_before; X.hist = hist_before;
+                    slot->exec = nullptr; S.graph_failed = true; n_launch = n_launch_before; X.hist = hist_before; X.pair_hist = pair_hist_before; X.flip = flip_before;
                     continue;
                 }
                 slot->hist = X.hist;
                 slot->hist.add(hist_before, -1);
+                slot->pair_hist = X.pair_hist;
+                slot->pair_hist.add(pair_hist_before, -1);
+                slot->n_launch = n_launch - n_launch_before; slot->flips = X.flip ^ flip_before;
                 DG_HIP(hipGraphLaunch(slot->exec, s));
             }
             l0 = l1;
@@ -262,6 +271,9 @@ struct Run {
         }
 #endif
         sweep_init_state(S, s);
+        // level pairs: the unsegmented pass over all planes, digests off, the per-level choice of the fast kernels left free
+        X.pairs_ok = !S.pairs.empty() && S.opt.pair_levels && n_seg == 1 && n_win() == 1 && !X.digest && S.opt.use_fast && S.opt.adaptive_rc && S.opt.test_force_rc == 0 &&
+                     X.small_state && X.rp_active == S.RP;
         if (n_seg == 1) {
             // whole lattice resident: one sweep with back-pointers, then the chain walk chunk by chunk, last first
             if (int rc = sweep_and_walk(0, S.d_bp.p ? 1 : n_chunks_all, true, true)) return rc;
@@ -357,6 +369,7 @@ static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result
     S.sink_host.clear();
     const int rc_run = run.forward_and_trace();
     S.launch_hist = run.X.hist;
+    S.pair_hist = run.X.pair_hist;
     if (rc_run) return rc_run;
     DG_HIP(hipMemcpyAsync(to.data(), S.d_ch_trace.p, sizeof(TraceOut) * to.size(), hipMemcpyDeviceToHost, s));
     DG_HIP(hipMemcpyAsync(edges.data(), S.d_ch_edges.p, 4 * edges.size(), hipMemcpyDeviceToHost, s));
@@ -486,6 +499,22 @@ extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
     memcpy(buf, out.c_str(), out.size() + 1);
     return DG_OK;
 }
+extern "C" int dg_dp_get_pair_profile(dg_ctx *c, char *buf, int cap) {
+    if (!c || !c->dp || !buf || cap < 2) { dgi::set_error("dg_dp_get_pair_profile: no state"); return DG_ERR_STATE; }
+    std::string out;
+    for (int q = 0; q < dgi::N_PAIR_RCS; ++q)
+        if (const int64_t n = c->dp->pair_hist.n[q]) out += (out.empty() ? "" : " ") + dgi::pair_variant_name(q) + ':' + std::to_string(n);
+    if ((int)out.size() + 1 > cap) { dgi::set_error("dg_dp_get_pair_profile: buffer too small (%zu needed)", out.size() + 1); return DG_ERR_ARG; }
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return DG_OK;
+}
+extern "C" int dg_dp_list_pair_variants(char *buf, int cap) {
+    std::string out;
+    for (int q = 0; q < dgi::N_PAIR_RCS; ++q) out += (out.empty() ? "" : " ") + dgi::pair_variant_name(q);
+    if (!buf || (int)out.size() + 1 > cap) { dgi::set_error("dg_dp_list_pair_variants: buffer too small (%zu needed)", out.size() + 1); return DG_ERR_ARG; }
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return DG_OK;
+}
 extern "C" int dg_dp_list_sweep_variants(char *buf, int cap) {
     std::string out;
     for (int q = 0; q < dgi::SweepVariant::count(); ++q)
@@ -511,6 +540,7 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     // read by dg_dp_load_graph: in effect at the next load
     {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},
     {"host_threads", &DpO::host_threads, 1, false}, {"host_tables", &DpO::host_tables, 0, false}, {"delta_cap_entries", &DpO::delta_cap_entries, 0, true},
+    {"pair_levels", &DpO::pair_levels, 0, false}, {"pair_min", &DpO::pair_min, 1, false},
     {"lattice_chunk_cells", &DpO::chunk_units_cfg, 1, false},   // 16-bit back-pointer units; below 1 is an error, else rounded up to even; empties the chunk pool at once
 };
 static int dp_option(dg_ctx *c, const char *what, const char *key, const int64_t *set, int64_t *get) {   // set or get, the other is null

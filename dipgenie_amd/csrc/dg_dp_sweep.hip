@@ -81,8 +81,8 @@ template <int RC, bool DIGEST>
 __device__ __forceinline__ void sweep_level_pairs(const SweepArgs &A, int lvl, int wave_id, int n_waves) {
     const LevelDesc d = A.descs[lvl];
     const int RP = A.RP;
-    const int32_t *__restrict__ cur = (const int32_t *)(A.ring + (size_t)DG_SLOT(lvl - 1) * A.slot_bytes + A.pad_bytes);
-    int32_t *__restrict__ nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(lvl) * A.slot_bytes + A.pad_bytes);
+    const int32_t *__restrict__ cur = (const int32_t *)(A.ring + (size_t)(DG_SLOT(lvl - 1) ^ A.flip) * A.slot_bytes + A.pad_bytes);
+    int32_t *__restrict__ nxt = (int32_t *)(A.ring + (size_t)(DG_SLOT(lvl) ^ A.flip) * A.slot_bytes + A.pad_bytes);
     const int lane = threadIdx.x & 63;
     const int nchunk = (RP + RC - 1) / RC;
     const int64_t ntask = (int64_t)d.k2 * d.ngroups * nchunk;
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(DG_PLAIN_WG) void dp_sweep_fast_kernel(const uint4 
     const int g = (int)blockIdx.x * DG_PLAIN_GW + (wv % DG_PLAIN_GW);    // always launched with DG_PLAIN_WG threads (reading blockDim would be a kernel-argument load)
     const int r0 = ((int)blockIdx.y * DG_PLAIN_CH + wv / DG_PLAIN_GW) * RC;
     if (g >= nblocks || r0 >= (rp_k & 0x1FFF)) return;                  // wave-uniform; no block barrier below
-    int32_t *nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(lvl) * A.slot_bytes + A.pad_bytes);
+    int32_t *nxt = (int32_t *)(A.ring + (size_t)(DG_SLOT(lvl) ^ A.flip) * A.slot_bytes + A.pad_bytes);
     sweep_task<RC, DIGEST, GENERAL, 0>(H, A, d, state_rsrc(cur, buf_bytes), nxt, (int)blockIdx.z, g, r0, lvl);
 }
 
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(256) void dp_sweep_coop_kernel(const uint4 *rowrec_
                                                             FastArgs A, LevelDesc d, int lvl, const uint16_t *dm, int dT, const int32_t *__restrict__ heavy_rows) {
     const LevelHead H{rowrec_l, slots_l, rowx_l, cur, dm, rowx_stride, rp_k & 0x1FFF, rp_k >> 13, A.pad_bytes, dT, A.buf_bytes};
     publish_level(A.progress, lvl);
-    int32_t *nxt = (int32_t *)(A.ring + (size_t)DG_SLOT(lvl) * A.slot_bytes + A.pad_bytes);
+    int32_t *nxt = (int32_t *)(A.ring + (size_t)(DG_SLOT(lvl) ^ A.flip) * A.slot_bytes + A.pad_bytes);
     const int r0 = (int)blockIdx.y * RC;                                // chunks of a row are neighbours in dispatch order: they share its delta row
     const int zc = 4 * n_heavy;
     if ((int)blockIdx.z < zc) {
@@ -493,6 +493,129 @@ __global__ __launch_bounds__(256) void dp_sweep_coop_kernel(const uint4 *rowrec_
     const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
     sweep_task<RC, DIGEST, GENERAL, 1>(H, A, d, state_rsrc(cur, A.buf_bytes), nxt, (int)blockIdx.z - zc, g, r0, lvl);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Level pair: destination levels (l - 1, l) as ONE composed transition from level l - 2 (tables: dg_dp_pairs.hip).  The task shape
+// is the plain fast kernel's -- one wave per (destination row, slot block, chunk of RC planes), the leading scalars preloaded,
+// two load rounds: {composed row records, composed slot records}, then {both score deltas, RC values} per composed row in-edge.
+// Each lane keeps per plane (value, ord, mid): ord = (255 - ru2) << 24 | (255 - rv2) << 16 | (255 - ru1) << 8 | (255 - rv1) makes the
+// plain lexicographic max the reference's order over both levels; mid = middle row << 16 | middle column << 8 | w2u + w2v rides
+// along with the winner, so the head lane addresses the middle cell without another load.  The state of level l - 1 is never
+// written.  The head stores value and back-pointer of its cell of level l, and the back-pointer ru1 << 8 | rv1 of the middle cell
+// it won through: cells that share a middle cell store the same word, middle cells nobody wins through stay unwritten (the walk
+// reaches a middle cell only from a winner).
+// ---------------------------------------------------------------------------------------------
+template <int RC>
+__device__ __forceinline__ void relax_pair(const int (&vals)[RC], int dl, uint32_t ord, uint32_t mid, int r0, int w, int RP,
+                                           int (&bval)[RC], uint32_t (&bord)[RC], uint32_t (&bmid)[RC]) {
+#pragma unroll
+    for (int q = 0; q < RC; ++q) {
+        const int cand = vals[q] + dl;
+        const bool ok = (r0 + q < RP) & (r0 + q - w >= 0) & (vals[q] != NEG_INF);
+        const bool take = ok & ((cand > bval[q]) | ((cand == bval[q]) & (ord > bord[q])));
+        bval[q] = take ? cand : bval[q];
+        bord[q] = take ? ord : bord[q];
+        bmid[q] = take ? mid : bmid[q];
+    }
+}
+__device__ __forceinline__ void merge_best_pair(int ov, uint32_t oo, uint32_t om, bool same, int &bv, uint32_t &bo, uint32_t &bm) {
+    const bool take = same & ((ov > bv) | ((ov == bv) & (oo > bo)));
+    bv = take ? ov : bv;
+    bo = take ? oo : bo;
+    bm = take ? om : bm;
+}
+
+template <int RC>
+__global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2,
+                                                            int nblocks, int rp_k, int pad_bytes, int dT1, int dT2, uint32_t buf_bytes,   // 16 dwords: preloaded
+                                                            int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl) {
+    publish_level(progress, lvl);
+    const int lane = threadIdx.x & 63;
+    const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), r0 = (int)blockIdx.y * RC, i2 = (int)blockIdx.z;
+    const int RP = rp_k & 0x1FFF, k0 = rp_k >> 13;
+    if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
+    // first load round: addresses from kernel arguments and the block index alone
+    const uint2 rec = prow_l[i2 * PAIR_MAX_INDEG + (lane & (PAIR_MAX_INDEG - 1))];   // composed row in-edge t in lanes t, t + 8, ...
+    const uint4 sl = pslots_l[g * 64 + lane];
+    const __amdgpu_buffer_rsrc_t cur_rsrc = state_rsrc(cur, buf_bytes);
+    const int du = __builtin_amdgcn_readfirstlane((int)(rec.x >> 25)) & 0xF;
+    const int steps = __builtin_amdgcn_readfirstlane((int)(sl.z >> 16)) & 0xF;
+    const bool act = sl.x != 0xFFFFFFFFu;
+    const int j = (int)(sl.x & 0x7FFFu), wv = (int)((sl.x >> 15) & 1u) + (int)((sl.x >> 24) & 1u);
+    const uint32_t lanemid = (((sl.x >> 16) & 0xFFu) << 8) | ((sl.x >> 24) & 1u);
+    const int j2 = act ? (int)((sl.z >> 20) & 0xFFu) : -1 - lane;
+    const int c2 = dT2 ? (int)(sl.y & 0xFFFFu) : 0, c1 = dT1 ? (int)(sl.y >> 16) : 0;
+    const uint32_t ordc = ((uint32_t)(BP_MAX_RANK - (int)(sl.z & 0xFFu)) << 16) | (uint32_t)(BP_MAX_RANK - (int)((sl.z >> 8) & 0xFFu));
+    int bval[RC];
+    uint32_t bord[RC], bmid[RC];
+#pragma unroll
+    for (int q = 0; q < RC; ++q) { bval[q] = NEG_INF; bord[q] = 0; bmid[q] = 0; }
+    const int rowbytes = k0 * 4;
+    // Source rows are r = r2 - w, w <= 4: rows -1 .. -4 land in the front padding (4 * max_k cells when pairs exist), a ragged last
+    // chunk in the tail padding; the select discards both, so every load is issued unconditionally.
+    constexpr int U = RC >= 4 ? 4 : 8;
+    for (int t = 0; t < du; t += U) {
+        if (act) {
+            int vals[U][RC], dl[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (t + u < du) {                                           // wave-uniform
+                    const uint32_t px = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, t + u), py = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, t + u);
+                    const int iu = (int)(px & 0x7FFFu), w = (int)((px >> 15) & 1u) + (int)((px >> 24) & 1u) + wv;
+                    const int off = ((iu * RP + (r0 - w)) * k0 + j) * 4 + pad_bytes;
+                    dl[u] = (int)dm2[(int)(py & 0x7FFu) * dT2 + c2] + (int)dm1[(int)((py >> 11) & 0x7FFu) * dT1 + c1];
+#pragma unroll
+                    for (int q = 0; q < RC; ++q) vals[u][q] = __builtin_amdgcn_raw_buffer_load_b32(cur_rsrc, off + q * rowbytes, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (t + u < du) {
+                    const uint32_t px = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, t + u), py = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, t + u);
+                    const int w = (int)((px >> 15) & 1u) + (int)((px >> 24) & 1u) + wv;
+                    const uint32_t ord = ((uint32_t)(BP_MAX_RANK - (int)((py >> 22) & 7u)) << 24) | ((uint32_t)(BP_MAX_RANK - (int)((py >> 25) & 7u)) << 8) | ordc;
+                    const uint32_t mid = ((((px >> 16) & 0xFFu) << 16) | ((px >> 24) & 1u)) + lanemid;
+                    relax_pair<RC>(vals[u], dl[u], ord, mid, r0, w, RP, bval, bord, bmid);
+                }
+            }
+        }
+    }
+    // segmented max over lanes with equal destination column (lanes of a column are adjacent)
+    if (steps > 0) {
+        const int oj2 = lane_down1(j2);
+        const bool same = (lane + 1 < 64) & (oj2 == j2);
+#pragma unroll
+        for (int q = 0; q < RC; ++q) merge_best_pair(lane_down1(bval[q]), (uint32_t)lane_down1((int)bord[q]), (uint32_t)lane_down1((int)bmid[q]), same, bval[q], bord[q], bmid[q]);
+    }
+    for (int st = 1, sh = 2; st < steps; ++st, sh <<= 1) {
+        const int oj2 = __shfl_down(j2, sh);
+        const bool same = (lane + sh < 64) & (oj2 == j2);
+#pragma unroll
+        for (int q = 0; q < RC; ++q)
+            merge_best_pair(__shfl_down(bval[q], sh), (uint32_t)__shfl_down((int)bord[q], sh), (uint32_t)__shfl_down((int)bmid[q], sh), same, bval[q], bord[q], bmid[q]);
+    }
+    const int pj2 = lane_up1(j2);
+    const bool head = act & ((lane == 0) | (pj2 != j2));
+    if (head) {
+        const int k1 = kk & 0xFF, k2 = kk >> 8;
+#pragma unroll
+        for (int q = 0; q < RC; ++q) {
+            const int r2 = r0 + q;
+            if (r2 < RP) {
+                const int idx = (i2 * RP + r2) * k2 + j2;
+                nxt[idx] = bval[q];
+                if (bp2) {
+                    const uint32_t b2 = ~(bord[q] >> 16);                   // ru2 << 8 | rv2; an untouched best keeps ord 0 -> 0xFFFF = unreachable
+                    if (nt) store_bp_nt(&bp2[idx], b2); else bp2[idx] = (uint16_t)b2;
+                    if (bord[q]) {                                          // reachable: mark the middle cell it came through (row r2 - w2u - w2v >= 0)
+                        const uint32_t m = bmid[q];
+                        bp1[((int)(m >> 16) * RP + r2 - (int)(m & 0xFFu)) * k1 + (int)((m >> 8) & 0xFFu)] = (uint16_t)~bord[q];
+                    }
+                }
+            }
+        }
+    }
 }
 
 // Sweep look-ahead: streams the graph tables (row records, slot records, in-edges, score deltas) of a batch of upcoming
@@ -545,7 +668,8 @@ __global__ void dp_pf_probe_wait_kernel(PfCtl *c, int token) {
 }
 __global__ void dp_pf_probe_set_kernel(PfCtl *c, int token) { __hip_atomic_store(&c->probe, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__restrict__ descs, FastArgs F, PfCtl *ctl, int seq, int lb, int le, int ahead_near, int delta_resident, int far) {
+__global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__restrict__ descs, FastArgs F, PfCtl *ctl, int seq, int lb, int le, int ahead_near, int delta_resident, int far,
+                                                            const int32_t *__restrict__ pair_at, const PairDesc *__restrict__ pairs, const uint2 *__restrict__ prow, const uint4 *__restrict__ pslots) {
     __shared__ int dump[64];
     // a load whose data nobody wants: straight into an LDS dump word per lane (no destination register, nothing to wait for)
 #define DG_DROP_LOAD(PTR) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(PTR), (__attribute__((address_space(3))) void *)dump, 4, 0, 0)
@@ -583,6 +707,23 @@ __global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__r
         if (lp - lv > ahead) { __builtin_amdgcn_s_sleep(48); continue; }
         const LevelDesc &d = descs[lp];
         const int k2 = __builtin_amdgcn_readfirstlane(d.k2), T = __builtin_amdgcn_readfirstlane(d.T);
+        // "paired with" word of the level (null: this range launches no pairs): the earlier level of a pair has no launch of its own, the
+        // later one reads the composed tables and both levels' score deltas.  (A pair that straddles the edge of a hipGraph batch or of a
+        // lattice chunk runs as two single launches whose own tables are then not prefetched: one pair per 1,000 levels, hints only.)
+        const int pa = pair_at ? __builtin_amdgcn_readfirstlane(pair_at[lp]) : -1;
+        if (pa == -2) { ++lp; ++done; continue; }
+        if (pa >= 0) {
+            const PairDesc &p = pairs[pa];
+            lines((const char *)(prow + p.row_first), 8LL * PAIR_MAX_INDEG * k2);
+            lines((const char *)(pslots + p.slot_first), 1024LL * p.nblocks);
+            if (delta_resident) {
+                const LevelDesc &d1 = descs[lp - 1];
+                if (d.delta_off >= 0 && (long long)T * T <= (128 << 10)) lines((const char *)(F.delta + d.delta_off), 2LL * T * T);
+                if (d1.delta_off >= 0 && (long long)d1.T * d1.T <= (128 << 10)) lines((const char *)(F.delta + d1.delta_off), 2LL * d1.T * d1.T);
+            }
+            ++lp; ++done;
+            continue;
+        }
         lines((const char *)(F.rowrec + d.b0), 16LL * k2);
         lines((const char *)(F.slots + d.slot_first), 512LL * d.nblocks);
         lines((const char *)(F.in_edge + d.in_base), 4LL * T);
@@ -650,11 +791,11 @@ void sweep_prepare(const DpState &S, SweepLaunch &X) {
     A.grp_begin = S.d_grp.as<uint32_t>(); A.in_dst = S.d_in_dst.as<int32_t>(); A.dead_cols = S.d_dead.as<int32_t>();
     A.delta = A.delta_zero = S.d_delta.as<uint16_t>();
     A.ring = S.d_ring.as<char>(); A.slot_bytes = S.state_alloc_bytes; A.pad_bytes = 4 * (size_t)S.pad_front;
-    A.bp = nullptr; A.digest = S.d_digest.as<unsigned long long>(); A.RP = S.RP;
+    A.bp = nullptr; A.digest = S.d_digest.as<unsigned long long>(); A.RP = S.RP; A.flip = 0;
     FastArgs &F = X.F;
     F.rowrec = S.d_rowrec.as<uint4>(); F.slots = S.d_slots.as<uint2>(); F.in_edge = A.in_edge; F.rowx = S.d_rowx.as<uint32_t>(); F.dead_cols = A.dead_cols;
     F.delta = F.delta_zero = A.delta; F.bp = nullptr; F.digest = A.digest; F.RP = S.RP;
-    F.ring = S.d_ring.as<char>(); F.slot_bytes = (uint32_t)S.state_alloc_bytes;
+    F.ring = S.d_ring.as<char>(); F.slot_bytes = (uint32_t)S.state_alloc_bytes; F.flip = 0;
 #ifdef DG_SWEEP_PROBE
     F.probe = S.d_probe.as<unsigned long long>();
 #endif
@@ -711,11 +852,12 @@ int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
         const dim3 grid((unsigned)((d.nblocks + 3) / 4), (unsigned)nch, (unsigned)(d.k2 + (v.coop ? 4 * d.n_heavy : 0)));
         const dim3 pgrid((unsigned)((d.nblocks + DG_PLAIN_GW - 1) / DG_PLAIN_GW), (unsigned)((nch + DG_PLAIN_CH - 1) / DG_PLAIN_CH), grid.z);
         const int32_t *hv = S.d_heavy.as<int32_t>();
-        const FastArgs &F = X.F;
+        FastArgs F = X.F;
+        F.flip = X.flip;
         const uint4 *rowrec_l = F.rowrec + d.b0;
         const uint2 *slots_l = F.slots + d.slot_first;
         const uint32_t *rowx_l = F.rowx + d.rowx_off;
-        const int32_t *cur = (const int32_t *)(F.ring + (size_t)DG_SLOT(l - 1) * F.slot_bytes);
+        const int32_t *cur = (const int32_t *)(F.ring + (size_t)(DG_SLOT(l - 1) ^ X.flip) * F.slot_bytes);
         const int dT = d.delta_off >= 0 ? d.T : 0;
         const uint16_t *dm = dT ? F.delta + d.delta_off - (int64_t)d.in_base * dT : F.delta_zero;   // (F.delta is biased by the resident delta window)
         const int rp_k = S.RP | (d.k << 13);
@@ -728,12 +870,57 @@ int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
         const int nchunk = (S.RP + X.rc_sel - 1) / X.rc_sel;
         const int64_t ntask = (int64_t)d.k2 * d.ngroups * nchunk;
         const unsigned grid = (unsigned)std::min<int64_t>((ntask + 3) / 4, S.opt.max_blocks);
-        const SweepArgs &A = X.A;
+        SweepArgs A = X.A;
+        A.flip = X.flip;
         auto generic = [&](auto RC, auto DG, auto) { hipLaunchKernelGGL((dp_sweep_kernel<RC.value, DG.value>), dim3(grid), dim3(256), 0, s, A, l); };
         launched = launch_variant<RC_ALL>(X.rc_sel, X.digest, false, generic);
     }
     if (!launched) { set_error("sweep of level %d: no %s kernel is instantiated for chunks of %d recombination counts", l, v.coop ? "cooperative" : v.rc ? "fast" : "generic", v.rc ? v.rc : X.rc_sel); return DG_ERR_STATE; }
     X.hist.n[(size_t)v.index()]++;
+    return DG_OK;
+}
+
+// the pair's chunk size by choose_rc's cost model: the wave's chain is the largest composed in-degree
+static int choose_pair_rc(const DpState &S, const PairDesc &p) {
+    int best_q = 0;
+    double best = 1e300;
+    for (int q = 0; q < N_PAIR_RCS; ++q) {
+        const int rc = PAIR_RCS[q];
+        const double W = (double)p.k2 * p.nblocks * ((S.RP + rc - 1) / rc);
+        const double T = std::max(1.0, W / (double)S.opt.rc_cap) * ((double)S.opt.rc_t0_ns + (double)p.dmax * rc * (double)S.opt.rc_tg_ps * 1e-3) + W * (double)S.opt.rc_tw_ps * 1e-3;
+        if (T <= best) { best = T; best_q = q; }
+    }
+    return best_q;
+}
+std::string pair_variant_name(int q) { return "dp_sweep_pair_kernel<" + std::to_string(PAIR_RCS[q]) + ">"; }
+
+template <int Q = 0>
+static void launch_pair_rc(int q, dim3 grid, hipStream_t s, const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2, int nblocks, int rp_k,
+                           int pad_bytes, int dT1, int dT2, uint32_t buf_bytes, int32_t *nxt, uint16_t *bp1, uint16_t *bp2, int kk, int nt, int *progress, int lvl) {
+    if constexpr (Q < N_PAIR_RCS) {
+        if (q == Q) hipLaunchKernelGGL((dp_sweep_pair_kernel<PAIR_RCS[Q]>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl);
+        else launch_pair_rc<Q + 1>(q, grid, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl);
+    }
+}
+
+// Levels l - 1 and l in one launch.  Level l - 2 is read from its slot; level l goes into the slot level l - 1 would have taken (the
+// two-slot ring cannot take it where level l - 2 lies), which flips the slot parity of every level from here on (SweepLaunch::flip).
+int sweep_launch_pair(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
+    const PairDesc &p = S.pairs[(size_t)S.pair_at[l]];
+    const LevelDesc &d2 = S.descs[l], &d1 = S.descs[l - 1];
+    const FastArgs &F = X.F;
+    const int q = choose_pair_rc(S, p), rc = PAIR_RCS[q];
+    const int nch = (S.RP + rc - 1) / rc;
+    const dim3 grid((unsigned)((p.nblocks + 3) / 4), (unsigned)nch, (unsigned)p.k2);
+    const int32_t *cur = (const int32_t *)(F.ring + (size_t)(DG_SLOT(l - 2) ^ X.flip) * F.slot_bytes);
+    int32_t *nxt = (int32_t *)(F.ring + (size_t)(DG_SLOT(l - 1) ^ X.flip) * F.slot_bytes + F.pad_bytes);
+    const int dT1 = d1.delta_off >= 0 ? d1.T : 0, dT2 = d2.delta_off >= 0 ? d2.T : 0;
+    const uint16_t *dm1 = dT1 ? F.delta + d1.delta_off : F.delta_zero, *dm2 = dT2 ? F.delta + d2.delta_off : F.delta_zero;
+    const int nt = (int64_t)d2.k2 * d2.k2 * S.RP >= S.opt.bp_nt_min_cells ? 1 : 0;
+    launch_pair_rc(q, grid, s, S.d_prow.as<uint2>() + p.row_first, S.d_pslots.as<uint4>() + p.slot_first, cur, dm1, dm2, p.nblocks, S.RP | (p.k0 << 13), F.pad_bytes, dT1, dT2,
+                   F.buf_bytes, nxt, F.bp ? F.bp + d1.bp_off : nullptr, F.bp ? F.bp + d2.bp_off : nullptr, p.k1 | (p.k2 << 8), nt, F.progress, l);
+    X.flip ^= 1;
+    X.pair_hist.n[q]++;
     return DG_OK;
 }
 
@@ -799,7 +986,8 @@ int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool 
     DG_HIP(hipStreamWaitEvent(S.pf_stream, S.pf_ev, 0));
     const int far = (int)S.opt.pf_far;
     hipLaunchKernelGGL(dp_l2_prefetch_kernel, dim3(PF_WORKGROUPS + (far > 0 ? PF_FAR_WORKGROUPS : 0)), dim3(64), 0, S.pf_stream, S.d_descs.as<LevelDesc>(), X.F,
-                       S.d_pfctl.as<PfCtl>(), seq, lb, le, (int)S.opt.l2_prefetch, delta_resident ? 1 : 0, far);
+                       S.d_pfctl.as<PfCtl>(), seq, lb, le, (int)S.opt.l2_prefetch, delta_resident ? 1 : 0, far,
+                       X.pairs_ok ? S.d_pair_at.as<int32_t>() : (const int32_t *)nullptr, S.d_pairs.as<PairDesc>(), S.d_prow.as<uint2>(), S.d_pslots.as<uint4>());
     S.pf_active = true;
     return DG_OK;
 }

@@ -566,6 +566,8 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     S.n_dtrans = (int64_t)dtrans.size();
     S.n_edges = g->out_off[nV];
     plan_delta_windows(S, dtrans, dblk_first);
+    if (int rc = dp_build_pairs(c, g, S)) return rc;
+    lap("level pairs");
     const size_t n_edges = (size_t)g->out_off[nV];
     const size_t st_bytes = (size_t)S.max_level_cells * 4 * 2, dl_bytes = (size_t)S.delta_buf_entries * 2;
     size_t bp_bytes = 0, ck_bytes = 0;
@@ -580,7 +582,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     if (int rc = S.d_ckpt.ensure(ck_bytes)) return rc;
     if (int rc = S.d_pfctl.ensure(256)) return rc;                  // PfCtl of the L2 table prefetcher
     DG_HIP(hipMemsetAsync(S.d_pfctl.p, 0, 256, s));
-    S.pad_front = 2 * (int64_t)max_k;
+    S.pad_front = (S.pairs.empty() ? 2 : 4) * (int64_t)max_k;   // rows r2 - w in front of row 0: w <= 2, a composed pair of levels w <= 4
     const size_t pad_bytes = 4 * (size_t)(S.pad_front + 33 * (int64_t)max_k);
     S.state_alloc_bytes = (((size_t)S.max_level_cells * 4 + pad_bytes) + 255) & ~(size_t)255;   // one slot
     if (int rc = S.d_ring.ensure(S.state_alloc_bytes * 2)) return rc;          // the two ping-pong slots

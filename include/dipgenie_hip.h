@@ -278,6 +278,9 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, and of what a slab of dg_dp_partner_marginals holds (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   partner_wide 0|1|2    level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 (default) never -- beyond 16384 cells the call is refused; 1 for a call beyond 16384 cells; 2 for every call (tests, A/B timing)
  *   objective_lds_bytes n largest size of a pair's four colour bitmaps that dg_dp_objective_paths / dg_dp_answer_objectives keep in LDS; larger ones live in device memory (default 131072, n <= 0 restores it; clamped to the device's LDS per workgroup)
+ *   pair_levels 0|1       1 (default): adjacent low-fan-in levels run as one composed launch where the run allows it (unsegmented, all planes, digest 0,
+ *                         fast 1, adaptive_rc 1, test_force_rc 0); 0: every level its own launch (next load)
+ *   pair_min n            the composed tables are built and used only for a graph with at least n such pairs (default 4096; next load)
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning
  * This list is documentation: struct DpOptions (csrc/dg_dp.hpp) is authoritative for the defaults, the key table beside dg_dp_set_option for the clamps. */
@@ -295,6 +298,12 @@ int dg_dp_get_launch_profile(dg_ctx *, char *buf, int cap);
  * them: the generic kernel, then per chunk size fast<rc,lean>, coop<rc,lean>, fast<rc,general>, coop<rc,general> (the cooperative
  * ones for the chunk sizes that have them).  Needs no context.  DG_ERR_ARG: buf is null or too small. */
 int dg_dp_list_sweep_variants(char *buf, int cap);
+/* measurement: the level-pair launches of the last dg_dp_run (two adjacent low-fan-in levels composed into one launch, options
+ * pair_levels / pair_min), as "dp_sweep_pair_kernel<rc>:count ...", empty if there were none.  dg_dp_get_launch_profile and
+ * dg_dp_list_sweep_variants list the single-level launches only; dg_dp_timing::n_forward_launches counts both kinds. */
+int dg_dp_get_pair_profile(dg_ctx *, char *buf, int cap);
+/* parity: the names of every pair kernel the dispatch can launch, space-separated, in the order of the pair profile.  Needs no context. */
+int dg_dp_list_pair_variants(char *buf, int cap);
 
 /* ---- haploid (vertex, r) DP ---- */
 typedef struct dg_hap_graph {         /* expanded graph after topologically_reorder: every edge u -> v has u < v */

@@ -27,3 +27,16 @@ runs = np.diff(np.flatnonzero(np.diff(np.concatenate([[0], pure.astype(np.int8),
 if runs.size: print(f"runs of consecutive pure-copy transitions: {runs.size}, mean length {runs.mean():.2f}, max {runs.max()}; a collapsed chain would have {L - 1 - int(pure.sum()) + runs.size} launches")
 nocol = (c_lvl[1:] == 0) & (c_lvl[:-1] == 0)
 print(f"colourless transitions: {100 * nocol.mean():.1f} %; max in-degree 1: {100 * (max_in[1:] == 1).mean():.1f} %; weight-free: {100 * (w_lvl[1:] == 0).mean():.1f} %")
+# level pairs (dipgenie_amd/csrc/dg_dp_pairs.hip): (l - 1, l) run as one composed launch if both levels are lean (no vertex with more than
+# 64 in-edges) without a dead column, narrower than 256 with at most 2,047 in-edges, and every vertex of l has a composed in-degree
+# (sum over its in-edges p -> v of the in-degree of p) of at most 8; pairs are chosen greedily left to right, disjoint
+comp = np.zeros(nV, np.int64); np.add.at(comp, g.out_dst, indeg[src])
+max_comp = np.zeros(L, np.int64); np.maximum.at(max_comp, lvl_of, comp)
+t_lvl = np.zeros(L, np.int64); np.add.at(t_lvl, lvl_of, indeg)
+lvl_ok = (min_in >= 1) & (max_in <= 64) & (width <= 255) & (t_lvl <= 2047)
+for limit in (4, 8, 16):
+    n_pairs, l = 0, 2
+    while l < L:
+        if lvl_ok[l - 1] and lvl_ok[l] and max_comp[l] <= limit: n_pairs += 1; l += 2
+        else: l += 1
+    print(f"level pairs, composed in-degree <= {limit}{' (the rule of pair_levels)' if limit == 8 else ''}: {n_pairs} = {100 * n_pairs / (L - 1):.1f} % of the launches")
