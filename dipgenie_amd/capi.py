@@ -69,6 +69,11 @@ class SketchTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("sort_ms", C.c_float), ("total_ms", C.c_float), ("n_emitted", C.c_int64)]
 
 
+class ReadTag(C.Structure):
+    """dg_read_tag: one row of what Context.sketch_tag_reads returns (columns in this order)"""
+    _fields_ = [("n_min", C.c_int32), ("only_a", C.c_int32), ("only_b", C.c_int32), ("both", C.c_int32)]
+
+
 # every symbol include/dipgenie_hip.h declares
 SYMBOLS = [
     "dg_create", "dg_destroy", "dg_last_error", "dg_set_stream", "dg_synchronize", "dg_device_info",
@@ -82,6 +87,7 @@ SYMBOLS = [
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
+    "dg_sketch_tag_reads",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -135,6 +141,7 @@ lib.dg_sketch_count_rank_dictionary_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_
 lib.dg_sketch_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
 lib.dg_sketch_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
 lib.dg_sketch_get_stat.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+lib.dg_sketch_tag_reads.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
 
 
 class HapGraph(C.Structure):
@@ -535,6 +542,23 @@ class Context:
         lib.dg_free(hp)
         lib.dg_free(pp)
         return h, p
+
+    def sketch_tag_reads(self, reads, k, w, hash_a, hash_b):
+        """reads: list of bytes; hash_a, hash_b: uint64 lists (any order, duplicates allowed, may be empty).  Returns int32[n_reads, 4]:
+        per read n_min, only_a, only_b, both (ReadTag)."""
+        bases = b"".join(reads)
+        off = np.zeros(len(reads) + 1, np.int64)
+        np.cumsum([len(r) for r in reads], out=off[1:])
+        return self.sketch_tag_reads_flat(bases, off, k, w, hash_a, hash_b)
+
+    def sketch_tag_reads_flat(self, bases, off, k, w, hash_a, hash_b):
+        off = np.ascontiguousarray(off, np.int64)
+        ha = np.ascontiguousarray(hash_a, np.uint64).ravel()
+        hb = np.ascontiguousarray(hash_b, np.uint64).ravel()
+        out = np.zeros((off.size - 1, 4), np.int32)                    # one ReadTag per row
+        _check(lib.dg_sketch_tag_reads(self.h, bases, off.ctypes.data, off.size - 1, k, w, ha.ctypes.data if ha.size else None, ha.size,
+                                       hb.ctypes.data if hb.size else None, hb.size, out.ctypes.data), "dg_sketch_tag_reads")
+        return out
 
     def hash_kmers(self, kmers, k):
         n = len(kmers) // k if k > 0 else 0          # (k outside 1..255 is the library's to reject)

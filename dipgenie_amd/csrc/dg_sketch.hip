@@ -513,7 +513,7 @@ __global__ __launch_bounds__(256) void compact_tiles_kernel(const int64_t *__res
 // Tile descriptors are built on the device from the sequence offsets (a million reads: no 8 MB offset download, no host
 // loop, no 32 MB descriptor upload per call).  seq_count: per sequence its tiles and windows; after exclusive scans of
 // both, seq_fill writes the descriptors and the sparse output offsets (a tile emits at most one minimizer per window).
-struct SeqCount { int64_t tiles, wins, multi; };   // per sequence (multi: 1 if it has several tiles); after the exclusive scan: first tile / first window (entry n_seq = totals)
+// SeqCount (dg_sketch.hpp): per sequence (multi: 1 if it has several tiles); after the exclusive scan: first tile / first window (entry n_seq = totals)
 struct SeqCountPlus { __host__ __device__ SeqCount operator()(const SeqCount &a, const SeqCount &b) const { return SeqCount{a.tiles + b.tiles, a.wins + b.wins, a.multi + b.multi}; } };
 __global__ void seq_count_kernel(const int64_t *__restrict__ off, int64_t n_seq, int k, int w, SeqCount *__restrict__ cnt) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -787,6 +787,16 @@ static int events(SketchState &S) {
     return DG_OK;
 }
 
+// the tile pass as dg_sketch_tag.hip sees it (dg_sketch.hpp)
+SketchState &sketch_state(dg_ctx *c) { return state(c); }
+int sketch_check_kw(int k, int w) { return check_kw(k, w); }
+int sketch_events(SketchState &S) { return events(S); }
+int sketch_prepare_tiles(dg_ctx *c, const int64_t *off_dev, int64_t n_seq, int k, int w, int64_t *n_tiles, int64_t *n_windows) { return prepare_tiles(c, off_dev, n_seq, k, w, n_tiles, n_windows); }
+int sketch_launch_tiles_reads(dg_ctx *c, const char *bases_dev, int64_t n_tiles, int64_t n_windows, int k, int w, int bucket_mode) {
+    return launch_tiles_sparse<false>(c, bases_dev, n_tiles, n_windows, k, w, bucket_mode);
+}
+int sketch_compact_tiles(dg_ctx *c, int64_t n_tiles, int64_t *n_emit) { return compact_tiles(c, n_tiles, n_emit); }
+
 // out_hash == nullptr: the spectrum stays in d_uniq / d_cnt (host API); otherwise it is written to the caller's device buffers.
 // Route: minimizers straight into hash-range buckets (MODE 3) -> if a bucket runs over its stride, the exact two-pass
 // placement from the sparse output -> if that is not possible either, the generic sort of all pairs.
@@ -895,6 +905,8 @@ static const struct SketchOptionName { const char *name; int64_t SketchOptions::
     {"host_buckets", &SketchOptions::host_buckets, 0, 256, "host_buckets must be 0 (default 256) .. 256", false},
     {"spill_cap", &SketchOptions::spill_cap, -1, (int64_t)1 << 28, "spill_cap must be -1 (none) .. 2^28, 0 = default", true},
     {"residual_cap", &SketchOptions::residual_cap, -1, 1024, "residual_cap must be -1 (none) .. 1024, 0 = default", false},
+    {"tag_lds_entries", &SketchOptions::tag_lds_entries, 0, 1024, "tag_lds_entries must be 0 (default 1024) .. 1024", false},
+    {"tag_table_bits", &SketchOptions::tag_table_bits, 0, 30, "tag_table_bits must be 0 (automatic) .. 30", false},
 };
 static int sketch_option(dg_ctx *c, const char *what, const char *name, const int64_t *set, int64_t *get) {   // set or get, the other is null
     if (int rc = bind(c)) return rc;
@@ -922,6 +934,9 @@ extern "C" int dg_sketch_get_stat(dg_ctx *c, const char *name, int64_t *value) {
     else if (n == "buckets") *value = S.stat_buckets;
     else if (n == "overflow_buckets") *value = S.stat_overflow;
     else if (n == "spilled_pairs") *value = S.stat_spilled;
+    else if (n == "tag_long_reads") *value = S.stat_tag_long;          // the last dg_sketch_tag_reads call (dg_sketch_tag.hip)
+    else if (n == "tag_dict_distinct") *value = S.stat_tag_distinct;
+    else if (n == "tag_table_slots") *value = S.stat_tag_slots;
     else { set_error("dg_sketch_get_stat: unknown name '%s'", name); return DG_ERR_ARG; }
     return DG_OK;
 }

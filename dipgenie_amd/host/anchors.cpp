@@ -44,6 +44,7 @@ std::string read_spectrum(Pipeline &p, std::vector<uint64_t> &sp_hash, std::vect
     sp_hash.assign(hh, hh + n);
     sp_count.assign(cc, cc + n);
     p.be.free_buf(hh); p.be.free_buf(cc);
+    if (!p.opt.tag_reads.empty()) { p.tag_bases = std::move(bases); p.tag_off = std::move(off); }   // --tag-reads: the same bytes are tagged after the DP
     return "";
 }
 

@@ -367,6 +367,48 @@ std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::v
     return "";
 }
 
+// read  length  n_min  only_1  only_2  both  tag: one row per read in input order.  Both sequences of the answer are sketched with the
+// backend's own (w,k) scheme, then every read's distinct minimizers are looked up in the two lists; tag = the haplotype with more
+// private minimizers of the read, 0 where neither has more
+std::string write_read_tags(Pipeline &p, const std::string *hs) {
+    const Backend &be = p.be;
+    if (!be.tag_reads) return "--tag-reads: this backend has no tag_reads";
+    const int64_t n_reads = (int64_t)p.reads.size();
+    if ((int64_t)p.tag_off.size() != n_reads + 1) return "--tag-reads: the reads were not kept (their spectrum came from elsewhere)";
+    uint64_t *hh[2] = {nullptr, nullptr};
+    int64_t nh[2] = {0, 0};
+    for (int q = 0; q < 2; ++q) {
+        int64_t *pos = nullptr;
+        if (be.sketch_haplotype(be.ctx, hs[q].data(), (int64_t)hs[q].size(), p.opt.k, p.opt.w, &hh[q], &pos, &nh[q]) != 0) {
+            if (q) be.free_buf(hh[0]);
+            return backend_error(be, "sketch_haplotype");
+        }
+        be.free_buf(pos);
+    }
+    std::vector<dg_read_tag> rec((size_t)n_reads);
+    const int rc = be.tag_reads(be.ctx, p.tag_bases.data(), p.tag_off.data(), n_reads, p.opt.k, p.opt.w, hh[0], nh[0], hh[1], nh[1], rec.data());
+    be.free_buf(hh[0]); be.free_buf(hh[1]);
+    if (rc != 0) return backend_error(be, "tag_reads");
+    ReadTags &rt = p.sum.read_tags;
+    rt = ReadTags();
+    rt.set = true;
+    rt.reads = n_reads;
+    std::string text = "read\tlength\tn_min\tonly_1\tonly_2\tboth\ttag\n";
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const dg_read_tag &t = rec[(size_t)r];
+        const int tag = t.only_a > t.only_b ? 1 : (t.only_b > t.only_a ? 2 : 0);
+        if (tag == 1) rt.hap1++; else if (tag == 2) rt.hap2++; else if (t.only_a > 0) rt.tie++; else rt.no_evidence++;
+        text += p.reads[(size_t)r].first + '\t' + std::to_string(p.reads[(size_t)r].second.size()) + '\t' + std::to_string(t.n_min) + '\t' + std::to_string(t.only_a) + '\t' +
+                std::to_string(t.only_b) + '\t' + std::to_string(t.both) + '\t' + std::to_string(tag) + '\n';
+    }
+    std::ofstream f(p.opt.tag_reads, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open read tag file " + p.opt.tag_reads;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + p.opt.tag_reads + " failed";
+    return "";
+}
+
 }  // namespace
 
 int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_bv,
@@ -443,6 +485,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         t0 = now_s();
         if (failed(write_site_margins(*this, g, classes), err)) return -1;
         stamp("site_margins", t0);
+    }
+    if (!opt.tag_reads.empty()) {
+        t0 = now_s();
+        if (failed(write_read_tags(*this, out.seq), err)) return -1;
+        stamp("tag_reads", t0);
     }
     return 0;
 }

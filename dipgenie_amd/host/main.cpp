@@ -128,6 +128,10 @@ static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_answer_objectives(x, budgets, n, out) : DG_ERR_NO_DEVICE;
 }
+static int b_tag_reads(void *c, const char *b, const int64_t *off, int64_t n, int k, int w, const uint64_t *ha, int64_t na, const uint64_t *hb, int64_t nb, dg_read_tag *out) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_sketch_tag_reads(x, b, off, n, k, w, ha, na, hb, nb, out) : DG_ERR_NO_DEVICE;
+}
 static int b_hap(void *c, const dg_hap_graph *g, int32_t *dp, int32_t *bv, int32_t *br) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_solve_haploid(x, g, dp, bv, br) : DG_ERR_NO_DEVICE;
@@ -236,6 +240,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
     fprintf(fp, "    --wide-levels         (MI355X build) with --site-margins: lift its limit of 16384 cells (widest level x (R + 1)) by keeping the level state in device memory (then: widest level <= 32767, <= 16777216 cells)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
+    fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
 
@@ -255,7 +260,7 @@ int main(int argc, char **argv) {
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
     std::string budgets_arg;
-    bool have_budgets = false, have_site_margins = false, have_objective_table = false;
+    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -280,6 +285,12 @@ int main(int argc, char **argv) {
                 have_objective_table = true;                           // (a missing value is an empty file name: refused below)
                 const char *v = val("--objective-table");
                 p.opt.objective_table = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--tag-reads", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) {
+                have_tag_reads = true;                                 // (a missing value is an empty file name: refused below)
+                const char *v = val("--tag-reads");
+                p.opt.tag_reads = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--budget-table", 14)) { const char *v = val("--budget-table"); if (v) { p.opt.budget_table = v; continue; } }
@@ -350,6 +361,12 @@ int main(int argc, char **argv) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
         if (p.opt.objective_table.empty()) { fprintf(stderr, "[E::main] --objective-table needs a file name\n"); return 1; }
     }
+    // --tag-reads FILE: the same
+    if (have_tag_reads) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --tag-reads tags the reads by the two haplotypes of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.tag_reads.empty()) { fprintf(stderr, "[E::main] --tag-reads needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --tag-reads does not go with --gpus / --shard-transport: the sharded path drops the reads once they are scored\n"); return 1; }
+    }
     g_wide_levels = p.opt.wide_levels;
     if (!sharded) g_lazy.start(device, p.opt.k, p.opt.w);
     p.be.ctx = &g_lazy;
@@ -360,6 +377,7 @@ int main(int argc, char **argv) {
     p.be.dp_run_budgets = b_dp_budgets;
     p.be.dp_call_margins = b_dp_call_margins;
     p.be.dp_answer_objectives = b_dp_answer_objectives;
+    p.be.tag_reads = b_tag_reads;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -438,6 +456,11 @@ int main(int argc, char **argv) {
                     else fprintf(f, "%s{\"r\": %d, \"dp_value\": null, \"objective\": null, \"hom_shared\": null, \"hom_single\": null, \"het_single\": null, \"het_both\": null}", i ? ", " : "", o.r);
                 }
                 fprintf(f, "]");
+            }
+            if (p.sum.read_tags.set) {                                  // hap1 + hap2 + tie + no_evidence = reads
+                const dg::ReadTags &rt = p.sum.read_tags;
+                fprintf(f, ", \"read_tags\": {\"reads\": %lld, \"hap1\": %lld, \"hap2\": %lld, \"tie\": %lld, \"no_evidence\": %lld}", (long long)rt.reads, (long long)rt.hap1, (long long)rt.hap2,
+                        (long long)rt.tie, (long long)rt.no_evidence);
             }
             fprintf(f, "}\n");
             fclose(f);

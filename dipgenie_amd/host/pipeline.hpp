@@ -68,6 +68,9 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // optional (--objective-table): after dp_run_budgets, the distinct-colour objective of the answers at the listed budgets
     // (dg_dp_answer_objectives)
     int (*dp_answer_objectives)(void *, const int32_t *budgets, int32_t n_budgets, dg_dp_pair_objective *out) = nullptr;
+    // optional (--tag-reads): every read's distinct minimizers against the minimizer lists of the two answer sequences (dg_sketch_tag_reads)
+    int (*tag_reads)(void *, const char *bases, const int64_t *read_off, int64_t n_reads, int k, int w, const uint64_t *hash_a, int64_t n_a,
+                     const uint64_t *hash_b, int64_t n_b, dg_read_tag *out) = nullptr;
 };
 
 struct Options {
@@ -90,6 +93,7 @@ struct Options {
     std::string site_margins;    // (ours) --site-margins: TSV of the call margins of both haplotypes of the answer at -R, per level (diploid)
     bool wide_levels = false;    // (ours) --wide-levels, with --site-margins: the backend keeps the level state of dp_call_margins in device memory where LDS cannot hold it
     std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
+    std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
 // ExpandedGraph.hpp:16-26, flattened: CSR adjacency (per-vertex order = the reference's push order),
@@ -178,6 +182,11 @@ struct SiteMargins {          // --site-margins: per haplotype, over the levels 
     double wall_s = 0;
 };
 
+struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
+    bool set = false;
+    int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
+};
+
 struct Summary {              // what tests and the CLI report
     int32_t dp_value = 0, s_het = 0, r1 = -1, r2 = -1, obj = 0, best_r_haploid = -1;
     int64_t len1 = 0, len2 = 0;
@@ -189,6 +198,7 @@ struct Summary {              // what tests and the CLI report
     std::vector<BudgetRow> budget_rows;   // --budgets: in the order listed
     SiteMargins site_margins;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
+    ReadTags read_tags;
 };
 
 // One anchor occurrence: vertex list vpool[off, off+len) of read-minimizer id `a` on haplotype `h`.
@@ -218,6 +228,9 @@ class Pipeline {
     std::vector<int32_t> top_order_map;
     std::vector<std::string> hap_id2name;
     std::vector<std::pair<std::string, std::string>> reads;
+    // --tag-reads only: the concatenated bases and the offsets the spectrum was computed from, kept for the tagging after the DP
+    std::string tag_bases;
+    std::vector<int64_t> tag_off;
     int32_t count_sp_r = 0;
     // Anchor_hits[a][h] flattened: occs sorted by (a, h, final occurrence order)
     std::vector<Occ> occs;

@@ -9,6 +9,9 @@ static int b_dp_load(void *c, const dg_dp_graph *g) { return dg_dp_load_graph((d
 static int b_dp_budgets(void *c, const int32_t *budgets, int32_t n, dg_dp_result *r) { return dg_dp_run_budgets((dg_ctx *)c, budgets, n, r); }
 static int b_dp_call_margins(void *c, int32_t budget, const int32_t *cls, dg_dp_call_margin *levels, int32_t *paths) { return dg_dp_call_margins((dg_ctx *)c, budget, cls, levels, paths); }
 static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) { return dg_dp_answer_objectives((dg_ctx *)c, budgets, n, out); }
+static int b_tag_reads(void *c, const char *b, const int64_t *off, int64_t n, int k, int w, const uint64_t *ha, int64_t na, const uint64_t *hb, int64_t nb, dg_read_tag *out) {
+    return dg_sketch_tag_reads((dg_ctx *)c, b, off, n, k, w, ha, na, hb, nb, out);
+}
 static int b_hap(void *c, const dg_hap_graph *g, int32_t *dp, int32_t *bv, int32_t *br) { return dg_dp_solve_haploid((dg_ctx *)c, g, dp, bv, br); }
 static int b_anchor_begin(void *c, int32_t nh, int32_t nv, const int32_t *top, int k, int w) { return dg_anchor_begin((dg_ctx *)c, nh, nv, top, k, w); }
 static int b_anchor_add(void *c, int32_t h, const char *s, int64_t len, const int32_t *sv, const int64_t *ss, int64_t ns, int64_t *n) { return dg_anchor_add_haplotype((dg_ctx *)c, h, s, len, sv, ss, ns, n); }
@@ -28,7 +31,7 @@ int dgr_wire_backend(dgr_handle *H, std::string &err) {
     dg::Pipeline &p = H->p;
     p.be.ctx = H->ctx;
     p.be.sketch_reads = b_sketch_reads; p.be.sketch_haplotype = b_sketch_hap; p.be.dp_solve_diploid = b_dp; p.be.dp_solve_haploid = b_hap;
-    p.be.dp_load_graph = b_dp_load; p.be.dp_run_budgets = b_dp_budgets; p.be.dp_call_margins = b_dp_call_margins; p.be.dp_answer_objectives = b_dp_answer_objectives;
+    p.be.dp_load_graph = b_dp_load; p.be.dp_run_budgets = b_dp_budgets; p.be.dp_call_margins = b_dp_call_margins; p.be.dp_answer_objectives = b_dp_answer_objectives; p.be.tag_reads = b_tag_reads;
     p.be.free_buf = dg_free; p.be.anchor_begin = b_anchor_begin; p.be.anchor_add_haplotype = b_anchor_add; p.be.anchor_finish = b_anchor_finish;
     p.be.anchor_add_haplotype_sketched = b_anchor_add_sk; p.be.hint_dp_soon = b_hint; p.be.last_error = b_err;
     return 0;

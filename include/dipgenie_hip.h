@@ -332,6 +332,24 @@ int dg_sketch_haplotype(dg_ctx *, const char *seq, int64_t len, int k, int w,
 int dg_hash_kmers(dg_ctx *, const char *kmers, int64_t n, int k, uint64_t *out);
 void dg_free(void *);
 
+/* which of two hash lists the minimizers of every read support (read-backed phasing: A / B = dg_sketch_haplotype of the two
+ * haplotypes).  reads as for dg_sketch_reads; S = the read's set of distinct minimizer hashes (exactly what Solver::compute_hashes
+ * collects); A, B = the SETS of the values in hash_a[n_a], hash_b[n_b]: any order, duplicates allowed, any 64-bit value (0 and
+ * 2^64 - 1 included, nothing is reserved), empty lists may be NULL.  out[r] for every read r; a read without a window
+ * (len < k + w - 1) answers all zeros; a hash counts once per read however often the read emits it.  All pointers are host memory.
+ * DG_ERR_ARG (out is not written): k or w outside 1..255, n_reads < 0, null read_off or out with n_reads > 0, negative n_a / n_b, a
+ * null list of positive length, a tag_table_bits (below) that leaves no empty slot.  n_reads = 0 is DG_OK.  Synchronises.  Leaves the
+ * spectrum options and every stat of dg_sketch_reads as they were; like any sketch call it ends the life of device pointers an
+ * earlier one returned.  dg_sketch_get_timing afterwards: kernel_ms = the tile pass, sort_ms = dictionary + tagging, total_ms = both,
+ * n_emitted = emissions before the per-read dedup. */
+typedef struct dg_read_tag {
+    int32_t n_min;              /* distinct minimizer hashes of the read: |S| */
+    int32_t only_a, only_b;     /* |S n (A \ B)|, |S n (B \ A)| */
+    int32_t both;               /* |S n A n B| */
+} dg_read_tag;                  /* 16 bytes */
+int dg_sketch_tag_reads(dg_ctx *, const char *bases, const int64_t *read_off, int64_t n_reads, int k, int w,
+                        const uint64_t *hash_a, int64_t n_a, const uint64_t *hash_b, int64_t n_b, dg_read_tag *out);
+
 typedef struct dg_sketch_timing { float kernel_ms, sort_ms, total_ms; int64_t n_emitted; } dg_sketch_timing;
 int dg_sketch_get_timing(dg_ctx *, dg_sketch_timing *);
 /* parity / test knobs of the read spectrum (Sp_R, src/solver.cpp:526-546; none is needed in normal use):
@@ -346,8 +364,14 @@ int dg_sketch_get_timing(dg_ctx *, dg_sketch_timing *);
  *   residual_cap n         0 (default): 1024 residual entries per bucket (third hashes of a table entry); fewer (-1: none)
  *                          leave more buckets to the host's per-segment finish
  *   host_buckets n         0 (default): up to 256 buckets may be left to the host before the generic path takes over; 1..256
+ * and of dg_sketch_tag_reads:
+ *   tag_lds_entries n      0 (default): a read of up to 1024 emissions is deduplicated in an LDS set, longer ones by a sort of their
+ *                          segment; 1..1024: that limit (tests: both routes give the same records)
+ *   tag_table_bits b       0 (default): the dictionary table has the power of two >= 2 x distinct hashes slots; 1..30: 2^b slots
+ *                          (DG_ERR_ARG from the call if that leaves no empty slot)
  * dg_sketch_get_stat names, about the last dg_sketch_reads / dg_sketch_reads_dev call: spectrum_path (0 buckets filled by the
- * tile kernel, 1 exact placement, 2 generic), buckets, overflow_buckets (finished by the host per segment), spilled_pairs
+ * tile kernel, 1 exact placement, 2 generic), buckets, overflow_buckets (finished by the host per segment), spilled_pairs;
+ * about the last dg_sketch_tag_reads call: tag_long_reads (reads that took the sort), tag_dict_distinct, tag_table_slots
  * This list is documentation: the option table beside dg_sketch_set_option (csrc/dg_sketch.hip) is authoritative for names, ranges and defaults. */
 int dg_sketch_set_option(dg_ctx *, const char *name, int64_t value);
 int dg_sketch_get_option(dg_ctx *, const char *name, int64_t *value);   /* the stored value (0 = the default of every option) */
