@@ -61,6 +61,10 @@ LEVEL_MARGIN = np.dtype([("best_vertex", np.int32), ("best_value", np.int32), ("
 # dg_dp_call_margin as a numpy record: one per (haplotype, level) of Context.dp_call_margins
 CALL_MARGIN = np.dtype([("vertex", np.int32), ("value", np.int32), ("alt_vertex", np.int32), ("alt_value", np.int32)])
 
+# dg_dp_genotype_margin as a numpy record: one per (query, level) of Context.dp_genotype_margins
+GENOTYPE_MARGIN = np.dtype([("vertex1", np.int32), ("vertex2", np.int32), ("value", np.int32), ("alt_vertex1", np.int32), ("alt_vertex2", np.int32),
+                            ("alt_value", np.int32), ("reserved", np.int32, (2,))])
+
 # dg_dp_pair_objective as a numpy record: what Context.dp_objective_paths and Context.dp_answer_objectives return
 PAIR_OBJECTIVE = np.dtype([("hom_shared", np.int32), ("hom_single", np.int32), ("het_single", np.int32), ("het_both", np.int32)])
 
@@ -87,7 +91,7 @@ SYMBOLS = [
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
-    "dg_sketch_tag_reads",
+    "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -109,6 +113,8 @@ lib.dg_dp_partner_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_v
 lib.dg_dp_get_answer_paths.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_call_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_partner_route.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+lib.dg_dp_genotype_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+lib.dg_dp_get_genotype_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
@@ -433,6 +439,41 @@ class Context:
         route, cells = C.c_int32(0), C.c_int64(0)
         _check(lib.dg_dp_get_partner_route(self.h, C.byref(route), C.byref(cells)), "dg_dp_get_partner_route")
         return route.value, cells.value
+
+    def dp_genotype_margins(self, called, budget, vertex_class=None, want_vertices=False):
+        """Genotype margins with both haplotypes free.  called: int32 [n, 2, n_levels] (or [2, n_levels] for n = 1), per query one
+        cell per level, every id inside its level -- the two rows of dp_answer_paths are such a query; budget >= 0, independent of the
+        graph's R; vertex_class: int32 [n_vertices], or None for "every vertex is its own class".  Returns (levels, best_value) or,
+        with want_vertices=True, (levels, best_value, vertex_values): a GENOTYPE_MARGIN record array [n, n_levels] (vertex1, vertex2:
+        the called cell; value: the best value of any pair of paths through it within the budget; alt_vertex1 <= alt_vertex2,
+        alt_value: the same for the best cell of another genotype, -1, -1 and NEG_INF where there is none), the best value of any pair
+        within the budget, and int32 [n_vertices]: the best value of any pair with one path through the vertex.  value - alt_value
+        is the margin of the called genotype at that level, negative where the called cell is not optimal.  An id outside its
+        level raises DgError naming the first (query, row, level).  Leaves the last run's answers alone."""
+        p = np.ascontiguousarray(called, np.int32)
+        if p.ndim == 2:
+            p = p[None]
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+            raise ValueError(f"called must have shape [n, 2, n_levels], got {p.shape}")
+        cls = None
+        if vertex_class is not None:
+            cls = np.ascontiguousarray(vertex_class, np.int32)
+            if g is not None and cls.shape != (g.n_vertices,):
+                raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
+        levels = np.zeros((p.shape[0], p.shape[2]), GENOTYPE_MARGIN)
+        values = np.zeros(g.n_vertices if g is not None else 1, np.int32) if want_vertices else None
+        best = C.c_int32(0)
+        _check(lib.dg_dp_genotype_margins(self.h, p.ctypes.data if p.size else None, p.shape[0], int(budget), cls.ctypes.data if cls is not None else None,
+                                          levels.ctypes.data if levels.size else None, values.ctypes.data if want_vertices else None, C.byref(best)),
+               "dg_dp_genotype_margins")
+        return (levels, best.value, values) if want_vertices else (levels, best.value)
+
+    def dp_genotype_stats(self):
+        """of the last dp_genotype_margins on this context: dict(n_segments, levels_twice, peak_bytes, launches)"""
+        out = np.zeros(4, np.int64)
+        _check(lib.dg_dp_get_genotype_stats(self.h, out.ctypes.data, 4), "dg_dp_get_genotype_stats")
+        return dict(zip(("n_segments", "levels_twice", "peak_bytes", "launches"), out.tolist()))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

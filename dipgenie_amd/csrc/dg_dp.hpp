@@ -1,6 +1,6 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
 // (dg_dp_tables.hip, dg_dp_pairs.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip,
-// dg_dp_objective.hip).
+// dg_dp_objective.hip, dg_dp_joint.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -189,6 +189,7 @@ struct DpOptions {
     int64_t partner_wide = 0;                           // partner_wide: the level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 never (LDS only), 1 for a call beyond the LDS limit, 2 always
     int64_t pair_levels = 1;                            // pair_levels: adjacent low-fan-in levels run as one composed launch (dg_dp_pairs.hip); next load
     int64_t pair_min = 4096;                            // pair_min: the composed tables are built and used only for a graph with at least this many pairs; next load
+    int64_t joint_state_bytes = (int64_t)8 << 30;       // joint_state_bytes: bound of the forward states of one segment of dg_dp_genotype_margins (a segment holds at least one level)
     int64_t objective_lds_bytes = 131072;              // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
 };
 
@@ -299,6 +300,9 @@ struct DpState {
     bool ob_dict = false;
     int64_t ob_ch = 0, ob_ct = 0;              // distinct hom / het colours
     DevBuf d_ob_hom_rank, d_ob_het_rank, d_ob_paths, d_ob_out, d_ob_err, d_ob_bits;
+    // ---- dg_dp_genotype_margins (dg_dp_joint.hip): nothing but the statistics of the last call outlives it (dg_dp_get_genotype_stats:
+    // segments, levels swept forward twice, peak bytes reserved, launches) ----
+    int64_t jt_stats[4] = {0, 0, 0, 0};
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -390,5 +394,10 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
 // ---- partner marginals: that DP forward and backward, combined per vertex (dg_dp_marginals.hip; shares dg_dp_partner.hpp with the above) ----
 int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
 int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
+
+// ---- genotype margins: the DP forward and backward with both haplotypes free, combined per cell (dg_dp_joint.hip) ----
+int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+                        int32_t *vertex_values, int32_t *best_value);
+int dp_genotype_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

@@ -1,0 +1,505 @@
+// dg_dp_genotype_margins: the max-marginals of the diploid DP with BOTH haplotypes free -- for every cell (i, j) of every level the
+// best value of any ordered pair of source -> sink paths (p, q) with p[l] = i, q[l] = j and r(p) + r(q) <= budget, and per level and
+// query the called cell's value against the best cell of another genotype.  Notation: d(u1, u2 -> v1, v2) = inter + symd of the
+// transition, what the sweep adds (one T x T uint16 matrix per coloured transition, indexed by the ranks of the two in-edges).
+//   forward   F_0[src, src][r] = 0; F_l[i][j][r] = max over the in-edge pairs (u -> i, w1), (v -> j, w2) with r - w1 - w2 >= 0 and a
+//             reachable source cell of F_{l-1}[u][v][r - w1 - w2] + d; NEG_INF where there is none (the sweep's values);
+//   backward  B_{L-1}[sink, sink][r] = 0; B_l[i][j][r] = max over the out-edge pairs (i -> i', w1), (j -> j', w2) with
+//             r - w1 - w2 >= 0 and a reachable destination cell of d + B_{l+1}[i'][j'][r - w1 - w2];
+//   through   T_l[i][j] = max over r = 0..b with both cells reachable of F_l[i][j][r] + B_l[i][j][b - r]; J[v] = max_j T_l[v][j].
+// Both tables mean "at most r", so a pair that spends r1 up to the level and r2 after it is counted at r = r1 whenever r1 + r2 <= b.
+// A level's state is int32 [i][j][r], r fastest, in device memory.  Every kernel is a gather: each cell is written once by one
+// lane, no output is an atomic, and nothing depends on the order in which lanes or workgroups run:
+//   * jt_scores_kernel: the T x T score matrix of one transition into a buffer of the call (the run's own window of matrices,
+//     DpState::d_delta / cur_win, is neither read nor written); the pairs with at most one coloured edge are answered from the edge
+//     flags and single-edge scores that dg_dp_load_graph leaves (read only), the others by the merges of dg_dp_setops.hpp;
+//   * jt_forward_kernel: one lane per (i, j, r) of the destination level, looping over in(i) x in(j);
+//   * jt_out_*: the device holds the in-CSR only, so once per call the in-edges are grouped by their source vertex (count, scan,
+//     fill: a counting sort; the order inside a group is the order the lanes arrive in, and a maximum does not depend on it);
+//   * jt_backward_kernel: one lane per (i, j, r) of level l, looping over out(i) x out(j) into level l + 1;
+//   * jt_combine_kernel: one workgroup per row i forms T[i][.] over r, its maximum J, and per query the best cell (i, j >= i) of
+//     another genotype than the called one as a key (value desc, i asc, j asc); T is symmetric, so the cells with j >= i are all of
+//     them and the alternative comes out with alt_vertex1 <= alt_vertex2;
+//   * jt_records_kernel: one workgroup per query reduces the rows' keys to the level's record, workgroup 0 the rows' maxima to
+//     the level maximum (the closing check: it must be V_b on every level).
+// One launch per level and pass: the kernel boundary orders the levels.  No cooperative launch, no grid barrier, no spinning.
+// Memory: F of all levels is 4 * sum k^2 (b + 1) bytes, so the call keeps F only at the first level of each segment (option
+// joint_state_bytes bounds the forward states of one segment; a segment holds at least one level) in a first forward pass, then
+// visits the segments from the last to the first: the forward states of the segment's levels are recomputed and kept, the backward
+// recurrence walks the segment with two rolling states, combination and records run per level.  With one segment the first pass
+// has nothing to do.  Every buffer is reserved inside the call and freed when it returns; nothing of a run is read or written.
+#include <algorithm>
+#include <cstring>
+
+#include "dg_dp_setops.hpp"
+
+namespace dgi {
+
+namespace {
+
+constexpr int JT_THREADS = 256;
+constexpr int JT_MAX_K = 32767;                         // widest level: a cell's two positions take 15 bits each in the tie key
+constexpr int JT_MAX_PLANES = 4096;                     // budget + 1
+constexpr int JT_MAX_QUERIES = 256;                     // called genotypes per call (the combine kernel loops over them)
+constexpr int JT_ROW_BLOCKS = 2048;                     // workgroups of the combine kernel (each owns one scratch row of T)
+constexpr int JT_X_BLOCKS = 4096;                       // workgroups per row of the recurrences (the lanes stride beyond)
+constexpr long long JT_NO_KEY = INT64_MIN;              // no cell (every key of a cell is larger: its value is >= 0)
+
+// value descending, then i ascending, then j ascending (positions inside the level, both <= 32766)
+__device__ __forceinline__ long long jt_key(int value, int i, int j) {
+    return (long long)(((unsigned long long)(uint32_t)value << 32) | ((uint32_t)(JT_MAX_K - i) << 15) | (uint32_t)(JT_MAX_K - j));
+}
+
+// n cells of NEG_INF but for [hot, hot + planes): 0 (level 0: the source's cell; level L - 1: the sink's)
+__global__ __launch_bounds__(JT_THREADS) void jt_fill_kernel(int32_t *__restrict__ st, int64_t n, int64_t hot, int planes) {
+    for (int64_t x = (int64_t)blockIdx.x * JT_THREADS + threadIdx.x; x < n; x += (int64_t)gridDim.x * JT_THREADS) st[x] = (x >= hot && x < hot + planes) ? 0 : NEG_INF;
+}
+
+// out[eu * T + ev] for the transition whose T in-edges start at in_base and whose source level starts at vertex a0
+__global__ __launch_bounds__(JT_THREADS) void jt_scores_kernel(int T, uint32_t in_base, int a0, const uint32_t *__restrict__ in_edge, const int32_t *__restrict__ in_dst,
+                                                               ColourCsr col, const uint8_t *__restrict__ eflags, const uint16_t *__restrict__ eself,
+                                                               uint16_t *__restrict__ out) {
+    for (int eu = (int)blockIdx.y; eu < T; eu += (int)gridDim.y) {
+        const uint32_t fu = eflags[in_base + eu];
+        for (int ev = (int)(blockIdx.x * JT_THREADS + threadIdx.x); ev < T; ev += (int)(gridDim.x * JT_THREADS)) {
+            const uint32_t fv = eflags[in_base + ev];
+            int sc = 0;
+            if ((fu | fv) == 0u) sc = 0;                                    // no colour on either edge
+            else if (fv == 0u) sc = eself[in_base + eu];                    // one coloured edge: its own score
+            else if (fu == 0u) sc = eself[in_base + ev];
+            else {
+                const int u1 = a0 + (int)(in_edge[in_base + eu] & 0x7FFFFFFFu), v1 = a0 + (int)(in_edge[in_base + ev] & 0x7FFFFFFFu);
+                const int u2 = in_dst[in_base + eu], v2 = in_dst[in_base + ev];
+                if (((fu | fv) & 3u) == 3u) sc += score_inter(col, u1, v1, u2, v2);
+                if (((fu | fv) & 12u) != 0u) sc += score_symd(col, u1, v1, u2, v2);
+            }
+            out[(int64_t)eu * T + ev] = (uint16_t)sc;
+        }
+    }
+}
+
+// grid (x blocks, k): row i = blockIdx.y, the lanes stride over (j, r).  prev = level l - 1 [kprev][kprev][B1], cur = level l [k][k][B1];
+// b0 = first vertex of level l, in_base / T = its in-edges; sc = its T x T scores, null: all zero
+__global__ __launch_bounds__(JT_THREADS) void jt_forward_kernel(const int32_t *__restrict__ prev, int32_t *__restrict__ cur, int kprev, int k, int B1, int b0,
+                                                                uint32_t in_base, int T, const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
+                                                                const uint16_t *__restrict__ sc) {
+    const int i = (int)blockIdx.y;
+    const uint32_t eu0 = in_off[b0 + i], eu1 = in_off[b0 + i + 1];
+    const int n = k * B1;
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += (int)(gridDim.x * JT_THREADS)) {
+        const int j = x / B1, r = x - j * B1;
+        const uint32_t ev0 = in_off[b0 + j], ev1 = in_off[b0 + j + 1];
+        int best = NEG_INF;
+        for (uint32_t eu = eu0; eu < eu1; ++eu) {
+            const uint32_t ru = in_edge[eu];
+            const uint32_t pu = ru & 0x7FFFFFFFu;
+            const int r1 = r - (int)(ru >> 31);
+            if (pu >= (uint32_t)kprev || r1 < 0 || eu - in_base >= (uint32_t)T) continue;
+            for (uint32_t ev = ev0; ev < ev1; ++ev) {
+                const uint32_t rv = in_edge[ev];
+                const uint32_t pv = rv & 0x7FFFFFFFu;
+                const int r2 = r1 - (int)(rv >> 31);
+                if (pv >= (uint32_t)kprev || r2 < 0 || ev - in_base >= (uint32_t)T) continue;
+                const int s = prev[((int64_t)pu * kprev + pv) * B1 + r2];
+                if (s == NEG_INF) continue;
+                const int d = sc ? (int)sc[(int64_t)(eu - in_base) * T + (ev - in_base)] : 0;
+                best = max(best, s + d);
+            }
+        }
+        cur[((int64_t)i * k + j) * B1 + r] = best;
+    }
+}
+
+// ---- the in-edges grouped by source vertex: cnt[v] = out-edges of v, then off = their exclusive scan, then oe[off[v] ..) = the in-edge
+// indices.  One workgroup per destination level l = blockIdx.x + 1 for count and fill ----
+__global__ __launch_bounds__(JT_THREADS) void jt_out_count_kernel(const LevelDesc *__restrict__ descs, int L, int nV, const uint32_t *__restrict__ in_edge,
+                                                                  uint32_t *__restrict__ cnt) {
+    const int l = (int)blockIdx.x + 1;
+    if (l >= L) return;
+    const LevelDesc d = descs[l];
+    for (int e = (int)threadIdx.x; e < d.T; e += JT_THREADS) {
+        const uint32_t pos = in_edge[d.in_base + e] & 0x7FFFFFFFu;
+        if (pos < (uint32_t)d.k && (uint32_t)d.a0 + pos < (uint32_t)nV) atomicAdd(&cnt[d.a0 + (int)pos], 1u);
+    }
+}
+
+// one workgroup: off[v] = sum of cnt[0 .. v), off[nV] = the total; cur (may be cnt itself) = a copy of off[0 .. nV) for the fill
+__global__ __launch_bounds__(1024) void jt_out_scan_kernel(const uint32_t *cnt, uint32_t *__restrict__ off, uint32_t *cur, int nV) {
+    __shared__ uint32_t s[1024];
+    const int t = (int)threadIdx.x;
+    uint32_t carry = 0;
+    for (int base = 0; base < nV; base += 1024) {
+        const int v = base + t;
+        const uint32_t x = v < nV ? cnt[v] : 0u;
+        s[t] = x;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {
+            const uint32_t y = t >= d ? s[t - d] : 0u;
+            __syncthreads();
+            s[t] += y;
+            __syncthreads();
+        }
+        const uint32_t excl = carry + s[t] - x;
+        if (v < nV) { off[v] = excl; cur[v] = excl; }
+        carry += s[1023];
+        __syncthreads();
+    }
+    if (t == 0) off[nV] = carry;
+}
+
+__global__ __launch_bounds__(JT_THREADS) void jt_out_fill_kernel(const LevelDesc *__restrict__ descs, int L, int nV, const uint32_t *__restrict__ in_edge,
+                                                                 uint32_t *__restrict__ cur, uint32_t *__restrict__ oe, uint32_t n_edges) {
+    const int l = (int)blockIdx.x + 1;
+    if (l >= L) return;
+    const LevelDesc d = descs[l];
+    for (int e = (int)threadIdx.x; e < d.T; e += JT_THREADS) {
+        const uint32_t pos = in_edge[d.in_base + e] & 0x7FFFFFFFu;
+        if (pos < (uint32_t)d.k && (uint32_t)d.a0 + pos < (uint32_t)nV) {
+            const uint32_t at = atomicAdd(&cur[d.a0 + (int)pos], 1u);
+            if (at < n_edges) oe[at] = d.in_base + (uint32_t)e;
+        }
+    }
+}
+
+// grid (x blocks, k): row i = blockIdx.y.  next = level l + 1 [kn][kn][B1], cur = level l [k][k][B1]; a0 = first vertex of level l, b0n = first
+// vertex of level l + 1, in_base / T = the in-edges of level l + 1, sc = their scores (null: all zero); oo / oe = the out-index
+__global__ __launch_bounds__(JT_THREADS) void jt_backward_kernel(const int32_t *__restrict__ next, int32_t *__restrict__ cur, int k, int kn, int B1, int a0, int b0n,
+                                                                 uint32_t in_base, int T, const uint32_t *__restrict__ oo, const uint32_t *__restrict__ oe,
+                                                                 const uint32_t *__restrict__ in_edge, const int32_t *__restrict__ in_dst,
+                                                                 const uint16_t *__restrict__ sc) {
+    const int i = (int)blockIdx.y;
+    const uint32_t ou0 = oo[a0 + i], ou1 = oo[a0 + i + 1];
+    const int n = k * B1;
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += (int)(gridDim.x * JT_THREADS)) {
+        const int j = x / B1, r = x - j * B1;
+        const uint32_t ov0 = oo[a0 + j], ov1 = oo[a0 + j + 1];
+        int best = NEG_INF;
+        for (uint32_t ou = ou0; ou < ou1; ++ou) {
+            const uint32_t eu = oe[ou] - in_base;                           // rank among the in-edges of level l + 1
+            if (eu >= (uint32_t)T) continue;
+            const uint32_t pi = (uint32_t)(in_dst[in_base + eu] - b0n);
+            const int r1 = r - (int)(in_edge[in_base + eu] >> 31);
+            if (pi >= (uint32_t)kn || r1 < 0) continue;
+            for (uint32_t ov = ov0; ov < ov1; ++ov) {
+                const uint32_t ev = oe[ov] - in_base;
+                if (ev >= (uint32_t)T) continue;
+                const uint32_t pj = (uint32_t)(in_dst[in_base + ev] - b0n);
+                const int r2 = r1 - (int)(in_edge[in_base + ev] >> 31);
+                if (pj >= (uint32_t)kn || r2 < 0) continue;
+                const int s = next[((int64_t)pi * kn + pj) * B1 + r2];
+                if (s == NEG_INF) continue;
+                const int d = sc ? (int)sc[(int64_t)eu * T + ev] : 0;
+                best = max(best, s + d);
+            }
+        }
+        cur[((int64_t)i * k + j) * B1 + r] = best;
+    }
+}
+
+// grid: min(k, JT_ROW_BLOCKS) workgroups, rows strided.  F, B = the two states of level l; row = [gridDim.x][k] scratch; J = [nV];
+// called = [n][2][L] vertex ids (validated by the host); cls = [nV] or null; part = [n][k] keys; cval = [n]
+__global__ __launch_bounds__(JT_THREADS) void jt_combine_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ B, int k, int B1, int b0, int32_t *row_all,
+                                                                int32_t *__restrict__ J, int n, const int32_t *__restrict__ called, int L, int l,
+                                                                const int32_t *__restrict__ cls, long long *__restrict__ part, int32_t *__restrict__ cval) {
+    __shared__ long long s_key[JT_MAX_QUERIES][JT_THREADS / 64];
+    __shared__ int s_max[JT_THREADS / 64];
+    const int t = (int)threadIdx.x;
+    int32_t *row = row_all + (int64_t)blockIdx.x * k;
+    for (int i = (int)blockIdx.x; i < k; i += (int)gridDim.x) {
+        int m = NEG_INF;
+        for (int j = t; j < k; j += JT_THREADS) {
+            const int32_t *f = F + ((int64_t)i * k + j) * B1, *b = B + ((int64_t)i * k + j) * B1;
+            int best = NEG_INF;
+            for (int r = 0; r < B1; ++r) {
+                const int fv = f[r], bv = b[B1 - 1 - r];
+                if (fv != NEG_INF && bv != NEG_INF) best = max(best, fv + bv);
+            }
+            row[j] = best;
+            m = max(m, best);
+        }
+        for (int d = 32; d; d >>= 1) m = max(m, __shfl_xor(m, d));
+        if ((t & 63) == 0) s_max[t >> 6] = m;
+        __syncthreads();                                                    // the row and the waves' maxima are in
+        if (t == 0) {
+            for (int w = 1; w < JT_THREADS / 64; ++w) m = max(m, s_max[w]);
+            J[b0 + i] = m;
+        }
+        const int ci = cls ? cls[b0 + i] : b0 + i;
+        for (int q = 0; q < n; ++q) {
+            const int c1 = called[((int64_t)q * 2) * L + l], c2 = called[((int64_t)q * 2 + 1) * L + l];
+            const int cc1 = cls ? cls[c1] : c1, cc2 = cls ? cls[c2] : c2;
+            if (t == 0 && i == c1 - b0) cval[q] = row[c2 - b0];
+            long long key = JT_NO_KEY;
+            for (int j = i + t; j < k; j += JT_THREADS) {
+                const int v = row[j];
+                if (v == NEG_INF) continue;
+                const int cj = cls ? cls[b0 + j] : b0 + j;
+                if ((ci == cc1 && cj == cc2) || (ci == cc2 && cj == cc1)) continue;      // the called genotype itself
+                key = max(key, jt_key(v, i, j));
+            }
+            for (int d = 32; d; d >>= 1) key = max(key, __shfl_xor(key, d));
+            if ((t & 63) == 0) s_key[q][t >> 6] = key;
+        }
+        __syncthreads();
+        for (int q = t; q < n; q += JT_THREADS) {
+            long long key = s_key[q][0];
+            for (int w = 1; w < JT_THREADS / 64; ++w) key = max(key, s_key[q][w]);
+            part[(int64_t)q * k + i] = key;
+        }
+        __syncthreads();                                                    // the next row overwrites the scratch row and the keys
+    }
+}
+
+// grid: n workgroups.  Query q: the largest of its k row keys -> rec[q][l]; workgroup 0 also the level's maximum of J -> lvlmax[l]
+__global__ __launch_bounds__(JT_THREADS) void jt_records_kernel(int k, int b0, const int32_t *__restrict__ J, const long long *__restrict__ part,
+                                                                const int32_t *__restrict__ cval, const int32_t *__restrict__ called, int L, int l,
+                                                                dg_dp_genotype_margin *__restrict__ rec, int32_t *__restrict__ lvlmax) {
+    __shared__ long long s_key[JT_THREADS / 64];
+    __shared__ int s_max[JT_THREADS / 64];
+    const int t = (int)threadIdx.x, q = (int)blockIdx.x;
+    long long key = JT_NO_KEY;
+    int m = NEG_INF;
+    for (int i = t; i < k; i += JT_THREADS) {
+        key = max(key, part[(int64_t)q * k + i]);
+        if (q == 0) m = max(m, J[b0 + i]);
+    }
+    for (int d = 32; d; d >>= 1) { key = max(key, __shfl_xor(key, d)); m = max(m, __shfl_xor(m, d)); }
+    if ((t & 63) == 0) { s_key[t >> 6] = key; s_max[t >> 6] = m; }
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) { key = max(key, s_key[w]); m = max(m, s_max[w]); }
+        dg_dp_genotype_margin r;
+        r.vertex1 = called[((int64_t)q * 2) * L + l];
+        r.vertex2 = called[((int64_t)q * 2 + 1) * L + l];
+        r.value = cval[q];
+        if (key == JT_NO_KEY) { r.alt_vertex1 = -1; r.alt_vertex2 = -1; r.alt_value = NEG_INF; }
+        else {
+            const uint32_t lo = (uint32_t)key;
+            r.alt_vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+            r.alt_vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+            r.alt_value = (int)(key >> 32);
+        }
+        r.reserved[0] = 0; r.reserved[1] = 0;
+        rec[(int64_t)q * L + l] = r;
+        if (q == 0) lvlmax[l] = m;
+    }
+}
+
+struct JtLevel { int a0, k; uint32_t in_base; int T; bool coloured; int64_t cells; };   // cells: k * k * (b + 1)
+
+// the buffers of one call: reserved here, released when the call returns; `now` / `peak` bytes for dg_dp_get_genotype_stats
+struct JtMem {
+    int64_t now = 0, peak = 0;
+    int get(DevBuf &b, int64_t bytes) {
+        if (int rc = b.ensure((size_t)std::max<int64_t>(bytes, 16))) return rc;
+        now += (int64_t)b.bytes;
+        peak = std::max(peak, now);
+        return DG_OK;
+    }
+    void drop(DevBuf &b) { now -= (int64_t)b.bytes; b.release(); }
+};
+
+unsigned jt_blocks(int64_t lanes, int cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((lanes + JT_THREADS - 1) / JT_THREADS, cap)); }
+
+}  // namespace
+
+int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+                        int32_t *vertex_values, int32_t *best_value) {
+    static const char *const FN = "dg_dp_genotype_margins";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
+    DpState &S = *Sp;
+    if (n < 1) { set_error("%s: n_called = %lld", FN, (long long)n); return DG_ERR_ARG; }
+    if (!called || !levels || !best_value) { set_error("%s: called, levels and best_value are required", FN); return DG_ERR_ARG; }
+    if (budget < 0) { set_error("%s: budget %d is negative", FN, budget); return DG_ERR_ARG; }
+    if (n > JT_MAX_QUERIES) { set_error("%s: %lld called genotypes exceed %d per call", FN, (long long)n, JT_MAX_QUERIES); return DG_ERR_UNSUPPORTED; }
+    if ((int64_t)budget + 1 > JT_MAX_PLANES) { set_error("%s: budget + 1 = %lld exceeds %d planes", FN, (long long)budget + 1, JT_MAX_PLANES); return DG_ERR_UNSUPPORTED; }
+    const int L = S.L, nV = S.nV, B1 = budget + 1;
+    if (L < 2 || (int)S.descs.size() < L) { set_error("%s: the loaded graph has %d levels", FN, L); return DG_ERR_STATE; }
+    std::vector<JtLevel> lv((size_t)L);
+    int kmax = 1;
+    int64_t tmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const LevelDesc &d = S.descs[(size_t)std::max(l, 1)];
+        lv[l] = l ? JtLevel{d.b0, d.k2, d.in_base, d.T, d.delta_off >= 0, 0} : JtLevel{d.a0, d.k, 0u, 0, false, 0};
+        lv[l].cells = (int64_t)lv[l].k * lv[l].k * B1;
+        kmax = std::max(kmax, lv[l].k);
+        if (lv[l].coloured) tmax = std::max<int64_t>(tmax, lv[l].T);
+    }
+    if (kmax > JT_MAX_K) { set_error("%s: widest level %d exceeds %d", FN, kmax, JT_MAX_K); return DG_ERR_UNSUPPORTED; }
+    for (int64_t q = 0; q < n; ++q)
+        for (int row = 0; row < 2; ++row)
+            for (int l = 0; l < L; ++l) {
+                const int32_t v = called[(q * 2 + row) * L + l];
+                if ((uint32_t)(v - lv[l].a0) >= (uint32_t)lv[l].k) {
+                    set_error("%s: query %lld row %d level %d: vertex %d is not in its level", FN, (long long)q, row, l, v);
+                    return DG_ERR_ARG;
+                }
+            }
+    hipStream_t s = c->stream;
+    // ---- the plan: segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
+    std::vector<int> seg{0};
+    {
+        int64_t in_seg = 0;
+        for (int l = 0; l < L; ++l) {
+            const int64_t bytes = 4 * lv[l].cells;
+            if (l > seg.back() && in_seg + bytes > S.opt.joint_state_bytes) { seg.push_back(l); in_seg = 0; }
+            in_seg += bytes;
+        }
+    }
+    const int n_seg = (int)seg.size();
+    seg.push_back(L);
+    std::vector<int64_t> ck_off((size_t)n_seg + 1, 0);                     // F of every segment's first level, int32 units
+    int64_t seg_cells = 1, roll_cells = 0, level_cells = 1;
+    for (int g = 0; g < n_seg; ++g) {
+        ck_off[g + 1] = ck_off[g] + lv[seg[g]].cells;
+        int64_t sum = 0;
+        for (int l = seg[g] + 1; l < seg[g + 1]; ++l) { sum += lv[l].cells; if (g + 1 < n_seg) roll_cells = std::max(roll_cells, lv[l].cells); }
+        seg_cells = std::max(seg_cells, sum);
+    }
+    for (int l = 0; l < L; ++l) level_cells = std::max(level_cells, lv[l].cells);
+    int64_t launches = 0, twice = 0;
+    JtMem M;
+    DevBuf d_called, d_cls, d_J, d_rec, d_lvlmax, d_cval, d_part, d_row, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back;
+    const int row_blocks = std::min(kmax, JT_ROW_BLOCKS);
+    if (int rc = M.get(d_called, n * 2 * L * 4)) return rc;
+    if (vertex_class) if (int rc = M.get(d_cls, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_J, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_rec, n * L * (int64_t)sizeof(dg_dp_genotype_margin))) return rc;
+    if (int rc = M.get(d_lvlmax, ((int64_t)L + 1) * 4)) return rc;                 // entry L: V_b, the sink's cell on plane `budget`
+    if (int rc = M.get(d_cval, n * 4)) return rc;
+    if (int rc = M.get(d_part, n * kmax * 8)) return rc;
+    if (int rc = M.get(d_row, (int64_t)row_blocks * kmax * 4)) return rc;
+    if (int rc = M.get(d_oo, ((int64_t)nV + 1) * 4)) return rc;
+    if (int rc = M.get(d_ocur, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
+    if (tmax) if (int rc = M.get(d_sc, tmax * tmax * 2)) return rc;
+    if (int rc = M.get(d_ck, ck_off[n_seg] * 4)) return rc;
+    DG_HIP(hipMemcpyAsync(d_called.p, called, (size_t)(n * 2 * L) * 4, hipMemcpyHostToDevice, s));
+    if (vertex_class) DG_HIP(hipMemcpyAsync(d_cls.p, vertex_class, (size_t)nV * 4, hipMemcpyHostToDevice, s));
+    const LevelDesc *descs = S.d_descs.as<LevelDesc>();
+    const uint32_t *in_off = S.d_in_off.as<uint32_t>(), *in_edge = S.d_in_edge.as<uint32_t>();
+    const int32_t *in_dst = S.d_in_dst.as<int32_t>();
+    uint16_t *sc = d_sc.as<uint16_t>();
+    // the in-edges grouped by source
+    DG_HIP(hipMemsetAsync(d_ocur.p, 0, (size_t)nV * 4, s));
+    hipLaunchKernelGGL(jt_out_count_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>());
+    hipLaunchKernelGGL(jt_out_scan_kernel, dim3(1), dim3(1024), 0, s, d_ocur.as<uint32_t>(), d_oo.as<uint32_t>(), d_ocur.as<uint32_t>(), nV);
+    hipLaunchKernelGGL(jt_out_fill_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>(), d_oe.as<uint32_t>(), (uint32_t)S.n_edges);
+    DG_HIP(hipGetLastError());
+    launches += 3;
+
+    auto scores = [&](int l) -> const uint16_t * {                          // the matrix of the transition into level l, in d_sc
+        const int T = lv[l].T;
+        if (!lv[l].coloured || T < 1) return nullptr;
+        hipLaunchKernelGGL(jt_scores_kernel, dim3(jt_blocks(T, 64), (unsigned)std::min(T, 16384)), dim3(JT_THREADS), 0, s, T, lv[l].in_base, lv[l - 1].a0, in_edge, in_dst,
+                           colour_csr(S), S.d_eflag.as<uint8_t>(), S.d_eself.as<uint16_t>(), sc);
+        ++launches;
+        return sc;
+    };
+    auto fill = [&](int32_t *st, int l, int pos) {                          // level l: 0 on every plane of the cell (pos, pos)
+        hipLaunchKernelGGL(jt_fill_kernel, dim3(jt_blocks(lv[l].cells, 65536)), dim3(JT_THREADS), 0, s, st, lv[l].cells, ((int64_t)pos * lv[l].k + pos) * B1, B1);
+        ++launches;
+    };
+    auto forward = [&](const int32_t *prev, int32_t *cur, int l) {
+        const uint16_t *m = scores(l);
+        hipLaunchKernelGGL(jt_forward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, prev, cur, lv[l - 1].k, lv[l].k, B1,
+                           lv[l].a0, lv[l].in_base, lv[l].T, in_off, in_edge, m);
+        ++launches;
+    };
+    // ---- pass 1: the state at every segment's first level ----
+    int32_t *ck = d_ck.as<int32_t>();
+    fill(ck, 0, 0);
+    if (n_seg > 1) {
+        if (int rc = M.get(d_roll, 2 * roll_cells * 4)) return rc;
+        int32_t *roll = d_roll.as<int32_t>();
+        const int32_t *prev = ck;
+        int g = 0;
+        for (int l = 1; l <= seg[n_seg - 1]; ++l) {
+            int32_t *dst;
+            if (l == seg[g + 1]) dst = ck + ck_off[++g];
+            else { dst = roll + (l & 1) * roll_cells; ++twice; }
+            forward(prev, dst, l);
+            prev = dst;
+        }
+        DG_HIP(hipGetLastError());
+        DG_HIP(hipStreamSynchronize(s));                                    // the rolling states go before the segment buffers come
+        M.drop(d_roll);
+    }
+    // ---- the segments, last first ----
+    if (int rc = M.get(d_seg, seg_cells * 4)) return rc;
+    if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
+    int32_t *back = d_back.as<int32_t>();
+    std::vector<const int32_t *> Fp((size_t)L, nullptr);
+    for (int g = n_seg - 1; g >= 0; --g) {
+        const int a = seg[g], e = seg[g + 1];
+        Fp[a] = ck + ck_off[g];
+        int64_t at = 0;
+        for (int l = a + 1; l < e; ++l) {
+            int32_t *dst = d_seg.as<int32_t>() + at;
+            at += lv[l].cells;
+            forward(Fp[l - 1], dst, l);
+            Fp[l] = dst;
+        }
+        for (int l = e - 1; l >= a; --l) {
+            int32_t *cur = back + (l & 1) * level_cells;
+            if (l == L - 1) {
+                const int sink = nV - 1 - lv[l].a0;
+                fill(cur, l, sink);
+                DG_HIP(hipMemcpyAsync(d_lvlmax.as<int32_t>() + L, Fp[l] + ((int64_t)sink * lv[l].k + sink) * B1 + budget, 4, hipMemcpyDeviceToDevice, s));
+            } else {
+                const uint16_t *m = scores(l + 1);
+                hipLaunchKernelGGL(jt_backward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s,
+                                   (const int32_t *)(back + ((l + 1) & 1) * level_cells), cur, lv[l].k, lv[l + 1].k, B1, lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base, lv[l + 1].T,
+                                   d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
+                ++launches;
+            }
+            hipLaunchKernelGGL(jt_combine_kernel, dim3((unsigned)std::min(lv[l].k, row_blocks)), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)cur, lv[l].k, B1, lv[l].a0,
+                               d_row.as<int32_t>(), d_J.as<int32_t>(), (int)n, d_called.as<int32_t>(), L, l, vertex_class ? d_cls.as<int32_t>() : nullptr,
+                               d_part.as<long long>(), d_cval.as<int32_t>());
+            hipLaunchKernelGGL(jt_records_kernel, dim3((unsigned)n), dim3(JT_THREADS), 0, s, lv[l].k, lv[l].a0, d_J.as<int32_t>(), d_part.as<long long>(), d_cval.as<int32_t>(),
+                               d_called.as<int32_t>(), L, l, d_rec.as<dg_dp_genotype_margin>(), d_lvlmax.as<int32_t>());
+            launches += 2;
+        }
+        DG_HIP(hipGetLastError());
+    }
+    // the caller's arrays are written only if the call succeeds
+    std::vector<dg_dp_genotype_margin> recs((size_t)(n * L));
+    std::vector<int32_t> lvlmax((size_t)L + 1), vals(vertex_values ? (size_t)nV : 0);
+    DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_genotype_margin), hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(lvlmax.data(), d_lvlmax.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (vertex_values) DG_HIP(hipMemcpyAsync(vals.data(), d_J.p, (size_t)nV * 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipStreamSynchronize(s));
+    S.jt_stats[0] = n_seg; S.jt_stats[1] = twice; S.jt_stats[2] = M.peak; S.jt_stats[3] = launches;
+    const int32_t V = lvlmax[(size_t)L];
+    // the closing check: on every level the best pair through any cell is the best pair
+    for (int l = 0; l < L; ++l)
+        if (lvlmax[l] != V) {
+            set_error("%s: level %d: the largest through-value is %d, the sink's value at budget %d is %d", FN, l, lvlmax[l], budget, V);
+            return DG_ERR_STATE;
+        }
+    memcpy(levels, recs.data(), recs.size() * sizeof(dg_dp_genotype_margin));
+    if (vertex_values) memcpy(vertex_values, vals.data(), vals.size() * 4);
+    *best_value = V;
+    return DG_OK;
+}
+
+int dp_genotype_stats(dg_ctx *c, int64_t *out, int n) {
+    if (!out || n < 4) { set_error("dg_dp_get_genotype_stats: out needs 4 words"); return DG_ERR_ARG; }
+    if (!c->dp) { set_error("dg_dp_get_genotype_stats: no graph loaded"); return DG_ERR_STATE; }
+    for (int q = 0; q < 4; ++q) out[q] = c->dp->jt_stats[q];
+    return DG_OK;
+}
+
+}  // namespace dgi
+
+extern "C" int dg_dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+                                      int32_t *vertex_values, int32_t *best_value) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_genotype_margins(c, called, n_called, budget, vertex_class, levels, vertex_values, best_value);
+}
+
+extern "C" int dg_dp_get_genotype_stats(dg_ctx *c, int64_t *out, int n) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_genotype_stats(c, out, n);
+}

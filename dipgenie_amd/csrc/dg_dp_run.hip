@@ -524,7 +524,7 @@ extern "C" int dg_dp_list_sweep_variants(char *buf, int cap) {
     return DG_OK;
 }
 // Options: parity / test knobs (digest, fast, adaptive_rc, coop, rowx, lean_chain, segment_cells, delta_cap_entries, lattice_chunk_cells,
-// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes, partner_wide, objective_lds_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
+// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes, partner_wide, joint_state_bytes, objective_lds_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
 // One row per key: its DpOptions field, the lower clamp, whether v <= 0 asks for the default (that of a fresh DpOptions).
 typedef dgi::DpOptions DpO;
 static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t lo; bool nonpos_is_default; } dp_option_keys[] = {
@@ -536,6 +536,7 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"side_stream", &DpO::side_stream, -1, false}, {"plane_limit", &DpO::plane_limit, 0, false}, {"test_poison_level", &DpO::test_poison_level, 0, false},
     {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"test_force_rc", &DpO::test_force_rc, 0, false}, {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
     {"partner_wide", &DpO::partner_wide, 0, false},                // 0..2: clamped from above below
+    {"joint_state_bytes", &DpO::joint_state_bytes, 0, true},
     {"objective_lds_bytes", &DpO::objective_lds_bytes, 0, true},   // clamped from above to objective_lds_limit(): the device's LDS per workgroup
     // read by dg_dp_load_graph: in effect at the next load
     {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},

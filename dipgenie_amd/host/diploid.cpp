@@ -96,7 +96,7 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
@@ -104,6 +104,8 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.site_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_call_margins)) return "--site-margins: this backend has no dp_call_margins";
     // and so does --objective-table: the answers' paths stay on the device
     if (!p.opt.objective_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_objectives)) return "--objective-table: this backend has no dp_answer_objectives";
+    // and --genotype-margins: the called genotype is the answer that stays behind
+    if (!p.opt.genotype_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_margins)) return "--genotype-margins: this backend has no dp_genotype_margins";
     if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
     std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
     for (const ChainAnswer &a : answers) res.push_back(a.res);
@@ -324,6 +326,17 @@ std::string write_raw_int32(const std::string &path, const std::vector<int32_t> 
     return f.good() ? "" : "write to " + path + " failed";
 }
 
+// what the margin tables call a vertex: the panel haplotype it lies on and the GFA segment it copies; '.' for what does not exist
+std::string panel_name(const Pipeline &p, const ExpandedGraph &g, int v) {
+    const int h = v >= 0 ? g.haplotype.at(v) : -1;
+    return h >= 0 && h < (int)p.hap_id2name.size() ? p.hap_id2name[h] : ".";
+}
+std::string segment_name(const Pipeline &p, const ExpandedGraph &g, int v) {
+    if (v < 0 || g.orig_len.at(v) < 1) return ".";
+    const int32_t seg = g.orig_pool[g.orig_off[v]];
+    return seg >= 0 && seg < (int32_t)p.node_name.size() ? p.node_name[seg] : ".";
+}
+
 // level  hap  vertex  panel_hap  segment  value  alt_vertex  alt_panel_hap  alt_segment  margin: levels 1 .. L - 2, haplotype 1 before
 // haplotype 2 within a level; '.' for what does not exist
 std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls) {
@@ -331,15 +344,8 @@ std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::v
     const int L = (int)g.level_off.size() - 1;
     std::vector<dg_dp_call_margin> rec(2 * (size_t)L);
     if (p.be.dp_call_margins(p.be.ctx, p.opt.R, cls.data(), rec.data(), nullptr) != 0) return backend_error(p.be, "dp_call_margins");
-    auto panel = [&](int v) -> std::string {
-        const int h = v >= 0 ? g.haplotype.at(v) : -1;
-        return h >= 0 && h < (int)p.hap_id2name.size() ? p.hap_id2name[h] : ".";
-    };
-    auto segment = [&](int v) -> std::string {
-        if (v < 0 || g.orig_len.at(v) < 1) return ".";
-        const int32_t seg = g.orig_pool[g.orig_off[v]];
-        return seg >= 0 && seg < (int32_t)p.node_name.size() ? p.node_name[seg] : ".";
-    };
+    auto panel = [&](int v) { return panel_name(p, g, v); };
+    auto segment = [&](int v) { return segment_name(p, g, v); };
     SiteMargins &sm = p.sum.site_margins;
     sm = SiteMargins();
     sm.set = true;
@@ -364,6 +370,53 @@ std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::v
     f.close();
     if (!f.good()) return "write to " + p.opt.site_margins + " failed";
     sm.wall_s = now_s() - t0;
+    return "";
+}
+
+// level  vertex1  panel_hap1  segment1  vertex2  panel_hap2  segment2  value  alt_vertex1  alt_segment1  alt_vertex2  alt_segment2  alt_value  margin:
+// levels 1 .. L - 2; the called cell is the answer at -R (its two paths), the alternative the best cell of another genotype with both
+// haplotypes free; '.' for what does not exist (no other genotype reachable; every field if no pair of paths fits -R)
+std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls) {
+    const double t0 = now_s();
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    std::vector<int32_t> paths(2 * (size_t)L);
+    if (be.dp_answer_paths(be.ctx, p.opt.R, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+    const bool fits = paths[0] >= 0;
+    std::vector<dg_dp_genotype_margin> rec((size_t)L);
+    int32_t best = 0;
+    GenotypeMargins &gm = p.sum.genotype_margins;
+    gm = GenotypeMargins();
+    gm.set = true;
+    if (fits) {
+        if (be.dp_genotype_margins(be.ctx, paths.data(), 1, p.opt.R, cls.data(), rec.data(), nullptr, &best) != 0) return backend_error(be, "dp_genotype_margins");
+        int64_t stats[4] = {0, 0, 0, 0};
+        if (be.dp_genotype_stats && be.dp_genotype_stats(be.ctx, stats, 4) != 0) return backend_error(be, "dp_genotype_stats");
+        gm.segments = stats[0];
+    }
+    std::string text = "level\tvertex1\tpanel_hap1\tsegment1\tvertex2\tpanel_hap2\tsegment2\tvalue\talt_vertex1\talt_segment1\talt_vertex2\talt_segment2\talt_value\tmargin\n";
+    for (int l = 1; l < L - 1; ++l) {
+        text += std::to_string(l);
+        if (!fits) { text += "\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\n"; continue; }
+        const dg_dp_genotype_margin &r = rec[(size_t)l];
+        text += '\t' + std::to_string(r.vertex1) + '\t' + panel_name(p, g, r.vertex1) + '\t' + segment_name(p, g, r.vertex1) + '\t' + std::to_string(r.vertex2) + '\t' +
+                panel_name(p, g, r.vertex2) + '\t' + segment_name(p, g, r.vertex2) + '\t' + std::to_string(r.value) + '\t';
+        if (r.alt_vertex1 >= 0) {
+            const int32_t margin = r.value - r.alt_value;
+            text += std::to_string(r.alt_vertex1) + '\t' + segment_name(p, g, r.alt_vertex1) + '\t' + std::to_string(r.alt_vertex2) + '\t' + segment_name(p, g, r.alt_vertex2) + '\t' +
+                    std::to_string(r.alt_value) + '\t' + std::to_string(margin);
+            gm.with_alternative++;
+            if (margin == 0) gm.margin0++;
+            else if (margin > 0 && (gm.min_positive_margin < 0 || margin < gm.min_positive_margin)) gm.min_positive_margin = margin;
+        } else text += ".\t.\t.\t.\t.\t.";
+        text += '\n';
+    }
+    std::ofstream f(p.opt.genotype_margins, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open genotype margins file " + p.opt.genotype_margins;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + p.opt.genotype_margins + " failed";
+    gm.wall_s = now_s() - t0;
     return "";
 }
 
@@ -441,6 +494,16 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
             err = "--site-margins: widest level " + std::to_string(widest) + " x (R + 1) " + std::to_string(R + 1) + " exceeds 16384 cells";
             return -1;
         }
+    }
+    if (!opt.genotype_margins.empty()) {                               // the limits of dg_dp_genotype_margins, known before the DP too
+        int64_t widest = 1;
+        for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
+        if (widest > 32767 || (int64_t)R + 1 > 4096) {
+            err = "--genotype-margins: widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            return -1;
+        }
+    }
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty()) {  // both tables speak of alleles
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
@@ -485,6 +548,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         t0 = now_s();
         if (failed(write_site_margins(*this, g, classes), err)) return -1;
         stamp("site_margins", t0);
+    }
+    if (!opt.genotype_margins.empty()) {
+        t0 = now_s();
+        if (failed(write_genotype_margins(*this, g, classes), err)) return -1;
+        stamp("genotype_margins", t0);
     }
     if (!opt.tag_reads.empty()) {
         t0 = now_s();

@@ -124,6 +124,18 @@ static int b_dp_call_margins(void *c, int32_t budget, const int32_t *cls, dg_dp_
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_call_margins(x, budget, cls, levels, paths) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_answer_paths(void *c, int32_t budget, int32_t *paths) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_answer_paths(x, budget, paths) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_genotype_margins(void *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *cls, dg_dp_genotype_margin *levels, int32_t *vv, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_genotype_margins(x, called, n, budget, cls, levels, vv, best) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_genotype_stats(void *c, int64_t *out, int n) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_genotype_stats(x, out, n) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_answer_objectives(x, budgets, n, out) : DG_ERR_NO_DEVICE;
@@ -239,6 +251,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --budget-table FILE   (MI355X build) with --budgets: one line r, DP value, r1, r2, len1, len2 per listed limit\n");
     fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
     fprintf(fp, "    --wide-levels         (MI355X build) with --site-margins: lift its limit of 16384 cells (widest level x (R + 1)) by keeping the level state in device memory (then: widest level <= 32767, <= 16777216 cells)\n");
+    fprintf(fp, "    --genotype-margins FILE   (MI355X build, -p2) per level: the genotype of the answer at -R against the best other genotype, both haplotypes free, and the margin (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
@@ -260,7 +273,7 @@ int main(int argc, char **argv) {
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
     std::string budgets_arg;
-    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false;
+    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -278,6 +291,12 @@ int main(int argc, char **argv) {
                 have_site_margins = true;                              // (a missing value is an empty file name: refused below)
                 const char *v = val("--site-margins");
                 p.opt.site_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--genotype-margins", 18) && (argv[i][18] == 0 || argv[i][18] == '=')) {
+                have_genotype_margins = true;                          // (a missing value is an empty file name: refused below)
+                const char *v = val("--genotype-margins");
+                p.opt.genotype_margins = v ? v : "";
                 continue;
             }
             if (!strcmp(argv[i], "--wide-levels")) { p.opt.wide_levels = true; continue; }
@@ -356,6 +375,12 @@ int main(int argc, char **argv) {
         if (p.opt.site_margins.empty()) { fprintf(stderr, "[E::main] --site-margins needs a file name\n"); return 1; }
     }
     if (p.opt.wide_levels && !have_site_margins) { fprintf(stderr, "[E::main] --wide-levels goes with --site-margins: it lifts the cell limit of that option alone\n"); return 1; }
+    // --genotype-margins FILE: the same
+    if (have_genotype_margins) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --genotype-margins describes the genotype of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.genotype_margins.empty()) { fprintf(stderr, "[E::main] --genotype-margins needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --genotype-margins does not go with --gpus / --shard-transport\n"); return 1; }
+    }
     // --objective-table FILE: the same
     if (have_objective_table) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
@@ -378,6 +403,9 @@ int main(int argc, char **argv) {
     p.be.dp_call_margins = b_dp_call_margins;
     p.be.dp_answer_objectives = b_dp_answer_objectives;
     p.be.tag_reads = b_tag_reads;
+    p.be.dp_answer_paths = b_dp_answer_paths;
+    p.be.dp_genotype_margins = b_dp_genotype_margins;
+    p.be.dp_genotype_stats = b_dp_genotype_stats;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -446,6 +474,12 @@ int main(int argc, char **argv) {
                     if (sm.min_positive_margin[h] >= 0) fprintf(f, "%d}", sm.min_positive_margin[h]); else fprintf(f, "null}");
                 }
                 fprintf(f, "], \"wall_s\": %.6f}", sm.wall_s);
+            }
+            if (p.sum.genotype_margins.set) {                           // over the levels 1 .. L - 2; min_positive_margin null: none is positive
+                const dg::GenotypeMargins &gm = p.sum.genotype_margins;
+                fprintf(f, ", \"genotype_margins\": {\"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", (long long)gm.with_alternative, (long long)gm.margin0);
+                if (gm.min_positive_margin >= 0) fprintf(f, "%d", gm.min_positive_margin); else fprintf(f, "null");
+                fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)gm.segments, gm.wall_s);
             }
             if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
                 fprintf(f, ", \"objectives\": [");

@@ -71,6 +71,13 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // optional (--tag-reads): every read's distinct minimizers against the minimizer lists of the two answer sequences (dg_sketch_tag_reads)
     int (*tag_reads)(void *, const char *bases, const int64_t *read_off, int64_t n_reads, int k, int w, const uint64_t *hash_a, int64_t n_a,
                      const uint64_t *hash_b, int64_t n_b, dg_read_tag *out) = nullptr;
+    // optional (--genotype-margins): after dp_run_budgets, the answer at a budget as two rows of vertex ids (dg_dp_get_answer_paths), the
+    // margin of its genotype against the best other genotype per level with both haplotypes free (dg_dp_genotype_margins), and that
+    // call's statistics (dg_dp_get_genotype_stats)
+    int (*dp_answer_paths)(void *, int32_t budget, int32_t *paths) = nullptr;
+    int (*dp_genotype_margins)(void *, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+                               int32_t *vertex_values, int32_t *best_value) = nullptr;
+    int (*dp_genotype_stats)(void *, int64_t *out, int n) = nullptr;
 };
 
 struct Options {
@@ -93,6 +100,7 @@ struct Options {
     std::string site_margins;    // (ours) --site-margins: TSV of the call margins of both haplotypes of the answer at -R, per level (diploid)
     bool wide_levels = false;    // (ours) --wide-levels, with --site-margins: the backend keeps the level state of dp_call_margins in device memory where LDS cannot hold it
     std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
+    std::string genotype_margins; // (ours) --genotype-margins: TSV of the margin of the answer's genotype at -R against the best other genotype, per level, both haplotypes free (diploid)
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -182,6 +190,13 @@ struct SiteMargins {          // --site-margins: per haplotype, over the levels 
     double wall_s = 0;
 };
 
+struct GenotypeMargins {      // --genotype-margins: over the levels 1 .. L - 2
+    bool set = false;
+    int64_t with_alternative = 0, margin0 = 0, segments = 0;
+    int32_t min_positive_margin = -1;            // -1: no level with a positive margin
+    double wall_s = 0;
+};
+
 struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
     bool set = false;
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
@@ -197,6 +212,7 @@ struct Summary {              // what tests and the CLI report
     std::vector<std::pair<std::string, double>> stage_s;
     std::vector<BudgetRow> budget_rows;   // --budgets: in the order listed
     SiteMargins site_margins;
+    GenotypeMargins genotype_margins;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
 };
@@ -223,7 +239,7 @@ class Pipeline {
     uint32_t n_vtx = 0, num_walks = 0;
     std::vector<std::vector<uint32_t>> adj_list;
     std::vector<std::string> node_seq;
-    std::vector<std::string> node_name;    // GFA segment names (kept with --site-margins only)
+    std::vector<std::string> node_name;    // GFA segment names (kept with --site-margins / --genotype-margins only)
     std::vector<std::vector<uint32_t>> paths;
     std::vector<int32_t> top_order_map;
     std::vector<std::string> hap_id2name;

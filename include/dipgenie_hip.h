@@ -226,6 +226,45 @@ int dg_dp_call_margins(dg_ctx *, int32_t budget, const int32_t *vertex_class, dg
  * that call's widest level x (largest budget + 1).  A call that fails before the route is chosen, or has nothing to launch (n = 0, an
  * unreachable budget of dg_dp_call_margins), leaves both as they were.  DG_ERR_ARG: a null argument. */
 int dg_dp_get_partner_route(dg_ctx *, int32_t *route, int64_t *cells);
+/* Genotype margins: the best pair of paths through every cell of a level, with BOTH haplotypes free (dg_dp_call_margins holds one
+ * fixed).  d(u1, u2 -> v1, v2) is what the sweep adds for the transition: inter + symd; parallel edges are one edge; an edge pair
+ * weighs w1 + w2, also when both paths take the same edge.  budget b >= 0 means "at most" and is independent of the graph's R.
+ * Forward: F_0[src, src][r] = 0 for r = 0..b; F_l[i][j][r] = max over the in-edge pairs (u -> i, w1), (v -> j, w2) with
+ * r - w1 - w2 >= 0 and a reachable source cell of F_{l-1}[u][v][r - w1 - w2] + d, NEG_INF where there is none (the sweep's values).
+ * Backward: B_{L-1}[sink, sink][r] = 0; B_l[i][j][r] = max over the out-edge pairs (i -> i', w1), (j -> j', w2) with
+ * r - w1 - w2 >= 0 and a reachable destination cell of d + B_{l+1}[i'][j'][r - w1 - w2].  Through-value: T_l[i][j] = max over
+ * r = 0..b with both cells reachable of F_l[i][j][r] + B_l[i][j][b - r], NEG_INF if there is none: the best value of any ordered pair
+ * of source -> sink paths (p, q) with p[l] = i, q[l] = j and r(p) + r(q) <= b.  T is symmetric.  V_b = F_{L-1}[sink, sink][b], and
+ * on every level the maximum of T is V_b.  J[v] = max_j T_l[v][j], the joint marginal of vertex v (>= the M of
+ * dg_dp_partner_marginals for either half of an optimal pair).  The genotype of a cell is the unordered pair of its vertices' classes. */
+typedef struct dg_dp_genotype_margin {
+    int32_t vertex1, vertex2;         /* the called cell of the level */
+    int32_t value;                    /* T at the called cell (NEG_INF: no pair within the budget passes through it) */
+    int32_t alt_vertex1, alt_vertex2; /* the cell with the largest T among the cells of another genotype than the called one, alt_vertex1 <= alt_vertex2; among equals the smallest alt_vertex1, then the smallest alt_vertex2; -1, -1 if no such cell is reachable */
+    int32_t alt_value;                /* its T; NEG_INF if there is none */
+    int32_t reserved[2];              /* written as 0 */
+} dg_dp_genotype_margin;
+/* called (host) = [n_called][2][n_levels] vertex ids: per query one cell per level (a list of cells: no edge is required between
+ * levels), every id inside its level; 1 <= n_called <= 256.  vertex_class (host) = [n_vertices] or NULL (every vertex is its own
+ * class), as for dg_dp_call_margins.  levels (host) = [n_called][n_levels]; vertex_values (host) = [n_vertices] receives J, may be
+ * NULL; *best_value = V_b.  value - alt_value is the margin of the called genotype at that level: a per-site genotype quality.  It
+ * is negative where the called cell is not optimal: an answer, not an error.  A budget that no pair fits is an answer too: NEG_INF /
+ * -1 everywhere, DG_OK.  Needs dg_dp_load_graph only and leaves the sink values, answer paths, digests, timing and resident
+ * score-delta window of an earlier run as they were.  Device memory: a level's state is 4 * width^2 * (b + 1) bytes; the forward
+ * states are kept for one segment of levels at a time (option joint_state_bytes bounds a segment's states, a segment holds at least
+ * one level) plus one state per segment, recomputed segment by segment from the last to the first, beside two backward states of the
+ * widest level, one score matrix of the largest coloured transition (2 * in-edges^2 bytes) and 8 bytes per edge; all of it is reserved
+ * inside the call and freed when it returns.  Closing check: the maximum of T is V_b on every level, DG_ERR_STATE naming the level
+ * otherwise.  DG_ERR_STATE: no graph loaded.  DG_ERR_ARG: a null called, levels or best_value, n_called < 1, a negative budget, an id
+ * outside its level (the message names the first such (query, row 0|1, level), in that order of significance).
+ * DG_ERR_UNSUPPORTED (the message names both numbers): widest level > 32767, budget + 1 > 4096, n_called > 256.  A failed call
+ * writes nothing.  Synchronises. */
+int dg_dp_genotype_margins(dg_ctx *, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class,
+                           dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value);
+/* measurement: the last successful dg_dp_genotype_margins on this context: out[0] = segments, out[1] = levels whose forward state was
+ * computed twice, out[2] = peak bytes of device memory the call had reserved, out[3] = kernel launches; n >= 4 (zeros before the
+ * first call).  DG_ERR_ARG: null out or n < 4.  DG_ERR_STATE: no DP state on this context yet. */
+int dg_dp_get_genotype_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
@@ -277,6 +316,7 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   score_slab_bytes n    bound of the path staging buffer of dg_dp_score_paths (default 256 MB, n <= 0 restores it; a slab holds at least one pair)
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, and of what a slab of dg_dp_partner_marginals holds (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   partner_wide 0|1|2    level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 (default) never -- beyond 16384 cells the call is refused; 1 for a call beyond 16384 cells; 2 for every call (tests, A/B timing)
+ *   joint_state_bytes n   bound of the forward states that dg_dp_genotype_margins keeps for one segment of levels (default 8 GB, n <= 0 restores it; a segment holds at least one level)
  *   objective_lds_bytes n largest size of a pair's four colour bitmaps that dg_dp_objective_paths / dg_dp_answer_objectives keep in LDS; larger ones live in device memory (default 131072, n <= 0 restores it; clamped to the device's LDS per workgroup)
  *   pair_levels 0|1       1 (default): adjacent low-fan-in levels run as one composed launch where the run allows it (unsegmented, all planes, digest 0,
  *                         fast 1, adaptive_rc 1, test_force_rc 0); 0: every level its own launch (next load)
