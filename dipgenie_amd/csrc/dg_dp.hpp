@@ -189,6 +189,8 @@ struct DpOptions {
     int64_t partner_wide = 0;                           // partner_wide: the level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 never (LDS only), 1 for a call beyond the LDS limit, 2 always
     int64_t pair_levels = 1;                            // pair_levels: adjacent low-fan-in levels run as one composed launch (dg_dp_pairs.hip); next load
     int64_t pair_min = 4096;                            // pair_min: the composed tables are built and used only for a graph with at least this many pairs; next load
+    int64_t pair_digest = 0;                            // pair_digest: 1 = with digest 1 the pair launches stay, in the pair kernel's digest form (tests: the later level's digest; the earlier level's entry stays 0)
+    int64_t test_force_pair_rc = 0;                     // test_force_pair_rc: n in PAIR_RCS = every pair launch takes chunks of n recombination counts; any other value: the cost model
     int64_t joint_state_bytes = (int64_t)8 << 30;       // joint_state_bytes: bound of the forward states of one segment of dg_dp_genotype_margins (a segment holds at least one level)
     int64_t objective_lds_bytes = 131072;              // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
 };

@@ -271,8 +271,9 @@ struct Run {
         }
 #endif
         sweep_init_state(S, s);
-        // level pairs: the unsegmented pass over all planes, digests off, the per-level choice of the fast kernels left free
-        X.pairs_ok = !S.pairs.empty() && S.opt.pair_levels && n_seg == 1 && n_win() == 1 && !X.digest && S.opt.use_fast && S.opt.adaptive_rc && S.opt.test_force_rc == 0 &&
+        // level pairs: the unsegmented pass over all planes, digests off (or pair_digest: the pair kernel's digest form), the per-level choice
+        // of the fast kernels left free
+        X.pairs_ok = !S.pairs.empty() && S.opt.pair_levels && n_seg == 1 && n_win() == 1 && (!X.digest || S.opt.pair_digest) && S.opt.use_fast && S.opt.adaptive_rc && S.opt.test_force_rc == 0 &&
                      X.small_state && X.rp_active == S.RP;
         if (n_seg == 1) {
             // whole lattice resident: one sweep with back-pointers, then the chain walk chunk by chunk, last first
@@ -534,7 +535,8 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"rc_cap", &DpO::rc_cap, 0, true}, {"max_blocks", &DpO::max_blocks, 0, true}, {"bp_nt_min_cells", &DpO::bp_nt_min_cells, 0, false}, {"warm_ahead", &DpO::warm_ahead, 0, false},
     {"graph_batch", &DpO::graph_batch, -1, false}, {"l2_prefetch", &DpO::l2_prefetch, 0, false}, {"delta_overlap", &DpO::delta_overlap, 0, false}, {"pf_far", &DpO::pf_far, 0, false},
     {"side_stream", &DpO::side_stream, -1, false}, {"plane_limit", &DpO::plane_limit, 0, false}, {"test_poison_level", &DpO::test_poison_level, 0, false},
-    {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"test_force_rc", &DpO::test_force_rc, 0, false}, {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
+    {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"test_force_rc", &DpO::test_force_rc, 0, false}, {"pair_digest", &DpO::pair_digest, 0, false}, {"test_force_pair_rc", &DpO::test_force_pair_rc, 0, false},
+    {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
     {"partner_wide", &DpO::partner_wide, 0, false},                // 0..2: clamped from above below
     {"joint_state_bytes", &DpO::joint_state_bytes, 0, true},
     {"objective_lds_bytes", &DpO::objective_lds_bytes, 0, true},   // clamped from above to objective_lds_limit(): the device's LDS per workgroup

@@ -526,10 +526,15 @@ __device__ __forceinline__ void merge_best_pair(int ov, uint32_t oo, uint32_t om
     bm = take ? om : bm;
 }
 
-template <int RC>
+// DG: empty -- the kernels the product runs, dp_sweep_pair_kernel<RC> -- or one trailing unsigned long long *digest (parity runs, options
+// digest + pair_digest): the head lane then also adds the oracle's term of every reachable cell of level l -- its predecessor is the
+// middle cell in bmid -- to digest[lvl]; level l - 1 is never materialised and keeps the 0 of the run's memset.
+template <int RC, typename... DG>
 __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2,
                                                             int nblocks, int rp_k, int pad_bytes, int dT1, int dT2, uint32_t buf_bytes,   // 16 dwords: preloaded
-                                                            int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl) {
+                                                            int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl,
+                                                            DG... digest) {
+    constexpr bool DIGEST = sizeof...(DG) != 0;
     publish_level(progress, lvl);
     const int lane = threadIdx.x & 63;
     const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), r0 = (int)blockIdx.y * RC, i2 = (int)blockIdx.z;
@@ -597,6 +602,7 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l,
     }
     const int pj2 = lane_up1(j2);
     const bool head = act & ((lane == 0) | (pj2 != j2));
+    unsigned long long dsum = 0;
     if (head) {
         const int k1 = kk & 0xFF, k2 = kk >> 8;
 #pragma unroll
@@ -613,8 +619,16 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l,
                         bp1[((int)(m >> 16) * RP + r2 - (int)(m & 0xFFu)) * k1 + (int)((m >> 8) & 0xFFu)] = (uint16_t)~bord[q];
                     }
                 }
+                if (DIGEST && bval[q] != NEG_INF) {
+                    const unsigned long long o = ((unsigned long long)r2 * k2 + i2) * k2 + j2;   // oracle's r-major index
+                    dsum += digest_term(bval[q], o, bmid[q] >> 16, (bmid[q] >> 8) & 0xFFu);
+                }
             }
         }
+    }
+    if constexpr (DIGEST) {
+        unsigned long long *const acc[] = {digest...};
+        if (dsum) atomicAdd(&acc[0][lvl], dsum);
     }
 }
 
@@ -882,6 +896,7 @@ int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
 
 // the pair's chunk size by choose_rc's cost model: the wave's chain is the largest composed in-degree
 static int choose_pair_rc(const DpState &S, const PairDesc &p) {
+    for (int q = 0; q < N_PAIR_RCS; ++q) if (S.opt.test_force_pair_rc == PAIR_RCS[q]) return q;     // tests: this chunk size for every pair
     int best_q = 0;
     double best = 1e300;
     for (int q = 0; q < N_PAIR_RCS; ++q) {
@@ -896,10 +911,12 @@ std::string pair_variant_name(int q) { return "dp_sweep_pair_kernel<" + std::to_
 
 template <int Q = 0>
 static void launch_pair_rc(int q, dim3 grid, hipStream_t s, const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2, int nblocks, int rp_k,
-                           int pad_bytes, int dT1, int dT2, uint32_t buf_bytes, int32_t *nxt, uint16_t *bp1, uint16_t *bp2, int kk, int nt, int *progress, int lvl) {
+                           int pad_bytes, int dT1, int dT2, uint32_t buf_bytes, int32_t *nxt, uint16_t *bp1, uint16_t *bp2, int kk, int nt, int *progress, int lvl,
+                           unsigned long long *digest) {                // digest: null = the product's kernel
     if constexpr (Q < N_PAIR_RCS) {
-        if (q == Q) hipLaunchKernelGGL((dp_sweep_pair_kernel<PAIR_RCS[Q]>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl);
-        else launch_pair_rc<Q + 1>(q, grid, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl);
+        if (q != Q) launch_pair_rc<Q + 1>(q, grid, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl, digest);
+        else if (digest) hipLaunchKernelGGL((dp_sweep_pair_kernel<PAIR_RCS[Q], unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl, digest);
+        else hipLaunchKernelGGL((dp_sweep_pair_kernel<PAIR_RCS[Q]>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl);
     }
 }
 
@@ -918,7 +935,7 @@ int sweep_launch_pair(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
     const uint16_t *dm1 = dT1 ? F.delta + d1.delta_off : F.delta_zero, *dm2 = dT2 ? F.delta + d2.delta_off : F.delta_zero;
     const int nt = (int64_t)d2.k2 * d2.k2 * S.RP >= S.opt.bp_nt_min_cells ? 1 : 0;
     launch_pair_rc(q, grid, s, S.d_prow.as<uint2>() + p.row_first, S.d_pslots.as<uint4>() + p.slot_first, cur, dm1, dm2, p.nblocks, S.RP | (p.k0 << 13), F.pad_bytes, dT1, dT2,
-                   F.buf_bytes, nxt, F.bp ? F.bp + d1.bp_off : nullptr, F.bp ? F.bp + d2.bp_off : nullptr, p.k1 | (p.k2 << 8), nt, F.progress, l);
+                   F.buf_bytes, nxt, F.bp ? F.bp + d1.bp_off : nullptr, F.bp ? F.bp + d2.bp_off : nullptr, p.k1 | (p.k2 << 8), nt, F.progress, l, X.digest ? F.digest : nullptr);
     X.flip ^= 1;
     X.pair_hist.n[q]++;
     return DG_OK;

@@ -321,6 +321,9 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   pair_levels 0|1       1 (default): adjacent low-fan-in levels run as one composed launch where the run allows it (unsegmented, all planes, digest 0,
  *                         fast 1, adaptive_rc 1, test_force_rc 0); 0: every level its own launch (next load)
  *   pair_min n            the composed tables are built and used only for a graph with at least n such pairs (default 4096; next load)
+ *   pair_digest 0|1       tests: 1 = with digest 1 the pair launches stay and run the pair kernel's digest form: the later level of a pair gets the
+ *                         oracle's digest, the earlier level (never materialised) keeps 0; 0 (default): digest 1 refuses pair launches
+ *   test_force_pair_rc n  tests: n one of the pair kernel's chunk sizes (1, 2, 4) = every pair launch takes it; any other value (default 0): the cost model
  *   host_tables 0|1       0 (default): the sweep's tables are built by device kernels from the uploaded graph; 1: on the host, then uploaded (parity twin; next load)
  *   rc_t0_ns, rc_tg_ps, rc_tw_ps, rc_cap, bp_nt_min_cells, max_blocks, host_threads   cost model / launch tuning
  * This list is documentation: struct DpOptions (csrc/dg_dp.hpp) is authoritative for the defaults, the key table beside dg_dp_set_option for the clamps. */

@@ -1,5 +1,5 @@
 """Graphs and a plain model for the level-pair form of the sweep (tests/test_pair_graphs.py on the CPU, tests/test_gpu_pair_levels.py
-on the GPU) -- test infrastructure.
+and tests/test_gpu_pair_cells.py on the GPU) -- test infrastructure.
 
 A level pair (l - 1, l) is swept by ONE launch as a composed transition from level l - 2 (dipgenie_amd/csrc/dg_dp_pairs.hip).  The
 graphs here are written out edge by edge, so that every in-degree, composed in-degree and composed in-edge count is what the case
@@ -89,18 +89,34 @@ def expected_pairs(g):
     return out
 
 
-def solve_colourless(g, pairs=(), order="ref"):
+DIGEST_PRED_MUL = 0x9E3779B97F4A7C15          # oracle/oracle_dp.cpp: weight of the predecessor term of a level digest
+
+
+def level_digest(k, cells):
+    """the oracle's digest of a level of width k: over its reachable cells {(i, j, r): (value, pred_i, pred_j)}, with t the r-major
+    cell index, the sum mod 2^64 of uint32(value + 1) * (t + 1) + DIGEST_PRED_MUL * (((pred_i << 15) | pred_j) + 1) * (t + 1)"""
+    d = 0
+    for (i, j, r), (v, pi, pj) in cells.items():
+        t = (r * k + i) * k + j
+        d += ((v + 1) & 0xFFFFFFFF) * (t + 1) + DIGEST_PRED_MUL * (((pi << 15) | pj) + 1) * (t + 1)
+    return d & 0xFFFFFFFFFFFFFFFF
+
+
+def solve_colourless(g, pairs=(), order="ref", want_digest=False):
     """The diploid DP on a graph without colours (every score delta 0), as plain loops.  A cell (i, j, r) of level l takes the best
     of state[l - 1][pi][pj][r - wu - wv] over its row in-edges (rank ru) and column in-edges (rank rv); ties go to (ru asc, rv asc).
     For l in `pairs` the levels (l - 1, l) are composed instead: the candidates are (ru2, ru1) x (rv2, rv1) read from level l - 2, ties
     go by order "ref" = (ru2, rv2, ru1, rv1) -- the level-by-level order -- or "ranks" = (ru2, ru1, rv2, rv1), the order of ranks
     within the composed lists; the winner writes the back-pointer of its cell and of the middle cell it came through.  Returns
-    (sink values per plane, p1, p2) with the paths as the oracle lists them: the weight-1 edges and, last, the edge into the sink."""
+    (sink values per plane, p1, p2) with the paths as the oracle lists them: the weight-1 edges and, last, the edge into the sink.
+    want_digest: a fourth entry, the per-level digests by the oracle's definition (level_digest) as Python ints -- of a composed pair
+    the later level's, whose predecessors are the middle cells, and 0 for the earlier level, which is never materialised."""
     assert g.hom_off[-1] == 0 and g.het_off[-1] == 0
     ins, RP, L = in_lists(g), g.R + 1, g.n_levels
     width = [int(g.level_off[l + 1] - g.level_off[l]) for l in range(L)]
     val = {0: {(0, 0, r): 0 for r in range(RP)}}
     bp = {}
+    pred = {}                                                   # level -> {cell: (value, pred_i, pred_j)}
     l = 1
     while l < L:
         b0 = int(g.level_off[l])
@@ -127,6 +143,7 @@ def solve_colourless(g, pairs=(), order="ref"):
                             nxt[(i2, j2, r)] = best[1]
                             bp[(l + 1, i2, j2, r)] = best[2]
                             bp[(l,) + best[3]] = best[4]
+                            pred.setdefault(l + 1, {})[(i2, j2, r)] = (best[1], best[3][0], best[3][1])
             val[l + 1] = nxt
             l += 2
             continue
@@ -139,10 +156,11 @@ def solve_colourless(g, pairs=(), order="ref"):
                         for rv, (pj, wv) in enumerate(ins[b0 + j2]):
                             v = cur.get((pi, pj, r - wu - wv))
                             if v is not None and (best is None or (-v, (ru, rv)) < best[0]):
-                                best = ((-v, (ru, rv)), v)
+                                best = ((-v, (ru, rv)), v, pi, pj)
                     if best is not None:
                         nxt[(i2, j2, r)] = best[1]
                         bp[(l, i2, j2, r)] = best[0][1]
+                        pred.setdefault(l, {})[(i2, j2, r)] = best[1:]
         val[l] = nxt
         l += 1
     sink = [val[L - 1].get((0, 0, r)) for r in range(RP)]
@@ -158,6 +176,8 @@ def solve_colourless(g, pairs=(), order="ref"):
             i, j, r = pi, pj, r - wu - wv
         p1.reverse()
         p2.reverse()
+    if want_digest:
+        return sink, p1, p2, [level_digest(width[lv], pred.get(lv, {})) for lv in range(L)]
     return sink, p1, p2
 
 
@@ -291,3 +311,293 @@ def parity_graph(n_pairable, coloured, seed=0):
     levels = range(1, len(widths) - 1)
     cl = {"none": (), "first": [l for l in levels if l & 1], "second": [l for l in levels if not l & 1], "both": list(levels)}[coloured]
     return layered(900 + 10 * n_pairable + seed, 4, widths, indeg, colour_levels=cl)
+
+
+# ---------------------------------------------------------------------------------------------- the cell-by-cell cases
+# tests/test_gpu_pair_cells.py runs every graph below (and those above) with the pair kernel's digest form, so that every cell of a
+# later level is compared with the oracle; tests/test_pair_graphs.py holds their properties on the CPU.
+COLOUR_MODES = ("neither", "first", "second", "both")
+
+
+def with_colours(g, levels, seed=0, n_colours=10):
+    """g with short hom / het lists, drawn as layered() draws them, on every vertex of the given levels (the other lists stay)"""
+    rng = np.random.default_rng(7000 + seed)
+    hom = {v: g.hom_col[g.hom_off[v]:g.hom_off[v + 1]].tolist() for v in range(g.n_vertices)}
+    het = {v: g.het_col[g.het_off[v]:g.het_off[v + 1]].tolist() for v in range(g.n_vertices)}
+    for l in levels:
+        for v in level_vertices(g, l):
+            if rng.random() < 0.7:
+                hom[v] = rng.integers(0, n_colours, int(rng.integers(1, 4))).tolist()
+            if rng.random() < 0.7:
+                het[v] = (n_colours + rng.integers(0, n_colours, int(rng.integers(1, 4)))).tolist()
+    lists = {}
+    for kind, given in (("hom", hom), ("het", het)):
+        per = [sorted(set(int(x) for x in given[v])) for v in range(g.n_vertices)]
+        off = np.zeros(g.n_vertices + 1, np.int64)
+        off[1:] = np.cumsum([len(x) for x in per])
+        lists[kind + "_off"] = off
+        lists[kind + "_col"] = np.array([c for x in per for c in x], np.int32)
+    return DpGraphArrays(g.R, level_off=g.level_off, out_off=g.out_off, out_dst=g.out_dst, out_w=g.out_w, **lists)
+
+
+def coloured(g, l, mode, seed=0):
+    """the score-delta routes of the pair (l - 1, l).  A transition scores where either of its levels carries a colour, so: "neither"
+    = no colours; "first" = level l - 2 coloured (transition into l - 1 only); "second" = level l coloured (transition into l only);
+    "both" = levels l - 2, l - 1 and l coloured"""
+    return with_colours(g, {"neither": (), "first": (l - 2,), "second": (l,), "both": (l - 2, l - 1, l)}[mode], seed)
+
+
+def delta_routes(g, l):
+    """(the transition into level l - 1 scores, the transition into level l scores)"""
+    has = [any(g.hom_off[v + 1] > g.hom_off[v] or g.het_off[v + 1] > g.het_off[v] for v in level_vertices(g, q)) for q in range(g.n_levels)]
+    return (has[l - 2] or has[l - 1], has[l - 1] or has[l])
+
+
+def _front(k_src, R, rng):
+    """levels 0..2 in front of a pair (3, 4): 4 vertices, then k_src vertices of in-degree 1 (the pair (1, 2) while k_src <= 255)"""
+    return [[(0, j, 0) for j in range(4)], [(int(rng.integers(0, 4)), j, int(rng.random() < 0.4)) for j in range(k_src)]]
+
+
+def _pick(rng, k, d, must=None):
+    """d distinct positions below k in rising order, `must` among them"""
+    s = set() if must is None else {must}
+    while len(s) < d:
+        s.add(int(rng.integers(0, k)))
+    return sorted(s)
+
+
+def width_limit_graph(role, width, R=3):
+    """pair (3, 4) from level 2: the source (2), middle (3) or later (4) level is `width` wide, the other two 6 to 40; in-degree 2 on
+    both levels of the pair, the last position of the wide level is used (position 254 at width 255), the sink has 3 in-edges"""
+    ks, km, kl = {"source": (width, 7, 9), "middle": (6, width, 40), "later": (6, 7, width)}[role]
+    rng = np.random.default_rng(300 + width + len(role))
+    e23 = [(i, m, int(rng.random() < 0.4)) for m in range(km) for i in _pick(rng, ks, 2, ks - 1 if m == 0 else None)]
+    e34 = [(m, j, int(rng.random() < 0.4)) for j in range(kl) for m in _pick(rng, km, 2, km - 1 if j == 0 else None)]
+    e45 = [(0, 0, 0), (1, 0, 1), (kl - 1, 0, 0)]
+    return from_edges(R, [1, 4, ks, km, kl, 1], _front(ks, R, rng) + [e23, e34, e45])
+
+
+def t_limit_graph(T1, R=1):
+    """pair (3, 4): 255 x 255 vertices, exactly T1 in-edges into level 3.  Positions 5..254 of level 3 have 8 in-edges and one
+    successor each (composed in-degree 8 on level 4); positions 0..4 are dead ends that take the remaining T1 - 2,000 in-edges (9
+    and more each: at most 64, so the level stays lean).  The in-edges of position 254 are the delta rows T1 - 8 .. T1 - 1."""
+    rng = np.random.default_rng(2047)
+    rest = T1 - 2000
+    deg = [9, 9, 9, 9, rest - 36] + [8] * 250
+    assert sum(deg) == T1 and 9 <= deg[4] <= 16
+    e23 = [(i, m, int(rng.random() < 0.4)) for m in range(255) for i in _pick(rng, 16, deg[m])]
+    e34 = [(max(j, 5), j, j & 1) for j in range(255)]
+    e45 = [(0, 0, 0), (100, 0, 1), (254, 0, 0)]
+    return from_edges(R, [1, 4, 16, 255, 255, 1], _front(16, R, rng) + [e23, e34, e45])
+
+
+def t2_max_graph(R=1):
+    """pair (3, 4) with the most in-edges the later level can have: 255 vertices x 8 in-edges over sources of in-degree 1 = 2,040
+    (every in-edge adds at least 1 to the composed in-degree, so 2,047 into the later level cannot be reached under the limit of 8)"""
+    rng = np.random.default_rng(2040)
+    e23 = [(int(rng.integers(0, 16)), m, int(rng.random() < 0.4)) for m in range(255)]
+    e34 = [(m, j, int(rng.random() < 0.4)) for j in range(255) for m in _pick(rng, 255, 8, 254 if j == 254 else None)]
+    e45 = [(0, 0, 0), (100, 0, 1), (254, 0, 0)]
+    return from_edges(R, [1, 4, 16, 255, 255, 1], _front(16, R, rng) + [e23, e34, e45])
+
+
+def lean_limit_graph(n, R=3):
+    """pair (3, 4): position 0 of level 3 is a dead end with n in-edges (64: the level is lean; 65: it takes the general variant and
+    nothing is paired with it); the other five have 2 in-edges, the 8 vertices of level 4 come from two of those (composed 4)"""
+    rng = np.random.default_rng(64)
+    e23 = [(i, 0, i & 1) for i in range(n)] + [(i, m, int(rng.random() < 0.4)) for m in range(1, 6) for i in _pick(rng, 70, 2)]
+    e34 = [(1 + m, j, int(rng.random() < 0.4)) for j in range(8) for m in _pick(rng, 5, 2)]
+    e45 = [(0, 0, 0), (1, 0, 1), (7, 0, 0)]
+    return from_edges(R, [1, 4, 70, 6, 8, 1], _front(70, R, rng) + [e23, e34, e45])
+
+
+def dead_column_graph(dead, R=3):
+    """pair (3, 4) of in-degree 2 on both levels; dead: position 3 of the middle level has no in-edge (and no successor)"""
+    rng = np.random.default_rng(33)
+    e23 = [(i, m, int(rng.random() < 0.4)) for m in range(7) for i in _pick(rng, 6, 2) if not (dead and m == 3)]
+    e34 = [(m, j, int(rng.random() < 0.4)) for j in range(9) for m in _pick(rng, 7, 2, 3 if j == 0 else None)]
+    if dead:
+        e34 = [(m, j, w) for (m, j, w) in e34 if m != 3] + [(4, 0, 1)]          # vertex 0 of level 4 keeps two in-edges
+        e34 = sorted(set(e34), key=lambda e: (e[1], e[0]))
+    e45 = [(0, 0, 0), (1, 0, 1), (8, 0, 0)]
+    return from_edges(R, [1, 4, 6, 7, 9, 1], _front(6, R, rng) + [e23, e34, e45])
+
+
+def wide_budget_graph(R=4096):
+    """R + 1 = 4,097 planes (bit 12 of the plane count, beside the source width from bit 13 on) on levels at most 3 wide: pairs
+    (1, 2), (3, 4), (5, 6), mixed weights"""
+    rng = np.random.default_rng(4096)
+    widths = [1, 2, 3, 3, 2, 3, 1]
+    edges = [[(0, 0, 0), (0, 1, 1)]] + [_rand_edges(rng, widths[l], widths[l + 1], lambda j: 2, 0.5) for l in range(1, 6)]
+    return from_edges(R, widths, edges)
+
+
+def _bundles(n, k, first, wbit):
+    """n in-edges as bundles of parallel edges over the k source positions, starting at position `first`: [(position, weight)];
+    the edges of a bundle share their weight (the loader refuses parallel edges of different weights), bundles alternate by wbit"""
+    size = [n // k + (1 if q < n % k else 0) for q in range(k)]
+    return [((first + q) % k, ((first + q) >> wbit) & 1) for q in range(k) for _ in range(size[q])]
+
+
+RANK_MIXES = [(8, 1), (4, 2), (2, 4), (1, 8)]
+
+
+def rank_graph(mix, R=6):
+    """pair (3, 4), composed in-degree 8 = a in-edges into every vertex of level 4 over middle vertices of b in-edges each, as bundles
+    of parallel edges from 3 (into level 3) and 4 (into level 4) positions: the ranks run up to a - 1 and b - 1 whatever the widths,
+    and bundles of weight 0 and of weight 1 come from neighbouring positions"""
+    a, b = mix
+    e01 = [(0, j, 0) for j in range(3)]
+    e12 = [(j, (j + 1) % 3, j & 1) for j in range(3)]
+    e23 = [(i, m, w) for m in range(4) for (i, w) in _bundles(b, 3, m % 3, 0)]
+    e34 = [(m, j, w) for j in range(4) for (m, w) in _bundles(a, 4, j, 0)]
+    e45 = [(j, 0, j & 1) for j in range(4)]
+    return from_edges(R, [1, 3, 3, 4, 4, 1], [e01, e12, e23, e34, e45])
+
+
+def composed_weights(g, l, v, ins=None):
+    """the set of w2 + w1 over the composed in-edges of vertex v (a vertex id) of level l"""
+    ins = ins or in_lists(g)
+    return {w2 + w1 for (m, w2) in ins[v] for (_, w1) in ins[int(g.level_off[l - 1]) + m]}
+
+
+PLANE_RPS = [1, 2, 3, 4, 5, 7, 19, 41]
+PLANE_WEIGHTS = {"w1": 1.0, "w0": 0.0, "mixed": 0.5}
+
+
+def plane_graph(RP, weights):
+    """pairs (1, 2), (3, 4), (5, 6) of in-degree 2 on RP planes; every edge weighs 1 ("w1": a composed candidate reads plane r2 - 4,
+    and level l is reachable from plane 2 l on), 0 ("w0") or either ("mixed")"""
+    rng = np.random.default_rng(500 + RP)
+    widths = [1, 3, 4, 3, 3, 2, 1]
+    edges = [_rand_edges(rng, widths[l], widths[l + 1], lambda j: 2, PLANE_WEIGHTS[weights]) for l in range(6)]
+    return from_edges(RP - 1, widths, edges)
+
+
+def delta_bound_pair_graph(M=10922):
+    """levels {0}, {1, 2}, {3, 4}, {5, 6}, {7, 8}, {9}, two disjoint chains, all weights 0, R = 1; pairs (1, 2) and (3, 4).  With a =
+    arange(M): the hom lists of the chain vertices alternate a, a + M along a chain and between the chains, the het lists are
+    disjoint blocks of M ids.  From level 2 on, the two chain edges of a transition then score 2 M + 4 M = 6 M = 65,532 against each
+    other with M = 10,922, the largest lists colour_lists_fit_delta accepts with both kinds: both transitions of the pair (3, 4)."""
+    a = list(range(M))
+    edges = [[(0, 0, 0), (0, 1, 0)]] + [[(0, 0, 0), (1, 1, 0)]] * 3 + [[(0, 0, 0), (1, 0, 0)]]
+    hom, het = {}, {}
+    for l in (2, 3, 4):
+        for c in (0, 1):
+            v = 1 + 2 * (l - 1) + c
+            hom[v] = [x + M * ((l + c) & 1) for x in a]
+            het[v] = [x + M * (2 + 2 * l + c) for x in a]
+    return from_edges(1, [1, 2, 2, 2, 2, 1], edges, hom, het)
+
+
+N_RANDOM = 42
+
+
+def random_layered(seed):
+    """9..15 levels of width 1..40, in-degrees 1..4 mixed inside a level, p_w1 in {0, 0.4, 1} and R in 0..24 by the seed; a level of
+    in-degree 9 at a place the seed chooses, so that runs of pairs start at odd and at even levels.  Every vertex has an in-edge, so
+    a level has a reachable cell as soon as R covers the lightest pair of paths into it: with p_w1 = 1 that is 2 per level, so those
+    graphs have at most 13 levels and R >= 2 (levels - 1); with p_w1 = 0, R is 0..3."""
+    rng = np.random.default_rng(8000 + seed)
+    p_w1 = (0.0, 0.4, 1.0)[seed % 3]
+    L = 9 + (seed // 3) % (5 if p_w1 == 1.0 else 7)
+    R = {0.0: (seed // 3) % 4, 0.4: [8, 13, 24, 5, 18][(seed // 3) % 5], 1.0: min(24, 2 * (L - 1) + (seed // 3) % 3)}[p_w1]
+    widths = [1] + [int(rng.integers(1, 41)) for _ in range(L - 2)] + [1]
+    block = 2 + seed % 5
+    widths[block - 1] = max(widths[block - 1], 9)
+    indeg = []
+    for l in range(L - 1):
+        if l + 1 == block:
+            indeg.append(9)
+        else:
+            top = int(rng.integers(1, 5))
+            indeg.append(lambda j, top=top, s=int(rng.integers(0, 4)): 1 + (j + s) % top)
+    return layered(8000 + seed, R, widths, indeg, p_w1=p_w1)
+
+
+# seed -> expected_pairs(random_layered(seed)), written out (tests/test_pair_graphs.py compares)
+RANDOM_PAIRS = {
+    0: [4, 7], 1: [2, 5, 7], 2: [2, 7], 3: [2, 4, 7, 9], 4: [2, 4, 8], 5: [4, 6, 8], 6: [2, 5, 7, 9], 7: [2, 6, 8, 10], 8: [2, 4, 7, 9],
+    9: [2, 4, 11], 10: [4, 6, 8, 10], 11: [2, 5, 9, 11], 12: [2, 7, 9, 11], 13: [2, 4, 7, 9, 11], 14: [2, 5, 8, 10, 12],
+    15: [4, 6, 8, 10, 12], 16: [2, 5, 7, 9, 11, 13], 17: [2, 6, 8], 18: [2, 4, 7, 9, 13], 19: [2, 5, 8, 10, 12, 14], 20: [4, 6, 8],
+    21: [2, 5, 8], 22: [2, 8], 23: [2, 4, 7, 10], 24: [2, 4, 9], 25: [4, 6, 9], 26: [2, 5, 7, 9, 11], 27: [2, 6, 8, 10], 28: [2, 4, 7, 10],
+    29: [2, 4, 8, 12], 30: [4, 6, 8, 10], 31: [2, 5, 7, 9, 11], 32: [2, 6, 8], 33: [2, 4, 7, 9, 11], 34: [2, 4, 8, 11], 35: [5, 7, 9],
+    36: [2, 5, 10, 12], 37: [2, 6, 8, 10, 12], 38: [2, 4, 7, 9], 39: [2, 4, 8, 10, 12, 14], 40: [4, 7, 10, 12, 14], 41: [2, 6, 8, 10],
+}
+
+
+def long_graph():
+    return layered(4242, 5, [1] + [10] * 7 + [1], [1, 2, 2, 2, 2, 2, 2, 4], colour_levels=(2, 3, 5, 8))     # pairs (1,2) (3,4) (5,6) (7,8)
+
+
+def _cell_cases():
+    """name -> (builder, the later levels of the pairs the library must choose); every graph has at least one pair"""
+    c = {}
+
+    def modes(name, build, pairs, l=4):
+        for q, mode in enumerate(COLOUR_MODES):
+            c[f"{name}/{mode}"] = (lambda build=build, mode=mode, q=q: coloured(build(), l, mode, q), pairs)
+    # field limits.  (The source level of a pair has no width limit of its own -- a source position has 15 bits -- so 256 sources are
+    # paired as well; the later level cannot have more than 255 x 8 = 2,040 in-edges.)
+    modes("width-source-255", lambda: width_limit_graph("source", 255), [2, 4])
+    modes("width-source-256", lambda: width_limit_graph("source", 256), [4])
+    modes("width-middle-255", lambda: width_limit_graph("middle", 255), [2, 4])
+    modes("width-later-255", lambda: width_limit_graph("later", 255), [2, 4])
+    modes("t1-2047", lambda: t_limit_graph(2047), [2, 4])
+    modes("t2-2040", t2_max_graph, [2, 4])
+    modes("lean-64", lambda: lean_limit_graph(64), [2, 4])
+    modes("planes-4097", wide_budget_graph, [2, 4, 6])
+    c["live-columns"] = (lambda: dead_column_graph(False), [2, 4])
+    c["delta-bound"] = (delta_bound_pair_graph, [2, 4])
+    for mix in RANK_MIXES:
+        modes(f"rank-{mix[0]}x{mix[1]}", lambda mix=mix: rank_graph(mix), [2, 4])
+    for RP in PLANE_RPS:
+        for w in PLANE_WEIGHTS:
+            modes(f"plane-{RP}-{w}", lambda RP=RP, w=w: plane_graph(RP, w), [2, 4, 6])
+    for seed in range(N_RANDOM):
+        c[f"random-{seed}"] = (lambda seed=seed: random_layered(seed), RANDOM_PAIRS[seed])
+    # the graphs of tests/test_gpu_pair_levels.py
+    for k, seed in TIE_ORDER_SEEDS.items():
+        c[f"tie-{k}"] = (lambda k=k, seed=seed: tie_graph(k, seed), [2, 4])
+    for R in (1, 2, 3, 4, 18):
+        c[f"plane-shift-{R}"] = (lambda R=R: plane_shift_graph(R), [2, 4, 6])
+    for mix in RANK_MIXES:
+        c[f"indeg-{mix[0]}x{mix[1]}"] = (lambda mix=mix: indeg_limit_graph(mix, 8), [2, 4])
+    for R in (3, 0, 1):
+        c[f"shared-middle-{R}"] = (lambda R=R: shared_middle_graph(R), [2, 4])
+    for t, k in SLOT_BLOCK_CASES:
+        c[f"slots-{t}-{k}"] = (lambda t=t, k=k: slot_block_graph(t, k, R=SLOT_BLOCK_R.get((t, k), 18)), [2, 4])
+    for n, pairs in ((1, [4]), (2, [2, 5]), (3, [2, 6]), (4, [2, 4])):
+        for mode in ("none", "first", "second", "both"):
+            c[f"parity-{n}-{mode}"] = (lambda n=n, mode=mode: parity_graph(n, mode), pairs)
+    c["long"] = (long_graph, [2, 4, 6, 8])
+    return c
+
+
+CELL_CASES = _cell_cases()
+
+# name -> (builder, the pairs that remain, the level at which the twin's pair is refused: neither it nor its predecessor may lie in a pair)
+REFUSED_TWINS = {
+    "width-middle-256": (lambda: width_limit_graph("middle", 256), [2, 5], 4),
+    "width-later-256": (lambda: width_limit_graph("later", 256), [2], 4),
+    "t1-2048": (lambda: coloured(t_limit_graph(2048), 4, "both"), [2, 5], 4),
+    "lean-65": (lambda: lean_limit_graph(65), [2, 5], 4),
+    "dead-column": (lambda: dead_column_graph(True), [2, 5], 4),
+    **{f"indeg-{a}x{b}+1": (lambda a=a, b=b: indeg_limit_graph((a, b), 9), [2], 4) for (a, b) in RANK_MIXES},
+}
+
+# Paired later levels without a reachable cell (digest 0): with every edge of weight 1, level l is reachable from plane 2 l on, so the
+# "w1" plane graphs below 13 planes cannot have one at their later pairs -- there the pin is that every cell is declared unreachable
+# (source rows in the front padding).  Everywhere else a paired later level has a non-zero digest.
+UNREACHABLE_PAIRED = {
+    **{f"plane-{RP}-w1/{m}": [2, 4, 6] for RP in (1, 2, 3, 4) for m in COLOUR_MODES},
+    **{f"plane-{RP}-w1/{m}": [4, 6] for RP in (5, 7) for m in COLOUR_MODES},
+    **{f"plane-1-mixed/{m}": [4, 6] for m in COLOUR_MODES}, **{f"plane-2-mixed/{m}": [6] for m in COLOUR_MODES},
+    "plane-shift-1": [6],                                       # (two planes, and nearly every edge of that graph weighs 1)
+}
+
+
+def budgets_checked(g):
+    """the budgets a case reads out and solves the oracle for: all of 0..R -- except on the 4,097-plane graph, where R + 1 oracle
+    solves of cost ~R each are minutes: there 0..16 (its paths weigh at most 12), the middle and the last two"""
+    return list(range(g.R + 1)) if g.R <= 64 else list(range(17)) + [g.R // 2 - 1, g.R // 2, g.R - 1, g.R]

@@ -15,7 +15,7 @@ DP_DEFAULTS = {
     "delta_overlap": 1, "warm_ahead": 128, "segment_cells": 0, "lattice_chunk_cells": 4 << 30, "delta_cap_entries": 4 << 30, "plane_limit": 1,
     "sync_every": 0, "side_stream": -1, "test_poison_level": 0, "test_poison_byte": 0xFF, "test_force_rc": 0, "score_slab_bytes": 256 << 20,
     "partner_slab_bytes": 4 << 30, "host_tables": 0, "rc_t0_ns": 3000, "rc_tg_ps": 20000, "rc_tw_ps": 50, "rc_cap": 65536,
-    "bp_nt_min_cells": 262144, "max_blocks": 1024, "host_threads": 16,
+    "bp_nt_min_cells": 262144, "max_blocks": 1024, "host_threads": 16, "pair_digest": 0, "test_force_pair_rc": 0,
 }
 NONPOSITIVE_IS_DEFAULT = ["delta_cap_entries", "rc_cap", "max_blocks", "score_slab_bytes", "partner_slab_bytes"]
 LOWER_CLAMP = {"graph_batch": -1, "side_stream": -1, "host_threads": 1}          # every other clamped key: 0
