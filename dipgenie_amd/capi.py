@@ -65,6 +65,9 @@ CALL_MARGIN = np.dtype([("vertex", np.int32), ("value", np.int32), ("alt_vertex"
 GENOTYPE_MARGIN = np.dtype([("vertex1", np.int32), ("vertex2", np.int32), ("value", np.int32), ("alt_vertex1", np.int32), ("alt_vertex2", np.int32),
                             ("alt_value", np.int32), ("reserved", np.int32, (2,))])
 
+# dg_dp_genotype_entry as a numpy record: one per (level, genotype) of Context.dp_genotype_table
+GENOTYPE_ENTRY = np.dtype([("class1", np.int32), ("class2", np.int32), ("vertex1", np.int32), ("vertex2", np.int32), ("value", np.int32), ("reserved", np.int32)])
+
 # dg_dp_pair_objective as a numpy record: what Context.dp_objective_paths and Context.dp_answer_objectives return
 PAIR_OBJECTIVE = np.dtype([("hom_shared", np.int32), ("hom_single", np.int32), ("het_single", np.int32), ("het_both", np.int32)])
 
@@ -91,7 +94,7 @@ SYMBOLS = [
     "dg_dp_run_budgets", "dg_dp_get_budget_values", "dg_dp_score_paths", "dg_dp_best_partners", "dg_dp_partner_marginals",
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
-    "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats",
+    "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -114,6 +117,8 @@ lib.dg_dp_get_answer_paths.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_call_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_partner_route.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
 lib.dg_dp_genotype_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+lib.dg_dp_genotype_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int32)]
 lib.dg_dp_get_genotype_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -469,11 +474,45 @@ class Context:
                "dg_dp_genotype_margins")
         return (levels, best.value, values) if want_vertices else (levels, best.value)
 
+    def dp_genotype_table(self, budget, vertex_class=None, called=None):
+        """The genotype table: per level and genotype (the unordered pair of its cell's classes) the best value of any pair of paths
+        through a cell of that genotype, and that cell.  budget, vertex_class as for dp_genotype_margins.  Returns (level_off,
+        entries, best_value): int64 [n_levels + 1], a GENOTYPE_ENTRY record array (class1 <= class2, vertex1 <= vertex2, value) whose
+        slice level_off[l] : level_off[l + 1] lists level l in ascending (class1, class2), genotypes without a reachable cell left
+        out, and the best value of any pair within the budget.  With called (as for dp_genotype_margins, at most 256 queries) a
+        fourth element follows: the GENOTYPE_MARGIN records dp_genotype_margins answers for it, from the same pass.  Leaves the last
+        run's answers alone."""
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        p = levels = None
+        if called is not None:
+            p = np.ascontiguousarray(called, np.int32)
+            if p.ndim == 2:
+                p = p[None]
+            if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+                raise ValueError(f"called must have shape [n, 2, n_levels], got {p.shape}")
+            levels = np.zeros((p.shape[0], p.shape[2]), GENOTYPE_MARGIN)
+        cls = None
+        if vertex_class is not None:
+            cls = np.ascontiguousarray(vertex_class, np.int32)
+            if g is not None and cls.shape != (g.n_vertices,):
+                raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
+        off = np.zeros((g.n_levels if g is not None else 0) + 1, np.int64)
+        ptr, n, best = C.c_void_p(None), C.c_int64(0), C.c_int32(0)
+        _check(lib.dg_dp_genotype_table(self.h, int(budget), cls.ctypes.data if cls is not None else None, p.ctypes.data if p is not None and p.size else None,
+                                        p.shape[0] if p is not None else 0, levels.ctypes.data if levels is not None and levels.size else None, off.ctypes.data,
+                                        C.byref(ptr), C.byref(n), C.byref(best)), "dg_dp_genotype_table")
+        try:
+            entries = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), (n.value * 6,)).view(GENOTYPE_ENTRY).copy() if n.value else np.zeros(0, GENOTYPE_ENTRY)
+        finally:
+            lib.dg_free(ptr)
+        return (off, entries, best.value) if called is None else (off, entries, best.value, levels)
+
     def dp_genotype_stats(self):
-        """of the last dp_genotype_margins on this context: dict(n_segments, levels_twice, peak_bytes, launches)"""
-        out = np.zeros(4, np.int64)
-        _check(lib.dg_dp_get_genotype_stats(self.h, out.ctypes.data, 4), "dg_dp_get_genotype_stats")
-        return dict(zip(("n_segments", "levels_twice", "peak_bytes", "launches"), out.tolist()))
+        """of the last dp_genotype_margins / dp_genotype_table on this context: dict(n_segments, levels_twice, peak_bytes, launches,
+        entries, staging_copies); the last two are 0 after dp_genotype_margins"""
+        out = np.zeros(6, np.int64)
+        _check(lib.dg_dp_get_genotype_stats(self.h, out.ctypes.data, 6), "dg_dp_get_genotype_stats")
+        return dict(zip(("n_segments", "levels_twice", "peak_bytes", "launches", "entries", "staging_copies"), out.tolist()))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

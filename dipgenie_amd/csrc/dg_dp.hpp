@@ -192,6 +192,10 @@ struct DpOptions {
     int64_t pair_digest = 0;                            // pair_digest: 1 = with digest 1 the pair launches stay, in the pair kernel's digest form (tests: the later level's digest; the earlier level's entry stays 0)
     int64_t test_force_pair_rc = 0;                     // test_force_pair_rc: n in PAIR_RCS = every pair launch takes chunks of n recombination counts; any other value: the cost model
     int64_t joint_state_bytes = (int64_t)8 << 30;       // joint_state_bytes: bound of the forward states of one segment of dg_dp_genotype_margins (a segment holds at least one level)
+    int64_t genotype_table_bytes = (int64_t)256 << 20;  // genotype_table_bytes: bound of the staging of finished entries of dg_dp_genotype_table, copied to the host when it fills and once per segment (a guess: nothing has measured another value); one level's bound A (A + 1) / 2 entries must fit
+    int64_t genotype_table_lanes = 0;                   // genotype_table_lanes: lanes that reduce one genotype over its rows in dg_dp_genotype_table: 0 = the level's mean rows per class, else n, either rounded down to a power of two in 1..64
+    int64_t genotype_table_tile_keys = 2048;            // genotype_table_tile_keys: keys of a level's dense genotype triangle that one workgroup of dg_dp_genotype_table's compaction counts and writes: 256 lanes x 1..8 keys, so 256..2048 in steps of 256
+    int64_t genotype_table_scan_tiles = 1024;           // genotype_table_scan_tiles: tiles that the one workgroup scanning a level's tile counts takes per pass (a carry links the passes): its lanes, 64..1024 in steps of 64
     int64_t objective_lds_bytes = 131072;              // objective_lds_bytes: the four colour bitmaps of a pair of dg_dp_objective_paths / dg_dp_answer_objectives live in LDS up to this size, in device memory beyond (clamped to the device's LDS per workgroup)
 };
 
@@ -302,9 +306,9 @@ struct DpState {
     bool ob_dict = false;
     int64_t ob_ch = 0, ob_ct = 0;              // distinct hom / het colours
     DevBuf d_ob_hom_rank, d_ob_het_rank, d_ob_paths, d_ob_out, d_ob_err, d_ob_bits;
-    // ---- dg_dp_genotype_margins (dg_dp_joint.hip): nothing but the statistics of the last call outlives it (dg_dp_get_genotype_stats:
-    // segments, levels swept forward twice, peak bytes reserved, launches) ----
-    int64_t jt_stats[4] = {0, 0, 0, 0};
+    // ---- dg_dp_genotype_margins / dg_dp_genotype_table (dg_dp_joint.hip): nothing but the statistics of the last call outlives it
+    // (dg_dp_get_genotype_stats: segments, levels swept forward twice, peak bytes reserved, launches, table entries, staging copies) ----
+    int64_t jt_stats[6] = {0, 0, 0, 0, 0, 0};
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -400,6 +404,8 @@ int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_d
 // ---- genotype margins: the DP forward and backward with both haplotypes free, combined per cell (dg_dp_joint.hip) ----
 int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
                         int32_t *vertex_values, int32_t *best_value);
+int dp_genotype_table(dg_ctx *c, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n, dg_dp_genotype_margin *levels, int64_t *level_off,
+                      dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value);
 int dp_genotype_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

@@ -28,6 +28,9 @@
 // visits the segments from the last to the first: the forward states of the segment's levels are recomputed and kept, the backward
 // recurrence walks the segment with two rolling states, combination and records run per level.  With one segment the first pass
 // has nothing to do.  Every buffer is reserved inside the call and freed when it returns; nothing of a run is read or written.
+// dg_dp_genotype_table is the same pass with one more step per level: the combine kernel gets one scratch row per row of the level, so
+// T of the level is whole, and the gt_* kernels below reduce it by genotype into a compacted list (their comment has the plan).
+// dg_dp_genotype_margins launches none of them and reserves none of their buffers.
 #include <algorithm>
 #include <cstring>
 
@@ -285,6 +288,175 @@ __global__ __launch_bounds__(JT_THREADS) void jt_records_kernel(int k, int b0, c
     }
 }
 
+// ---- dg_dp_genotype_table: a level's through-values reduced by genotype.  The call runs the combine kernel with one scratch row per
+// row of the level, so T[k][k] of the level is whole when these run.  rank[v] = dense rank of v's class among the classes of its level
+// (ascending, signed), perm = the level's positions ordered by (rank, position), goff[a] .. goff[a + 1] = the slice of perm with rank a
+// (host-built, A + 1 offsets).  All gathers: every word has one owner.
+//   * gt_rows_kernel: one wave per row i walks the row in perm order, 64 cells at a time: a segmented max-scan over the runs of equal
+//     rank, the run's key so far carried from chunk to chunk; the lane at the end of a run writes part[i][a'] (every rank has a cell, so
+//     every word of part is written);
+//   * gt_pairs_kernel: 2^lp lanes per genotype (a <= a') take the maximum of part[i][a'] over the rows i of rank a -- T is symmetric and
+//     the key holds (min, max), so this covers both orders of a cell -- into the dense triangle, row a at a * A - a (a - 1) / 2;
+//   * gt_count_kernel / gt_scan_kernel / gt_scatter_kernel: the reachable genotypes of the triangle, in its order (ascending
+//     (class1, class2)), go to the staging behind the levels before: per tile of 256 * items keys the count and the largest value, one
+//     workgroup scans the tiles, blockDim.x of them per pass with a carry, and moves the call's cursor, the tiles write their entries.
+constexpr int GT_MAX_ITEMS = 8;                         // most keys per lane of a tile (contiguous, so a tile's entries stay in order): option genotype_table_tile_keys / 256
+constexpr int GT_MAX_SCAN = 1024;                       // most lanes of the scan's workgroup = tiles per pass: option genotype_table_scan_tiles
+
+__global__ __launch_bounds__(JT_THREADS) void gt_rows_kernel(const int32_t *__restrict__ T, int k, int A, const int32_t *__restrict__ rank, const int32_t *__restrict__ perm,
+                                                             long long *__restrict__ part) {
+    const int lane = (int)threadIdx.x & 63;
+    const int waves = (int)gridDim.x * (JT_THREADS / 64);
+    for (int i = (int)blockIdx.x * (JT_THREADS / 64) + ((int)threadIdx.x >> 6); i < k; i += waves) {      // uniform per wave
+        long long carry = JT_NO_KEY;
+        int carry_c = -1;
+        for (int base = 0; base < k; base += 64) {
+            const int x = base + lane;
+            int c = A;                                                      // beyond the row: a rank nobody has
+            long long key = JT_NO_KEY;
+            if (x < k) {
+                const uint32_t j = (uint32_t)perm[x];
+                if (j < (uint32_t)k) {
+                    c = rank[j];
+                    const int v = T[(int64_t)i * k + j];
+                    if (v != NEG_INF) key = jt_key(v, min(i, (int)j), max(i, (int)j));
+                }
+            }
+            int cn = __shfl_down(c, 1);
+            if (lane == 63) {
+                cn = -1;
+                if (x + 1 < k) { const uint32_t j = (uint32_t)perm[x + 1]; cn = j < (uint32_t)k ? rank[j] : A; }
+            }
+            if (lane == 0 && c == carry_c) key = max(key, carry);
+            for (int d = 1; d < 64; d <<= 1) {
+                const long long ok = __shfl_up(key, d);
+                const int oc = __shfl_up(c, d);
+                if (lane >= d && oc == c) key = max(key, ok);
+            }
+            if (cn != c && (uint32_t)c < (uint32_t)A) part[(int64_t)i * A + c] = key;
+            carry = __shfl(key, 63);
+            carry_c = __shfl(c, 63);
+        }
+    }
+}
+
+// grid (x, y): rank a = blockIdx.y (strided), the lanes of x cover a' = a .. A - 1, 1 << lp of them each
+__global__ __launch_bounds__(JT_THREADS) void gt_pairs_kernel(const long long *__restrict__ part, int k, int A, const int32_t *__restrict__ perm, const int32_t *__restrict__ goff,
+                                                              int lp, long long *__restrict__ dense) {
+    const int sub = (int)threadIdx.x & ((1 << lp) - 1);
+    for (int a = (int)blockIdx.y; a < A; a += (int)gridDim.y) {
+        const int x0 = goff[a], x1 = min(goff[a + 1], k);
+        const int64_t row0 = (int64_t)a * A - (int64_t)a * (a - 1) / 2, lanes = (int64_t)(A - a) << lp;
+        for (int64_t t0 = (int64_t)blockIdx.x * JT_THREADS; t0 < lanes; t0 += (int64_t)gridDim.x * JT_THREADS) {      // uniform per workgroup
+            const int g = (int)((t0 + threadIdx.x) >> lp);
+            long long key = JT_NO_KEY;
+            if (g < A - a && x0 >= 0)
+                for (int x = x0 + sub; x < x1; x += 1 << lp) {
+                    const uint32_t i = (uint32_t)perm[x];
+                    if (i < (uint32_t)k) key = max(key, part[(int64_t)i * A + a + g]);
+                }
+            for (int d = (1 << lp) >> 1; d; d >>= 1) key = max(key, __shfl_xor(key, d));
+            if (g < A - a && sub == 0) dense[row0 + g] = key;
+        }
+    }
+}
+
+// one workgroup per tile: cnt[tile] = its reachable genotypes, tmax[tile] = their largest value
+__global__ __launch_bounds__(JT_THREADS) void gt_count_kernel(const long long *__restrict__ dense, int64_t n, int items, uint32_t *__restrict__ cnt, int32_t *__restrict__ tmax) {
+    __shared__ uint32_t s_n[JT_THREADS / 64];
+    __shared__ int s_m[JT_THREADS / 64];
+    const int t = (int)threadIdx.x;
+    const int64_t first = ((int64_t)blockIdx.x * JT_THREADS + t) * items;
+    uint32_t c = 0;
+    int m = NEG_INF;
+    for (int q = 0; q < items; ++q)
+        if (first + q < n) {
+            const long long key = dense[first + q];
+            if (key != JT_NO_KEY) { ++c; m = max(m, (int)(key >> 32)); }
+        }
+    for (int d = 32; d; d >>= 1) { c += __shfl_xor(c, d); m = max(m, __shfl_xor(m, d)); }
+    if ((t & 63) == 0) { s_n[t >> 6] = c; s_m[t >> 6] = m; }
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) { c += s_n[w]; m = max(m, s_m[w]); }
+        cnt[blockIdx.x] = c;
+        tmax[blockIdx.x] = m;
+    }
+}
+
+// one workgroup: cnt[0 .. nt) becomes its exclusive scan; the level's entries start at *cursor, which moves on by their number.
+// out = the level's three words: first entry in the staging, entries, largest value
+__global__ __launch_bounds__(GT_MAX_SCAN) void gt_scan_kernel(uint32_t *cnt, const int32_t *__restrict__ tmax, int64_t nt, long long *cursor, long long *__restrict__ out) {
+    __shared__ uint32_t s[GT_MAX_SCAN];
+    __shared__ int s_m[GT_MAX_SCAN / 64];
+    const int t = (int)threadIdx.x, W = (int)blockDim.x;                    // W: a multiple of 64, at most GT_MAX_SCAN
+    long long carry = 0;
+    int m = NEG_INF;
+    for (int64_t base = 0; base < nt; base += W) {
+        const int64_t b = base + t;
+        const uint32_t x = b < nt ? cnt[b] : 0u;
+        if (b < nt) m = max(m, tmax[b]);
+        s[t] = x;
+        __syncthreads();
+        for (int d = 1; d < W; d <<= 1) {
+            const uint32_t y = t >= d ? s[t - d] : 0u;
+            __syncthreads();
+            s[t] += y;
+            __syncthreads();
+        }
+        if (b < nt) cnt[b] = (uint32_t)(carry + s[t] - x);                  // a level has fewer than 2^30 genotypes
+        carry += s[W - 1];
+        __syncthreads();
+    }
+    for (int d = 32; d; d >>= 1) m = max(m, __shfl_xor(m, d));
+    if ((t & 63) == 0) s_m[t >> 6] = m;
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < W / 64; ++w) m = max(m, s_m[w]);
+        const long long at = *cursor;
+        out[0] = at; out[1] = carry; out[2] = m;
+        *cursor = at + carry;
+    }
+}
+
+// one workgroup per tile: its reachable genotypes as entries, from stage[lvl[0] + off[tile]] on (cap = entries the staging holds)
+__global__ __launch_bounds__(JT_THREADS) void gt_scatter_kernel(const long long *__restrict__ dense, int64_t n, int items, const uint32_t *__restrict__ off, const long long *__restrict__ lvl,
+                                                                int b0, const int32_t *__restrict__ cls, dg_dp_genotype_entry *__restrict__ stage, int64_t cap) {
+    __shared__ uint32_t s[JT_THREADS];
+    const int t = (int)threadIdx.x;
+    const int64_t first = ((int64_t)blockIdx.x * JT_THREADS + t) * items;
+    long long keys[GT_MAX_ITEMS];
+    uint32_t c = 0;
+    for (int q = 0; q < GT_MAX_ITEMS; ++q) {
+        keys[q] = q < items && first + q < n ? dense[first + q] : JT_NO_KEY;
+        c += keys[q] != JT_NO_KEY;
+    }
+    s[t] = c;
+    __syncthreads();
+    for (int d = 1; d < JT_THREADS; d <<= 1) {
+        const uint32_t y = t >= d ? s[t - d] : 0u;
+        __syncthreads();
+        s[t] += y;
+        __syncthreads();
+    }
+    int64_t at = (int64_t)lvl[0] + off[blockIdx.x] + (s[t] - c);
+    for (int q = 0; q < GT_MAX_ITEMS; ++q) {
+        if (keys[q] == JT_NO_KEY) continue;
+        const uint32_t lo = (uint32_t)keys[q];
+        dg_dp_genotype_entry e;
+        e.vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+        e.vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+        const int c1 = cls ? cls[e.vertex1] : e.vertex1, c2 = cls ? cls[e.vertex2] : e.vertex2;
+        e.class1 = min(c1, c2);
+        e.class2 = max(c1, c2);
+        e.value = (int)(keys[q] >> 32);
+        e.reserved = 0;
+        if (at >= 0 && at < cap) stage[at] = e;
+        ++at;
+    }
+}
+
+
 struct JtLevel { int a0, k; uint32_t in_base; int T; bool coloured; int64_t cells; };   // cells: k * k * (b + 1)
 
 // the buffers of one call: reserved here, released when the call returns; `now` / `peak` bytes for dg_dp_get_genotype_stats
@@ -303,14 +475,27 @@ unsigned jt_blocks(int64_t lanes, int cap) { return (unsigned)std::max<int64_t>(
 
 }  // namespace
 
-int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
-                        int32_t *vertex_values, int32_t *best_value) {
-    static const char *const FN = "dg_dp_genotype_margins";
+// the outputs of dg_dp_genotype_table (null for dg_dp_genotype_margins: then nothing of the table is reserved or launched)
+struct JtTable { int64_t *level_off; dg_dp_genotype_entry **entries; int64_t *n_entries; };
+
+namespace {
+
+// both entry points: tab = null is dg_dp_genotype_margins
+int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+            int32_t *vertex_values, int32_t *best_value, const JtTable *tab) {
     DpState *Sp = c->dp;
     if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
     DpState &S = *Sp;
-    if (n < 1) { set_error("%s: n_called = %lld", FN, (long long)n); return DG_ERR_ARG; }
-    if (!called || !levels || !best_value) { set_error("%s: called, levels and best_value are required", FN); return DG_ERR_ARG; }
+    if (tab) {
+        if (!tab->level_off || !tab->entries || !tab->n_entries || !best_value) { set_error("%s: level_off, entries, n_entries and best_value are required", FN); return DG_ERR_ARG; }
+        if (n < 0 || (n == 0) != (!called && !levels) || (!called) != (!levels)) {
+            set_error("%s: called and levels go together, with n_called = %lld", FN, (long long)n);
+            return DG_ERR_ARG;
+        }
+    } else {
+        if (n < 1) { set_error("%s: n_called = %lld", FN, (long long)n); return DG_ERR_ARG; }
+        if (!called || !levels || !best_value) { set_error("%s: called, levels and best_value are required", FN); return DG_ERR_ARG; }
+    }
     if (budget < 0) { set_error("%s: budget %d is negative", FN, budget); return DG_ERR_ARG; }
     if (n > JT_MAX_QUERIES) { set_error("%s: %lld called genotypes exceed %d per call", FN, (long long)n, JT_MAX_QUERIES); return DG_ERR_UNSUPPORTED; }
     if ((int64_t)budget + 1 > JT_MAX_PLANES) { set_error("%s: budget + 1 = %lld exceeds %d planes", FN, (long long)budget + 1, JT_MAX_PLANES); return DG_ERR_UNSUPPORTED; }
@@ -336,6 +521,57 @@ int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t bud
                     return DG_ERR_ARG;
                 }
             }
+    // ---- the table's plan, before anything is launched: per level the dense rank of every vertex's class (ascending, signed), the
+    // positions ordered by (rank, position), the A + 1 offsets of the ranks (level l's start at a0 + l: A <= k), the bound A (A + 1) / 2 ----
+    std::vector<int32_t> t_rank, t_perm, t_goff, t_A;
+    int64_t cap_entries = 0, bound_sum = 0, bound_max = 0, gpart_max = 1;
+    // the two sizes of the compaction: keys per tile (256 lanes x 1..8 keys) and tiles per pass of the scan (its lanes, 64..1024 in whole waves)
+    const int gt_items = (int)std::min<int64_t>(std::max<int64_t>(S.opt.genotype_table_tile_keys / JT_THREADS, 1), GT_MAX_ITEMS), gt_tile = gt_items * JT_THREADS;
+    const int gt_scan = (int)std::min<int64_t>(std::max<int64_t>(S.opt.genotype_table_scan_tiles / 64, 1) * 64, GT_MAX_SCAN);
+    const bool dbg = tab && getenv("DG_DEBUG") != nullptr;
+    const double t_plan0 = wall_s();
+    double t_copies = 0, t_plan = 0;
+    if (tab) {
+        cap_entries = S.opt.genotype_table_bytes / (int64_t)sizeof(dg_dp_genotype_entry);
+        t_rank.resize((size_t)nV); t_perm.resize((size_t)nV); t_goff.assign((size_t)nV + (size_t)L, 0); t_A.resize((size_t)L);
+        for (int l = 0; l < L; ++l) {
+            const int a0 = lv[l].a0, k = lv[l].k;
+            int32_t *perm = t_perm.data() + a0, *rank = t_rank.data() + a0, *goff = t_goff.data() + a0 + l;
+            for (int x = 0; x < k; ++x) perm[x] = x;
+            int A = k;
+            if (vertex_class) {
+                const int32_t *cl = vertex_class + a0;
+                std::sort(perm, perm + k, [cl](int32_t x, int32_t y) { return cl[x] != cl[y] ? cl[x] < cl[y] : x < y; });
+                A = 0;
+                for (int x = 0; x < k; ++x) {
+                    if (x == 0 || cl[perm[x]] != cl[perm[x - 1]]) goff[A++] = x;
+                    rank[perm[x]] = A - 1;
+                }
+                goff[A] = k;
+            } else
+                for (int x = 0; x <= k; ++x) { if (x < k) rank[x] = x; goff[x] = x; }
+            t_A[(size_t)l] = A;
+            const int64_t bound = (int64_t)A * (A + 1) / 2;
+            if (bound > cap_entries) {
+                set_error("%s: level %d: up to %lld genotypes (%d classes) do not fit genotype_table_bytes = %lld (%lld entries)", FN, l, (long long)bound, A,
+                          (long long)S.opt.genotype_table_bytes, (long long)cap_entries);
+                return DG_ERR_UNSUPPORTED;
+            }
+            bound_sum += bound;
+            bound_max = std::max(bound_max, bound);
+            gpart_max = std::max(gpart_max, (int64_t)k * A);
+        }
+    }
+    t_plan = wall_s() - t_plan0;
+    // without a query the combine and record kernels still form T and the level maxima: one cell per level stands in, its records are dropped
+    const bool want_levels = levels != nullptr;
+    std::vector<int32_t> stand_in;
+    if (n == 0) {
+        stand_in.resize((size_t)2 * L);
+        for (int l = 0; l < L; ++l) stand_in[(size_t)l] = stand_in[(size_t)L + l] = lv[l].a0;
+        called = stand_in.data();
+        n = 1;
+    }
     hipStream_t s = c->stream;
     // ---- the plan: segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
     std::vector<int> seg{0};
@@ -361,7 +597,8 @@ int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t bud
     int64_t launches = 0, twice = 0;
     JtMem M;
     DevBuf d_called, d_cls, d_J, d_rec, d_lvlmax, d_cval, d_part, d_row, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back;
-    const int row_blocks = std::min(kmax, JT_ROW_BLOCKS);
+    DevBuf d_trank, d_tperm, d_tgoff, d_gpart, d_dense, d_tcnt, d_tmax, d_tlvl, d_stage;
+    const int row_blocks = tab ? kmax : std::min(kmax, JT_ROW_BLOCKS);      // the table keeps every row of T: one scratch row per row
     if (int rc = M.get(d_called, n * 2 * L * 4)) return rc;
     if (vertex_class) if (int rc = M.get(d_cls, (int64_t)nV * 4)) return rc;
     if (int rc = M.get(d_J, (int64_t)nV * 4)) return rc;
@@ -375,6 +612,42 @@ int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t bud
     if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
     if (tmax) if (int rc = M.get(d_sc, tmax * tmax * 2)) return rc;
     if (int rc = M.get(d_ck, ck_off[n_seg] * 4)) return rc;
+    const int64_t stage_cap = std::min(cap_entries, bound_sum), tiles_max = (bound_max + gt_tile - 1) / gt_tile;
+    if (tab) {
+        if (int rc = M.get(d_trank, (int64_t)nV * 4)) return rc;
+        if (int rc = M.get(d_tperm, (int64_t)nV * 4)) return rc;
+        if (int rc = M.get(d_tgoff, ((int64_t)nV + L) * 4)) return rc;
+        if (int rc = M.get(d_gpart, gpart_max * 8)) return rc;
+        if (int rc = M.get(d_dense, bound_max * 8)) return rc;
+        if (int rc = M.get(d_tcnt, tiles_max * 4)) return rc;
+        if (int rc = M.get(d_tmax, tiles_max * 4)) return rc;
+        if (int rc = M.get(d_tlvl, ((int64_t)3 * L + 1) * 8)) return rc;                // per level: first entry in the staging, entries, largest value; then the cursor
+        if (int rc = M.get(d_stage, stage_cap * (int64_t)sizeof(dg_dp_genotype_entry))) return rc;
+        DG_HIP(hipMemcpyAsync(d_trank.p, t_rank.data(), (size_t)nV * 4, hipMemcpyHostToDevice, s));
+        DG_HIP(hipMemcpyAsync(d_tperm.p, t_perm.data(), (size_t)nV * 4, hipMemcpyHostToDevice, s));
+        DG_HIP(hipMemcpyAsync(d_tgoff.p, t_goff.data(), ((size_t)nV + (size_t)L) * 4, hipMemcpyHostToDevice, s));
+        DG_HIP(hipMemsetAsync(d_tlvl.p, 0, ((size_t)3 * L + 1) * 8, s));
+    }
+    long long *const t_cursor = tab ? d_tlvl.as<long long>() + (int64_t)3 * L : nullptr;
+    std::vector<dg_dp_genotype_entry> found;                               // the entries in the order the levels finish: L - 1 .. 0
+    int64_t staged_bound = 0, copies = 0;
+    auto flush = [&]() -> int {                                             // the staging's entries to the host; the cursor back to 0
+        staged_bound = 0;
+        long long have = 0;
+        const double t0 = wall_s();
+        DG_HIP(hipMemcpyAsync(&have, t_cursor, 8, hipMemcpyDeviceToHost, s));
+        DG_HIP(hipStreamSynchronize(s));
+        if (have < 0 || have > stage_cap) { set_error("%s: the staging holds %lld entries of %lld", FN, have, (long long)stage_cap); return DG_ERR_STATE; }
+        if (!have) return DG_OK;
+        const size_t at = found.size();
+        found.resize(at + (size_t)have);
+        DG_HIP(hipMemcpyAsync(found.data() + at, d_stage.p, (size_t)have * sizeof(dg_dp_genotype_entry), hipMemcpyDeviceToHost, s));
+        DG_HIP(hipMemsetAsync(t_cursor, 0, 8, s));
+        DG_HIP(hipStreamSynchronize(s));
+        ++copies;
+        t_copies += wall_s() - t0;                                          // (with the wait for the kernels still in flight)
+        return DG_OK;
+    };
     DG_HIP(hipMemcpyAsync(d_called.p, called, (size_t)(n * 2 * L) * 4, hipMemcpyHostToDevice, s));
     if (vertex_class) DG_HIP(hipMemcpyAsync(d_cls.p, vertex_class, (size_t)nV * 4, hipMemcpyHostToDevice, s));
     const LevelDesc *descs = S.d_descs.as<LevelDesc>();
@@ -460,17 +733,43 @@ int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t bud
             hipLaunchKernelGGL(jt_records_kernel, dim3((unsigned)n), dim3(JT_THREADS), 0, s, lv[l].k, lv[l].a0, d_J.as<int32_t>(), d_part.as<long long>(), d_cval.as<int32_t>(),
                                d_called.as<int32_t>(), L, l, d_rec.as<dg_dp_genotype_margin>(), d_lvlmax.as<int32_t>());
             launches += 2;
+            if (tab) {
+                const int k = lv[l].k, A = t_A[(size_t)l];
+                const int64_t bound = (int64_t)A * (A + 1) / 2, tiles = (bound + gt_tile - 1) / gt_tile;
+                if (staged_bound + bound > stage_cap) if (int rc = flush()) return rc;
+                staged_bound += bound;
+                int lp = 0;                                                 // lanes per genotype: the mean rows per rank, as a power of two
+                const int64_t per = S.opt.genotype_table_lanes > 0 ? S.opt.genotype_table_lanes : (k + A - 1) / A;
+                while (lp < 6 && ((int64_t)1 << (lp + 1)) <= std::max<int64_t>(per, 1)) ++lp;
+                const int32_t *perm = d_tperm.as<int32_t>() + lv[l].a0;
+                long long *lvl3 = d_tlvl.as<long long>() + (int64_t)3 * l;
+                hipLaunchKernelGGL(gt_rows_kernel, dim3((unsigned)((k + JT_THREADS / 64 - 1) / (JT_THREADS / 64))), dim3(JT_THREADS), 0, s, (const int32_t *)d_row.as<int32_t>(), k, A,
+                                   (const int32_t *)(d_trank.as<int32_t>() + lv[l].a0), perm, d_gpart.as<long long>());
+                hipLaunchKernelGGL(gt_pairs_kernel, dim3(jt_blocks((int64_t)A << lp, 65535), (unsigned)std::min(A, 65535)), dim3(JT_THREADS), 0, s,
+                                   (const long long *)d_gpart.as<long long>(), k, A, perm, (const int32_t *)(d_tgoff.as<int32_t>() + lv[l].a0 + l), lp, d_dense.as<long long>());
+                hipLaunchKernelGGL(gt_count_kernel, dim3((unsigned)tiles), dim3(JT_THREADS), 0, s, (const long long *)d_dense.as<long long>(), bound, gt_items,
+                                   d_tcnt.as<uint32_t>(), d_tmax.as<int32_t>());
+                hipLaunchKernelGGL(gt_scan_kernel, dim3(1), dim3((unsigned)gt_scan), 0, s, d_tcnt.as<uint32_t>(), (const int32_t *)d_tmax.as<int32_t>(), tiles, t_cursor, lvl3);
+                hipLaunchKernelGGL(gt_scatter_kernel, dim3((unsigned)tiles), dim3(JT_THREADS), 0, s, (const long long *)d_dense.as<long long>(), bound, gt_items,
+                                   (const uint32_t *)d_tcnt.as<uint32_t>(), (const long long *)lvl3, lv[l].a0, vertex_class ? (const int32_t *)d_cls.as<int32_t>() : nullptr,
+                                   d_stage.as<dg_dp_genotype_entry>(), stage_cap);
+                launches += 5;
+            }
         }
         DG_HIP(hipGetLastError());
+        if (tab) if (int rc = flush()) return rc;                           // at the latest once per segment
     }
     // the caller's arrays are written only if the call succeeds
     std::vector<dg_dp_genotype_margin> recs((size_t)(n * L));
     std::vector<int32_t> lvlmax((size_t)L + 1), vals(vertex_values ? (size_t)nV : 0);
+    std::vector<long long> tlvl(tab ? (size_t)3 * L : 0);
+    if (tab) DG_HIP(hipMemcpyAsync(tlvl.data(), d_tlvl.p, tlvl.size() * 8, hipMemcpyDeviceToHost, s));
     DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_genotype_margin), hipMemcpyDeviceToHost, s));
     DG_HIP(hipMemcpyAsync(lvlmax.data(), d_lvlmax.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
     if (vertex_values) DG_HIP(hipMemcpyAsync(vals.data(), d_J.p, (size_t)nV * 4, hipMemcpyDeviceToHost, s));
     DG_HIP(hipStreamSynchronize(s));
     S.jt_stats[0] = n_seg; S.jt_stats[1] = twice; S.jt_stats[2] = M.peak; S.jt_stats[3] = launches;
+    S.jt_stats[4] = (int64_t)found.size(); S.jt_stats[5] = copies;
     const int32_t V = lvlmax[(size_t)L];
     // the closing check: on every level the best pair through any cell is the best pair
     for (int l = 0; l < L; ++l)
@@ -478,16 +777,57 @@ int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t bud
             set_error("%s: level %d: the largest through-value is %d, the sink's value at budget %d is %d", FN, l, lvlmax[l], budget, V);
             return DG_ERR_STATE;
         }
-    memcpy(levels, recs.data(), recs.size() * sizeof(dg_dp_genotype_margin));
+    if (tab) {                                                              // the levels came last first: turn them round
+        const double t_turn0 = wall_s();
+        std::vector<int64_t> off((size_t)L + 1, 0);
+        for (int l = 0; l < L; ++l) {
+            if (tlvl[(size_t)3 * l + 2] != V) {
+                set_error("%s: level %d: the largest genotype value is %lld, the sink's value at budget %d is %d", FN, l, tlvl[(size_t)3 * l + 2], budget, V);
+                return DG_ERR_STATE;
+            }
+            off[(size_t)l + 1] = off[(size_t)l] + tlvl[(size_t)3 * l + 1];
+        }
+        if (off[(size_t)L] != (int64_t)found.size()) { set_error("%s: %lld entries counted, %zu copied", FN, (long long)off[(size_t)L], found.size()); return DG_ERR_STATE; }
+        dg_dp_genotype_entry *out = nullptr;
+        if (!found.empty()) {
+            out = (dg_dp_genotype_entry *)malloc(found.size() * sizeof(dg_dp_genotype_entry));
+            if (!out) { set_error("%s: out of host memory for %zu entries", FN, found.size()); return DG_ERR_OOM; }
+            size_t at = 0;
+            for (int l = L - 1; l >= 0; --l) {
+                const size_t cnt = (size_t)(off[(size_t)l + 1] - off[(size_t)l]);
+                if (cnt) memcpy(out + off[(size_t)l], found.data() + at, cnt * sizeof(dg_dp_genotype_entry));
+                at += cnt;
+            }
+        }
+        memcpy(tab->level_off, off.data(), off.size() * 8);
+        *tab->entries = out;
+        *tab->n_entries = (int64_t)found.size();
+        if (dbg) fprintf(stderr, "[dipgenie_hip] genotype_table: host plan %.3f s, %lld staging copies %.3f s (with their waits for the stream), turning the levels round %.3f s\n", t_plan,
+                         (long long)copies, t_copies, wall_s() - t_turn0);
+    }
+    if (want_levels) memcpy(levels, recs.data(), recs.size() * sizeof(dg_dp_genotype_margin));
     if (vertex_values) memcpy(vertex_values, vals.data(), vals.size() * 4);
     *best_value = V;
     return DG_OK;
 }
 
+}  // namespace
+
+int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+                        int32_t *vertex_values, int32_t *best_value) {
+    return jt_call(c, "dg_dp_genotype_margins", called, n, budget, vertex_class, levels, vertex_values, best_value, nullptr);
+}
+
+int dp_genotype_table(dg_ctx *c, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n, dg_dp_genotype_margin *levels, int64_t *level_off,
+                      dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) {
+    const JtTable tab{level_off, entries, n_entries};
+    return jt_call(c, "dg_dp_genotype_table", called, n, budget, vertex_class, levels, nullptr, best_value, &tab);
+}
+
 int dp_genotype_stats(dg_ctx *c, int64_t *out, int n) {
     if (!out || n < 4) { set_error("dg_dp_get_genotype_stats: out needs 4 words"); return DG_ERR_ARG; }
     if (!c->dp) { set_error("dg_dp_get_genotype_stats: no graph loaded"); return DG_ERR_STATE; }
-    for (int q = 0; q < 4; ++q) out[q] = c->dp->jt_stats[q];
+    for (int q = 0; q < (n >= 6 ? 6 : 4); ++q) out[q] = c->dp->jt_stats[q];
     return DG_OK;
 }
 
@@ -497,6 +837,12 @@ extern "C" int dg_dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t 
                                       int32_t *vertex_values, int32_t *best_value) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_genotype_margins(c, called, n_called, budget, vertex_class, levels, vertex_values, best_value);
+}
+
+extern "C" int dg_dp_genotype_table(dg_ctx *c, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called, dg_dp_genotype_margin *levels,
+                                    int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_genotype_table(c, budget, vertex_class, called, n_called, levels, level_off, entries, n_entries, best_value);
 }
 
 extern "C" int dg_dp_get_genotype_stats(dg_ctx *c, int64_t *out, int n) {

@@ -525,7 +525,7 @@ extern "C" int dg_dp_list_sweep_variants(char *buf, int cap) {
     return DG_OK;
 }
 // Options: parity / test knobs (digest, fast, adaptive_rc, coop, rowx, lean_chain, segment_cells, delta_cap_entries, lattice_chunk_cells,
-// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes, partner_wide, joint_state_bytes, objective_lds_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
+// graph_batch, warm_ahead, score_slab_bytes, partner_slab_bytes, partner_wide, joint_state_bytes, genotype_table_bytes, genotype_table_lanes, genotype_table_tile_keys, genotype_table_scan_tiles, objective_lds_bytes), profiler aid (sync_every), tuning (rc_*, bp_nt_min_cells, max_blocks, host_threads).
 // One row per key: its DpOptions field, the lower clamp, whether v <= 0 asks for the default (that of a fresh DpOptions).
 typedef dgi::DpOptions DpO;
 static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t lo; bool nonpos_is_default; } dp_option_keys[] = {
@@ -539,6 +539,8 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
     {"partner_wide", &DpO::partner_wide, 0, false},                // 0..2: clamped from above below
     {"joint_state_bytes", &DpO::joint_state_bytes, 0, true},
+    {"genotype_table_bytes", &DpO::genotype_table_bytes, 0, true}, {"genotype_table_lanes", &DpO::genotype_table_lanes, 0, false},
+    {"genotype_table_tile_keys", &DpO::genotype_table_tile_keys, 256, true}, {"genotype_table_scan_tiles", &DpO::genotype_table_scan_tiles, 64, true},   // rounded down to a multiple of 256 / 64, clamped from above below
     {"objective_lds_bytes", &DpO::objective_lds_bytes, 0, true},   // clamped from above to objective_lds_limit(): the device's LDS per workgroup
     // read by dg_dp_load_graph: in effect at the next load
     {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},
@@ -562,6 +564,8 @@ static int dp_option(dg_ctx *c, const char *what, const char *key, const int64_t
         }
         if (o.field == &DpO::objective_lds_bytes) v = std::min(v, dgi::objective_lds_limit(c));
         if (o.field == &DpO::partner_wide) v = std::min<int64_t>(v, 2);
+        if (o.field == &DpO::genotype_table_tile_keys && v > 0) v = std::min<int64_t>(std::max<int64_t>(v / 256, 1) * 256, 2048);
+        if (o.field == &DpO::genotype_table_scan_tiles && v > 0) v = std::min<int64_t>(std::max<int64_t>(v / 64, 1) * 64, 1024);
         S.opt.*o.field = o.nonpos_is_default && v <= 0 ? DpO().*o.field : v < o.lo ? o.lo : v;
         return DG_OK;
     }

@@ -96,7 +96,7 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
@@ -106,6 +106,8 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.objective_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_objectives)) return "--objective-table: this backend has no dp_answer_objectives";
     // and --genotype-margins: the called genotype is the answer that stays behind
     if (!p.opt.genotype_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_margins)) return "--genotype-margins: this backend has no dp_genotype_margins";
+    // and --genotype-table: the same pass lists every genotype
+    if (!p.opt.genotype_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_table || !be.free_buf)) return "--genotype-table: this backend has no dp_genotype_table";
     if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
     std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
     for (const ChainAnswer &a : answers) res.push_back(a.res);
@@ -376,24 +378,56 @@ std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::v
 // level  vertex1  panel_hap1  segment1  vertex2  panel_hap2  segment2  value  alt_vertex1  alt_segment1  alt_vertex2  alt_segment2  alt_value  margin:
 // levels 1 .. L - 2; the called cell is the answer at -R (its two paths), the alternative the best cell of another genotype with both
 // haplotypes free; '.' for what does not exist (no other genotype reachable; every field if no pair of paths fits -R)
-std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls) {
+// What --genotype-margins and --genotype-table share: the answer at -R as the called cells, and ONE pass over the graph with both
+// haplotypes free -- dp_genotype_table when the table is asked for (it answers the margin records too), dp_genotype_margins otherwise
+struct GenotypePass {
+    const Backend *be = nullptr;
+    bool fits = false;                                   // a pair of paths fits -R (none: no device call, both files say so)
+    std::vector<int32_t> paths;                          // [2][L]
+    std::vector<dg_dp_genotype_margin> rec;              // [L]
+    std::vector<int64_t> level_off;                      // [L + 1], with the table
+    dg_dp_genotype_entry *entries = nullptr;             // the backend's buffer
+    int64_t n_entries = 0, segments = 0;
+    int32_t best = 0;
+    double wall_s = 0;
+    GenotypePass() = default;
+    GenotypePass(const GenotypePass &) = delete;
+    GenotypePass &operator=(const GenotypePass &) = delete;
+    ~GenotypePass() { if (entries && be) be->free_buf(entries); }
+};
+
+std::string genotype_pass(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, GenotypePass &gp) {
     const double t0 = now_s();
     const Backend &be = p.be;
+    gp.be = &be;
     const int L = (int)g.level_off.size() - 1;
-    std::vector<int32_t> paths(2 * (size_t)L);
-    if (be.dp_answer_paths(be.ctx, p.opt.R, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
-    const bool fits = paths[0] >= 0;
-    std::vector<dg_dp_genotype_margin> rec((size_t)L);
-    int32_t best = 0;
+    gp.paths.assign(2 * (size_t)L, 0);
+    if (be.dp_answer_paths(be.ctx, p.opt.R, gp.paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+    gp.fits = gp.paths[0] >= 0;
+    gp.rec.assign((size_t)L, dg_dp_genotype_margin());
+    gp.level_off.assign((size_t)L + 1, 0);
+    if (gp.fits) {
+        if (!p.opt.genotype_table.empty()) {
+            if (be.dp_genotype_table(be.ctx, p.opt.R, cls.data(), gp.paths.data(), 1, gp.rec.data(), gp.level_off.data(), &gp.entries, &gp.n_entries, &gp.best) != 0)
+                return backend_error(be, "dp_genotype_table");
+        } else if (be.dp_genotype_margins(be.ctx, gp.paths.data(), 1, p.opt.R, cls.data(), gp.rec.data(), nullptr, &gp.best) != 0) return backend_error(be, "dp_genotype_margins");
+        int64_t stats[4] = {0, 0, 0, 0};
+        if (be.dp_genotype_stats && be.dp_genotype_stats(be.ctx, stats, 4) != 0) return backend_error(be, "dp_genotype_stats");
+        gp.segments = stats[0];
+    }
+    gp.wall_s = now_s() - t0;
+    return "";
+}
+
+std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const GenotypePass &gp) {
+    const double t0 = now_s();
+    const int L = (int)g.level_off.size() - 1;
+    const bool fits = gp.fits;
+    const std::vector<dg_dp_genotype_margin> &rec = gp.rec;
     GenotypeMargins &gm = p.sum.genotype_margins;
     gm = GenotypeMargins();
     gm.set = true;
-    if (fits) {
-        if (be.dp_genotype_margins(be.ctx, paths.data(), 1, p.opt.R, cls.data(), rec.data(), nullptr, &best) != 0) return backend_error(be, "dp_genotype_margins");
-        int64_t stats[4] = {0, 0, 0, 0};
-        if (be.dp_genotype_stats && be.dp_genotype_stats(be.ctx, stats, 4) != 0) return backend_error(be, "dp_genotype_stats");
-        gm.segments = stats[0];
-    }
+    gm.segments = gp.segments;
     std::string text = "level\tvertex1\tpanel_hap1\tsegment1\tvertex2\tpanel_hap2\tsegment2\tvalue\talt_vertex1\talt_segment1\talt_vertex2\talt_segment2\talt_value\tmargin\n";
     for (int l = 1; l < L - 1; ++l) {
         text += std::to_string(l);
@@ -416,7 +450,42 @@ std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const st
     f.write(text.data(), (std::streamsize)text.size());
     f.close();
     if (!f.good()) return "write to " + p.opt.genotype_margins + " failed";
-    gm.wall_s = now_s() - t0;
+    gm.wall_s = gp.wall_s + (now_s() - t0);
+    return "";
+}
+
+// level  vertex1  segment1  vertex2  segment2  value  delta  called: levels 1 .. L - 2, per level one row for every genotype that a pair
+// of paths within -R passes through, in ascending (class1, class2) of the allele classes; (vertex1, vertex2) its best cell, delta = the
+// DP value - value, called = 1 for the genotype of the answer's cell.  The header alone if no pair of paths fits -R
+std::string write_genotype_table(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, const GenotypePass &gp) {
+    const double t0 = now_s();
+    const int L = (int)g.level_off.size() - 1;
+    GenotypeTable &gt = p.sum.genotype_table;
+    gt = GenotypeTable();
+    gt.set = true;
+    std::string text = "level\tvertex1\tsegment1\tvertex2\tsegment2\tvalue\tdelta\tcalled\n";
+    for (int l = 1; gp.fits && l < L - 1; ++l) {
+        const int32_t c1 = cls.at((size_t)gp.paths[(size_t)l]), c2 = cls.at((size_t)gp.paths[(size_t)L + l]);
+        const int64_t a = gp.level_off[(size_t)l], e = gp.level_off[(size_t)l + 1];
+        int64_t at_best = 0;
+        for (int64_t x = a; x < e; ++x) {
+            const dg_dp_genotype_entry &r = gp.entries[x];
+            const bool called = r.class1 == std::min(c1, c2) && r.class2 == std::max(c1, c2);
+            text += std::to_string(l) + '\t' + std::to_string(r.vertex1) + '\t' + segment_name(p, g, r.vertex1) + '\t' + std::to_string(r.vertex2) + '\t' + segment_name(p, g, r.vertex2) +
+                    '\t' + std::to_string(r.value) + '\t' + std::to_string(gp.best - r.value) + '\t' + (called ? '1' : '0') + '\n';
+            at_best += r.value == gp.best;
+        }
+        gt.entries += e - a;
+        gt.levels_with_choice += e - a >= 2;
+        gt.co_optimal_levels += at_best >= 2;
+        gt.max_per_level = std::max(gt.max_per_level, e - a);
+    }
+    std::ofstream f(p.opt.genotype_table, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open genotype table file " + p.opt.genotype_table;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + p.opt.genotype_table + " failed";
+    gt.wall_s = gp.wall_s + (now_s() - t0);
     return "";
 }
 
@@ -495,15 +564,15 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
             return -1;
         }
     }
-    if (!opt.genotype_margins.empty()) {                               // the limits of dg_dp_genotype_margins, known before the DP too
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = "--genotype-margins: widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(opt.genotype_margins.empty() ? "--genotype-table" : "--genotype-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
-    if (!opt.site_margins.empty() || !opt.genotype_margins.empty()) {  // both tables speak of alleles
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty()) {  // all three tables speak of alleles
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
@@ -549,10 +618,19 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         if (failed(write_site_margins(*this, g, classes), err)) return -1;
         stamp("site_margins", t0);
     }
-    if (!opt.genotype_margins.empty()) {
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty()) {   // one pass serves both files
         t0 = now_s();
-        if (failed(write_genotype_margins(*this, g, classes), err)) return -1;
-        stamp("genotype_margins", t0);
+        GenotypePass gp;
+        if (failed(genotype_pass(*this, g, classes, gp), err)) return -1;
+        if (!opt.genotype_margins.empty()) {
+            if (failed(write_genotype_margins(*this, g, gp), err)) return -1;
+            stamp("genotype_margins", t0);
+        }
+        if (!opt.genotype_table.empty()) {
+            const double t1 = opt.genotype_margins.empty() ? t0 : now_s();
+            if (failed(write_genotype_table(*this, g, classes, gp), err)) return -1;
+            stamp("genotype_table", t1);
+        }
     }
     if (!opt.tag_reads.empty()) {
         t0 = now_s();

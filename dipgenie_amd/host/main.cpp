@@ -132,6 +132,11 @@ static int b_dp_genotype_margins(void *c, const int32_t *called, int64_t n, int3
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_genotype_margins(x, called, n, budget, cls, levels, vv, best) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_genotype_table(void *c, int32_t budget, const int32_t *cls, const int32_t *called, int64_t n, dg_dp_genotype_margin *levels, int64_t *level_off,
+                               dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_genotype_table(x, budget, cls, called, n, levels, level_off, entries, n_entries, best) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_genotype_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_genotype_stats(x, out, n) : DG_ERR_NO_DEVICE;
@@ -252,6 +257,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
     fprintf(fp, "    --wide-levels         (MI355X build) with --site-margins: lift its limit of 16384 cells (widest level x (R + 1)) by keeping the level state in device memory (then: widest level <= 32767, <= 16777216 cells)\n");
     fprintf(fp, "    --genotype-margins FILE   (MI355X build, -p2) per level: the genotype of the answer at -R against the best other genotype, both haplotypes free, and the margin (TSV)\n");
+    fprintf(fp, "    --genotype-table FILE     (MI355X build, -p2) per level one row for every genotype a pair of paths within -R passes through: its best cell, value, distance to the DP value, whether the answer has it (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
@@ -273,7 +279,7 @@ int main(int argc, char **argv) {
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
     std::string budgets_arg;
-    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false;
+    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -297,6 +303,12 @@ int main(int argc, char **argv) {
                 have_genotype_margins = true;                          // (a missing value is an empty file name: refused below)
                 const char *v = val("--genotype-margins");
                 p.opt.genotype_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--genotype-table", 16) && (argv[i][16] == 0 || argv[i][16] == '=')) {
+                have_genotype_table = true;                            // (a missing value is an empty file name: refused below)
+                const char *v = val("--genotype-table");
+                p.opt.genotype_table = v ? v : "";
                 continue;
             }
             if (!strcmp(argv[i], "--wide-levels")) { p.opt.wide_levels = true; continue; }
@@ -381,6 +393,12 @@ int main(int argc, char **argv) {
         if (p.opt.genotype_margins.empty()) { fprintf(stderr, "[E::main] --genotype-margins needs a file name\n"); return 1; }
         if (sharded) { fprintf(stderr, "[E::main] --genotype-margins does not go with --gpus / --shard-transport\n"); return 1; }
     }
+    // --genotype-table FILE: the same
+    if (have_genotype_table) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --genotype-table lists the genotypes of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.genotype_table.empty()) { fprintf(stderr, "[E::main] --genotype-table needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --genotype-table does not go with --gpus / --shard-transport\n"); return 1; }
+    }
     // --objective-table FILE: the same
     if (have_objective_table) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
@@ -406,6 +424,7 @@ int main(int argc, char **argv) {
     p.be.dp_answer_paths = b_dp_answer_paths;
     p.be.dp_genotype_margins = b_dp_genotype_margins;
     p.be.dp_genotype_stats = b_dp_genotype_stats;
+    p.be.dp_genotype_table = b_dp_genotype_table;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -480,6 +499,11 @@ int main(int argc, char **argv) {
                 fprintf(f, ", \"genotype_margins\": {\"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", (long long)gm.with_alternative, (long long)gm.margin0);
                 if (gm.min_positive_margin >= 0) fprintf(f, "%d", gm.min_positive_margin); else fprintf(f, "null");
                 fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)gm.segments, gm.wall_s);
+            }
+            if (p.sum.genotype_table.set) {                             // a recount of FILE: its rows, levels with >= 2 rows, levels with >= 2 rows of delta 0, most rows of a level
+                const dg::GenotypeTable &gt = p.sum.genotype_table;
+                fprintf(f, ", \"genotype_table\": {\"entries\": %lld, \"levels_with_choice\": %lld, \"co_optimal_levels\": %lld, \"max_per_level\": %lld, \"wall_s\": %.6f}",
+                        (long long)gt.entries, (long long)gt.levels_with_choice, (long long)gt.co_optimal_levels, (long long)gt.max_per_level, gt.wall_s);
             }
             if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
                 fprintf(f, ", \"objectives\": [");

@@ -78,6 +78,10 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     int (*dp_genotype_margins)(void *, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
                                int32_t *vertex_values, int32_t *best_value) = nullptr;
     int (*dp_genotype_stats)(void *, int64_t *out, int n) = nullptr;
+    // optional (--genotype-table): every genotype of every level with its best pair of paths, and the margin records of the call above
+    // from the same pass (dg_dp_genotype_table); *entries is released with free_buf
+    int (*dp_genotype_table)(void *, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called, dg_dp_genotype_margin *levels, int64_t *level_off,
+                             dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) = nullptr;
 };
 
 struct Options {
@@ -101,6 +105,7 @@ struct Options {
     bool wide_levels = false;    // (ours) --wide-levels, with --site-margins: the backend keeps the level state of dp_call_margins in device memory where LDS cannot hold it
     std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
     std::string genotype_margins; // (ours) --genotype-margins: TSV of the margin of the answer's genotype at -R against the best other genotype, per level, both haplotypes free (diploid)
+    std::string genotype_table;  // (ours) --genotype-table: TSV with one row per genotype of every level: its best pair of paths against the answer at -R, both haplotypes free (diploid)
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -190,6 +195,12 @@ struct SiteMargins {          // --site-margins: per haplotype, over the levels 
     double wall_s = 0;
 };
 
+struct GenotypeTable {        // --genotype-table: over the levels 1 .. L - 2
+    bool set = false;
+    int64_t entries = 0, levels_with_choice = 0, co_optimal_levels = 0, max_per_level = 0;   // rows; levels with >= 2 genotypes; with >= 2 at the DP value; most rows of a level
+    double wall_s = 0;
+};
+
 struct GenotypeMargins {      // --genotype-margins: over the levels 1 .. L - 2
     bool set = false;
     int64_t with_alternative = 0, margin0 = 0, segments = 0;
@@ -213,6 +224,7 @@ struct Summary {              // what tests and the CLI report
     std::vector<BudgetRow> budget_rows;   // --budgets: in the order listed
     SiteMargins site_margins;
     GenotypeMargins genotype_margins;
+    GenotypeTable genotype_table;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
 };
@@ -239,7 +251,7 @@ class Pipeline {
     uint32_t n_vtx = 0, num_walks = 0;
     std::vector<std::vector<uint32_t>> adj_list;
     std::vector<std::string> node_seq;
-    std::vector<std::string> node_name;    // GFA segment names (kept with --site-margins / --genotype-margins only)
+    std::vector<std::string> node_name;    // GFA segment names (kept with --site-margins / --genotype-margins / --genotype-table only)
     std::vector<std::vector<uint32_t>> paths;
     std::vector<int32_t> top_order_map;
     std::vector<std::string> hap_id2name;

@@ -261,9 +261,42 @@ typedef struct dg_dp_genotype_margin {
  * writes nothing.  Synchronises. */
 int dg_dp_genotype_margins(dg_ctx *, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class,
                            dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value);
-/* measurement: the last successful dg_dp_genotype_margins on this context: out[0] = segments, out[1] = levels whose forward state was
- * computed twice, out[2] = peak bytes of device memory the call had reserved, out[3] = kernel launches; n >= 4 (zeros before the
- * first call).  DG_ERR_ARG: null out or n < 4.  DG_ERR_STATE: no DP state on this context yet. */
+/* Genotype table: for every level l and every genotype g = (class1 <= class2, compared as signed integers) with a reachable cell,
+ * G_l[g] = the largest T_l[i][j] over the cells of that genotype, and its representative cell: the one attaining it with
+ * vertex1 <= vertex2, among equals the smallest vertex1, then the smallest vertex2 (the rule of alt_vertex1 / alt_vertex2 above).  A
+ * genotype without a reachable cell is not listed.  This is the integer analogue of a PL vector per site: the largest value of a
+ * level is V_b; with vertex_class = NULL the entries of a level are its reachable cells i <= j; the margin record of a called cell is
+ * the entry of its genotype (if the called cell is its genotype's best) against the best entry of another genotype, ties to the
+ * smallest vertex1, then vertex2; J[v] <= the largest entry whose genotype contains the class of v, with equality for NULL classes. */
+typedef struct dg_dp_genotype_entry {
+    int32_t class1, class2;           /* the genotype, class1 <= class2 */
+    int32_t vertex1, vertex2;         /* its best cell, vertex1 <= vertex2 by id, ties as above */
+    int32_t value;                    /* G_l[g] */
+    int32_t reserved;                 /* written as 0 */
+} dg_dp_genotype_entry;
+/* budget, vertex_class, the recurrences, the limits and the errors are those of dg_dp_genotype_margins, from the same pass.  called /
+ * levels are optional: both NULL with n_called = 0, or 0 < n_called <= 256 and levels receives exactly the records
+ * dg_dp_genotype_margins writes for the same arguments (called without levels, the reverse, or NULL with n_called != 0: DG_ERR_ARG).
+ * level_off (host) = [n_levels + 1]: entries level_off[l] .. level_off[l + 1] are level l's, in ascending (class1, class2); *entries is
+ * malloc'ed by the library (dg_free), *n_entries = level_off[n_levels], *best_value = V_b.  A budget that no pair fits is an answer:
+ * *n_entries = 0, *entries = NULL, level_off all 0, *best_value = NEG_INF, levels as dg_dp_genotype_margins fills them, DG_OK.
+ * Plan, before any launch: the classes of a level are ranked densely (A_l distinct ones, = the width with NULL classes); the level can
+ * hold up to A_l (A_l + 1) / 2 genotypes.  Finished entries are staged on the device in at most option genotype_table_bytes (default
+ * 256 MB) and copied to the host when the next level's bound no longer fits, at the latest once per segment, so a result of any size
+ * comes out; a level whose bound alone does not fit is DG_ERR_UNSUPPORTED (the message names the level, the bound and the option's
+ * value; nothing was launched, the statistics are those of the call before).  Beside what dg_dp_genotype_margins reserves the call
+ * holds T of the widest level (4 * width^2 bytes), one key per (row, class) and per possible genotype of a level (8 bytes each) and
+ * 12 bytes per vertex; all of it counts in the peak bytes.  Closing check: on every level the level maximum and the largest entry are
+ * V_b, DG_ERR_STATE otherwise.  DG_ERR_ARG also for a null level_off, entries, n_entries or best_value.  A failed call writes nothing
+ * to any output and allocates nothing the caller must free.  Needs dg_dp_load_graph only and leaves a run's sink values, answer paths,
+ * digests, timing and resident score-delta window as they were.  Synchronises. */
+int dg_dp_genotype_table(dg_ctx *, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called,
+                         dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries,
+                         int32_t *best_value);
+/* measurement: the last successful dg_dp_genotype_margins / dg_dp_genotype_table on this context: out[0] = segments, out[1] = levels
+ * whose forward state was computed twice, out[2] = peak bytes of device memory the call had reserved, out[3] = kernel launches; n >= 4
+ * (zeros before the first call).  With n >= 6 also out[4] = entries of the last call's table (0 after dg_dp_genotype_margins) and
+ * out[5] = its copies of the staging to the host.  DG_ERR_ARG: null out or n < 4.  DG_ERR_STATE: no DP state on this context yet. */
 int dg_dp_get_genotype_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
@@ -317,6 +350,10 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   partner_slab_bytes n  bound of the back-pointers, edge scores and paths of one slab of dg_dp_best_partners, and of what a slab of dg_dp_partner_marginals holds (default 4 GB, n <= 0 restores it; a slab holds at least one query)
  *   partner_wide 0|1|2    level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 (default) never -- beyond 16384 cells the call is refused; 1 for a call beyond 16384 cells; 2 for every call (tests, A/B timing)
  *   joint_state_bytes n   bound of the forward states that dg_dp_genotype_margins keeps for one segment of levels (default 8 GB, n <= 0 restores it; a segment holds at least one level)
+ *   genotype_table_bytes n  bound of the device staging of finished entries of dg_dp_genotype_table (default 256 MB, a guess that nothing has measured; n <= 0 restores it; one level's bound must fit)
+ *   genotype_table_lanes n  lanes that reduce one genotype of dg_dp_genotype_table over its rows: 0 (default) = the level's mean rows per class, else n; rounded down to a power of two in 1..64 (tests: 1 and 64)
+ *   genotype_table_tile_keys n   keys of a level's dense genotype triangle per workgroup of dg_dp_genotype_table's compaction: 256..2048 in steps of 256 (default 2048, n <= 0 restores it; tests: 256)
+ *   genotype_table_scan_tiles n  tiles that the workgroup scanning a level's tile counts takes per pass: 64..1024 in steps of 64 (default 1024, n <= 0 restores it; tests: 64, so that 65 tiles make a second pass)
  *   objective_lds_bytes n largest size of a pair's four colour bitmaps that dg_dp_objective_paths / dg_dp_answer_objectives keep in LDS; larger ones live in device memory (default 131072, n <= 0 restores it; clamped to the device's LDS per workgroup)
  *   pair_levels 0|1       1 (default): adjacent low-fan-in levels run as one composed launch where the run allows it (unsegmented, all planes, digest 0,
  *                         fast 1, adaptive_rc 1, test_force_rc 0); 0: every level its own launch (next load)
