@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void bt_in_edges_kernel(int64_t E, const uint3
 
 // row record {first in-edge, in-degree, in-edge 0, in-edge 1}; bit 16 of the two words: "the source vertex has exactly one
 // in-edge itself" (the chain walk then skips a back-pointer load)
-__global__ __launch_bounds__(256) void bt_rowrec_kernel(int nV, const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
+__global__ __launch_bounds__(256) void bt_rowrec_kernel(int nV, int64_t E, const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
                                                         const int32_t *__restrict__ level_of, const int32_t *__restrict__ level_off, uint4 *__restrict__ rowrec) {
     const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (v >= nV) return;
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void bt_rowrec_kernel(int nV, const uint32_t *
     const int a0v = level_off[max(0, level_of[v] - 1)];
     uint32_t word[2] = {0, 0};
     for (uint32_t q = 0; q < 2; ++q)
-        if (dv > q) {
+        if (dv > q && (int64_t)e0 + q < E) {                     // (overlapping out_off ranges of a refused graph count an edge twice: in_off may pass E)
             word[q] = in_edge[e0 + q];
             const int src = min(a0v + (int)(word[q] & 0x7FFFu), nV - 1);
             if (in_off[src + 1] - in_off[src] == 1) word[q] |= 1u << 16;
@@ -404,7 +404,7 @@ int dp_build_tables_device(dg_ctx *c, const dg_dp_graph *g, DpState &S, std::vec
     }
     hipLaunchKernelGGL(bt_colours_kernel, dim3(nblk(nV, 256)), dim3(256), 0, s, nV, col, n_hom, n_het, level_of, t_hascol.as<uint8_t>(), st);
     hipLaunchKernelGGL(bt_in_edges_kernel, dim3(nblk(E, 256)), dim3(256), 0, s, E, in_edge, in_dst, in_off, level_of, level_off, t_hascol.as<uint8_t>(), col, st);
-    hipLaunchKernelGGL(bt_rowrec_kernel, dim3(nblk(nV, 256)), dim3(256), 0, s, nV, in_off, in_edge, level_of, level_off, S.d_rowrec.as<uint4>());
+    hipLaunchKernelGGL(bt_rowrec_kernel, dim3(nblk(nV, 256)), dim3(256), 0, s, nV, E, in_off, in_edge, level_of, level_off, S.d_rowrec.as<uint4>());
     // ---- level pass 1: counts -> exclusive scans
     const size_t LS = (size_t)L + 1;
     if (int rc = t_cnt.ensure(8 * LS * NQ)) return rc;

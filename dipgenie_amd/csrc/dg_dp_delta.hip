@@ -118,8 +118,8 @@ void delta_launch_edge_flags(const DpState &S, hipStream_t s) {
 const uint16_t *delta_launch_window(DpState &S, int w, hipStream_t s) {
     const int t0 = S.dwin_t[w], t1 = S.dwin_t[w + 1];
     const uint16_t *biased = S.d_delta.as<uint16_t>();
-    if (t1 > t0) {
-        const int64_t b0 = S.dblk_first_host[t0], b1 = S.dblk_first_host[t1];
+    const int64_t b0 = S.dblk_first_host[t0], b1 = S.dblk_first_host[t1];
+    if (b1 > b0) {                                                          // (coloured transitions without an in-edge have no block: nothing to launch)
         const int64_t base_off = S.descs[S.dtrans_host[t0]].delta_off;          // global entry offset of the window's first matrix
         uint16_t *out = S.d_delta.as<uint16_t>() + DELTA_PAD - base_off;
         hipLaunchKernelGGL(dp_delta_kernel, dim3((unsigned)(b1 - b0)), dim3(256), 0, s, S.d_descs.as<LevelDesc>(), S.d_dtrans.as<int32_t>(),
@@ -178,6 +178,7 @@ const uint16_t *delta_launch_overlapped(DpState &S, hipStream_t s) {
         S.delta_piece_level[k] = t0 < nt ? S.dtrans_host[t0] : S.L;
         if (t1 <= t0) continue;
         const int64_t b0 = S.dblk_first_host[t0], b1 = S.dblk_first_host[t1];
+        if (b1 <= b0) { if (k > 0) (void)hipEventRecord(S.delta_piece_ev[k], side); continue; }   // transitions without an in-edge: no block
         hipStream_t q = k == 0 ? s : side;
         hipLaunchKernelGGL(dp_delta_kernel, dim3((unsigned)(b1 - b0)), dim3(256), 0, q, S.d_descs.as<LevelDesc>(), S.d_dtrans.as<int32_t>(),
                            S.d_dblk_first.as<int64_t>(), nt, S.d_in_edge.as<uint32_t>(), S.d_in_dst.as<int32_t>(), colour_csr(S),

@@ -104,11 +104,11 @@ int Builder::validate_and_index() {
     for (int t = 0; t < NT; ++t) max_k = std::max(max_k, tmax_k[t]);
     if (max_k > MAX_K) { set_error("level width %d exceeds the supported %d", max_k, MAX_K); return DG_ERR_UNSUPPORTED; }
     if (g->out_off[0] != 0) { set_error("out_off must start at 0"); return DG_ERR_ARG; }
-    for (int t = 1; t <= NT; ++t) {                            // monotone at the range seams (inside: checked by the owner)
+    E = g->out_off[nV];                                        // (its own refusal below, as on the device)
+    for (int t = 1; t < NT; ++t) {                             // non-negative at the range seams (inside: checked by the owner), the device's text
         const int v = lcut[t] < L ? g->level_off[lcut[t]] : nV;
-        if (g->out_off[v] < 0) { set_error("out_off negative at %d", v); return DG_ERR_ARG; }
+        if (v < nV && g->out_off[v] < 0) { set_error("out_off not monotone at %d", v); return DG_ERR_ARG; }
     }
-    E = g->out_off[nV];
     if (E < 0 || E >= (int64_t)1 << 31) { set_error("unsupported number of edges (%lld)", (long long)E); return DG_ERR_UNSUPPORTED; }
     return DG_OK;
 }
@@ -155,6 +155,8 @@ int Builder::build_in_csr() {
 
 int Builder::check_colours() {   // colour lists must be sorted (the merges rely on it) and fit the uint16 delta (colour_lists_fit_delta, dg_dp.hpp)
     if (g->hom_off[0] != 0 || g->het_off[0] != 0) { set_error("colour offsets must start at 0"); return DG_ERR_ARG; }
+    const int64_t n_hom = g->hom_off[nV], n_het = g->het_off[nV];
+    if (n_hom < 0 || n_het < 0) { set_error("colour offsets must be non-negative"); return DG_ERR_ARG; }
     std::vector<int64_t> tmax_list(2 * (size_t)NT, 0);      // per thread: longest hom list, longest het list
     has_col.assign(L, 0);
     run_threads([&](int t) {
@@ -162,7 +164,9 @@ int Builder::check_colours() {   // colour lists must be sorted (the merges rely
             for (int pass = 0; pass < 2; ++pass) {
                 const int64_t *off = pass ? g->het_off : g->hom_off;
                 const int32_t *colv = pass ? g->het_col : g->hom_col;
-                if (off[v + 1] < off[v]) { tfail(t, DG_ERR_ARG, "colour offsets not monotone at %d", v); return; }
+                const int64_t n = pass ? n_het : n_hom;
+                // both ends inside the id array before the list is walked (every v tests its own off[v]: the range seams too)
+                if (off[v] < 0 || off[v + 1] < off[v] || off[v + 1] > n) { tfail(t, DG_ERR_ARG, "colour offsets not monotone at %d", v); return; }
                 tmax_list[2 * t + pass] = std::max(tmax_list[2 * t + pass], off[v + 1] - off[v]);
                 if (off[v + 1] > off[v]) has_col[level_of[v]] = 1;
                 for (int64_t q = off[v] + 1; q < off[v + 1]; ++q)
@@ -511,6 +515,14 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     const bool dbg = getenv("DG_DEBUG") != nullptr;
     double tl0 = wall_s();
     auto lap = [&](const char *what) { if (dbg) { double t = wall_s(); fprintf(stderr, "[dipgenie_hip] load: %-22s %.3f s\n", what, t - tl0); tl0 = t; } };
+    if (DpState *Sp = c->dp) {                                  // whatever was resident goes first, with its run's answers: a refused load
+        graphs_clear(*Sp);                                      // leaves no graph loaded, wherever it is refused
+        Sp->loaded = false;
+        Sp->run_ok = false;
+        Sp->ob_dict = false;                                    // the colour dictionary of dg_dp_objective_paths belongs to the graph that goes
+        Sp->sink_host.clear();
+        Sp->digest_host.clear();
+    }
     if (!g || !g->level_off || !g->out_off || !g->out_dst || !g->out_w || !g->hom_off || !g->het_off) {
         set_error("dg_dp_load_graph: null array"); return DG_ERR_ARG;
     }
@@ -520,9 +532,6 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
     if (g->level_off[1] != 1) { set_error("level 0 must hold exactly the source vertex"); return DG_ERR_ARG; }
     if (!c->dp) c->dp = new DpState(c->device);
     DpState &S = *c->dp;
-    graphs_clear(S);
-    S.loaded = false;
-    S.ob_dict = false;                                          // the colour dictionary of dg_dp_objective_paths belongs to the graph that goes
     S.nV = nV; S.L = L; S.R = R; S.RP = R + 1;
     hipStream_t s = c->stream;
     PoolPause pause(S);                                         // the pool thread maps no chunk while this function allocates

@@ -88,7 +88,26 @@ typedef struct dg_dp_timing {         /* HIP-event times of the last dg_dp_run, 
  * are kept). Mapping 100+ GB takes seconds and stalls every other HIP call meanwhile, so the CLI issues it where
  * only host work follows; dg_dp_load_graph adopts the chunks and dg_dp_run waits for any still missing. */
 int dg_dp_prealloc(dg_ctx *, int64_t bytes);
-int dg_dp_load_graph(dg_ctx *, const dg_dp_graph *);   /* validate + upload + build in-CSR; resident until next load */
+/* validate + upload + build in-CSR; resident until the next load.  The refusals, with the text of dg_last_error (U, V vertices, L a level):
+ *   DG_ERR_ARG          a null array
+ *   DG_ERR_ARG          "bad sizes": n_vertices < 2, n_levels < 2, or R outside 0..4096
+ *   DG_ERR_ARG          "level_off must span [0, n_vertices]"; "level 0 must hold exactly the source vertex"; "level L is empty"
+ *   DG_ERR_UNSUPPORTED  "level width W exceeds the supported 32768"
+ *   DG_ERR_ARG          "out_off must start at 0"; "out_off not monotone at U" (a list that ends before it starts, or outside 0..out_off[n_vertices])
+ *   DG_ERR_UNSUPPORTED  "unsupported number of edges": out_off[n_vertices] outside 0..2^31 - 1
+ *   DG_ERR_ARG          "edge U->V does not go to the next level" (V outside 0..n_vertices - 1 included)
+ *   DG_ERR_ARG          "edge weight W > 1"
+ *   DG_ERR_UNSUPPORTED  "parallel edges with different weights into vertex V" (the tie order would depend on the schedule)
+ *   DG_ERR_ARG          "colour offsets must start at 0" / "must be non-negative"; "colour offsets not monotone at V" (as for out_off)
+ *   DG_ERR_ARG          "colour list of vertex V is not sorted-unique"
+ *   DG_ERR_UNSUPPORTED  colour lists too long for the 16-bit score deltas (see dg_dp_graph)
+ * and DG_ERR_OOM where state, tables or lattice do not fit.  Both constructions of the tables (device kernels; host threads: option
+ * host_tables) refuse alike; where one defect shows at several vertices, which of them is named is not defined.  No array is read
+ * outside [0, its offsets' last entry).  A refused load leaves NO graph loaded, whatever was resident before: the run, digest and
+ * query entry points answer DG_ERR_STATE until a load succeeds, which then behaves as in a fresh context.
+ * Valid and answered with value NEG_INF = INT32_MIN / 4 and empty edge lists where nothing reaches the sink: vertices without out-edges
+ * (dead ends) on any level, levels that no edge enters, and a graph without any edge. */
+int dg_dp_load_graph(dg_ctx *, const dg_dp_graph *);
 int dg_dp_run(dg_ctx *, dg_dp_result *);               /* all kernels on the resident graph (dg_dp_run_budgets with the one budget R); synchronises */
 int dg_dp_get_timing(dg_ctx *, dg_dp_timing *);
 int dg_dp_solve_diploid(dg_ctx *, const dg_dp_graph *, dg_dp_result *);   /* = load_graph + run */

@@ -3,7 +3,8 @@ graphs of tests/test_gpu_score_paths.py, for every budget 0..3: T equals the max
 through the cell, for every cell, unreachable ones included; T is symmetric; its maximum on every level is V_b, which is the
 oracle's value at that budget; the joint marginal J is at least the conditional M of tests/marginals_model.py for either half of an
 optimal pair, and strictly greater somewhere; the alternative of a record is the brute-force one for three kinds of classes; and the
-numpy form is the plain one.  This validates the yardstick of tests/test_gpu_genotype_margins.py."""
+numpy form is the plain one.  This validates the yardstick of tests/test_gpu_genotype_margins.py.  Cases 5..10 are the same graphs with dead-end vertices
+(tests/loader_graphs.py): the yardstick of tests/test_gpu_dead_ends.py."""
 import numpy as np
 import pytest
 
@@ -12,7 +13,7 @@ from genotype_margins_model import genotype_margins_np, joint_marginals, level_r
 from marginals_model import partner_marginals
 from paths_model import NEG_INF, PathModel
 from test_gpu_score_paths import ENUMERABLE
-from test_partner_model import enumerable_graph
+from test_partner_model import DEAD_ENDS, enumerable_graph
 from test_paths_model import oracle_values
 
 BUDGETS = range(4)
@@ -54,7 +55,7 @@ def case(q):
     return _CASES[q]
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_through_value_is_the_brute_force_maximum_in_every_cell(q):
     g, m, P, rec, S, model, brute = case(q)
     assert g.R == 3
@@ -109,7 +110,7 @@ def _called_kinds(m, P, rec, S, V, b, seed):
     return out
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_the_alternative_is_the_brute_force_one(q):
     g, m, P, rec, S, model, brute = case(q)
     n_alt = n_none = 0
@@ -137,7 +138,7 @@ def test_the_alternative_is_the_brute_force_one(q):
     assert n_alt > 0 and n_none > 0
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_the_numpy_form_is_the_plain_form(q):
     g, m, P, rec, S, model, brute = case(q)
     for b in BUDGETS:

@@ -3,7 +3,8 @@ of tests/test_gpu_score_paths.py, for every budget 0..3 and three kinds of class
 of any enumerated ordered pair of paths whose cell has that genotype, with the smallest (min, max) cell among the best; genotypes no
 pair passes through are absent; and the table implies the margin records (level_records) and bounds the joint marginals
 (joint_marginals) as its definition says.  The numpy form is the plain one.  This validates the yardstick of
-tests/test_gpu_genotype_table.py."""
+tests/test_gpu_genotype_table.py.  Cases 5..10 are the same graphs with dead-end vertices (tests/loader_graphs.py): the yardstick of
+tests/test_gpu_dead_ends.py."""
 import numpy as np
 import pytest
 
@@ -12,6 +13,7 @@ from genotype_margins_model import joint_marginals, level_records
 from genotype_table_model import genotype_table, genotype_table_np, record_from_table, vertex_maxima_from_table
 from paths_model import NEG_INF
 from test_genotype_margins_model import BUDGETS, _called_kinds, case
+from test_partner_model import DEAD_ENDS
 from test_gpu_score_paths import ENUMERABLE
 
 
@@ -19,7 +21,7 @@ def _c(cls, v):
     return int(v) if cls is None else int(cls[v])
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_every_entry_is_the_brute_force_best_of_its_genotype(q):
     g, m, P, rec, S, model, brute = case(q)
     listed = absent = 0
@@ -53,7 +55,7 @@ def test_every_entry_is_the_brute_force_best_of_its_genotype(q):
     assert listed > 0 and absent > 0
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_the_table_implies_the_margin_records_and_bounds_the_marginals(q):
     g, m, P, rec, S, model, brute = case(q)
     own = other = 0

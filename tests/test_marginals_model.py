@@ -2,7 +2,8 @@
 of tests/test_gpu_score_paths.py, for every sixth path as the given one and every budget 0..R + 1: M[v] is the maximum of
 PathModel.score(given, q) over all paths q through v with r(q) <= b, NEG_INF exactly where there is none; source and sink, and the
 best vertex of every level, are worth what partner_model.best_partner answers; the level records follow the tie rule; and the
-batched form is the plain one.  This validates the yardstick of tests/test_gpu_marginals.py."""
+batched form is the plain one.  This validates the yardstick of tests/test_gpu_marginals.py.  Cases 5..10 are the same graphs with
+dead-end vertices (tests/loader_graphs.py; every second path given): the yardstick of tests/test_gpu_dead_ends.py."""
 import numpy as np
 import pytest
 
@@ -10,7 +11,7 @@ from marginals_model import level_records, partner_marginals, partner_marginals_
 from partner_model import best_partner
 from paths_model import NEG_INF, PathModel
 from test_gpu_score_paths import ENUMERABLE
-from test_partner_model import enumerable_graph
+from test_partner_model import DEAD_ENDS, enumerable_graph
 
 BUDGETS = range(5)                                      # 0..4 = 0..R + 1 of these graphs
 _CASES = {}
@@ -23,13 +24,13 @@ def case(q):
         m = PathModel(g)
         paths = m.all_paths()
         rec = [m.recombinations(p) for p in paths]
-        some = list(range(0, len(paths), 6))
+        some = list(range(0, len(paths), 2 if q in DEAD_ENDS else 6))      # (the graphs with dead ends have as few as five paths)
         answers = {(a, b): partner_marginals(m, paths[a], b) for a in some for b in BUDGETS}
         _CASES[q] = (g, m, paths, rec, some, answers)
     return _CASES[q]
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_marginal_is_the_brute_force_maximum_through_the_vertex(q):
     g, m, paths, rec, some, answers = case(q)
     assert g.R == 3 and len(some) >= 2
@@ -45,7 +46,7 @@ def test_marginal_is_the_brute_force_maximum_through_the_vertex(q):
             assert M == want, (q, a, b)
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_source_sink_and_every_level_are_worth_the_best_partner(q):
     g, m, paths, rec, some, answers = case(q)
     for a in some:
@@ -62,7 +63,7 @@ def test_source_sink_and_every_level_are_worth_the_best_partner(q):
             assert max(M) == value and (value != NEG_INF or set(M) == {NEG_INF})
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_level_records_follow_the_tie_rule(q):
     """stated once more without a sort: best = the first vertex in id order that reaches the level's maximum, second = the first
     other vertex that reaches the maximum of the rest"""
@@ -100,7 +101,7 @@ def test_the_cases_are_not_vacuous():
     assert unreachable >= 1 and ties >= 1 and margins >= 1
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_the_batched_model_is_the_model(q):
     g, m, paths, rec, some, answers = case(q)
     keys = [(a, b) for a in some for b in BUDGETS]

@@ -2,11 +2,13 @@
 the enumerable graphs of tests/test_gpu_score_paths.py, for every path p and every budget b: the model's value is the brute-force
 maximum of PathModel.score(p, q) over all q with r(q) <= b, NEG_INF exactly where no such q exists, and the returned partner scores
 that value; and for every b the maximum over p of model(p, b - r(p)) is the enumerated optimum of plane b and the oracle's value.
-This validates the yardstick of tests/test_gpu_partner.py."""
+This validates the yardstick of tests/test_gpu_partner.py.  Cases 5..10 are the same graphs with dead-end
+vertices (tests/loader_graphs.py): the yardstick of tests/test_gpu_dead_ends.py."""
 import numpy as np
 import pytest
 
 import graphgen
+from loader_graphs import N_ENUMERABLE_DEAD, dead_ends_enumerable
 from partner_model import best_partner, best_partners
 from paths_model import NEG_INF, PathModel
 from test_gpu_score_paths import ENUMERABLE
@@ -14,9 +16,12 @@ from test_paths_model import oracle_values
 
 BUDGETS = range(4)                                      # 0..3 = 0..R of these graphs
 _CASES = {}
+DEAD_ENDS = range(len(ENUMERABLE), len(ENUMERABLE) + N_ENUMERABLE_DEAD)   # cases 5..: the same graphs with dead-end vertices (tests/loader_graphs.py)
 
 
 def enumerable_graph(q):
+    if q >= len(ENUMERABLE):
+        return dead_ends_enumerable(q - len(ENUMERABLE))
     seed, n_levels, extra, p_w1, p_colour = ENUMERABLE[q]
     return graphgen.random_levelized(seed, n_levels=n_levels, max_width=4, R=3, extra_edges=extra, p_w1=p_w1, p_colour=p_colour)
 
@@ -33,7 +38,7 @@ def case(q):
     return _CASES[q]
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_model_is_the_brute_force_maximum(q):
     g, m, paths, rec, answers = case(q)
     assert g.R == 3
@@ -51,7 +56,7 @@ def test_model_is_the_brute_force_maximum(q):
             assert planes[b] == value and planes == [answers[(a, r)][0] for r in range(b + 1)]       # "at most": plane r is budget r's answer
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_maximum_over_given_paths_is_the_plane_of_the_sweep(q):
     g, m, paths, rec, answers = case(q)
     best, _ = m.best_per_budget(g.R, paths)
@@ -88,7 +93,7 @@ def test_a_decided_tie_goes_to_the_smallest_source():
     assert seen >= 1
 
 
-@pytest.mark.parametrize("q", range(len(ENUMERABLE)))
+@pytest.mark.parametrize("q", [*range(len(ENUMERABLE)), *DEAD_ENDS])
 def test_the_batched_model_is_the_model(q):
     g, m, paths, rec, answers = case(q)
     given = np.array([p for p in paths for b in BUDGETS], np.int32)
