@@ -1007,7 +1007,10 @@ extern "C" int dg_sketch_get_timing(dg_ctx *c, dg_sketch_timing *t) {
 extern "C" int dg_sketch_count_dictionary_dev(dg_ctx *c, const uint64_t *dict_dev, int64_t n_dict, const uint64_t *hash_dev,
                                               const int32_t *count_dev, int64_t n, int32_t *counts_dev) {
     if (int rc = bind(c)) return rc;
-    if (n_dict <= 0) return DG_OK;
+    if (n_dict < 0 || n < 0 || (n_dict > 0 && (!dict_dev || !counts_dev)) || (n > 0 && (!hash_dev || !count_dev))) {
+        set_error("dg_sketch_count_dictionary_dev: bad arguments"); return DG_ERR_ARG;
+    }
+    if (n_dict == 0) return DG_OK;
     hipLaunchKernelGGL(dict_count_kernel, dim3((unsigned)((n_dict + 255) / 256)), dim3(256), 0, c->stream, dict_dev, n_dict, hash_dev, count_dev, n, counts_dev);
     DG_HIP(hipGetLastError());
     return DG_OK;
@@ -1018,6 +1021,9 @@ extern "C" int dg_sketch_merge_runs_dev(dg_ctx *c, const uint64_t *hash_dev, con
     if (int rc = bind(c)) return rc;
     if (!n_out) { set_error("dg_sketch_merge_runs_dev: null n_out"); return DG_ERR_ARG; }
     *n_out = 0;
+    if (n < 0 || cap < 0 || (n > 0 && (!hash_dev || !count_dev)) || (cap > 0 && (!out_hash_dev || !out_count_dev))) {
+        set_error("dg_sketch_merge_runs_dev: bad arguments"); return DG_ERR_ARG;
+    }
     if (n == 0) return DG_OK;
     SketchState &S = state(c);
     hipStream_t s = c->stream;
@@ -1064,7 +1070,10 @@ extern "C" int dg_sketch_partition_dev(dg_ctx *c, const uint64_t *hash_dev, int6
 extern "C" int dg_sketch_rank_dictionary_dev(dg_ctx *c, const uint64_t *dict_dev, int64_t n_dict, const uint64_t *hash_dev, int64_t n, int64_t base,
                                              int64_t *rank1_dev) {
     if (int rc = bind(c)) return rc;
-    if (n_dict <= 0) return DG_OK;
+    if (n_dict < 0 || n < 0 || (n_dict > 0 && (!dict_dev || !rank1_dev)) || (n > 0 && !hash_dev)) {
+        set_error("dg_sketch_rank_dictionary_dev: bad arguments"); return DG_ERR_ARG;
+    }
+    if (n_dict == 0) return DG_OK;
     hipLaunchKernelGGL(dict_rank_kernel, dim3((unsigned)((n_dict + 255) / 256)), dim3(256), 0, c->stream, dict_dev, n_dict, hash_dev, n, base, rank1_dev);
     DG_HIP(hipGetLastError());
     return DG_OK;
@@ -1073,7 +1082,10 @@ extern "C" int dg_sketch_rank_dictionary_dev(dg_ctx *c, const uint64_t *dict_dev
 extern "C" int dg_sketch_count_rank_dictionary_dev(dg_ctx *c, const uint64_t *dict_dev, int64_t n_dict, const uint64_t *hash_dev,
                                                    const int32_t *count_dev, int64_t n, int64_t base, int32_t *counts_dev, int64_t *rank1_dev) {
     if (int rc = bind(c)) return rc;
-    if (n_dict <= 0) return DG_OK;
+    if (n_dict < 0 || n < 0 || (n_dict > 0 && (!dict_dev || !counts_dev || !rank1_dev)) || (n > 0 && (!hash_dev || !count_dev))) {
+        set_error("dg_sketch_count_rank_dictionary_dev: bad arguments"); return DG_ERR_ARG;
+    }
+    if (n_dict == 0) return DG_OK;
     hipLaunchKernelGGL(dict_count_rank_kernel, dim3((unsigned)((n_dict + 255) / 256)), dim3(256), 0, c->stream, dict_dev, n_dict, hash_dev, count_dev, n, base,
                        counts_dev, rank1_dev);
     DG_HIP(hipGetLastError());

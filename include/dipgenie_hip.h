@@ -508,7 +508,9 @@ int dg_sketch_rank_dictionary_dev(dg_ctx *, const uint64_t *dict_dev, int64_t n_
  * spectrum is the global one).  Asynchronous. */
 int dg_sketch_count_rank_dictionary_dev(dg_ctx *, const uint64_t *dict_dev, int64_t n_dict, const uint64_t *hash_dev,
                                         const int32_t *count_dev, int64_t n, int64_t base, int32_t *counts_dev, int64_t *rank1_dev);
-/* hist_dev[min(count, n_bins-1)] += 1 per entry: this range's share of Hist_kmer (solver.cpp:745-755).  Asynchronous. */
+/* hist_dev[min(max(count, 0), n_bins-1)] += 1 per entry: this range's share of Hist_kmer (solver.cpp:745-755).  Asynchronous.
+ * The count / merge / partition / rank / count_rank / histogram entry points above answer DG_ERR_ARG ("<entry point>: bad arguments") to a negative size and to a null pointer whose
+ * size is positive, and write nothing then; a size of 0 with null pointers is no error. */
 int dg_sketch_histogram_dev(dg_ctx *, const int32_t *count_dev, int64_t n, int n_bins, uint64_t *hist_dev);
 
 /* ---- read-sharded scoring inside ONE process (bin/DipGenie --gpus N; SURVEY.md s8e, BASELINE configs[3]) ----

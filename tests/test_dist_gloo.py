@@ -12,60 +12,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-class CpuOps:
-    """test shim for dist_sketch.HipOps: same methods, CPU tensors (uint64 hashes held as int64, like the device path)"""
-    stream = None
-
-    def __init__(self, orc):
-        self.orc = orc
-
-    @staticmethod
-    def _u(t):
-        return t.numpy().view(np.uint64)
-
-    def sketch_reads(self, bases_t, off_t, k, w):
-        b, off = bases_t.numpy().tobytes(), off_t.numpy()
-        reads = [b[off[i]:off[i + 1]] for i in range(off.size - 1)]
-        h, c = self.orc.sketch_reads(reads, k, w)
-        return torch.from_numpy(h.view(np.int64).copy()), torch.from_numpy(c.copy())
-
-    def count_dictionary(self, dict_t, h, c):
-        d, hh = self._u(dict_t), self._u(h)
-        out = np.zeros(d.size, np.int32)
-        if hh.size:
-            pos = np.searchsorted(hh, d)
-            hit = (pos < hh.size) & (hh[np.minimum(pos, hh.size - 1)] == d)
-            out[hit] = c.numpy()[pos[hit]]
-        return torch.from_numpy(out)
-
-    def partition(self, h, world):
-        hh = self._u(h)
-        owner = ((hh >> np.uint64(32)) * np.uint64(world)) >> np.uint64(32)
-        return torch.from_numpy(np.searchsorted(owner, np.arange(world + 1), side="left").astype(np.int64))
-
-    def merge_runs(self, h, c):
-        hh, cc = self._u(h), c.numpy()
-        order = np.argsort(hh, kind="stable")
-        hh, cc = hh[order], cc[order]
-        if hh.size == 0:
-            return h[:0], c[:0]
-        uh, idx = np.unique(hh, return_index=True)
-        uc = np.add.reduceat(cc, idx).astype(np.int32)
-        if uh[-1] == np.uint64(0xFFFFFFFFFFFFFFFF) and uc[-1] == 0:           # padding of the fixed-size exchange (as dg_sketch_merge_runs_dev)
-            uh, uc = uh[:-1], uc[:-1]
-        return torch.from_numpy(uh.view(np.int64).copy()), torch.from_numpy(uc.copy())
-
-    def rank_dictionary(self, dict_t, h, rank1):
-        d, hh, out = self._u(dict_t), self._u(h), rank1.numpy()
-        if hh.size:
-            pos = np.searchsorted(hh, d)
-            hit = (pos < hh.size) & (hh[np.minimum(pos, hh.size - 1)] == d)
-            out[hit] += pos[hit] + 1
-
-    def histogram(self, c, hist):
-        out = hist.numpy()
-        out += np.bincount(np.minimum(c.numpy(), out.size - 1), minlength=out.size)
+from shard_ops_model import CpuOps
 
 
 def reference(orc, reads, dict_hashes, k, w, n_bins):

@@ -41,7 +41,7 @@ def _worker(rank, world, port, a, q):
     import sys
     sys.path.insert(0, ROOT); sys.path.insert(0, HERE)
     import oracle_py as orc
-    from test_dist_gloo import CpuOps
+    from shard_ops_model import CpuOps
     from dipgenie_amd import run_sharded as rs
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     if world > 1:
