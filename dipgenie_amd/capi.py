@@ -95,6 +95,7 @@ SYMBOLS = [
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
+    "dg_dp_run_pinned", "dg_dp_get_pin_stats",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -110,6 +111,8 @@ lib.dg_dp_load_graph.argtypes = [C.c_void_p, C.POINTER(DpGraph)]
 lib.dg_dp_run.argtypes = [C.c_void_p, C.POINTER(DpResult)]
 lib.dg_dp_run_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DpResult)]
 lib.dg_dp_get_budget_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+lib.dg_dp_run_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(DpResult)]
+lib.dg_dp_get_pin_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_best_partners.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_partner_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -268,6 +271,18 @@ def outcome_from(res, bufs):
     return DpOutcome(res, p1, p2)
 
 
+PIN_REQUIRE, PIN_FORBID = 0, 1
+
+
+def genotype_pins(level, v1, v2, kind=PIN_REQUIRE):
+    """the pins of an unordered genotype: cell (v1, v2) of `level` in both orders (one pin where v1 == v2), as rows
+    (level, vertex1, vertex2, kind) for Context.dp_run_pinned"""
+    rows = [(int(level), int(v1), int(v2), int(kind))]
+    if int(v1) != int(v2):
+        rows.append((int(level), int(v2), int(v1), int(kind)))
+    return rows
+
+
 @contextlib.contextmanager
 def _options(get, set_, kv):
     saved = []
@@ -350,6 +365,32 @@ class Context:
         want = np.asarray(budgets, np.int32)
         _check(lib.dg_dp_run_budgets(self.h, want.ctypes.data if want.size else None, len(budgets), arr), "dg_dp_run_budgets")
         return [outcome_from(arr[q], keep[q]) for q in range(len(budgets))]
+
+    def dp_run_pinned(self, pins, budgets=None):
+        """dp_run_budgets on the DP in which some cells are unreachable.  pins: int32 [n, 4] or an iterable of (level, vertex1,
+        vertex2, kind): the pin matches cell (i, j) of its level -- i the vertex of haplotype 1, j of haplotype 2, ordered -- if
+        vertex1 is -1 or i and vertex2 is -1 or j; kind 0 (PIN_REQUIRE): the level's cell must match one of its require-pins, 1
+        (PIN_FORBID): it must match none of its forbid-pins.  budgets defaults to [R].  Returns a DpOutcome per budget; a
+        constraint set nothing satisfies within a budget has value NEG_INF and empty paths.  The call is the last run for
+        dp_budget_values, dp_answer_paths, dp_answer_objectives, dp_timing and the profiles; dp_call_margins refuses it."""
+        p = np.ascontiguousarray(np.asarray(list(pins) if not isinstance(pins, np.ndarray) else pins, np.int32).reshape(-1, 4))
+        budgets = [self._g.R] if budgets is None else [int(b) for b in budgets]
+        arr = (DpResult * max(len(budgets), 1))()
+        keep = []
+        for q, b in enumerate(budgets):
+            res, bufs = make_result(max(b, 0) + 8)
+            arr[q] = res
+            keep.append(bufs)
+        want = np.asarray(budgets, np.int32)
+        _check(lib.dg_dp_run_pinned(self.h, p.ctypes.data if p.size else None, p.shape[0], want.ctypes.data if want.size else None, len(budgets), arr),
+               "dg_dp_run_pinned")
+        return [outcome_from(arr[q], keep[q]) for q in range(len(budgets))]
+
+    def dp_pin_stats(self):
+        """of the last dp_run_pinned with pins on this context: dict(pins, levels, mask_launches, pairs_as_singles, batches_plain)"""
+        out = np.zeros(5, np.int64)
+        _check(lib.dg_dp_get_pin_stats(self.h, out.ctypes.data, 5), "dg_dp_get_pin_stats")
+        return dict(zip(("pins", "levels", "mask_launches", "pairs_as_singles", "batches_plain"), out.tolist()))
 
     def dp_budget_values(self):
         """the sink's value on planes 0..R of the last dp_run / dp_run_budgets (int32[R + 1], NEG_INF where unreachable)"""

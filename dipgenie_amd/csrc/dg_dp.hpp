@@ -1,6 +1,6 @@
 // Diploid pair-of-paths DP: types and entry points shared by the translation units of the DP
 // (dg_dp_tables.hip, dg_dp_pairs.hip, dg_dp_delta.hip, dg_dp_sweep.hip, dg_dp_trace.hip, dg_dp_budgets.hip, dg_dp_run.hip, dg_dp_score.hip, dg_dp_partner.hip, dg_dp_marginals.hip,
-// dg_dp_objective.hip, dg_dp_joint.hip).
+// dg_dp_objective.hip, dg_dp_joint.hip, dg_dp_pins.hip).
 //
 // Replaces the level loop + sink read-out of Approximator::diploid_dp_approximation_solver
 // (/root/reference/src/approximator.cpp:532-716, 757-785).  Design:
@@ -309,6 +309,12 @@ struct DpState {
     // ---- dg_dp_genotype_margins / dg_dp_genotype_table (dg_dp_joint.hip): nothing but the statistics of the last call outlives it
     // (dg_dp_get_genotype_stats: segments, levels swept forward twice, peak bytes reserved, launches, table entries, staging copies) ----
     int64_t jt_stats[6] = {0, 0, 0, 0, 0, 0};
+    // ---- dg_dp_run_pinned (dg_dp_pins.hip): the call's pins sorted by level (uploaded once per call), whether the last run on the loaded
+    // graph was a pinned one, and the statistics of the last pinned run (dg_dp_get_pin_stats: pins, pinned levels, mask launches, pairs
+    // run as singles, batches issued plainly) ----
+    DevBuf d_pins;
+    bool run_pinned = false;
+    int64_t pin_stats[5] = {0, 0, 0, 0, 0};
 };
 
 inline ColourCsr colour_csr(const DpState &S) {
@@ -400,6 +406,19 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
 // ---- partner marginals: that DP forward and backward, combined per vertex (dg_dp_marginals.hip; shares dg_dp_partner.hpp with the above) ----
 int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
 int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
+
+// ---- pinned runs (dg_dp_pins.hip): the per-level cell constraints of one dg_dp_run_pinned ----
+struct PinSet {
+    std::vector<int32_t> off;            // [L + 1]: the pins of level l are d_pins[off[l] .. off[l + 1]) (sorted by level, input order inside a level)
+    const dg_dp_pin *d_pins = nullptr;   // device
+    int64_t n_mask = 0, n_pairs_split = 0, n_batches_plain = 0;   // what the run at hand issued because of them
+    bool has(int l) const { return off[(size_t)l + 1] > off[(size_t)l]; }
+    bool any_in(int l0, int l1) const { return off[(size_t)l1] > off[(size_t)l0]; }
+};
+// validates the pins against the loaded graph (DG_ERR_ARG naming the first offending pin), sorts them by level and uploads them
+int pins_prepare(dg_ctx *c, DpState &S, const dg_dp_pin *pins, int64_t n, PinSet &P);
+// stores NEG_INF into the cells of `level` that its pins do not allow, on all RP planes of the level's state slab `state` ([i][r][j])
+void pins_launch_mask(const DpState &S, PinSet &P, int level, int32_t *state, hipStream_t s);
 
 // ---- genotype margins: the DP forward and backward with both haplotypes free, combined per cell (dg_dp_joint.hip) ----
 int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,

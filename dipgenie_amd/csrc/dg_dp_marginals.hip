@@ -489,6 +489,10 @@ int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_d
     DpState *Sp = c->dp;
     if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
     DpState &S = *Sp;
+    if (S.run_pinned) {
+        set_error("%s: the last run was dg_dp_run_pinned: the margins check the run's value against an unconstrained partner DP, which a constrained answer need not reach", FN);
+        return DG_ERR_STATE;
+    }
     const int L = S.L, nV = S.nV;
     int kmax = 1;
     for (int l = 1; l < L; ++l) kmax = std::max(kmax, S.descs[l].k2);

@@ -103,8 +103,9 @@ struct Run {
     double host_enqueue_s = 0;                          // host time spent issuing the sweep's launches (DG_DEBUG)
     int n_chains = 1;                                   // chains walked from the sink, one per budget (dg_dp_run: 1)
     std::vector<uint16_t *> pool_base;
+    PinSet *P;                                          // dg_dp_run_pinned: the call's cell constraints; null in every other run
 
-    Run(dg_ctx *c_, DpState &S_) : c(c_), S(S_), s(c_->stream) { sweep_prepare(S, X); }
+    Run(dg_ctx *c_, DpState &S_, PinSet *P_ = nullptr) : c(c_), S(S_), s(c_->stream), P(P_) { sweep_prepare(S, X); }
     int n_win() const { return (int)S.dwin_t.size() - 1; }
     int32_t *state_ptr(int level) const { return (int32_t *)(S.d_ring.as<char>() + (size_t)((level & 1) ^ X.flip) * S.state_alloc_bytes) + S.pad_front; }   // (the slot parity as the launches issued so far left it)
     size_t level_cells(int level) const {               // state size of a level (level 0: the source, k = 1)
@@ -124,11 +125,20 @@ struct Run {
             }
             if (l >= next_warm) next_warm = l + (int)std::max<int64_t>(S.opt.warm_ahead, 1);
             // a level pair (dg_dp_pairs.hip) runs as one launch where both of its levels lie inside this batch; else each level as ever
-            if (X.pairs_ok && l + 1 < l1 && S.pair_at[l + 1] >= 0) {
+            // (a pinned run: the pair kernel never writes the state of its earlier level, so a pin there makes the pair two single launches)
+            const bool pair_here = X.pairs_ok && l + 1 < l1 && S.pair_at[l + 1] >= 0;
+            if (pair_here && !(P && P->has(l))) {
                 if (S.level_win[l + 1] >= 0 && S.level_win[l + 1] != S.cur_win) load_window(S.level_win[l + 1]);
                 if (int rc = sweep_launch_pair(S, X, ++l, s)) return rc;
-            } else if (int rc = sweep_launch_level(S, X, l, s)) return rc;
+            } else {
+                if (pair_here) ++P->n_pairs_split;
+                if (int rc = sweep_launch_level(S, X, l, s)) return rc;
+            }
             ++n_launch;
+            // The mask of a pinned level follows the launch that wrote it, on the same stream: whatever reads the level next -- the next
+            // launch, the checkpoint copy in front of a segment (a pin on a segment's last level is in the checkpoint), the sink copy --
+            // is ordered behind it.  state_ptr: the slot parity as that launch left it, a pair's flip included.
+            if (P && P->has(l)) pins_launch_mask(S, *P, l, state_ptr(l), s);
             // profiling aid: rocprofv3 --pmc crashes when ~10^5 dispatches are queued without a drain
             if (S.opt.sync_every > 0 && n_launch % S.opt.sync_every == 0) DG_HIP(hipStreamSynchronize(s));
         }
@@ -153,8 +163,13 @@ struct Run {
         // prefetcher's far blocks -- part of the cache key (a second DP state on the device switches the prefetcher off)
         for (int l0 = lb; l0 < le;) {
             const int pf_key = ((S.pf_active && S.opt.pf_far > 0) ? 1 : 0) | (X.flip << 1) | (X.rp_active << 2);
-            const bool use_graph = gb > 0 && n_win() == 1 && S.opt.sync_every == 0 && !S.graph_failed;
-            const int l1 = use_graph ? (int)std::min<int64_t>((int64_t)l0 + gb, le) : le;
+            const bool graph_ok = gb > 0 && n_win() == 1 && S.opt.sync_every == 0 && !S.graph_failed;
+            const int l1 = graph_ok ? (int)std::min<int64_t>((int64_t)l0 + gb, le) : le;
+            // a pinned run: a batch that holds a pinned level is issued plainly, neither replayed from S.graphs nor stored there (the batch
+            // bounds stay, so the batches around it find their cache entries; the slot flip on entry is part of their key)
+            const bool pinned_batch = P && P->any_in(l0, l1);
+            if (graph_ok && pinned_batch) ++P->n_batches_plain;
+            const bool use_graph = graph_ok && !pinned_batch;
             // score deltas computed beside the sweep (delta_launch_overlapped): the stream waits for the pieces that hold a level below l1
             while (S.delta_piece_next < (int)S.delta_piece_level.size() && S.delta_piece_level[S.delta_piece_next] < l1) {
                 DG_HIP(hipStreamWaitEvent(s, S.delta_piece_ev[S.delta_piece_next], 0));
@@ -357,14 +372,15 @@ static int emit_result(const DpState &S, const TraceOut &to, const int32_t *edge
 
 // One pass over the resident graph (the callers have checked that one is loaded): one chain per budgets[q] into res[q], all walked
 // by one launch per lattice chunk (dg_dp_trace.hip).  name_budget: error texts say which budget's chain failed.
-static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result *res, bool name_budget) {
+static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result *res, bool name_budget, PinSet *P = nullptr) {
     DpState &S = *c->dp;
-    Run run(c, S);
+    Run run(c, S, P);
     hipStream_t s = c->stream;
     if (int rc = run.wait_for_chunks()) return rc;
     std::vector<TraceOut> to((size_t)n_budgets);
     std::vector<int32_t> edges(4 * (size_t)S.cap * (size_t)n_budgets);
     S.run_ok = false;                                                   // the chains' buffers are about to be rewritten
+    S.run_pinned = P != nullptr;
     if (int rc = budgets_prepare(S, budgets, n_budgets, s)) return rc;
     run.n_chains = n_budgets;
     S.sink_host.clear();
@@ -411,19 +427,43 @@ static int dp_run(dg_ctx *c, const int32_t *budgets, int n_budgets, dg_dp_result
     return DG_OK;
 }
 
-static int dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n, dg_dp_result *results) {
-    DpState *Sp = c->dp;
-    if (!Sp || !Sp->loaded) { set_error("dg_dp_run_budgets: no graph loaded"); return DG_ERR_STATE; }
-    if (!budgets || !results || n <= 0) { set_error("dg_dp_run_budgets: budgets, results and n_budgets > 0 are required"); return DG_ERR_ARG; }
+// the budget rules of dg_dp_run_budgets and dg_dp_run_pinned (fn: the entry point's name, for the messages)
+static int check_budgets(const char *fn, const DpState *Sp, const int32_t *budgets, int32_t n, const dg_dp_result *results) {
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", fn); return DG_ERR_STATE; }
+    if (!budgets || !results || n <= 0) { set_error("%s: budgets, results and n_budgets > 0 are required", fn); return DG_ERR_ARG; }
     std::vector<char> seen((size_t)Sp->RP, 0);
     for (int q = 0; q < n; ++q) {
         const int b = budgets[q];
-        if (b < 0 || b > Sp->R) { set_error("dg_dp_run_budgets: budget %d (entry %d) outside 0..%d, the R of the loaded graph", b, q, Sp->R); return DG_ERR_ARG; }
-        if (seen[b]) { set_error("dg_dp_run_budgets: budget %d listed twice", b); return DG_ERR_ARG; }
+        if (b < 0 || b > Sp->R) { set_error("%s: budget %d (entry %d) outside 0..%d, the R of the loaded graph", fn, b, q, Sp->R); return DG_ERR_ARG; }
+        if (seen[b]) { set_error("%s: budget %d listed twice", fn, b); return DG_ERR_ARG; }
         seen[b] = 1;
-        if (results[q].cap < b + 2) { set_error("dg_dp_run_budgets: results[%d].cap = %d, budget %d needs %d", q, results[q].cap, b, b + 2); return DG_ERR_ARG; }
+        if (results[q].cap < b + 2) { set_error("%s: results[%d].cap = %d, budget %d needs %d", fn, q, results[q].cap, b, b + 2); return DG_ERR_ARG; }
     }
+    return DG_OK;
+}
+
+static int dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n, dg_dp_result *results) {
+    if (int rc = check_budgets("dg_dp_run_budgets", c->dp, budgets, n, results)) return rc;
     return dp_run(c, budgets, n, results, true);
+}
+
+// dg_dp_run_pinned: every argument is checked before anything of the last run is touched
+static int dp_run_pinned(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n, dg_dp_result *results) {
+    if (n_pins == 0) return dp_run_budgets(c, budgets, n, results);
+    if (int rc = check_budgets("dg_dp_run_pinned", c->dp, budgets, n, results)) return rc;
+    DpState &S = *c->dp;
+    if (S.opt.want_digest) {
+        set_error("dg_dp_run_pinned: option digest is 1: the sweep accumulates a level's digest before the level's mask runs, so the digest would describe another DP");
+        return DG_ERR_STATE;
+    }
+    PinSet P;
+    if (int rc = pins_prepare(c, S, pins, n_pins, P)) return rc;
+    const int rc = dp_run(c, budgets, n, results, true, &P);
+    int64_t n_levels = 0;
+    for (int l = 1; l < S.L; ++l) n_levels += P.has(l);
+    const int64_t st[5] = {n_pins, n_levels, P.n_mask, P.n_pairs_split, P.n_batches_plain};
+    memcpy(S.pin_stats, st, sizeof st);
+    return rc;
 }
 
 // dg_dp_run: the one-chain case -- the chain of budget R, named by no budget in its messages.  (No check of res->cap against the
@@ -448,6 +488,16 @@ extern "C" int dg_dp_run(dg_ctx *c, dg_dp_result *r) {
 extern "C" int dg_dp_run_budgets(dg_ctx *c, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_run_budgets(c, budgets, n_budgets, results);
+}
+extern "C" int dg_dp_run_pinned(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_run_pinned(c, pins, n_pins, budgets, n_budgets, results);
+}
+extern "C" int dg_dp_get_pin_stats(dg_ctx *c, int64_t *out, int n) {
+    if (!c || !c->dp) { dgi::set_error("dg_dp_get_pin_stats: no state"); return DG_ERR_STATE; }
+    if (!out || n < 5) { dgi::set_error("dg_dp_get_pin_stats: out with n >= 5 entries is required"); return DG_ERR_ARG; }
+    memcpy(out, c->dp->pin_stats, sizeof c->dp->pin_stats);
+    return DG_OK;
 }
 extern "C" int dg_dp_get_budget_values(dg_ctx *c, int32_t *out, int32_t n) {
     if (!c || !c->dp || !out) { dgi::set_error("dg_dp_get_budget_values: no state"); return DG_ERR_STATE; }

@@ -519,6 +519,7 @@ int dp_load(dg_ctx *c, const dg_dp_graph *g) {
         graphs_clear(*Sp);                                      // leaves no graph loaded, wherever it is refused
         Sp->loaded = false;
         Sp->run_ok = false;
+        Sp->run_pinned = false;
         Sp->ob_dict = false;                                    // the colour dictionary of dg_dp_objective_paths belongs to the graph that goes
         Sp->sink_host.clear();
         Sp->digest_host.clear();

@@ -91,12 +91,12 @@ void dump_graph(DpGraphStorage &dpg, const ExpandedGraph &g, const std::string &
 // ---- the level loop + sink read-out: DEVICE (approximator.cpp:532-716, 774-785) ----
 // answers[q] is filled for budgets[q].  --budgets: the listed budgets and -R itself from ONE sweep of the graph loaded with R
 // (plane r of the sink is the cell a run with -R r reads out; one chain walk per budget).  Without the option: the plain call, as ever.
-std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &budgets, std::vector<ChainAnswer> &answers) {
+std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &budgets, std::vector<ChainAnswer> &answers, const std::vector<dg_dp_pin> &pins) {
     const Backend &be = p.be;
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty() && p.opt.pins_file.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
@@ -108,13 +108,58 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.genotype_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_margins)) return "--genotype-margins: this backend has no dp_genotype_margins";
     // and --genotype-table: the same pass lists every genotype
     if (!p.opt.genotype_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_table || !be.free_buf)) return "--genotype-table: this backend has no dp_genotype_table";
+    // and --pins: the same run under the file's cell constraints
+    if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
     if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
     std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
     for (const ChainAnswer &a : answers) res.push_back(a.res);
     int rc = be.dp_load_graph(be.ctx, &view);
-    if (rc == 0) rc = be.dp_run_budgets(be.ctx, budgets.data(), (int32_t)budgets.size(), res.data());
+    if (rc == 0 && !p.opt.pins_file.empty()) {
+        rc = be.dp_run_pinned(be.ctx, pins.data(), (int64_t)pins.size(), budgets.data(), (int32_t)budgets.size(), res.data());
+        if (rc != 0) return backend_error(be, "dp_run_pinned");
+    } else if (rc == 0) rc = be.dp_run_budgets(be.ctx, budgets.data(), (int32_t)budgets.size(), res.data());
     if (rc != 0) return backend_error(be, "dp_run_budgets");
     for (size_t q = 0; q < answers.size(); ++q) answers[q].res = res[q];
+    return "";
+}
+
+// --pins: the rows against the levels of the graph, as pins of the C ABI.  "" or what is wrong with the first bad row
+std::string expand_pin_rows(const std::vector<PinRow> &rows, const ExpandedGraph &g, std::vector<dg_dp_pin> &pins) {
+    const int L = (int)g.level_off.size() - 1;
+    for (const PinRow &r : rows) {
+        const std::string at = "--pins: line " + std::to_string(r.line) + ": ";
+        if (r.level < 1 || r.level > L - 2) return at + "level " + std::to_string(r.level) + " outside 1.." + std::to_string(L - 2);
+        for (int32_t v : {r.vertex1, r.vertex2})
+            if (v != -1 && (v < g.level_off[(size_t)r.level] || v >= g.level_off[(size_t)r.level + 1]))
+                return at + "vertex " + std::to_string(v) + " is not on level " + std::to_string(r.level) + " (" + std::to_string(g.level_off[(size_t)r.level]) + ".." +
+                       std::to_string(g.level_off[(size_t)r.level + 1] - 1) + ")";
+        pins.push_back(dg_dp_pin{r.level, r.vertex1, r.vertex2, r.forbid ? 1 : 0});
+        if (!r.ordered && r.vertex1 != r.vertex2) pins.push_back(dg_dp_pin{r.level, r.vertex2, r.vertex1, r.forbid ? 1 : 0});
+    }
+    return "";
+}
+
+// --pins: the run's statistics, and whether the answer at -R passes only allowed cells (checked here, on the paths the run walked)
+std::string summarize_pins(Pipeline &p, const ExpandedGraph &g, const std::vector<dg_dp_pin> &pins, bool reachable) {
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    PinSummary &ps = p.sum.pins;
+    ps.set = true;
+    ps.rows = (int64_t)p.opt.pin_rows.size();
+    int64_t st[5] = {0, 0, 0, 0, 0};
+    if (!pins.empty() && be.dp_pin_stats(be.ctx, st, 5) != 0) return backend_error(be, "dp_pin_stats");
+    ps.pins = (int64_t)pins.size(); ps.levels = st[1]; ps.pairs_as_singles = st[3];
+    ps.satisfied = false;
+    if (!reachable) return "";
+    std::vector<int32_t> paths(2 * (size_t)L);
+    if (be.dp_answer_paths(be.ctx, p.opt.R, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+    std::vector<char> any_req((size_t)L, 0), req((size_t)L, 0), forbid((size_t)L, 0);
+    for (const dg_dp_pin &q : pins) {
+        const bool m = (q.vertex1 == -1 || q.vertex1 == paths[(size_t)q.level]) && (q.vertex2 == -1 || q.vertex2 == paths[(size_t)L + q.level]);
+        if (q.kind == 0) { any_req[(size_t)q.level] = 1; req[(size_t)q.level] |= m; } else forbid[(size_t)q.level] |= m;
+    }
+    ps.satisfied = true;
+    for (int l = 0; l < L; ++l) if ((any_req[(size_t)l] && !req[(size_t)l]) || forbid[(size_t)l]) ps.satisfied = false;
     return "";
 }
 
@@ -533,6 +578,44 @@ std::string write_read_tags(Pipeline &p, const std::string *hs) {
 
 }  // namespace
 
+std::string read_pins_file(const std::string &path, std::vector<PinRow> &rows) {
+    std::ifstream f(path, std::ios::in | std::ios::binary);
+    if (!f.is_open()) return "--pins: cannot open " + path;
+    std::string line;
+    for (int n = 1; std::getline(f, line); ++n) {
+        const std::string at = "--pins: line " + std::to_string(n) + ": ";
+        line = line.substr(0, line.find('#'));
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        std::vector<std::string> col;
+        for (size_t a = 0; a <= line.size();) {
+            size_t b = line.find('\t', a);
+            if (b == std::string::npos) b = line.size();
+            col.push_back(line.substr(a, b - a));
+            a = b + 1;
+        }
+        if (col.size() < 3 || col.size() > 4) return at + "expected level, vertex1, vertex2 and an optional kind, separated by tabs; found " + std::to_string(col.size()) + " columns";
+        PinRow r;
+        r.line = n;
+        int32_t *dst[3] = {&r.level, &r.vertex1, &r.vertex2};
+        for (int q = 0; q < 3; ++q) {
+            const std::string &s = col[(size_t)q];
+            if (q > 0 && s == ".") { *dst[q] = -1; continue; }
+            if (s.empty() || s.size() > 9 || s.find_first_not_of("0123456789") != std::string::npos)
+                return at + "'" + s + "' is not a " + (q ? "vertex id (a non-negative integer, or . for any)" : "level (a non-negative integer)");
+            *dst[q] = atoi(s.c_str());
+        }
+        const std::string kind = col.size() == 4 ? col[3] : "require";
+        if (kind == "require") {}
+        else if (kind == "forbid") r.forbid = true;
+        else if (kind == "require-ordered") r.ordered = true;
+        else if (kind == "forbid-ordered") r.forbid = r.ordered = true;
+        else return at + "kind '" + kind + "' is not one of require, forbid, require-ordered, forbid-ordered";
+        rows.push_back(r);
+    }
+    return "";
+}
+
 int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_bv,
                       const std::vector<std::vector<AnchorRec>> &anchorsByHap, std::string &err) {
     double t0 = now_s();
@@ -576,6 +659,8 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
+    std::vector<dg_dp_pin> pins;                                       // --pins: a row outside the graph ends the run before the DP
+    if (!opt.pins_file.empty() && failed(expand_pin_rows(opt.pin_rows, g, pins), err)) { sum.pins.bad_rows = true; return -1; }
     if (!opt.dump_prefix.empty()) dump_graph(dpg, g, opt.dump_prefix + ".dpg", R);
     if (opt.dump_only) { err = "dump_only"; return 1; }
 
@@ -587,12 +672,13 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     std::vector<ChainAnswer> answers;
     answers.reserve(budgets.size());
     for (size_t q = 0; q < budgets.size(); ++q) answers.emplace_back(R + 8);
-    if (failed(run_dp(*this, g, budgets, answers), err)) return -1;
+    if (failed(run_dp(*this, g, budgets, answers, pins), err)) return -1;
     stamp("dp_level_loop", t0);
 
     t0 = now_s();
     const ChainAnswer &top = answers[(size_t)(std::find(budgets.begin(), budgets.end(), (int32_t)R) - budgets.begin())];
     sum.dp_value = top.res.value; sum.s_het = top.res.s_het; sum.cells = top.res.cells; sum.relaxations = top.res.relaxations;
+    if (!opt.pins_file.empty() && failed(summarize_pins(*this, g, pins, top.reachable()), err)) return -1;
     if (!opt.quiet) std::cout << "DP value: " << top.res.value << std::endl;   // :776
     const auto [wp1, wp2] = top.edge_lists();
     PathReadout out;

@@ -120,6 +120,14 @@ static int b_dp_budgets(void *c, const int32_t *budgets, int32_t n, dg_dp_result
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_run_budgets(x, budgets, n, r) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_pinned(void *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n, dg_dp_result *r) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_run_pinned(x, pins, n_pins, budgets, n, r) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_pin_stats(void *c, int64_t *out, int n) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_pin_stats(x, out, n) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_call_margins(void *c, int32_t budget, const int32_t *cls, dg_dp_call_margin *levels, int32_t *paths) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_call_margins(x, budget, cls, levels, paths) : DG_ERR_NO_DEVICE;
@@ -260,6 +268,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --genotype-table FILE     (MI355X build, -p2) per level one row for every genotype a pair of paths within -R passes through: its best cell, value, distance to the DP value, whether the answer has it (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
+    fprintf(fp, "    --pins FILE           (MI355X build, -p2) run the DP under cell constraints: rows level, vertex1, vertex2 [, require|forbid|require-ordered|forbid-ordered], tab-separated, . = any vertex, ids as --genotype-table prints them\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
 
@@ -279,7 +288,7 @@ int main(int argc, char **argv) {
     int n_gpus = 1, shard_transport = -1;
     std::vector<int> shard_devices;
     std::string budgets_arg;
-    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false;
+    bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -309,6 +318,12 @@ int main(int argc, char **argv) {
                 have_genotype_table = true;                            // (a missing value is an empty file name: refused below)
                 const char *v = val("--genotype-table");
                 p.opt.genotype_table = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--pins", 6) && (argv[i][6] == 0 || argv[i][6] == '=')) {
+                have_pins = true;                                      // (a missing value is an empty file name: refused below)
+                const char *v = val("--pins");
+                p.opt.pins_file = v ? v : "";
                 continue;
             }
             if (!strcmp(argv[i], "--wide-levels")) { p.opt.wide_levels = true; continue; }
@@ -410,6 +425,17 @@ int main(int argc, char **argv) {
         if (p.opt.tag_reads.empty()) { fprintf(stderr, "[E::main] --tag-reads needs a file name\n"); return 1; }
         if (sharded) { fprintf(stderr, "[E::main] --tag-reads does not go with --gpus / --shard-transport: the sharded path drops the reads once they are scored\n"); return 1; }
     }
+    // --pins FILE: the same; the margin and table options describe the unconstrained DP, the sharded path has no pinned run
+    if (have_pins) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --pins constrains the pair of paths of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.pins_file.empty()) { fprintf(stderr, "[E::main] --pins needs a file name\n"); return 1; }
+        if (have_site_margins || have_genotype_margins || have_genotype_table) {
+            fprintf(stderr, "[E::main] --pins does not go with --site-margins / --genotype-margins / --genotype-table: they describe the unconstrained DP\n"); return 1;
+        }
+        if (sharded) { fprintf(stderr, "[E::main] --pins does not go with --gpus / --shard-transport\n"); return 1; }
+        const std::string e = dg::read_pins_file(p.opt.pins_file, p.opt.pin_rows);   // a malformed row: exit status 2, before any device is asked for
+        if (!e.empty()) { fprintf(stderr, "[E::main] %s\n", e.c_str()); return 2; }
+    }
     g_wide_levels = p.opt.wide_levels;
     if (!sharded) g_lazy.start(device, p.opt.k, p.opt.w);
     p.be.ctx = &g_lazy;
@@ -425,6 +451,8 @@ int main(int argc, char **argv) {
     p.be.dp_genotype_margins = b_dp_genotype_margins;
     p.be.dp_genotype_stats = b_dp_genotype_stats;
     p.be.dp_genotype_table = b_dp_genotype_table;
+    p.be.dp_run_pinned = b_dp_pinned;
+    p.be.dp_pin_stats = b_dp_pin_stats;
     p.be.free_buf = dg_free;
     p.be.hint_dp_soon = b_hint;
     p.be.dp_solve_haploid = b_hap;
@@ -454,6 +482,7 @@ int main(int argc, char **argv) {
     dg_ctx *ctx = g_lazy.get();
     if (!ctx) { fprintf(stderr, "[E::main] %s\n", g_lazy.err.c_str()); return 2; }   // no gfx950 device: no CPU fallback
     if (rc != 0 && err == "dump_only") { std::cout.flush(); fflush(nullptr); _exit(0); }   // -X: stop after the dump(s)
+    if (rc != 0 && p.sum.pins.bad_rows) { fprintf(stderr, "[E::main] %s\n", err.c_str()); dg_destroy(ctx); return 2; }   // --pins: a level or a vertex the graph does not have
     if (rc != 0) { fprintf(stderr, "[E::main] %s\n", err.c_str()); dg_destroy(ctx); return 1; }
     dg_dp_timing tm;
     const bool have_tm = p.opt.ploidy == 2 && dg_dp_get_timing(ctx, &tm) == DG_OK;
@@ -514,6 +543,11 @@ int main(int argc, char **argv) {
                     else fprintf(f, "%s{\"r\": %d, \"dp_value\": null, \"objective\": null, \"hom_shared\": null, \"hom_single\": null, \"het_single\": null, \"het_both\": null}", i ? ", " : "", o.r);
                 }
                 fprintf(f, "]");
+            }
+            if (p.sum.pins.set) {                                       // the file's rows, the run's pins and pinned levels, pairs it ran as two launches, the answer at -R passes only allowed cells
+                const dg::PinSummary &ps = p.sum.pins;
+                fprintf(f, ", \"pins\": {\"rows\": %lld, \"pins\": %lld, \"levels\": %lld, \"pairs_as_singles\": %lld, \"satisfied\": %s}", (long long)ps.rows, (long long)ps.pins, (long long)ps.levels,
+                        (long long)ps.pairs_as_singles, ps.satisfied ? "true" : "false");
             }
             if (p.sum.read_tags.set) {                                  // hap1 + hap2 + tie + no_evidence = reads
                 const dg::ReadTags &rt = p.sum.read_tags;

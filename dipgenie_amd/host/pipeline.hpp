@@ -82,7 +82,17 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // from the same pass (dg_dp_genotype_table); *entries is released with free_buf
     int (*dp_genotype_table)(void *, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called, dg_dp_genotype_margin *levels, int64_t *level_off,
                              dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) = nullptr;
+    // optional (--pins): the run of dp_run_budgets with per-level cell constraints (dg_dp_run_pinned), and that run's statistics
+    // (dg_dp_get_pin_stats)
+    int (*dp_run_pinned)(void *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) = nullptr;
+    int (*dp_pin_stats)(void *, int64_t *out, int n) = nullptr;
 };
+
+// one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
+// pins of the C ABI where the vertices differ) or the ordered cell (one)
+struct PinRow { int32_t level = 0, vertex1 = -1, vertex2 = -1; bool forbid = false, ordered = false; int line = 0; };
+// parses FILE (rows "level <tab> vertex1 <tab> vertex2 [<tab> kind]", '.' = any, '#' starts a comment); "" or what is wrong with the first bad row
+std::string read_pins_file(const std::string &path, std::vector<PinRow> &rows);
 
 struct Options {
     int threads = 4;          // -t
@@ -106,6 +116,8 @@ struct Options {
     std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
     std::string genotype_margins; // (ours) --genotype-margins: TSV of the margin of the answer's genotype at -R against the best other genotype, per level, both haplotypes free (diploid)
     std::string genotype_table;  // (ours) --genotype-table: TSV with one row per genotype of every level: its best pair of paths against the answer at -R, both haplotypes free (diploid)
+    std::string pins_file;       // (ours) --pins: the DP runs under the cell constraints of this file's rows (diploid); parsed into pin_rows before anything else runs
+    std::vector<PinRow> pin_rows;
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -213,6 +225,12 @@ struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more priv
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
 };
 
+struct PinSummary {           // --pins: rows of the file, pins and pinned levels of the run, level pairs it ran as two launches, whether the answer at -R passes only allowed cells
+    bool set = false, bad_rows = false;          // bad_rows: a row names a level or a vertex the graph does not have (the run ended before the DP)
+    int64_t rows = 0, pins = 0, levels = 0, pairs_as_singles = 0;
+    bool satisfied = false;
+};
+
 struct Summary {              // what tests and the CLI report
     int32_t dp_value = 0, s_het = 0, r1 = -1, r2 = -1, obj = 0, best_r_haploid = -1;
     int64_t len1 = 0, len2 = 0;
@@ -227,6 +245,7 @@ struct Summary {              // what tests and the CLI report
     GenotypeTable genotype_table;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
+    PinSummary pins;
 };
 
 // One anchor occurrence: vertex list vpool[off, off+len) of read-minimizer id `a` on haplotype `h`.

@@ -7,6 +7,8 @@ static int b_sketch_hap(void *c, const char *s, int64_t len, int k, int w, uint6
 static int b_dp(void *c, const dg_dp_graph *g, dg_dp_result *r) { return dg_dp_solve_diploid((dg_ctx *)c, g, r); }
 static int b_dp_load(void *c, const dg_dp_graph *g) { return dg_dp_load_graph((dg_ctx *)c, g); }
 static int b_dp_budgets(void *c, const int32_t *budgets, int32_t n, dg_dp_result *r) { return dg_dp_run_budgets((dg_ctx *)c, budgets, n, r); }
+static int b_dp_pinned(void *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n, dg_dp_result *r) { return dg_dp_run_pinned((dg_ctx *)c, pins, n_pins, budgets, n, r); }
+static int b_dp_pin_stats(void *c, int64_t *out, int n) { return dg_dp_get_pin_stats((dg_ctx *)c, out, n); }
 static int b_dp_call_margins(void *c, int32_t budget, const int32_t *cls, dg_dp_call_margin *levels, int32_t *paths) { return dg_dp_call_margins((dg_ctx *)c, budget, cls, levels, paths); }
 static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) { return dg_dp_answer_objectives((dg_ctx *)c, budgets, n, out); }
 static int b_tag_reads(void *c, const char *b, const int64_t *off, int64_t n, int k, int w, const uint64_t *ha, int64_t na, const uint64_t *hb, int64_t nb, dg_read_tag *out) {
@@ -31,7 +33,7 @@ int dgr_wire_backend(dgr_handle *H, std::string &err) {
     dg::Pipeline &p = H->p;
     p.be.ctx = H->ctx;
     p.be.sketch_reads = b_sketch_reads; p.be.sketch_haplotype = b_sketch_hap; p.be.dp_solve_diploid = b_dp; p.be.dp_solve_haploid = b_hap;
-    p.be.dp_load_graph = b_dp_load; p.be.dp_run_budgets = b_dp_budgets; p.be.dp_call_margins = b_dp_call_margins; p.be.dp_answer_objectives = b_dp_answer_objectives; p.be.tag_reads = b_tag_reads;
+    p.be.dp_load_graph = b_dp_load; p.be.dp_run_budgets = b_dp_budgets; p.be.dp_run_pinned = b_dp_pinned; p.be.dp_pin_stats = b_dp_pin_stats; p.be.dp_call_margins = b_dp_call_margins; p.be.dp_answer_objectives = b_dp_answer_objectives; p.be.tag_reads = b_tag_reads;
     p.be.free_buf = dg_free; p.be.anchor_begin = b_anchor_begin; p.be.anchor_add_haplotype = b_anchor_add; p.be.anchor_finish = b_anchor_finish;
     p.be.anchor_add_haplotype_sketched = b_anchor_add_sk; p.be.hint_dp_soon = b_hint; p.be.last_error = b_err;
     return 0;

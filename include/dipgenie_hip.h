@@ -125,6 +125,29 @@ int dg_dp_run_budgets(dg_ctx *, const int32_t *budgets, int32_t n_budgets, dg_dp
 /* the sink's value on planes 0..R (NEG_INF where unreachable) of the last dg_dp_run / dg_dp_run_budgets on the loaded graph;
  * out has n >= R + 1 entries */
 int dg_dp_get_budget_values(dg_ctx *, int32_t *out, int32_t n);
+/* Pinned run: dg_dp_run_budgets on the DP in which some cells of some levels are unreachable on every plane.  A pin matches cell
+ * (i, j) of its level -- i the vertex of haplotype 1 (dg_dp_result's p1, row 0 of dg_dp_get_answer_paths), j that of haplotype 2 -- if
+ * vertex1 is -1 or i and vertex2 is -1 or j; pins are ordered: (a, b) is not (b, a).  A cell of a level is allowed if the level has no
+ * require-pin or one of them matches it, and no forbid-pin of the level matches it.  Recurrence, NEG_INF, tie order (the winner
+ * among the candidates that remain), "at most" budgets, the finish kernel's check of every chain: the run's.  A constraint set that
+ * no pair of paths satisfies within a budget is an answer, not an error: value NEG_INF and empty edge lists for that budget.
+ * n_pins = 0 (pins may be NULL) is exactly dg_dp_run_budgets.  The sweep kernels run unchanged: after the launch that writes a
+ * pinned level one mask launch stores NEG_INF over the level's cells that are not allowed, on all R + 1 planes (csrc/dg_dp_pins.hip);
+ * a level pair whose earlier level is pinned runs as two launches in this call, a captured batch that holds a pinned level is issued
+ * plainly in this call and the batch cache stays as it was.
+ * DG_ERR_ARG, naming the first offending pin and leaving the state of the last run alone: a level outside 1 .. n_levels - 2, a vertex
+ * that is neither -1 nor inside its level, a kind other than 0 or 1, n_pins < 0 or > 65536, null pins with n_pins > 0; the budget
+ * rules are those of dg_dp_run_budgets.  DG_ERR_STATE: no graph loaded, or option digest 1 (the sweep accumulates a level's digest
+ * before the mask runs).  The call is "the last run" for dg_dp_get_budget_values, dg_dp_get_answer_paths, dg_dp_answer_objectives,
+ * dg_dp_get_timing and the launch and pair profiles; dg_dp_call_margins, which checks the run's value against an unconstrained
+ * partner DP, answers DG_ERR_STATE after it until the next unpinned run.  Synchronises. */
+typedef struct dg_dp_pin { int32_t level, vertex1, vertex2, kind; } dg_dp_pin;   /* kind: 0 require, 1 forbid; vertex -1 = any */
+int dg_dp_run_pinned(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results);
+/* measurement: the last dg_dp_run_pinned with n_pins > 0 on this context: out[0] = pins, out[1] = pinned levels, out[2] = mask
+ * launches (a segmented run masks a level once per pass), out[3] = level pairs run as two launches, out[4] = batches issued plainly
+ * that would have been captured or replayed; n >= 5 (zeros before the first such call).  DG_ERR_ARG: null out or n < 5.
+ * DG_ERR_STATE: no DP state on this context yet. */
+int dg_dp_get_pin_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth on the loaded graph (the question the sweep answers with a maximum: plane r of the
  * sink is the best `value` over all pairs with r1 + r2 <= r).  For the transition into level l the ordered pair (path 1, path 2)
  * contributes what the sweep adds to cell (i, j) for the in-edge pair (p1[l-1] -> p1[l], p2[l-1] -> p2[l]): |(Hom u Hom) n (Hom u Hom)|
