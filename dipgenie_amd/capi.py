@@ -95,7 +95,7 @@ SYMBOLS = [
     "dg_dp_get_option", "dg_sketch_get_option", "dg_dp_list_sweep_variants", "dg_dp_get_answer_paths", "dg_dp_call_margins",
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
-    "dg_dp_run_pinned", "dg_dp_get_pin_stats",
+    "dg_dp_run_pinned", "dg_dp_get_pin_stats", "dg_dp_genotype_margins_pinned", "dg_dp_genotype_table_pinned",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -123,6 +123,8 @@ lib.dg_dp_genotype_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_in
 lib.dg_dp_genotype_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int32)]
 lib.dg_dp_get_genotype_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+lib.dg_dp_genotype_margins_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_margins.argtypes[1:]
+lib.dg_dp_genotype_table_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_table.argtypes[1:]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 lib.dg_dp_get_timing.argtypes = [C.c_void_p, C.POINTER(DpTiming)]
@@ -274,6 +276,11 @@ def outcome_from(res, bufs):
 PIN_REQUIRE, PIN_FORBID = 0, 1
 
 
+def _pin_rows(pins):
+    """pins as int32 [n, 4]: from an array or an iterable of (level, vertex1, vertex2, kind)"""
+    return np.ascontiguousarray(np.asarray(list(pins) if not isinstance(pins, np.ndarray) else pins, np.int32).reshape(-1, 4))
+
+
 def genotype_pins(level, v1, v2, kind=PIN_REQUIRE):
     """the pins of an unordered genotype: cell (v1, v2) of `level` in both orders (one pin where v1 == v2), as rows
     (level, vertex1, vertex2, kind) for Context.dp_run_pinned"""
@@ -373,7 +380,7 @@ class Context:
         (PIN_FORBID): it must match none of its forbid-pins.  budgets defaults to [R].  Returns a DpOutcome per budget; a
         constraint set nothing satisfies within a budget has value NEG_INF and empty paths.  The call is the last run for
         dp_budget_values, dp_answer_paths, dp_answer_objectives, dp_timing and the profiles; dp_call_margins refuses it."""
-        p = np.ascontiguousarray(np.asarray(list(pins) if not isinstance(pins, np.ndarray) else pins, np.int32).reshape(-1, 4))
+        p = _pin_rows(pins)
         budgets = [self._g.R] if budgets is None else [int(b) for b in budgets]
         arr = (DpResult * max(len(budgets), 1))()
         keep = []
@@ -496,6 +503,17 @@ class Context:
         within the budget, and int32 [n_vertices]: the best value of any pair with one path through the vertex.  value - alt_value
         is the margin of the called genotype at that level, negative where the called cell is not optimal.  An id outside its
         level raises DgError naming the first (query, row, level).  Leaves the last run's answers alone."""
+        return self._genotype_margins(None, called, budget, vertex_class, want_vertices)
+
+    def dp_genotype_margins_pinned(self, pins, called, budget, vertex_class=None, want_vertices=False):
+        """dp_genotype_margins on the DP that the pins constrain (pins as for dp_run_pinned): value is the best value of any ordered
+        pair of paths through the ordered called cell that satisfies the pins, best_value what dp_run_pinned(pins) gives for the
+        budget.  Pins are ordered, so the through-values need not be symmetric: the alternative (alt_vertex1 <= alt_vertex2) is worth
+        the better of its two orders, vertex_values the best of the ordered row.  A pin set nothing satisfies within the budget is
+        NEG_INF / -1 everywhere.  No pins: dp_genotype_margins.  Leaves the last run's answers, pins and statistics alone."""
+        return self._genotype_margins(_pin_rows(pins), called, budget, vertex_class, want_vertices)
+
+    def _genotype_margins(self, pins, called, budget, vertex_class, want_vertices):
         p = np.ascontiguousarray(called, np.int32)
         if p.ndim == 2:
             p = p[None]
@@ -510,9 +528,12 @@ class Context:
         levels = np.zeros((p.shape[0], p.shape[2]), GENOTYPE_MARGIN)
         values = np.zeros(g.n_vertices if g is not None else 1, np.int32) if want_vertices else None
         best = C.c_int32(0)
-        _check(lib.dg_dp_genotype_margins(self.h, p.ctypes.data if p.size else None, p.shape[0], int(budget), cls.ctypes.data if cls is not None else None,
-                                          levels.ctypes.data if levels.size else None, values.ctypes.data if want_vertices else None, C.byref(best)),
-               "dg_dp_genotype_margins")
+        args = (p.ctypes.data if p.size else None, p.shape[0], int(budget), cls.ctypes.data if cls is not None else None,
+                levels.ctypes.data if levels.size else None, values.ctypes.data if want_vertices else None, C.byref(best))
+        if pins is None:
+            _check(lib.dg_dp_genotype_margins(self.h, *args), "dg_dp_genotype_margins")
+        else:
+            _check(lib.dg_dp_genotype_margins_pinned(self.h, pins.ctypes.data if pins.size else None, pins.shape[0], *args), "dg_dp_genotype_margins_pinned")
         return (levels, best.value, values) if want_vertices else (levels, best.value)
 
     def dp_genotype_table(self, budget, vertex_class=None, called=None):
@@ -523,6 +544,16 @@ class Context:
         out, and the best value of any pair within the budget.  With called (as for dp_genotype_margins, at most 256 queries) a
         fourth element follows: the GENOTYPE_MARGIN records dp_genotype_margins answers for it, from the same pass.  Leaves the last
         run's answers alone."""
+        return self._genotype_table(None, budget, vertex_class, called)
+
+    def dp_genotype_table_pinned(self, pins, budget, vertex_class=None, called=None):
+        """dp_genotype_table on the DP that the pins constrain (pins as for dp_run_pinned): an entry is the best value of any pair of
+        paths that satisfies the pins through a cell of the genotype in either order (vertex1 <= vertex2), the records are those of
+        dp_genotype_margins_pinned.  A pin set nothing satisfies within the budget is the empty table.  No pins: dp_genotype_table.
+        Leaves the last run's answers, pins and statistics alone."""
+        return self._genotype_table(_pin_rows(pins), budget, vertex_class, called)
+
+    def _genotype_table(self, pins, budget, vertex_class, called):
         g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
         p = levels = None
         if called is not None:
@@ -539,9 +570,13 @@ class Context:
                 raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
         off = np.zeros((g.n_levels if g is not None else 0) + 1, np.int64)
         ptr, n, best = C.c_void_p(None), C.c_int64(0), C.c_int32(0)
-        _check(lib.dg_dp_genotype_table(self.h, int(budget), cls.ctypes.data if cls is not None else None, p.ctypes.data if p is not None and p.size else None,
-                                        p.shape[0] if p is not None else 0, levels.ctypes.data if levels is not None and levels.size else None, off.ctypes.data,
-                                        C.byref(ptr), C.byref(n), C.byref(best)), "dg_dp_genotype_table")
+        args = (int(budget), cls.ctypes.data if cls is not None else None, p.ctypes.data if p is not None and p.size else None,
+                p.shape[0] if p is not None else 0, levels.ctypes.data if levels is not None and levels.size else None, off.ctypes.data,
+                C.byref(ptr), C.byref(n), C.byref(best))
+        if pins is None:
+            _check(lib.dg_dp_genotype_table(self.h, *args), "dg_dp_genotype_table")
+        else:
+            _check(lib.dg_dp_genotype_table_pinned(self.h, pins.ctypes.data if pins.size else None, pins.shape[0], *args), "dg_dp_genotype_table_pinned")
         try:
             entries = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), (n.value * 6,)).view(GENOTYPE_ENTRY).copy() if n.value else np.zeros(0, GENOTYPE_ENTRY)
         finally:
@@ -554,6 +589,13 @@ class Context:
         out = np.zeros(6, np.int64)
         _check(lib.dg_dp_get_genotype_stats(self.h, out.ctypes.data, 6), "dg_dp_get_genotype_stats")
         return dict(zip(("n_segments", "levels_twice", "peak_bytes", "launches", "entries", "staging_copies"), out.tolist()))
+
+    def dp_genotype_pin_stats(self):
+        """of the last dp_genotype_margins(_pinned) / dp_genotype_table(_pinned) on this context: dict(pins, mask_launches), both 0
+        after an unpinned call"""
+        out = np.zeros(8, np.int64)
+        _check(lib.dg_dp_get_genotype_stats(self.h, out.ctypes.data, 8), "dg_dp_get_genotype_stats")
+        return dict(pins=int(out[6]), mask_launches=int(out[7]))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

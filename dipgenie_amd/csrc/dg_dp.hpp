@@ -307,8 +307,9 @@ struct DpState {
     int64_t ob_ch = 0, ob_ct = 0;              // distinct hom / het colours
     DevBuf d_ob_hom_rank, d_ob_het_rank, d_ob_paths, d_ob_out, d_ob_err, d_ob_bits;
     // ---- dg_dp_genotype_margins / dg_dp_genotype_table (dg_dp_joint.hip): nothing but the statistics of the last call outlives it
-    // (dg_dp_get_genotype_stats: segments, levels swept forward twice, peak bytes reserved, launches, table entries, staging copies) ----
-    int64_t jt_stats[6] = {0, 0, 0, 0, 0, 0};
+    // (dg_dp_get_genotype_stats: segments, levels swept forward twice, peak bytes reserved, launches, table entries, staging copies, pins,
+    // mask launches: the last two are 0 after an unpinned call) ----
+    int64_t jt_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // ---- dg_dp_run_pinned (dg_dp_pins.hip): the call's pins sorted by level (uploaded once per call), whether the last run on the loaded
     // graph was a pinned one, and the statistics of the last pinned run (dg_dp_get_pin_stats: pins, pinned levels, mask launches, pairs
     // run as singles, batches issued plainly) ----
@@ -407,7 +408,8 @@ int dp_best_partners(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *
 int dp_partner_marginals(dg_ctx *c, const int32_t *given, int64_t n, const int32_t *budgets, dg_dp_level_margin *levels, int32_t *vertex_values);
 int dp_call_margins(dg_ctx *c, int32_t budget, const int32_t *vertex_class, dg_dp_call_margin *levels, int32_t *paths);
 
-// ---- pinned runs (dg_dp_pins.hip): the per-level cell constraints of one dg_dp_run_pinned ----
+// ---- pinned calls (dg_dp_pins.hip): the per-level cell constraints of one dg_dp_run_pinned, dg_dp_genotype_margins_pinned or
+// dg_dp_genotype_table_pinned ----
 struct PinSet {
     std::vector<int32_t> off;            // [L + 1]: the pins of level l are d_pins[off[l] .. off[l + 1]) (sorted by level, input order inside a level)
     const dg_dp_pin *d_pins = nullptr;   // device
@@ -415,16 +417,20 @@ struct PinSet {
     bool has(int l) const { return off[(size_t)l + 1] > off[(size_t)l]; }
     bool any_in(int l0, int l1) const { return off[(size_t)l1] > off[(size_t)l0]; }
 };
-// validates the pins against the loaded graph (DG_ERR_ARG naming the first offending pin), sorts them by level and uploads them
-int pins_prepare(dg_ctx *c, DpState &S, const dg_dp_pin *pins, int64_t n, PinSet &P);
+// validates the pins against the loaded graph (DG_ERR_ARG naming fn, the entry point, and the first offending pin), sorts them by level
+// and uploads them into buf (the run: DpState::d_pins; the joint pass: a buffer of the call)
+int pins_prepare(const char *fn, const DpState &S, const dg_dp_pin *pins, int64_t n, PinSet &P, DevBuf &buf);
 // stores NEG_INF into the cells of `level` that its pins do not allow, on all RP planes of the level's state slab `state` ([i][r][j])
 void pins_launch_mask(const DpState &S, PinSet &P, int level, int32_t *state, hipStream_t s);
+// the same for a state of the joint pass: [i][j][r] with `planes` planes, k = the level's width
+void pins_launch_joint_mask(PinSet &P, int level, int32_t *state, int k, int planes, hipStream_t s);
 
 // ---- genotype margins: the DP forward and backward with both haplotypes free, combined per cell (dg_dp_joint.hip) ----
-int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
-                        int32_t *vertex_values, int32_t *best_value);
-int dp_genotype_table(dg_ctx *c, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n, dg_dp_genotype_margin *levels, int64_t *level_off,
-                      dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value);
+// pinned = false: the unpinned entry points (pins ignored); true: the *_pinned ones, which with n_pins = 0 run the same pass
+int dp_genotype_margins(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class,
+                        dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value);
+int dp_genotype_table(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n,
+                      dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value);
 int dp_genotype_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

@@ -31,6 +31,11 @@
 // dg_dp_genotype_table is the same pass with one more step per level: the combine kernel gets one scratch row per row of the level, so
 // T of the level is whole, and the gt_* kernels below reduce it by genotype into a compacted list (their comment has the plan).
 // dg_dp_genotype_margins launches none of them and reserves none of their buffers.
+// dg_dp_genotype_margins_pinned / dg_dp_genotype_table_pinned are the same pass on the DP that per-level cell constraints leave (the pins
+// of dg_dp_run_pinned): after every launch that writes a forward or backward state of a pinned level, jt_pin_mask_kernel
+// (dg_dp_pins.hip) stores NEG_INF over the level's cells that are not allowed, and the recurrences, which skip a NEG_INF source cell,
+// do the rest.  Pins are ordered, so T is no longer symmetric: the pinned calls run the ORDERED instantiations of jt_combine_kernel and
+// gt_rows_kernel, which give the unordered cell (i, j >= i) the value max(T[i][j], T[j][i]); n_pins = 0 runs what the unpinned calls run.
 #include <algorithm>
 #include <cstring>
 
@@ -200,7 +205,11 @@ __global__ __launch_bounds__(JT_THREADS) void jt_backward_kernel(const int32_t *
 }
 
 // grid: min(k, JT_ROW_BLOCKS) workgroups, rows strided.  F, B = the two states of level l; row = [gridDim.x][k] scratch; J = [nV];
-// called = [n][2][L] vertex ids (validated by the host); cls = [nV] or null; part = [n][k] keys; cval = [n]
+// called = [n][2][L] vertex ids (validated by the host); cls = [nV] or null; part = [n][k] keys; cval = [n].
+// ORDERED (a pinned call: T need not be symmetric): a second scratch row per workgroup, behind the gridDim.x first ones, takes the
+// column T[.][i], and the key of the unordered cell (i, j >= i) holds max(T[i][j], T[j][i]); J and the called cell's value stay those
+// of the ordered row.  ORDERED = false is the kernel as it was: no load, store or branch more.
+template <bool ORDERED>
 __global__ __launch_bounds__(JT_THREADS) void jt_combine_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ B, int k, int B1, int b0, int32_t *row_all,
                                                                 int32_t *__restrict__ J, int n, const int32_t *__restrict__ called, int L, int l,
                                                                 const int32_t *__restrict__ cls, long long *__restrict__ part, int32_t *__restrict__ cval) {
@@ -208,6 +217,7 @@ __global__ __launch_bounds__(JT_THREADS) void jt_combine_kernel(const int32_t *_
     __shared__ int s_max[JT_THREADS / 64];
     const int t = (int)threadIdx.x;
     int32_t *row = row_all + (int64_t)blockIdx.x * k;
+    int32_t *col = ORDERED ? row_all + ((int64_t)gridDim.x + blockIdx.x) * k : nullptr;
     for (int i = (int)blockIdx.x; i < k; i += (int)gridDim.x) {
         int m = NEG_INF;
         for (int j = t; j < k; j += JT_THREADS) {
@@ -219,6 +229,15 @@ __global__ __launch_bounds__(JT_THREADS) void jt_combine_kernel(const int32_t *_
             }
             row[j] = best;
             m = max(m, best);
+            if (ORDERED && j >= i) {
+                const int32_t *f2 = F + ((int64_t)j * k + i) * B1, *b2 = B + ((int64_t)j * k + i) * B1;
+                int other = NEG_INF;
+                for (int r = 0; r < B1; ++r) {
+                    const int fv = f2[r], bv = b2[B1 - 1 - r];
+                    if (fv != NEG_INF && bv != NEG_INF) other = max(other, fv + bv);
+                }
+                col[j] = other;
+            }
         }
         for (int d = 32; d; d >>= 1) m = max(m, __shfl_xor(m, d));
         if ((t & 63) == 0) s_max[t >> 6] = m;
@@ -234,7 +253,7 @@ __global__ __launch_bounds__(JT_THREADS) void jt_combine_kernel(const int32_t *_
             if (t == 0 && i == c1 - b0) cval[q] = row[c2 - b0];
             long long key = JT_NO_KEY;
             for (int j = i + t; j < k; j += JT_THREADS) {
-                const int v = row[j];
+                const int v = ORDERED ? max(row[j], col[j]) : row[j];
                 if (v == NEG_INF) continue;
                 const int cj = cls ? cls[b0 + j] : b0 + j;
                 if ((ci == cc1 && cj == cc2) || (ci == cc2 && cj == cc1)) continue;      // the called genotype itself
@@ -303,6 +322,9 @@ __global__ __launch_bounds__(JT_THREADS) void jt_records_kernel(int k, int b0, c
 constexpr int GT_MAX_ITEMS = 8;                         // most keys per lane of a tile (contiguous, so a tile's entries stay in order): option genotype_table_tile_keys / 256
 constexpr int GT_MAX_SCAN = 1024;                       // most lanes of the scan's workgroup = tiles per pass: option genotype_table_scan_tiles
 
+// ORDERED (a pinned call: T need not be symmetric): the unordered cell's value is max(T[i][j], T[j][i]), so what the later steps see is
+// symmetric again; ORDERED = false is the kernel as it was.
+template <bool ORDERED>
 __global__ __launch_bounds__(JT_THREADS) void gt_rows_kernel(const int32_t *__restrict__ T, int k, int A, const int32_t *__restrict__ rank, const int32_t *__restrict__ perm,
                                                              long long *__restrict__ part) {
     const int lane = (int)threadIdx.x & 63;
@@ -318,7 +340,7 @@ __global__ __launch_bounds__(JT_THREADS) void gt_rows_kernel(const int32_t *__re
                 const uint32_t j = (uint32_t)perm[x];
                 if (j < (uint32_t)k) {
                     c = rank[j];
-                    const int v = T[(int64_t)i * k + j];
+                    const int v = ORDERED ? max(T[(int64_t)i * k + j], T[(int64_t)j * k + i]) : T[(int64_t)i * k + j];
                     if (v != NEG_INF) key = jt_key(v, min(i, (int)j), max(i, (int)j));
                 }
             }
@@ -480,8 +502,9 @@ struct JtTable { int64_t *level_off; dg_dp_genotype_entry **entries; int64_t *n_
 
 namespace {
 
-// both entry points: tab = null is dg_dp_genotype_margins
-int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
+// all four entry points: tab = null is dg_dp_genotype_margins (_pinned); n_pins = 0 is the unpinned call -- no PinSet, no mask launch,
+// the kernels' unordered instantiations
+int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
             int32_t *vertex_values, int32_t *best_value, const JtTable *tab) {
     DpState *Sp = c->dp;
     if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
@@ -521,6 +544,11 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
                     return DG_ERR_ARG;
                 }
             }
+    // ---- the pins: validated, sorted by level and uploaded into a buffer of this call (DpState::d_pins belongs to the last pinned run) ----
+    PinSet pin_set;
+    DevBuf d_jpins;
+    if (n_pins != 0) if (int rc = pins_prepare(FN, S, pins, n_pins, pin_set, d_jpins)) return rc;
+    PinSet *const P = n_pins != 0 ? &pin_set : nullptr;
     // ---- the table's plan, before anything is launched: per level the dense rank of every vertex's class (ascending, signed), the
     // positions ordered by (rank, position), the A + 1 offsets of the ranks (level l's start at a0 + l: A <= k), the bound A (A + 1) / 2 ----
     std::vector<int32_t> t_rank, t_perm, t_goff, t_A;
@@ -596,6 +624,7 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
     for (int l = 0; l < L; ++l) level_cells = std::max(level_cells, lv[l].cells);
     int64_t launches = 0, twice = 0;
     JtMem M;
+    if (P) { M.now += (int64_t)d_jpins.bytes; M.peak = M.now; }
     DevBuf d_called, d_cls, d_J, d_rec, d_lvlmax, d_cval, d_part, d_row, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back;
     DevBuf d_trank, d_tperm, d_tgoff, d_gpart, d_dense, d_tcnt, d_tmax, d_tlvl, d_stage;
     const int row_blocks = tab ? kmax : std::min(kmax, JT_ROW_BLOCKS);      // the table keeps every row of T: one scratch row per row
@@ -606,7 +635,7 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
     if (int rc = M.get(d_lvlmax, ((int64_t)L + 1) * 4)) return rc;                 // entry L: V_b, the sink's cell on plane `budget`
     if (int rc = M.get(d_cval, n * 4)) return rc;
     if (int rc = M.get(d_part, n * kmax * 8)) return rc;
-    if (int rc = M.get(d_row, (int64_t)row_blocks * kmax * 4)) return rc;
+    if (int rc = M.get(d_row, (int64_t)row_blocks * kmax * 4 * (P ? 2 : 1))) return rc;       // (pinned: the columns behind the rows)
     if (int rc = M.get(d_oo, ((int64_t)nV + 1) * 4)) return rc;
     if (int rc = M.get(d_ocur, (int64_t)nV * 4)) return rc;
     if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
@@ -679,6 +708,7 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
         hipLaunchKernelGGL(jt_forward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, prev, cur, lv[l - 1].k, lv[l].k, B1,
                            lv[l].a0, lv[l].in_base, lv[l].T, in_off, in_edge, m);
         ++launches;
+        if (P && P->has(l)) { pins_launch_joint_mask(*P, l, cur, lv[l].k, B1, s); ++launches; }       // before anything reads the level
     };
     // ---- pass 1: the state at every segment's first level ----
     int32_t *ck = d_ck.as<int32_t>();
@@ -703,6 +733,8 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
     if (int rc = M.get(d_seg, seg_cells * 4)) return rc;
     if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
     int32_t *back = d_back.as<int32_t>();
+    const auto combine = P ? jt_combine_kernel<true> : jt_combine_kernel<false>;       // ordered pins: both orders of a cell
+    const auto gt_rows = P ? gt_rows_kernel<true> : gt_rows_kernel<false>;
     std::vector<const int32_t *> Fp((size_t)L, nullptr);
     for (int g = n_seg - 1; g >= 0; --g) {
         const int a = seg[g], e = seg[g + 1];
@@ -726,8 +758,9 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
                                    (const int32_t *)(back + ((l + 1) & 1) * level_cells), cur, lv[l].k, lv[l + 1].k, B1, lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base, lv[l + 1].T,
                                    d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
                 ++launches;
+                if (P && P->has(l)) { pins_launch_joint_mask(*P, l, cur, lv[l].k, B1, s); ++launches; }
             }
-            hipLaunchKernelGGL(jt_combine_kernel, dim3((unsigned)std::min(lv[l].k, row_blocks)), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)cur, lv[l].k, B1, lv[l].a0,
+            hipLaunchKernelGGL(combine, dim3((unsigned)std::min(lv[l].k, row_blocks)), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)cur, lv[l].k, B1, lv[l].a0,
                                d_row.as<int32_t>(), d_J.as<int32_t>(), (int)n, d_called.as<int32_t>(), L, l, vertex_class ? d_cls.as<int32_t>() : nullptr,
                                d_part.as<long long>(), d_cval.as<int32_t>());
             hipLaunchKernelGGL(jt_records_kernel, dim3((unsigned)n), dim3(JT_THREADS), 0, s, lv[l].k, lv[l].a0, d_J.as<int32_t>(), d_part.as<long long>(), d_cval.as<int32_t>(),
@@ -743,7 +776,7 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
                 while (lp < 6 && ((int64_t)1 << (lp + 1)) <= std::max<int64_t>(per, 1)) ++lp;
                 const int32_t *perm = d_tperm.as<int32_t>() + lv[l].a0;
                 long long *lvl3 = d_tlvl.as<long long>() + (int64_t)3 * l;
-                hipLaunchKernelGGL(gt_rows_kernel, dim3((unsigned)((k + JT_THREADS / 64 - 1) / (JT_THREADS / 64))), dim3(JT_THREADS), 0, s, (const int32_t *)d_row.as<int32_t>(), k, A,
+                hipLaunchKernelGGL(gt_rows, dim3((unsigned)((k + JT_THREADS / 64 - 1) / (JT_THREADS / 64))), dim3(JT_THREADS), 0, s, (const int32_t *)d_row.as<int32_t>(), k, A,
                                    (const int32_t *)(d_trank.as<int32_t>() + lv[l].a0), perm, d_gpart.as<long long>());
                 hipLaunchKernelGGL(gt_pairs_kernel, dim3(jt_blocks((int64_t)A << lp, 65535), (unsigned)std::min(A, 65535)), dim3(JT_THREADS), 0, s,
                                    (const long long *)d_gpart.as<long long>(), k, A, perm, (const int32_t *)(d_tgoff.as<int32_t>() + lv[l].a0 + l), lp, d_dense.as<long long>());
@@ -770,6 +803,7 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
     DG_HIP(hipStreamSynchronize(s));
     S.jt_stats[0] = n_seg; S.jt_stats[1] = twice; S.jt_stats[2] = M.peak; S.jt_stats[3] = launches;
     S.jt_stats[4] = (int64_t)found.size(); S.jt_stats[5] = copies;
+    S.jt_stats[6] = P ? n_pins : 0; S.jt_stats[7] = P ? P->n_mask : 0;
     const int32_t V = lvlmax[(size_t)L];
     // the closing check: on every level the best pair through any cell is the best pair
     for (int l = 0; l < L; ++l)
@@ -813,21 +847,21 @@ int jt_call(dg_ctx *c, const char *FN, const int32_t *called, int64_t n, int32_t
 
 }  // namespace
 
-int dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
-                        int32_t *vertex_values, int32_t *best_value) {
-    return jt_call(c, "dg_dp_genotype_margins", called, n, budget, vertex_class, levels, vertex_values, best_value, nullptr);
+int dp_genotype_margins(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class,
+                        dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value) {
+    return jt_call(c, pinned ? "dg_dp_genotype_margins_pinned" : "dg_dp_genotype_margins", pinned ? pins : nullptr, pinned ? n_pins : 0, called, n, budget, vertex_class, levels, vertex_values, best_value, nullptr);
 }
 
-int dp_genotype_table(dg_ctx *c, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n, dg_dp_genotype_margin *levels, int64_t *level_off,
-                      dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) {
+int dp_genotype_table(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n,
+                      dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) {
     const JtTable tab{level_off, entries, n_entries};
-    return jt_call(c, "dg_dp_genotype_table", called, n, budget, vertex_class, levels, nullptr, best_value, &tab);
+    return jt_call(c, pinned ? "dg_dp_genotype_table_pinned" : "dg_dp_genotype_table", pinned ? pins : nullptr, pinned ? n_pins : 0, called, n, budget, vertex_class, levels, nullptr, best_value, &tab);
 }
 
 int dp_genotype_stats(dg_ctx *c, int64_t *out, int n) {
     if (!out || n < 4) { set_error("dg_dp_get_genotype_stats: out needs 4 words"); return DG_ERR_ARG; }
     if (!c->dp) { set_error("dg_dp_get_genotype_stats: no graph loaded"); return DG_ERR_STATE; }
-    for (int q = 0; q < (n >= 6 ? 6 : 4); ++q) out[q] = c->dp->jt_stats[q];
+    for (int q = 0; q < (n >= 8 ? 8 : n >= 6 ? 6 : 4); ++q) out[q] = c->dp->jt_stats[q];
     return DG_OK;
 }
 
@@ -836,13 +870,26 @@ int dp_genotype_stats(dg_ctx *c, int64_t *out, int n) {
 extern "C" int dg_dp_genotype_margins(dg_ctx *c, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
                                       int32_t *vertex_values, int32_t *best_value) {
     if (int rc = dgi::bind(c)) return rc;
-    return dgi::dp_genotype_margins(c, called, n_called, budget, vertex_class, levels, vertex_values, best_value);
+    return dgi::dp_genotype_margins(c, false, nullptr, 0, called, n_called, budget, vertex_class, levels, vertex_values, best_value);
 }
 
 extern "C" int dg_dp_genotype_table(dg_ctx *c, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called, dg_dp_genotype_margin *levels,
                                     int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) {
     if (int rc = dgi::bind(c)) return rc;
-    return dgi::dp_genotype_table(c, budget, vertex_class, called, n_called, levels, level_off, entries, n_entries, best_value);
+    return dgi::dp_genotype_table(c, false, nullptr, 0, budget, vertex_class, called, n_called, levels, level_off, entries, n_entries, best_value);
+}
+
+extern "C" int dg_dp_genotype_margins_pinned(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n_called, int32_t budget,
+                                             const int32_t *vertex_class, dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_genotype_margins(c, true, pins, n_pins, called, n_called, budget, vertex_class, levels, vertex_values, best_value);
+}
+
+extern "C" int dg_dp_genotype_table_pinned(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called,
+                                           int64_t n_called, dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries,
+                                           int64_t *n_entries, int32_t *best_value) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_genotype_table(c, true, pins, n_pins, budget, vertex_class, called, n_called, levels, level_off, entries, n_entries, best_value);
 }
 
 extern "C" int dg_dp_get_genotype_stats(dg_ctx *c, int64_t *out, int n) {

@@ -457,7 +457,7 @@ static int dp_run_pinned(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const
         return DG_ERR_STATE;
     }
     PinSet P;
-    if (int rc = pins_prepare(c, S, pins, n_pins, P)) return rc;
+    if (int rc = pins_prepare("dg_dp_run_pinned", S, pins, n_pins, P, S.d_pins)) return rc;
     const int rc = dp_run(c, budgets, n, results, true, &P);
     int64_t n_levels = 0;
     for (int l = 1; l < S.L; ++l) n_levels += P.has(l);

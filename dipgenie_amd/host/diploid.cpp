@@ -110,6 +110,9 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.genotype_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_table || !be.free_buf)) return "--genotype-table: this backend has no dp_genotype_table";
     // and --pins: the same run under the file's cell constraints
     if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
+    // and --pinned-genotype-margins / --pinned-genotype-table: the joint pass under the same constraints
+    if (!p.opt.pinned_genotype_margins.empty() && !be.dp_genotype_margins_pinned) return "--pinned-genotype-margins: this backend has no dp_genotype_margins_pinned";
+    if (!p.opt.pinned_genotype_table.empty() && (!be.dp_genotype_table_pinned || !be.free_buf)) return "--pinned-genotype-table: this backend has no dp_genotype_table_pinned";
     if (!be.dp_load_graph || !be.dp_run_budgets) return "--budgets: this backend has no dp_run_budgets";
     std::vector<dg_dp_result> res;                                     // (the ABI takes the results as one array)
     for (const ChainAnswer &a : answers) res.push_back(a.res);
@@ -424,7 +427,8 @@ std::string write_site_margins(Pipeline &p, const ExpandedGraph &g, const std::v
 // levels 1 .. L - 2; the called cell is the answer at -R (its two paths), the alternative the best cell of another genotype with both
 // haplotypes free; '.' for what does not exist (no other genotype reachable; every field if no pair of paths fits -R)
 // What --genotype-margins and --genotype-table share: the answer at -R as the called cells, and ONE pass over the graph with both
-// haplotypes free -- dp_genotype_table when the table is asked for (it answers the margin records too), dp_genotype_margins otherwise
+// haplotypes free -- dp_genotype_table when the table is asked for (it answers the margin records too), dp_genotype_margins otherwise.
+// --pinned-genotype-margins and --pinned-genotype-table share the same on the DP under --pins: the called cells are the pinned answer's
 struct GenotypePass {
     const Backend *be = nullptr;
     bool fits = false;                                   // a pair of paths fits -R (none: no device call, both files say so)
@@ -441,7 +445,8 @@ struct GenotypePass {
     ~GenotypePass() { if (entries && be) be->free_buf(entries); }
 };
 
-std::string genotype_pass(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, GenotypePass &gp) {
+// pins = null: the unconstrained DP; else the DP under these pins (the *_pinned calls)
+std::string genotype_pass(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, GenotypePass &gp, bool want_table, const std::vector<dg_dp_pin> *pins = nullptr) {
     const double t0 = now_s();
     const Backend &be = p.be;
     gp.be = &be;
@@ -452,7 +457,14 @@ std::string genotype_pass(Pipeline &p, const ExpandedGraph &g, const std::vector
     gp.rec.assign((size_t)L, dg_dp_genotype_margin());
     gp.level_off.assign((size_t)L + 1, 0);
     if (gp.fits) {
-        if (!p.opt.genotype_table.empty()) {
+        if (pins) {
+            if (want_table) {
+                if (be.dp_genotype_table_pinned(be.ctx, pins->data(), (int64_t)pins->size(), p.opt.R, cls.data(), gp.paths.data(), 1, gp.rec.data(), gp.level_off.data(), &gp.entries,
+                                                &gp.n_entries, &gp.best) != 0)
+                    return backend_error(be, "dp_genotype_table_pinned");
+            } else if (be.dp_genotype_margins_pinned(be.ctx, pins->data(), (int64_t)pins->size(), gp.paths.data(), 1, p.opt.R, cls.data(), gp.rec.data(), nullptr, &gp.best) != 0)
+                return backend_error(be, "dp_genotype_margins_pinned");
+        } else if (want_table) {
             if (be.dp_genotype_table(be.ctx, p.opt.R, cls.data(), gp.paths.data(), 1, gp.rec.data(), gp.level_off.data(), &gp.entries, &gp.n_entries, &gp.best) != 0)
                 return backend_error(be, "dp_genotype_table");
         } else if (be.dp_genotype_margins(be.ctx, gp.paths.data(), 1, p.opt.R, cls.data(), gp.rec.data(), nullptr, &gp.best) != 0) return backend_error(be, "dp_genotype_margins");
@@ -464,17 +476,17 @@ std::string genotype_pass(Pipeline &p, const ExpandedGraph &g, const std::vector
     return "";
 }
 
-std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const GenotypePass &gp) {
+// (pinned: the file of the DP under --pins; without a pair of paths that satisfies them within -R it holds the header alone)
+std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const GenotypePass &gp, const std::string &path, GenotypeMargins &gm, bool pinned) {
     const double t0 = now_s();
     const int L = (int)g.level_off.size() - 1;
     const bool fits = gp.fits;
     const std::vector<dg_dp_genotype_margin> &rec = gp.rec;
-    GenotypeMargins &gm = p.sum.genotype_margins;
     gm = GenotypeMargins();
     gm.set = true;
     gm.segments = gp.segments;
     std::string text = "level\tvertex1\tpanel_hap1\tsegment1\tvertex2\tpanel_hap2\tsegment2\tvalue\talt_vertex1\talt_segment1\talt_vertex2\talt_segment2\talt_value\tmargin\n";
-    for (int l = 1; l < L - 1; ++l) {
+    for (int l = 1; l < L - 1 && (fits || !pinned); ++l) {
         text += std::to_string(l);
         if (!fits) { text += "\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\n"; continue; }
         const dg_dp_genotype_margin &r = rec[(size_t)l];
@@ -490,11 +502,11 @@ std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const Ge
         } else text += ".\t.\t.\t.\t.\t.";
         text += '\n';
     }
-    std::ofstream f(p.opt.genotype_margins, std::ios::out | std::ios::binary);
-    if (!f.is_open()) return "cannot open genotype margins file " + p.opt.genotype_margins;
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open genotype margins file " + path;
     f.write(text.data(), (std::streamsize)text.size());
     f.close();
-    if (!f.good()) return "write to " + p.opt.genotype_margins + " failed";
+    if (!f.good()) return "write to " + path + " failed";
     gm.wall_s = gp.wall_s + (now_s() - t0);
     return "";
 }
@@ -502,10 +514,9 @@ std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const Ge
 // level  vertex1  segment1  vertex2  segment2  value  delta  called: levels 1 .. L - 2, per level one row for every genotype that a pair
 // of paths within -R passes through, in ascending (class1, class2) of the allele classes; (vertex1, vertex2) its best cell, delta = the
 // DP value - value, called = 1 for the genotype of the answer's cell.  The header alone if no pair of paths fits -R
-std::string write_genotype_table(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, const GenotypePass &gp) {
+std::string write_genotype_table(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, const GenotypePass &gp, const std::string &path, GenotypeTable &gt) {
     const double t0 = now_s();
     const int L = (int)g.level_off.size() - 1;
-    GenotypeTable &gt = p.sum.genotype_table;
     gt = GenotypeTable();
     gt.set = true;
     std::string text = "level\tvertex1\tsegment1\tvertex2\tsegment2\tvalue\tdelta\tcalled\n";
@@ -525,11 +536,11 @@ std::string write_genotype_table(Pipeline &p, const ExpandedGraph &g, const std:
         gt.co_optimal_levels += at_best >= 2;
         gt.max_per_level = std::max(gt.max_per_level, e - a);
     }
-    std::ofstream f(p.opt.genotype_table, std::ios::out | std::ios::binary);
-    if (!f.is_open()) return "cannot open genotype table file " + p.opt.genotype_table;
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open genotype table file " + path;
     f.write(text.data(), (std::streamsize)text.size());
     f.close();
-    if (!f.good()) return "write to " + p.opt.genotype_table + " failed";
+    if (!f.good()) return "write to " + path + " failed";
     gt.wall_s = gp.wall_s + (now_s() - t0);
     return "";
 }
@@ -647,15 +658,16 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
             return -1;
         }
     }
-    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table, known before the DP too
+    const bool pinned_joint = !opt.pinned_genotype_margins.empty() || !opt.pinned_genotype_table.empty();
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = std::string(opt.genotype_margins.empty() ? "--genotype-table" : "--genotype-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : opt.genotype_margins.empty() ? "--genotype-table" : "--genotype-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
-    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty()) {  // all three tables speak of alleles
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint) {  // all these tables speak of alleles
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
@@ -707,15 +719,29 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
     if (!opt.genotype_margins.empty() || !opt.genotype_table.empty()) {   // one pass serves both files
         t0 = now_s();
         GenotypePass gp;
-        if (failed(genotype_pass(*this, g, classes, gp), err)) return -1;
+        if (failed(genotype_pass(*this, g, classes, gp, !opt.genotype_table.empty()), err)) return -1;
         if (!opt.genotype_margins.empty()) {
-            if (failed(write_genotype_margins(*this, g, gp), err)) return -1;
+            if (failed(write_genotype_margins(*this, g, gp, opt.genotype_margins, sum.genotype_margins, false), err)) return -1;
             stamp("genotype_margins", t0);
         }
         if (!opt.genotype_table.empty()) {
             const double t1 = opt.genotype_margins.empty() ? t0 : now_s();
-            if (failed(write_genotype_table(*this, g, classes, gp), err)) return -1;
+            if (failed(write_genotype_table(*this, g, classes, gp, opt.genotype_table, sum.genotype_table), err)) return -1;
             stamp("genotype_table", t1);
+        }
+    }
+    if (pinned_joint) {                                                   // the same under --pins: one pass serves both files
+        t0 = now_s();
+        GenotypePass gp;
+        if (failed(genotype_pass(*this, g, classes, gp, !opt.pinned_genotype_table.empty(), &pins), err)) return -1;
+        if (!opt.pinned_genotype_margins.empty()) {
+            if (failed(write_genotype_margins(*this, g, gp, opt.pinned_genotype_margins, sum.pinned_genotype_margins, true), err)) return -1;
+            stamp("pinned_genotype_margins", t0);
+        }
+        if (!opt.pinned_genotype_table.empty()) {
+            const double t1 = opt.pinned_genotype_margins.empty() ? t0 : now_s();
+            if (failed(write_genotype_table(*this, g, classes, gp, opt.pinned_genotype_table, sum.pinned_genotype_table), err)) return -1;
+            stamp("pinned_genotype_table", t1);
         }
     }
     if (!opt.tag_reads.empty()) {

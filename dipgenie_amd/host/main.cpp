@@ -145,6 +145,16 @@ static int b_dp_genotype_table(void *c, int32_t budget, const int32_t *cls, cons
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_genotype_table(x, budget, cls, called, n, levels, level_off, entries, n_entries, best) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_genotype_margins_pinned(void *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n, int32_t budget, const int32_t *cls,
+                                        dg_dp_genotype_margin *levels, int32_t *vv, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_genotype_margins_pinned(x, pins, n_pins, called, n, budget, cls, levels, vv, best) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_genotype_table_pinned(void *c, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *cls, const int32_t *called, int64_t n,
+                                      dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_genotype_table_pinned(x, pins, n_pins, budget, cls, called, n, levels, level_off, entries, n_entries, best) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_genotype_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_genotype_stats(x, out, n) : DG_ERR_NO_DEVICE;
@@ -269,6 +279,8 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --pins FILE           (MI355X build, -p2) run the DP under cell constraints: rows level, vertex1, vertex2 [, require|forbid|require-ordered|forbid-ordered], tab-separated, . = any vertex, ids as --genotype-table prints them\n");
+    fprintf(fp, "    --pinned-genotype-margins FILE   (MI355X build, -p2, with --pins) --genotype-margins of the DP under the pins: the genotype of the pinned answer at -R against the best other genotype that satisfies them\n");
+    fprintf(fp, "    --pinned-genotype-table FILE     (MI355X build, -p2, with --pins) --genotype-table of the DP under the pins: every genotype a pair of paths that satisfies them passes through\n");
     fprintf(fp, "    --gpus INT   (MI355X build) shard the minimizer scoring over INT devices (RCCL); the DP runs on the first [1]\n");
 }
 
@@ -289,6 +301,7 @@ int main(int argc, char **argv) {
     std::vector<int> shard_devices;
     std::string budgets_arg;
     bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
+    bool have_pinned_margins = false, have_pinned_table = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -324,6 +337,18 @@ int main(int argc, char **argv) {
                 have_pins = true;                                      // (a missing value is an empty file name: refused below)
                 const char *v = val("--pins");
                 p.opt.pins_file = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--pinned-genotype-margins", 25) && (argv[i][25] == 0 || argv[i][25] == '=')) {
+                have_pinned_margins = true;                            // (a missing value is an empty file name: refused below)
+                const char *v = val("--pinned-genotype-margins");
+                p.opt.pinned_genotype_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--pinned-genotype-table", 23) && (argv[i][23] == 0 || argv[i][23] == '=')) {
+                have_pinned_table = true;                              // (a missing value is an empty file name: refused below)
+                const char *v = val("--pinned-genotype-table");
+                p.opt.pinned_genotype_table = v ? v : "";
                 continue;
             }
             if (!strcmp(argv[i], "--wide-levels")) { p.opt.wide_levels = true; continue; }
@@ -425,6 +450,15 @@ int main(int argc, char **argv) {
         if (p.opt.tag_reads.empty()) { fprintf(stderr, "[E::main] --tag-reads needs a file name\n"); return 1; }
         if (sharded) { fprintf(stderr, "[E::main] --tag-reads does not go with --gpus / --shard-transport: the sharded path drops the reads once they are scored\n"); return 1; }
     }
+    // --pinned-genotype-margins FILE, --pinned-genotype-table FILE: the joint pass on the DP that --pins constrains; checked here too
+    if (have_pinned_margins || have_pinned_table) {
+        const char *which = have_pinned_margins ? "--pinned-genotype-margins" : "--pinned-genotype-table";
+        if (!have_pins) { fprintf(stderr, "[E::main] --pinned-genotype-margins / --pinned-genotype-table describe the DP under --pins: they need it\n"); return 1; }
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] %s describes the genotypes of the diploid route (-p2)\n", which); return 1; }
+        if (have_pinned_margins && p.opt.pinned_genotype_margins.empty()) { fprintf(stderr, "[E::main] --pinned-genotype-margins needs a file name\n"); return 1; }
+        if (have_pinned_table && p.opt.pinned_genotype_table.empty()) { fprintf(stderr, "[E::main] --pinned-genotype-table needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] %s does not go with --gpus / --shard-transport\n", which); return 1; }
+    }
     // --pins FILE: the same; the margin and table options describe the unconstrained DP, the sharded path has no pinned run
     if (have_pins) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --pins constrains the pair of paths of the diploid route (-p2)\n"); return 1; }
@@ -451,6 +485,8 @@ int main(int argc, char **argv) {
     p.be.dp_genotype_margins = b_dp_genotype_margins;
     p.be.dp_genotype_stats = b_dp_genotype_stats;
     p.be.dp_genotype_table = b_dp_genotype_table;
+    p.be.dp_genotype_margins_pinned = b_dp_genotype_margins_pinned;
+    p.be.dp_genotype_table_pinned = b_dp_genotype_table_pinned;
     p.be.dp_run_pinned = b_dp_pinned;
     p.be.dp_pin_stats = b_dp_pin_stats;
     p.be.free_buf = dg_free;
@@ -523,16 +559,18 @@ int main(int argc, char **argv) {
                 }
                 fprintf(f, "], \"wall_s\": %.6f}", sm.wall_s);
             }
-            if (p.sum.genotype_margins.set) {                           // over the levels 1 .. L - 2; min_positive_margin null: none is positive
-                const dg::GenotypeMargins &gm = p.sum.genotype_margins;
-                fprintf(f, ", \"genotype_margins\": {\"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", (long long)gm.with_alternative, (long long)gm.margin0);
-                if (gm.min_positive_margin >= 0) fprintf(f, "%d", gm.min_positive_margin); else fprintf(f, "null");
-                fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)gm.segments, gm.wall_s);
-            }
-            if (p.sum.genotype_table.set) {                             // a recount of FILE: its rows, levels with >= 2 rows, levels with >= 2 rows of delta 0, most rows of a level
-                const dg::GenotypeTable &gt = p.sum.genotype_table;
-                fprintf(f, ", \"genotype_table\": {\"entries\": %lld, \"levels_with_choice\": %lld, \"co_optimal_levels\": %lld, \"max_per_level\": %lld, \"wall_s\": %.6f}",
-                        (long long)gt.entries, (long long)gt.levels_with_choice, (long long)gt.co_optimal_levels, (long long)gt.max_per_level, gt.wall_s);
+            for (int pinned = 0; pinned < 2; ++pinned) {                // the unpinned objects, then (with --pins) the same fields of the DP under the pins
+                const dg::GenotypeMargins &gm = pinned ? p.sum.pinned_genotype_margins : p.sum.genotype_margins;
+                if (gm.set) {                                           // over the levels 1 .. L - 2; min_positive_margin null: none is positive
+                    fprintf(f, ", \"%sgenotype_margins\": {\"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", pinned ? "pinned_" : "", (long long)gm.with_alternative, (long long)gm.margin0);
+                    if (gm.min_positive_margin >= 0) fprintf(f, "%d", gm.min_positive_margin); else fprintf(f, "null");
+                    fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)gm.segments, gm.wall_s);
+                }
+                const dg::GenotypeTable &gt = pinned ? p.sum.pinned_genotype_table : p.sum.genotype_table;
+                if (gt.set) {                                           // a recount of FILE: its rows, levels with >= 2 rows, levels with >= 2 rows of delta 0, most rows of a level
+                    fprintf(f, ", \"%sgenotype_table\": {\"entries\": %lld, \"levels_with_choice\": %lld, \"co_optimal_levels\": %lld, \"max_per_level\": %lld, \"wall_s\": %.6f}", pinned ? "pinned_" : "",
+                            (long long)gt.entries, (long long)gt.levels_with_choice, (long long)gt.co_optimal_levels, (long long)gt.max_per_level, gt.wall_s);
+                }
             }
             if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
                 fprintf(f, ", \"objectives\": [");

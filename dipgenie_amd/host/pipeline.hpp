@@ -86,6 +86,12 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // (dg_dp_get_pin_stats)
     int (*dp_run_pinned)(void *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *budgets, int32_t n_budgets, dg_dp_result *results) = nullptr;
     int (*dp_pin_stats)(void *, int64_t *out, int n) = nullptr;
+    // optional (--pinned-genotype-margins / --pinned-genotype-table): the two genotype calls above on the DP that the pins constrain
+    // (dg_dp_genotype_margins_pinned, dg_dp_genotype_table_pinned)
+    int (*dp_genotype_margins_pinned)(void *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n_called, int32_t budget, const int32_t *vertex_class,
+                                      dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value) = nullptr;
+    int (*dp_genotype_table_pinned)(void *, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called,
+                                    dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) = nullptr;
 };
 
 // one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
@@ -118,6 +124,8 @@ struct Options {
     std::string genotype_table;  // (ours) --genotype-table: TSV with one row per genotype of every level: its best pair of paths against the answer at -R, both haplotypes free (diploid)
     std::string pins_file;       // (ours) --pins: the DP runs under the cell constraints of this file's rows (diploid); parsed into pin_rows before anything else runs
     std::vector<PinRow> pin_rows;
+    std::string pinned_genotype_margins; // (ours) --pinned-genotype-margins, with --pins: the file of --genotype-margins for the DP under the pins, the called cells those of the pinned answer at -R
+    std::string pinned_genotype_table;   // (ours) --pinned-genotype-table, with --pins: the file of --genotype-table for the DP under the pins
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -243,6 +251,8 @@ struct Summary {              // what tests and the CLI report
     SiteMargins site_margins;
     GenotypeMargins genotype_margins;
     GenotypeTable genotype_table;
+    GenotypeMargins pinned_genotype_margins;   // --pinned-genotype-margins: the same fields, of the DP under --pins
+    GenotypeTable pinned_genotype_table;       // --pinned-genotype-table
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
     PinSummary pins;

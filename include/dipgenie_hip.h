@@ -338,8 +338,30 @@ int dg_dp_genotype_table(dg_ctx *, int32_t budget, const int32_t *vertex_class, 
 /* measurement: the last successful dg_dp_genotype_margins / dg_dp_genotype_table on this context: out[0] = segments, out[1] = levels
  * whose forward state was computed twice, out[2] = peak bytes of device memory the call had reserved, out[3] = kernel launches; n >= 4
  * (zeros before the first call).  With n >= 6 also out[4] = entries of the last call's table (0 after dg_dp_genotype_margins) and
- * out[5] = its copies of the staging to the host.  DG_ERR_ARG: null out or n < 4.  DG_ERR_STATE: no DP state on this context yet. */
+ * out[5] = its copies of the staging to the host.  With n >= 8 also out[6] = pins of the last call and out[7] = its mask launches
+ * (both 0 after an unpinned call).  DG_ERR_ARG: null out or n < 4.  DG_ERR_STATE: no DP state on this context yet. */
 int dg_dp_get_genotype_stats(dg_ctx *, int64_t *out, int n);
+/* The joint pass on the pinned DP: dg_dp_genotype_margins / dg_dp_genotype_table with the cell constraints of dg_dp_run_pinned (the
+ * pins, "allowed", the limits and the DG_ERR_ARG cases are that call's; the messages name the entry point at hand and the first
+ * offending pin).  With a pin set P, F_l and B_l are the recurrences above with NEG_INF on every plane of every cell of level l that
+ * is not allowed, so T_l[i][j | P] is the best value of any ORDERED pair (p, q) of source -> sink paths that satisfies P with
+ * p[l] = i, q[l] = j and r(p) + r(q) <= b: plane b of dg_dp_run_pinned(P + require (l, i, j)).  V_b(P) = F_{L-1}[sink, sink][b] is
+ * plane b of dg_dp_run_pinned(P), and on every level the maximum of T is V_b(P) (the closing check).  T(. | P) <= T(.) cell by cell.
+ * Pins are ordered, so T is NOT symmetric in general: the called cell's value is T at the ordered called cell (vertex1 = haplotype 1)
+ * and J[v] = max_j T_l[v][j] over the ordered row, while a genotype is unordered: the alternative of a record and the entries of the
+ * table take the cells vertex1 <= vertex2 as above with the value max(T[i][j], T[j][i]), ties by the same rule.  That maximum changes
+ * nothing where P is symmetric or empty.  A pin set that no pair satisfies within the budget is an answer: NEG_INF / -1 everywhere,
+ * an empty table, DG_OK.  n_pins = 0 (pins may be NULL) is the unpinned call: the same pass, no mask launch, every output identical.
+ * Device: after every launch that writes a forward or backward state of a pinned level (the checkpointing pass, every segment's
+ * recompute, the backward recurrence) one launch of jt_pin_mask_kernel (csrc/dg_dp_pins.hip) stores NEG_INF over all b + 1 planes of
+ * the level's cells that are not allowed; no other kernel changes, the combination of a pinned call takes both orders of a cell.  The
+ * sorted pins live in a buffer of the call.  Like their twins the calls read and write nothing of a run: the pins, statistics and
+ * "pinned" state of an earlier dg_dp_run_pinned stay as they were, and a failed call writes nothing.  Synchronises. */
+int dg_dp_genotype_margins_pinned(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n_called, int32_t budget,
+                                  const int32_t *vertex_class, dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value);
+int dg_dp_genotype_table_pinned(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called,
+                                int64_t n_called, dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries,
+                                int64_t *n_entries, int32_t *best_value);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
