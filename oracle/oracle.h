@@ -67,6 +67,12 @@ typedef struct orc_dp_result {
  * i.e. it pins the value AND the winning predecessor (tie-break :657-659) of every cell. */
 int      orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, uint64_t *level_digest);
 
+/* The same level loop (one statement of it serves both entry points), keeping for every cell of every level the winning
+ * (pred_i, pred_j) of :657-659 and the plane of its source cell, then walked back from the sink cell (R, 0, 0) as the reference's
+ * read-out :774-775 chooses it: paths[0 * n_levels + l] is the vertex of the first path (i) on level l, paths[1 * n_levels + l] of
+ * the second (j).  *value is the sink cell's value; if that cell is unreachable every entry of paths is -1. */
+int      orc_dp_paths_diploid(const orc_dp_graph *g, int32_t *value, int32_t *paths /* [2][n_levels] vertex ids */);
+
 /* ---- haploid DP (src/approximator.cpp:44-72) ---- */
 typedef struct orc_hap_graph {      /* expanded graph after topologically_reorder: every edge u -> v has u < v */
     int32_t n_vertices, R;

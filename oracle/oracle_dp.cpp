@@ -59,13 +59,16 @@ struct Entry {                                                      // :390-410
     int pred_i, pred_j, value, s_het;
     int64_t p1_tail, p2_tail;
     int p1_count, p2_count;
+    int pred_r;                                                     // not in the reference: the plane of the winning source cell (orc_dp_paths_diploid)
 };
 const int IMAX = std::numeric_limits<int>::max();
-}
+const int32_t NEG_INF = std::numeric_limits<int32_t>::min() / 4;    // :413
+struct Back { int pred_i, pred_j, pred_r; };
 
-extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, uint64_t *level_digest) {
+// The level loop and the sink read-out, stated once for both entry points.  back (optional) receives, per destination level l = 1..L-1
+// (index l), the winning (pred_i, pred_j, source plane) of every cell in the lattice's own order [r][i][j].
+int solve_diploid(const orc_dp_graph *g, orc_dp_result *res, uint64_t *level_digest, std::vector<std::vector<Back>> *back) {
     const int L = g->n_levels, R = g->R;
-    const int32_t NEG_INF = std::numeric_limits<int32_t>::min() / 4;  // :413
     if (L < 1) return -1;
     // pos_in_level (:372-379): ids are level-sorted, so pos = v - level_off[level(v)]
     std::vector<int> pos(g->n_vertices);
@@ -79,7 +82,7 @@ extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, u
 
     std::vector<EdgeNode> pool1, pool2;
     std::vector<Entry> cur, nxt;
-    Entry e0{IMAX, IMAX, 0, 0, -1, -1, 0, 0};
+    Entry e0{IMAX, IMAX, 0, 0, -1, -1, 0, 0, -1};
     cur.assign((size_t)(R + 1), e0);                                 // :534-535 (level 0 has k=1)
     if (g->level_off[1] - g->level_off[0] != 1) return -2;
 
@@ -113,7 +116,7 @@ extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, u
         const int a0 = g->level_off[l], k = g->level_off[l + 1] - a0;
         const int b0 = g->level_off[l + 1], k2 = g->level_off[l + 2] - b0;
         const size_t szN = (size_t)(R + 1) * k2 * k2;
-        Entry reset{IMAX, IMAX, NEG_INF, 0, -1, -1, 0, 0};           // :565-576
+        Entry reset{IMAX, IMAX, NEG_INF, 0, -1, -1, 0, 0, -1};       // :565-576
         nxt.assign(szN, reset);
         cells += szN;
 
@@ -169,7 +172,7 @@ extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, u
                                 (cand == dst.value && i == dst.pred_i && j < dst.pred_j)) {
                                 dst.value = cand;
                                 dst.s_het = src.s_het + s_hets[idx];
-                                dst.pred_i = i; dst.pred_j = j;
+                                dst.pred_i = i; dst.pred_j = j; dst.pred_r = r;
                                 dst.p1_tail = src.p1_tail; dst.p2_tail = src.p2_tail;
                                 dst.p1_count = src.p1_count; dst.p2_count = src.p2_count;
                                 if (wu > 0) {                        // :673-677
@@ -192,6 +195,11 @@ extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, u
                     }
                 }
         cur.swap(nxt);                                               // :706
+        if (back) {
+            std::vector<Back> &bl = (*back)[l + 1];
+            bl.resize(cur.size());
+            for (size_t t = 0; t < cur.size(); ++t) bl[t] = Back{cur[t].pred_i, cur[t].pred_j, cur[t].pred_r};
+        }
         if (((l + 1) % 1000) == 0) { compact(pool1, true); compact(pool2, false); }   // :710-713
         if (level_digest) {
             uint64_t d = 0;
@@ -220,6 +228,34 @@ extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, u
     res->n_p1 = materialize(pool1, sink.p1_tail, res->p1_from, res->p1_to);
     res->n_p2 = materialize(pool2, sink.p2_tail, res->p2_from, res->p2_to);
     return 0;
+}
+}  // namespace
+
+extern "C" int orc_dp_solve_diploid(const orc_dp_graph *g, orc_dp_result *res, uint64_t *level_digest) {
+    return solve_diploid(g, res, level_digest, nullptr);
+}
+
+extern "C" int orc_dp_paths_diploid(const orc_dp_graph *g, int32_t *value, int32_t *paths) {
+    const int L = g->n_levels;
+    if (L < 1) return -1;
+    std::vector<std::vector<Back>> back((size_t)L);
+    orc_dp_result res{};                                             // cap 0: the edge lists are counted, not written
+    const int rc = solve_diploid(g, &res, nullptr, &back);
+    if (rc) return rc;
+    *value = res.value;
+    for (int t = 0; t < 2 * L; ++t) paths[t] = -1;
+    if (res.value == NEG_INF) return 0;                              // the sink cell (R, 0, 0) is unreachable
+    int r = g->R, i = 0, j = 0;                                      // :774-775 (best_r = R), then pred_i / pred_j level by level
+    for (int l = L - 1; l >= 0; --l) {
+        paths[l] = g->level_off[l] + i;
+        paths[L + l] = g->level_off[l] + j;
+        if (l == 0) break;
+        const int k2 = g->level_off[l + 1] - g->level_off[l];
+        const Back b = back[l][((size_t)r * k2 + i) * k2 + j];
+        if (b.pred_r < 0 || b.pred_r > r) return -3;                 // a reachable cell always has a source
+        i = b.pred_i; j = b.pred_j; r = b.pred_r;
+    }
+    return (r >= 0 && i == 0 && j == 0) ? 0 : -3;
 }
 
 extern "C" int orc_dp_haploid(const orc_hap_graph *g, int32_t *dp, int32_t *back_vtx, int32_t *back_r) {   // :44-72

@@ -14,8 +14,7 @@ def build():
     subprocess.check_call(["make", "-s", "-C", ORC_DIR, "restate"])
 
 
-if not os.path.exists(ORC_PATH):
-    build()
+build()                                 # make decides: a missing library, or one older than its sources (from before a symbol was added), is rebuilt
 lib = C.CDLL(ORC_PATH)
 
 
@@ -46,6 +45,7 @@ lib.orc_sketch_reads.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c
 lib.orc_free.argtypes = [C.c_void_p]
 lib.orc_free.restype = None
 lib.orc_dp_solve_diploid.argtypes = [C.POINTER(OrcGraph), C.POINTER(OrcResult), C.c_void_p]
+lib.orc_dp_paths_diploid.argtypes = [C.POINTER(OrcGraph), C.POINTER(C.c_int32), C.c_void_p]
 lib.orc_inter_union2x2.argtypes = [C.c_void_p, C.c_int] * 4
 lib.orc_symdiff_union2x2.argtypes = [C.c_void_p, C.c_int] * 4
 
@@ -119,3 +119,17 @@ def dp_solve(g, want_digest=False):
     if want_digest:
         out["digest"] = dig
     return out
+
+
+def dp_paths(g):
+    """the pair of paths the oracle's lattice decodes to from the sink cell (R, 0, 0): (value, int32 [2, n_levels] of vertex ids -- row 0
+    the first path, row 1 the second), or (value, None) where that cell is unreachable"""
+    st = g.as_struct(OrcGraph)
+    value = C.c_int32(0)
+    paths = np.full((2, g.n_levels), -7, np.int32)
+    rc = lib.orc_dp_paths_diploid(C.byref(st), C.byref(value), paths.ctypes.data)
+    assert rc == 0, rc
+    if (paths == -1).all():
+        return value.value, None
+    assert (paths >= 0).all()
+    return value.value, paths

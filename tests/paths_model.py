@@ -45,6 +45,12 @@ def repeat_edge(g, edge, copies):
     return DpGraphArrays(g.R, **arrs)
 
 
+def edge_list(m, path):
+    """the weight-1 hops of a path of the PathModel m and its last hop once more (approximator.cpp:673-692), sorted"""
+    hops = [(int(path[l - 1]), int(path[l])) for l in range(1, m.L) if m.succ[int(path[l - 1])][int(path[l])] == 1]
+    return sorted(hops + [(int(path[m.L - 2]), int(path[m.L - 1]))])
+
+
 class PathModel:
     def __init__(self, g):
         self.level_off = np.asarray(_get(g, "level_off"), np.int64)

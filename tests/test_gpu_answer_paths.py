@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from dipgenie_amd import capi
-from paths_model import NEG_INF, PathModel
+from paths_model import NEG_INF, PathModel, edge_list
 from test_gpu_partner import CASES
 
 pytestmark = pytest.mark.gpu
@@ -28,12 +28,6 @@ def graph_of(name, R=None):
             g.R = R
         _GRAPHS[(name, R)] = (g, PathModel(g))
     return _GRAPHS[(name, R)]
-
-
-def edge_list(m, path):
-    """the weight-1 hops of a path and its last hop once more (approximator.cpp:673-692), sorted"""
-    hops = [(int(path[l - 1]), int(path[l])) for l in range(1, m.L) if m.succ[int(path[l - 1])][int(path[l])] == 1]
-    return sorted(hops + [(int(path[m.L - 2]), int(path[m.L - 1]))])
 
 
 def check_answers(ctx, g, m, outs, budgets):
