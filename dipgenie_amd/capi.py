@@ -96,6 +96,7 @@ SYMBOLS = [
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
     "dg_dp_run_pinned", "dg_dp_get_pin_stats", "dg_dp_genotype_margins_pinned", "dg_dp_genotype_table_pinned",
+    "dg_dp_genotype_margins_budgets",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -124,6 +125,7 @@ lib.dg_dp_genotype_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void
                                      C.POINTER(C.c_int32)]
 lib.dg_dp_get_genotype_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_genotype_margins_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_margins.argtypes[1:]
+lib.dg_dp_genotype_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_genotype_table_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_table.argtypes[1:]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -535,6 +537,35 @@ class Context:
         else:
             _check(lib.dg_dp_genotype_margins_pinned(self.h, pins.ctypes.data if pins.size else None, pins.shape[0], *args), "dg_dp_genotype_margins_pinned")
         return (levels, best.value, values) if want_vertices else (levels, best.value)
+
+    def dp_genotype_margins_budgets(self, called, budgets, vertex_class=None, pins=None):
+        """dp_genotype_margins with one budget per query, from one joint pass at the largest of them.  called: int32 [n, 2, n_levels],
+        or [2, n_levels] with a scalar budget; budgets: n integers >= 0, in any order, repeats allowed; vertex_class as for
+        dp_genotype_margins; pins as for dp_run_pinned (None or empty: the unpinned DP).  Returns (levels, best_values): the
+        GENOTYPE_MARGIN records [n, n_levels], query q exactly what dp_genotype_margins(called[q], budgets[q], vertex_class) -- with
+        pins dp_genotype_margins_pinned -- answers, and int32 [n]: the best value of any pair within budgets[q].  A budget that no
+        pair fits gives NEG_INF / -1 records for its query only.  At most 256 queries.  Leaves the last run's answers alone."""
+        p = np.ascontiguousarray(called, np.int32)
+        if p.ndim == 2 and np.ndim(budgets) == 0:
+            p, budgets = p[None], [budgets]
+        b = np.ascontiguousarray(budgets, np.int32)          # (a scalar with [n, 2, n_levels] comes out as [1]: refused below unless n = 1)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+            raise ValueError(f"called must have shape [n, 2, n_levels], got {p.shape}")
+        if b.shape != (p.shape[0],):
+            raise ValueError(f"budgets must have shape [{p.shape[0]}], got {b.shape}")
+        cls = None
+        if vertex_class is not None:
+            cls = np.ascontiguousarray(vertex_class, np.int32)
+            if g is not None and cls.shape != (g.n_vertices,):
+                raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
+        pins = _pin_rows(pins) if pins is not None else None
+        levels = np.zeros((p.shape[0], p.shape[2]), GENOTYPE_MARGIN)
+        best = np.zeros(p.shape[0], np.int32)
+        _check(lib.dg_dp_genotype_margins_budgets(self.h, pins.ctypes.data if pins is not None and pins.size else None, pins.shape[0] if pins is not None else 0,
+                                                  p.ctypes.data if p.size else None, b.ctypes.data if b.size else None, p.shape[0], cls.ctypes.data if cls is not None else None,
+                                                  levels.ctypes.data if levels.size else None, best.ctypes.data if best.size else None), "dg_dp_genotype_margins_budgets")
+        return levels, best
 
     def dp_genotype_table(self, budget, vertex_class=None, called=None):
         """The genotype table: per level and genotype (the unordered pair of its cell's classes) the best value of any pair of paths

@@ -431,6 +431,9 @@ int dp_genotype_margins(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n
                         dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value);
 int dp_genotype_table(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n,
                       dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value);
+// one budget per query, from one pass at the largest (n_pins = 0: unpinned)
+int dp_genotype_margins_budgets(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *vertex_class,
+                                dg_dp_genotype_margin *levels, int32_t *best_values);
 int dp_genotype_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

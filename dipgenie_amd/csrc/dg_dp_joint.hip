@@ -36,6 +36,9 @@
 // (dg_dp_pins.hip) stores NEG_INF over the level's cells that are not allowed, and the recurrences, which skip a NEG_INF source cell,
 // do the rest.  Pins are ordered, so T is no longer symmetric: the pinned calls run the ORDERED instantiations of jt_combine_kernel and
 // gt_rows_kernel, which give the unordered cell (i, j >= i) the value max(T[i][j], T[j][i]); n_pins = 0 runs what the unpinned calls run.
+// dg_dp_genotype_margins_budgets answers every query at a budget of its own from the same pass run once at the largest budget: the
+// recurrences, score matrices and masks are launched once, jt_combine_budgets_kernel / jt_records_budgets_kernel (their comment has the
+// plan) take the places of jt_combine_kernel / jt_records_kernel.  The other entry points launch neither and reserve none of their buffers.
 #include <algorithm>
 #include <cstring>
 
@@ -307,6 +310,121 @@ __global__ __launch_bounds__(JT_THREADS) void jt_records_kernel(int k, int b0, c
     }
 }
 
+// ---- dg_dp_genotype_margins_budgets: the states are "at most r" planes, so F and B at B1 = bmax + 1 hold T^b for every b <= bmax:
+// T^b[i][j] = max over r = 0..b of F[i][j][r] + B[i][j][b - r].  Siblings of the two kernels above with one more grid dimension:
+//   * jt_combine_budgets_kernel: grid (row blocks, distinct budgets).  Workgroup (x, d) forms the rows of T^bud[d] in a scratch row of its
+//     own, their maxima into Jb[d][.], and the keys of the queries of that budget only (qlist[qoff[d] .. qoff[d + 1])): part[q][i] and
+//     cval[q] have one owner as before, since a query has one budget.  f / b of a cell are read once per distinct budget, by different
+//     workgroups of the same launch: the repeats are served by the L2, and a narrow level gets nd times the workgroups it had;
+//   * jt_records_budgets_kernel: one workgroup per query; the first query of each budget also reduces Jb[d][.] to lvlmax[d][l].
+// bud[d] < B1 (the host sorts the distinct budgets, the largest is B1 - 1); Jb = [nd][kstride].
+template <bool ORDERED>
+__global__ __launch_bounds__(JT_THREADS) void jt_combine_budgets_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ B, int k, int B1, int b0, int32_t *row_all,
+                                                                        int32_t *__restrict__ Jb, int kstride, const int32_t *__restrict__ bud, const int32_t *__restrict__ qoff,
+                                                                        const int32_t *__restrict__ qlist, const int32_t *__restrict__ called, int L, int l,
+                                                                        const int32_t *__restrict__ cls, long long *__restrict__ part, int32_t *__restrict__ cval) {
+    __shared__ long long s_key[JT_MAX_QUERIES][JT_THREADS / 64];
+    __shared__ int s_max[JT_THREADS / 64];
+    const int t = (int)threadIdx.x, d = (int)blockIdx.y;
+    const int bb = min(bud[d], B1 - 1);
+    const int q0 = qoff[d], nq = min(qoff[d + 1] - q0, JT_MAX_QUERIES);
+    const int64_t slot = (int64_t)blockIdx.y * gridDim.x + blockIdx.x, slots = (int64_t)gridDim.x * gridDim.y;
+    int32_t *row = row_all + slot * k;
+    int32_t *col = ORDERED ? row_all + (slots + slot) * k : nullptr;
+    for (int i = (int)blockIdx.x; i < k; i += (int)gridDim.x) {
+        int m = NEG_INF;
+        for (int j = t; j < k; j += JT_THREADS) {
+            const int32_t *f = F + ((int64_t)i * k + j) * B1, *b = B + ((int64_t)i * k + j) * B1;
+            int best = NEG_INF;
+            for (int r = 0; r <= bb; ++r) {
+                const int fv = f[r], bv = b[bb - r];
+                if (fv != NEG_INF && bv != NEG_INF) best = max(best, fv + bv);
+            }
+            row[j] = best;
+            m = max(m, best);
+            if (ORDERED && j >= i) {
+                const int32_t *f2 = F + ((int64_t)j * k + i) * B1, *b2 = B + ((int64_t)j * k + i) * B1;
+                int other = NEG_INF;
+                for (int r = 0; r <= bb; ++r) {
+                    const int fv = f2[r], bv = b2[bb - r];
+                    if (fv != NEG_INF && bv != NEG_INF) other = max(other, fv + bv);
+                }
+                col[j] = other;
+            }
+        }
+        for (int w = 32; w; w >>= 1) m = max(m, __shfl_xor(m, w));
+        if ((t & 63) == 0) s_max[t >> 6] = m;
+        __syncthreads();                                                    // the row and the waves' maxima are in
+        if (t == 0) {
+            for (int w = 1; w < JT_THREADS / 64; ++w) m = max(m, s_max[w]);
+            Jb[(int64_t)d * kstride + i] = m;
+        }
+        const int ci = cls ? cls[b0 + i] : b0 + i;
+        for (int x = 0; x < nq; ++x) {
+            const int q = qlist[q0 + x];
+            const int c1 = called[((int64_t)q * 2) * L + l], c2 = called[((int64_t)q * 2 + 1) * L + l];
+            const int cc1 = cls ? cls[c1] : c1, cc2 = cls ? cls[c2] : c2;
+            if (t == 0 && i == c1 - b0) cval[q] = row[c2 - b0];
+            long long key = JT_NO_KEY;
+            for (int j = i + t; j < k; j += JT_THREADS) {
+                const int v = ORDERED ? max(row[j], col[j]) : row[j];
+                if (v == NEG_INF) continue;
+                const int cj = cls ? cls[b0 + j] : b0 + j;
+                if ((ci == cc1 && cj == cc2) || (ci == cc2 && cj == cc1)) continue;      // the called genotype itself
+                key = max(key, jt_key(v, i, j));
+            }
+            for (int w = 32; w; w >>= 1) key = max(key, __shfl_xor(key, w));
+            if ((t & 63) == 0) s_key[x][t >> 6] = key;
+        }
+        __syncthreads();
+        for (int x = t; x < nq; x += JT_THREADS) {
+            long long key = s_key[x][0];
+            for (int w = 1; w < JT_THREADS / 64; ++w) key = max(key, s_key[x][w]);
+            part[(int64_t)qlist[q0 + x] * k + i] = key;
+        }
+        __syncthreads();                                                    // the next row overwrites the scratch row and the keys
+    }
+}
+
+// grid: n workgroups.  Query q of budget index d = qd[q]: the largest of its k row keys -> rec[q][l]; the first query of d also the
+// maximum of Jb[d][.] -> lvlmax[d][l]
+__global__ __launch_bounds__(JT_THREADS) void jt_records_budgets_kernel(int k, int b0, const int32_t *__restrict__ Jb, int kstride, const int32_t *__restrict__ qd,
+                                                                        const int32_t *__restrict__ qoff, const int32_t *__restrict__ qlist, const long long *__restrict__ part,
+                                                                        const int32_t *__restrict__ cval, const int32_t *__restrict__ called, int L, int l,
+                                                                        dg_dp_genotype_margin *__restrict__ rec, int32_t *__restrict__ lvlmax) {
+    __shared__ long long s_key[JT_THREADS / 64];
+    __shared__ int s_max[JT_THREADS / 64];
+    const int t = (int)threadIdx.x, q = (int)blockIdx.x;
+    const int d = qd[q];
+    const bool lead = qlist[qoff[d]] == q;                                  // uniform per workgroup
+    long long key = JT_NO_KEY;
+    int m = NEG_INF;
+    for (int i = t; i < k; i += JT_THREADS) {
+        key = max(key, part[(int64_t)q * k + i]);
+        if (lead) m = max(m, Jb[(int64_t)d * kstride + i]);
+    }
+    for (int w = 32; w; w >>= 1) { key = max(key, __shfl_xor(key, w)); m = max(m, __shfl_xor(m, w)); }
+    if ((t & 63) == 0) { s_key[t >> 6] = key; s_max[t >> 6] = m; }
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) { key = max(key, s_key[w]); m = max(m, s_max[w]); }
+        dg_dp_genotype_margin r;
+        r.vertex1 = called[((int64_t)q * 2) * L + l];
+        r.vertex2 = called[((int64_t)q * 2 + 1) * L + l];
+        r.value = cval[q];
+        if (key == JT_NO_KEY) { r.alt_vertex1 = -1; r.alt_vertex2 = -1; r.alt_value = NEG_INF; }
+        else {
+            const uint32_t lo = (uint32_t)key;
+            r.alt_vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+            r.alt_vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+            r.alt_value = (int)(key >> 32);
+        }
+        r.reserved[0] = 0; r.reserved[1] = 0;
+        rec[(int64_t)q * L + l] = r;
+        if (lead) lvlmax[(int64_t)d * L + l] = m;
+    }
+}
+
 // ---- dg_dp_genotype_table: a level's through-values reduced by genotype.  The call runs the combine kernel with one scratch row per
 // row of the level, so T[k][k] of the level is whole when these run.  rank[v] = dense rank of v's class among the classes of its level
 // (ascending, signed), perm = the level's positions ordered by (rank, position), goff[a] .. goff[a + 1] = the slice of perm with rank a
@@ -499,13 +617,16 @@ unsigned jt_blocks(int64_t lanes, int cap) { return (unsigned)std::max<int64_t>(
 
 // the outputs of dg_dp_genotype_table (null for dg_dp_genotype_margins: then nothing of the table is reserved or launched)
 struct JtTable { int64_t *level_off; dg_dp_genotype_entry **entries; int64_t *n_entries; };
+// one budget per query (dg_dp_genotype_margins_budgets; null for the others: then `budget` holds for all and nothing here is reserved or launched)
+struct JtBudgets { const int32_t *budgets; int32_t *best_values; };
 
 namespace {
 
-// all four entry points: tab = null is dg_dp_genotype_margins (_pinned); n_pins = 0 is the unpinned call -- no PinSet, no mask launch,
-// the kernels' unordered instantiations
+// all five entry points: tab = null is dg_dp_genotype_margins (_pinned); n_pins = 0 is the unpinned call -- no PinSet, no mask launch,
+// the kernels' unordered instantiations; mb != null is dg_dp_genotype_margins_budgets: the same schedule once at the largest budget, the
+// combination and the closing check per distinct budget (tab, vertex_values and best_value are null then, `budget` is ignored)
 int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class, dg_dp_genotype_margin *levels,
-            int32_t *vertex_values, int32_t *best_value, const JtTable *tab) {
+            int32_t *vertex_values, int32_t *best_value, const JtTable *tab, const JtBudgets *mb = nullptr) {
     DpState *Sp = c->dp;
     if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
     DpState &S = *Sp;
@@ -517,7 +638,16 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
         }
     } else {
         if (n < 1) { set_error("%s: n_called = %lld", FN, (long long)n); return DG_ERR_ARG; }
-        if (!called || !levels || !best_value) { set_error("%s: called, levels and best_value are required", FN); return DG_ERR_ARG; }
+        if (mb) {
+            if (!called || !levels || !mb->budgets || !mb->best_values) { set_error("%s: called, budgets, levels and best_values are required", FN); return DG_ERR_ARG; }
+        } else if (!called || !levels || !best_value) { set_error("%s: called, levels and best_value are required", FN); return DG_ERR_ARG; }
+    }
+    if (mb && n <= JT_MAX_QUERIES) {                                        // the pass runs at the largest budget
+        budget = 0;
+        for (int64_t q = 0; q < n; ++q) {
+            if (mb->budgets[q] < 0) { set_error("%s: query %lld: budget %d is negative", FN, (long long)q, mb->budgets[q]); return DG_ERR_ARG; }
+            budget = std::max(budget, mb->budgets[q]);
+        }
     }
     if (budget < 0) { set_error("%s: budget %d is negative", FN, budget); return DG_ERR_ARG; }
     if (n > JT_MAX_QUERIES) { set_error("%s: %lld called genotypes exceed %d per call", FN, (long long)n, JT_MAX_QUERIES); return DG_ERR_UNSUPPORTED; }
@@ -600,6 +730,24 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
         called = stand_in.data();
         n = 1;
     }
+    // ---- the distinct budgets, ascending; per query its index among them; the queries grouped by it (in their own order) ----
+    std::vector<int32_t> bud, bq;                                           // bq = [nd + 1] offsets, [n] the grouped queries, [n] the index per query
+    int nd = 1;
+    if (mb) {
+        bud.assign(mb->budgets, mb->budgets + n);
+        std::sort(bud.begin(), bud.end());
+        bud.erase(std::unique(bud.begin(), bud.end()), bud.end());
+        nd = (int)bud.size();
+        bq.assign((size_t)nd + 1 + 2 * (size_t)n, 0);
+        int32_t *qoff = bq.data(), *qlist = qoff + nd + 1, *qd = qlist + n;
+        for (int64_t q = 0; q < n; ++q) {
+            qd[q] = (int32_t)(std::lower_bound(bud.begin(), bud.end(), mb->budgets[q]) - bud.begin());
+            ++qoff[qd[q] + 1];
+        }
+        for (int d = 0; d < nd; ++d) qoff[d + 1] += qoff[d];
+        std::vector<int32_t> at(qoff, qoff + nd);
+        for (int64_t q = 0; q < n; ++q) qlist[at[(size_t)qd[q]]++] = (int32_t)q;
+    }
     hipStream_t s = c->stream;
     // ---- the plan: segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
     std::vector<int> seg{0};
@@ -626,13 +774,22 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
     JtMem M;
     if (P) { M.now += (int64_t)d_jpins.bytes; M.peak = M.now; }
     DevBuf d_called, d_cls, d_J, d_rec, d_lvlmax, d_cval, d_part, d_row, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back;
+    DevBuf d_bud, d_bq, d_Jb, d_V;
     DevBuf d_trank, d_tperm, d_tgoff, d_gpart, d_dense, d_tcnt, d_tmax, d_tlvl, d_stage;
-    const int row_blocks = tab ? kmax : std::min(kmax, JT_ROW_BLOCKS);      // the table keeps every row of T: one scratch row per row
+    // the table keeps every row of T: one scratch row per row; the budgets share the rows of the one-budget call among them
+    const int rows_per_budget = std::max(1, std::min(kmax, JT_ROW_BLOCKS / nd));
+    const int row_blocks = tab ? kmax : mb ? rows_per_budget * nd : std::min(kmax, JT_ROW_BLOCKS);
     if (int rc = M.get(d_called, n * 2 * L * 4)) return rc;
     if (vertex_class) if (int rc = M.get(d_cls, (int64_t)nV * 4)) return rc;
     if (int rc = M.get(d_J, (int64_t)nV * 4)) return rc;
     if (int rc = M.get(d_rec, n * L * (int64_t)sizeof(dg_dp_genotype_margin))) return rc;
-    if (int rc = M.get(d_lvlmax, ((int64_t)L + 1) * 4)) return rc;                 // entry L: V_b, the sink's cell on plane `budget`
+    if (int rc = M.get(d_lvlmax, mb ? (int64_t)nd * L * 4 : ((int64_t)L + 1) * 4)) return rc;       // entry L: V_b, the sink's cell on plane `budget` (budgets: [nd][L], V in d_V)
+    if (mb) {
+        if (int rc = M.get(d_bud, (int64_t)nd * 4)) return rc;
+        if (int rc = M.get(d_bq, (int64_t)bq.size() * 4)) return rc;
+        if (int rc = M.get(d_Jb, (int64_t)nd * kmax * 4)) return rc;
+        if (int rc = M.get(d_V, (int64_t)B1 * 4)) return rc;                       // the sink's cell, every plane
+    }
     if (int rc = M.get(d_cval, n * 4)) return rc;
     if (int rc = M.get(d_part, n * kmax * 8)) return rc;
     if (int rc = M.get(d_row, (int64_t)row_blocks * kmax * 4 * (P ? 2 : 1))) return rc;       // (pinned: the columns behind the rows)
@@ -679,6 +836,11 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
     };
     DG_HIP(hipMemcpyAsync(d_called.p, called, (size_t)(n * 2 * L) * 4, hipMemcpyHostToDevice, s));
     if (vertex_class) DG_HIP(hipMemcpyAsync(d_cls.p, vertex_class, (size_t)nV * 4, hipMemcpyHostToDevice, s));
+    if (mb) {
+        DG_HIP(hipMemcpyAsync(d_bud.p, bud.data(), (size_t)nd * 4, hipMemcpyHostToDevice, s));
+        DG_HIP(hipMemcpyAsync(d_bq.p, bq.data(), bq.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    const int32_t *d_qoff = d_bq.as<int32_t>(), *d_qlist = mb ? d_qoff + nd + 1 : nullptr, *d_qd = mb ? d_qlist + n : nullptr;
     const LevelDesc *descs = S.d_descs.as<LevelDesc>();
     const uint32_t *in_off = S.d_in_off.as<uint32_t>(), *in_edge = S.d_in_edge.as<uint32_t>();
     const int32_t *in_dst = S.d_in_dst.as<int32_t>();
@@ -734,6 +896,7 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
     if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
     int32_t *back = d_back.as<int32_t>();
     const auto combine = P ? jt_combine_kernel<true> : jt_combine_kernel<false>;       // ordered pins: both orders of a cell
+    const auto combine_budgets = P ? jt_combine_budgets_kernel<true> : jt_combine_budgets_kernel<false>;
     const auto gt_rows = P ? gt_rows_kernel<true> : gt_rows_kernel<false>;
     std::vector<const int32_t *> Fp((size_t)L, nullptr);
     for (int g = n_seg - 1; g >= 0; --g) {
@@ -751,7 +914,8 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
             if (l == L - 1) {
                 const int sink = nV - 1 - lv[l].a0;
                 fill(cur, l, sink);
-                DG_HIP(hipMemcpyAsync(d_lvlmax.as<int32_t>() + L, Fp[l] + ((int64_t)sink * lv[l].k + sink) * B1 + budget, 4, hipMemcpyDeviceToDevice, s));
+                if (mb) DG_HIP(hipMemcpyAsync(d_V.p, Fp[l] + ((int64_t)sink * lv[l].k + sink) * B1, (size_t)B1 * 4, hipMemcpyDeviceToDevice, s));
+                else DG_HIP(hipMemcpyAsync(d_lvlmax.as<int32_t>() + L, Fp[l] + ((int64_t)sink * lv[l].k + sink) * B1 + budget, 4, hipMemcpyDeviceToDevice, s));
             } else {
                 const uint16_t *m = scores(l + 1);
                 hipLaunchKernelGGL(jt_backward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s,
@@ -759,6 +923,16 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
                                    d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
                 ++launches;
                 if (P && P->has(l)) { pins_launch_joint_mask(*P, l, cur, lv[l].k, B1, s); ++launches; }
+            }
+            if (mb) {
+                hipLaunchKernelGGL(combine_budgets, dim3((unsigned)std::min(lv[l].k, rows_per_budget), (unsigned)nd), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)cur, lv[l].k, B1,
+                                   lv[l].a0, d_row.as<int32_t>(), d_Jb.as<int32_t>(), kmax, (const int32_t *)d_bud.as<int32_t>(), d_qoff, d_qlist, (const int32_t *)d_called.as<int32_t>(), L, l,
+                                   vertex_class ? (const int32_t *)d_cls.as<int32_t>() : nullptr, d_part.as<long long>(), d_cval.as<int32_t>());
+                hipLaunchKernelGGL(jt_records_budgets_kernel, dim3((unsigned)n), dim3(JT_THREADS), 0, s, lv[l].k, lv[l].a0, (const int32_t *)d_Jb.as<int32_t>(), kmax, d_qd, d_qoff, d_qlist,
+                                   (const long long *)d_part.as<long long>(), (const int32_t *)d_cval.as<int32_t>(), (const int32_t *)d_called.as<int32_t>(), L, l,
+                                   d_rec.as<dg_dp_genotype_margin>(), d_lvlmax.as<int32_t>());
+                launches += 2;
+                continue;
             }
             hipLaunchKernelGGL(combine, dim3((unsigned)std::min(lv[l].k, row_blocks)), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)cur, lv[l].k, B1, lv[l].a0,
                                d_row.as<int32_t>(), d_J.as<int32_t>(), (int)n, d_called.as<int32_t>(), L, l, vertex_class ? d_cls.as<int32_t>() : nullptr,
@@ -794,16 +968,29 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
     }
     // the caller's arrays are written only if the call succeeds
     std::vector<dg_dp_genotype_margin> recs((size_t)(n * L));
-    std::vector<int32_t> lvlmax((size_t)L + 1), vals(vertex_values ? (size_t)nV : 0);
+    std::vector<int32_t> lvlmax(mb ? (size_t)nd * L : (size_t)L + 1), vals(vertex_values ? (size_t)nV : 0), Vs(mb ? (size_t)B1 : 0);
     std::vector<long long> tlvl(tab ? (size_t)3 * L : 0);
     if (tab) DG_HIP(hipMemcpyAsync(tlvl.data(), d_tlvl.p, tlvl.size() * 8, hipMemcpyDeviceToHost, s));
     DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_genotype_margin), hipMemcpyDeviceToHost, s));
-    DG_HIP(hipMemcpyAsync(lvlmax.data(), d_lvlmax.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(lvlmax.data(), d_lvlmax.p, lvlmax.size() * 4, hipMemcpyDeviceToHost, s));
+    if (mb) DG_HIP(hipMemcpyAsync(Vs.data(), d_V.p, Vs.size() * 4, hipMemcpyDeviceToHost, s));
     if (vertex_values) DG_HIP(hipMemcpyAsync(vals.data(), d_J.p, (size_t)nV * 4, hipMemcpyDeviceToHost, s));
     DG_HIP(hipStreamSynchronize(s));
     S.jt_stats[0] = n_seg; S.jt_stats[1] = twice; S.jt_stats[2] = M.peak; S.jt_stats[3] = launches;
     S.jt_stats[4] = (int64_t)found.size(); S.jt_stats[5] = copies;
     S.jt_stats[6] = P ? n_pins : 0; S.jt_stats[7] = P ? P->n_mask : 0;
+    if (mb) {                                                               // the closing check, per distinct budget
+        for (int d = 0; d < nd; ++d)
+            for (int l = 0; l < L; ++l)
+                if (lvlmax[(size_t)d * L + l] != Vs[(size_t)bud[(size_t)d]]) {
+                    set_error("%s: level %d: the largest through-value at budget %d is %d, the sink's value at that budget is %d", FN, l, bud[(size_t)d], lvlmax[(size_t)d * L + l],
+                              Vs[(size_t)bud[(size_t)d]]);
+                    return DG_ERR_STATE;
+                }
+        memcpy(levels, recs.data(), recs.size() * sizeof(dg_dp_genotype_margin));
+        for (int64_t q = 0; q < n; ++q) mb->best_values[q] = Vs[(size_t)mb->budgets[q]];
+        return DG_OK;
+    }
     const int32_t V = lvlmax[(size_t)L];
     // the closing check: on every level the best pair through any cell is the best pair
     for (int l = 0; l < L; ++l)
@@ -852,6 +1039,12 @@ int dp_genotype_margins(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n
     return jt_call(c, pinned ? "dg_dp_genotype_margins_pinned" : "dg_dp_genotype_margins", pinned ? pins : nullptr, pinned ? n_pins : 0, called, n, budget, vertex_class, levels, vertex_values, best_value, nullptr);
 }
 
+int dp_genotype_margins_budgets(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *vertex_class,
+                                dg_dp_genotype_margin *levels, int32_t *best_values) {
+    const JtBudgets mb{budgets, best_values};
+    return jt_call(c, "dg_dp_genotype_margins_budgets", n_pins != 0 ? pins : nullptr, n_pins, called, n, 0, vertex_class, levels, nullptr, nullptr, nullptr, &mb);
+}
+
 int dp_genotype_table(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n,
                       dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) {
     const JtTable tab{level_off, entries, n_entries};
@@ -890,6 +1083,12 @@ extern "C" int dg_dp_genotype_table_pinned(dg_ctx *c, const dg_dp_pin *pins, int
                                            int64_t *n_entries, int32_t *best_value) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_genotype_table(c, true, pins, n_pins, budget, vertex_class, called, n_called, levels, level_off, entries, n_entries, best_value);
+}
+
+extern "C" int dg_dp_genotype_margins_budgets(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n_called,
+                                              const int32_t *vertex_class, dg_dp_genotype_margin *levels, int32_t *best_values) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_genotype_margins_budgets(c, pins, n_pins, called, budgets, n_called, vertex_class, levels, best_values);
 }
 
 extern "C" int dg_dp_get_genotype_stats(dg_ctx *c, int64_t *out, int n) {

@@ -108,6 +108,8 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.genotype_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_margins)) return "--genotype-margins: this backend has no dp_genotype_margins";
     // and --genotype-table: the same pass lists every genotype
     if (!p.opt.genotype_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_table || !be.free_buf)) return "--genotype-table: this backend has no dp_genotype_table";
+    // and --budget-genotype-margins: the answers at the listed limits stay behind, one joint pass describes them all
+    if (!p.opt.budget_genotype_margins.empty() && (!be.dp_answer_paths || !be.dp_genotype_margins_budgets)) return "--budget-genotype-margins: this backend has no dp_genotype_margins_budgets";
     // and --pins: the same run under the file's cell constraints
     if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
     // and --pinned-genotype-margins / --pinned-genotype-table: the joint pass under the same constraints
@@ -511,6 +513,73 @@ std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const Ge
     return "";
 }
 
+// r and the columns of --genotype-margins: per listed limit r with an answer, in the order of the list, the levels 1 .. L - 2 with the
+// answer at r as the called cells and the alternative within r.  ONE device call serves every limit (dp_genotype_margins_budgets: the
+// joint pass at the largest of them).  A limit nobody fits is left out: it has no paths to call.  On every level the called cell must be
+// worth the run's DP value at r.
+std::string write_budget_genotype_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, const std::vector<int32_t> &budgets, const std::vector<ChainAnswer> &answers) {
+    const double t0 = now_s();
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    BudgetGenotypeMargins &bm = p.sum.budget_genotype_margins;
+    bm = BudgetGenotypeMargins();
+    bm.set = true;
+    std::vector<int32_t> called, limits, values;                     // [n][2][L], [n], the run's DP value at each
+    std::vector<int32_t> paths(2 * (size_t)L);
+    for (const int r : p.opt.budgets) {
+        const size_t q = (size_t)(std::find(budgets.begin(), budgets.end(), (int32_t)r) - budgets.begin());
+        if (q >= answers.size() || !answers[q].reachable()) continue;
+        if (be.dp_answer_paths(be.ctx, r, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+        if (paths[0] < 0) continue;
+        called.insert(called.end(), paths.begin(), paths.end());
+        limits.push_back(r);
+        values.push_back(answers[q].res.value);
+    }
+    const int64_t n = (int64_t)limits.size();
+    std::vector<dg_dp_genotype_margin> rec((size_t)n * (size_t)L);
+    std::vector<int32_t> best((size_t)n);
+    if (n > 0) {
+        if (be.dp_genotype_margins_budgets(be.ctx, nullptr, 0, called.data(), limits.data(), n, cls.data(), rec.data(), best.data()) != 0) return backend_error(be, "dp_genotype_margins_budgets");
+        int64_t stats[4] = {0, 0, 0, 0};
+        if (be.dp_genotype_stats && be.dp_genotype_stats(be.ctx, stats, 4) != 0) return backend_error(be, "dp_genotype_stats");
+        bm.segments = stats[0];
+    }
+    std::string text = "r\tlevel\tvertex1\tpanel_hap1\tsegment1\tvertex2\tpanel_hap2\tsegment2\tvalue\talt_vertex1\talt_segment1\talt_vertex2\talt_segment2\talt_value\tmargin\n";
+    for (int64_t q = 0; q < n; ++q) {
+        BudgetGenotypeMargins::Row row;
+        row.r = limits[(size_t)q];
+        if (best[(size_t)q] != values[(size_t)q])
+            return "--budget-genotype-margins: limit " + std::to_string(row.r) + ": the joint pass finds " + std::to_string(best[(size_t)q]) + ", the run's DP value is " + std::to_string(values[(size_t)q]);
+        for (int l = 0; l < L; ++l) {
+            const dg_dp_genotype_margin &r = rec[(size_t)q * (size_t)L + (size_t)l];
+            if (r.value != values[(size_t)q])
+                return "--budget-genotype-margins: limit " + std::to_string(row.r) + " level " + std::to_string(l) + ": the answer's cell is worth " + std::to_string(r.value) +
+                       ", the run's DP value is " + std::to_string(values[(size_t)q]);
+            if (l < 1 || l >= L - 1) continue;
+            text += std::to_string(row.r) + '\t' + std::to_string(l) + '\t' + std::to_string(r.vertex1) + '\t' + panel_name(p, g, r.vertex1) + '\t' + segment_name(p, g, r.vertex1) + '\t' +
+                    std::to_string(r.vertex2) + '\t' + panel_name(p, g, r.vertex2) + '\t' + segment_name(p, g, r.vertex2) + '\t' + std::to_string(r.value) + '\t';
+            if (r.alt_vertex1 >= 0) {
+                const int32_t margin = r.value - r.alt_value;
+                text += std::to_string(r.alt_vertex1) + '\t' + segment_name(p, g, r.alt_vertex1) + '\t' + std::to_string(r.alt_vertex2) + '\t' + segment_name(p, g, r.alt_vertex2) + '\t' +
+                        std::to_string(r.alt_value) + '\t' + std::to_string(margin);
+                row.with_alternative++;
+                if (margin == 0) row.margin0++;
+                else if (margin > 0 && (row.min_positive_margin < 0 || margin < row.min_positive_margin)) row.min_positive_margin = margin;
+            } else text += ".\t.\t.\t.\t.\t.";
+            text += '\n';
+        }
+        bm.rows.push_back(row);
+    }
+    const std::string &path = p.opt.budget_genotype_margins;
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open budget genotype margins file " + path;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + path + " failed";
+    bm.wall_s = now_s() - t0;
+    return "";
+}
+
 // level  vertex1  segment1  vertex2  segment2  value  delta  called: levels 1 .. L - 2, per level one row for every genotype that a pair
 // of paths within -R passes through, in ascending (class1, class2) of the allele classes; (vertex1, vertex2) its best cell, delta = the
 // DP value - value, called = 1 for the genotype of the answer's cell.  The header alone if no pair of paths fits -R
@@ -659,15 +728,15 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         }
     }
     const bool pinned_joint = !opt.pinned_genotype_margins.empty() || !opt.pinned_genotype_table.empty();
-    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table, known before the DP too
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : opt.genotype_margins.empty() ? "--genotype-table" : "--genotype-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : "--budget-genotype-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
-    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint) {  // all these tables speak of alleles
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty()) {  // all these tables speak of alleles
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
@@ -729,6 +798,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
             if (failed(write_genotype_table(*this, g, classes, gp, opt.genotype_table, sum.genotype_table), err)) return -1;
             stamp("genotype_table", t1);
         }
+    }
+    if (!opt.budget_genotype_margins.empty()) {                           // after --genotype-margins: that option alone is exactly what it was
+        t0 = now_s();
+        if (failed(write_budget_genotype_margins(*this, g, classes, budgets, answers), err)) return -1;
+        stamp("budget_genotype_margins", t0);
     }
     if (pinned_joint) {                                                   // the same under --pins: one pass serves both files
         t0 = now_s();

@@ -155,6 +155,11 @@ static int b_dp_genotype_table_pinned(void *c, const dg_dp_pin *pins, int64_t n_
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_genotype_table_pinned(x, pins, n_pins, budget, cls, called, n, levels, level_off, entries, n_entries, best) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_genotype_margins_budgets(void *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *cls,
+                                         dg_dp_genotype_margin *levels, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_genotype_margins_budgets(x, pins, n_pins, called, budgets, n, cls, levels, best) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_genotype_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_genotype_stats(x, out, n) : DG_ERR_NO_DEVICE;
@@ -275,6 +280,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --site-margins FILE   (MI355X build, -p2) per level and haplotype of the answer at -R: called vertex, best other allele, margin (TSV)\n");
     fprintf(fp, "    --wide-levels         (MI355X build) with --site-margins: lift its limit of 16384 cells (widest level x (R + 1)) by keeping the level state in device memory (then: widest level <= 32767, <= 16777216 cells)\n");
     fprintf(fp, "    --genotype-margins FILE   (MI355X build, -p2) per level: the genotype of the answer at -R against the best other genotype, both haplotypes free, and the margin (TSV)\n");
+    fprintf(fp, "    --budget-genotype-margins FILE   (MI355X build, -p2, with --budgets) the rows of --genotype-margins for the answer at every listed limit that has one, each against the best other genotype within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
     fprintf(fp, "    --genotype-table FILE     (MI355X build, -p2) per level one row for every genotype a pair of paths within -R passes through: its best cell, value, distance to the DP value, whether the answer has it (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
@@ -301,7 +307,7 @@ int main(int argc, char **argv) {
     std::vector<int> shard_devices;
     std::string budgets_arg;
     bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
-    bool have_pinned_margins = false, have_pinned_table = false;
+    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -325,6 +331,12 @@ int main(int argc, char **argv) {
                 have_genotype_margins = true;                          // (a missing value is an empty file name: refused below)
                 const char *v = val("--genotype-margins");
                 p.opt.genotype_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--budget-genotype-margins", 25) && (argv[i][25] == 0 || argv[i][25] == '=')) {
+                have_budget_margins = true;                            // (a missing value is an empty file name: refused below)
+                const char *v = val("--budget-genotype-margins");
+                p.opt.budget_genotype_margins = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--genotype-table", 16) && (argv[i][16] == 0 || argv[i][16] == '=')) {
@@ -400,6 +412,14 @@ int main(int argc, char **argv) {
     const bool sharded = n_gpus > 1 || shard_transport >= 0;
     if (n_gpus < 1 || n_gpus > 64) { fprintf(stderr, "[E::main] --gpus must be 1 .. 64\n"); return 1; }
     if (sharded && p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --gpus shards the diploid path (-p2)\n"); return 1; }
+    // --budget-genotype-margins FILE: checked here, before any device is asked for; it describes the answers of --budgets on the unconstrained DP
+    if (have_budget_margins) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --budget-genotype-margins describes the genotypes of the diploid route (-p2)\n"); return 1; }
+        if (!have_budgets) { fprintf(stderr, "[E::main] --budget-genotype-margins needs --budgets\n"); return 1; }
+        if (p.opt.budget_genotype_margins.empty()) { fprintf(stderr, "[E::main] --budget-genotype-margins needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --budget-genotype-margins does not go with --gpus / --shard-transport\n"); return 1; }
+        if (have_pins) { fprintf(stderr, "[E::main] --budget-genotype-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
+    }
     // --budgets all|a,b,c: checked here, before any device is asked for
     if (!p.opt.budget_table.empty() && !have_budgets) { fprintf(stderr, "[E::main] --budget-table needs --budgets\n"); return 1; }
     if (have_budgets) {
@@ -485,6 +505,7 @@ int main(int argc, char **argv) {
     p.be.dp_genotype_margins = b_dp_genotype_margins;
     p.be.dp_genotype_stats = b_dp_genotype_stats;
     p.be.dp_genotype_table = b_dp_genotype_table;
+    p.be.dp_genotype_margins_budgets = b_dp_genotype_margins_budgets;
     p.be.dp_genotype_margins_pinned = b_dp_genotype_margins_pinned;
     p.be.dp_genotype_table_pinned = b_dp_genotype_table_pinned;
     p.be.dp_run_pinned = b_dp_pinned;
@@ -571,6 +592,15 @@ int main(int argc, char **argv) {
                     fprintf(f, ", \"%sgenotype_table\": {\"entries\": %lld, \"levels_with_choice\": %lld, \"co_optimal_levels\": %lld, \"max_per_level\": %lld, \"wall_s\": %.6f}", pinned ? "pinned_" : "",
                             (long long)gt.entries, (long long)gt.levels_with_choice, (long long)gt.co_optimal_levels, (long long)gt.max_per_level, gt.wall_s);
                 }
+            }
+            if (p.sum.budget_genotype_margins.set) {                    // per listed limit with an answer the fields of genotype_margins; one device call
+                const dg::BudgetGenotypeMargins &bm = p.sum.budget_genotype_margins;
+                fprintf(f, ", \"budget_genotype_margins\": {\"budgets\": [");
+                for (size_t i = 0; i < bm.rows.size(); ++i) {
+                    fprintf(f, "%s{\"r\": %d, \"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", i ? ", " : "", bm.rows[i].r, (long long)bm.rows[i].with_alternative, (long long)bm.rows[i].margin0);
+                    if (bm.rows[i].min_positive_margin >= 0) fprintf(f, "%d}", bm.rows[i].min_positive_margin); else fprintf(f, "null}");
+                }
+                fprintf(f, "], \"segments\": %lld, \"wall_s\": %.6f}", (long long)bm.segments, bm.wall_s);
             }
             if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
                 fprintf(f, ", \"objectives\": [");

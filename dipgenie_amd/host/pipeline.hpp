@@ -92,6 +92,10 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
                                       dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value) = nullptr;
     int (*dp_genotype_table_pinned)(void *, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called, int64_t n_called,
                                     dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries, int64_t *n_entries, int32_t *best_value) = nullptr;
+    // optional (--budget-genotype-margins): the margin records of dp_genotype_margins for one called genotype per listed limit, each at
+    // its own budget, from one joint pass (dg_dp_genotype_margins_budgets)
+    int (*dp_genotype_margins_budgets)(void *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n_called, const int32_t *vertex_class,
+                                       dg_dp_genotype_margin *levels, int32_t *best_values) = nullptr;
 };
 
 // one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
@@ -121,6 +125,7 @@ struct Options {
     bool wide_levels = false;    // (ours) --wide-levels, with --site-margins: the backend keeps the level state of dp_call_margins in device memory where LDS cannot hold it
     std::string objective_table; // (ours) --objective-table: TSV of the surrogate and the distinct-colour objective of the answer at every listed budget (diploid)
     std::string genotype_margins; // (ours) --genotype-margins: TSV of the margin of the answer's genotype at -R against the best other genotype, per level, both haplotypes free (diploid)
+    std::string budget_genotype_margins; // (ours) --budget-genotype-margins, with --budgets: the rows of --genotype-margins for the answer at every listed limit that has one, behind a column r, from one joint pass (diploid)
     std::string genotype_table;  // (ours) --genotype-table: TSV with one row per genotype of every level: its best pair of paths against the answer at -R, both haplotypes free (diploid)
     std::string pins_file;       // (ours) --pins: the DP runs under the cell constraints of this file's rows (diploid); parsed into pin_rows before anything else runs
     std::vector<PinRow> pin_rows;
@@ -228,6 +233,14 @@ struct GenotypeMargins {      // --genotype-margins: over the levels 1 .. L - 2
     double wall_s = 0;
 };
 
+struct BudgetGenotypeMargins { // --budget-genotype-margins: per listed limit with an answer the fields of GenotypeMargins; one device call for all
+    bool set = false;
+    struct Row { int32_t r = 0; int64_t with_alternative = 0, margin0 = 0; int32_t min_positive_margin = -1; };
+    std::vector<Row> rows;
+    int64_t segments = 0;
+    double wall_s = 0;
+};
+
 struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
     bool set = false;
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
@@ -251,6 +264,7 @@ struct Summary {              // what tests and the CLI report
     SiteMargins site_margins;
     GenotypeMargins genotype_margins;
     GenotypeTable genotype_table;
+    BudgetGenotypeMargins budget_genotype_margins;
     GenotypeMargins pinned_genotype_margins;   // --pinned-genotype-margins: the same fields, of the DP under --pins
     GenotypeTable pinned_genotype_table;       // --pinned-genotype-table
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)

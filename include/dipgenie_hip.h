@@ -362,6 +362,28 @@ int dg_dp_genotype_margins_pinned(dg_ctx *, const dg_dp_pin *pins, int64_t n_pin
 int dg_dp_genotype_table_pinned(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins, int32_t budget, const int32_t *vertex_class, const int32_t *called,
                                 int64_t n_called, dg_dp_genotype_margin *levels, int64_t *level_off, dg_dp_genotype_entry **entries,
                                 int64_t *n_entries, int32_t *best_value);
+/* Genotype margins with one budget per query, from ONE joint pass.  F_l[i][j][r] and B_l[i][j][r] mean "at most r", so they do not
+ * depend on the budget a call is made with, and T^b_l[i][j] = max over r = 0..b of F_l[i][j][r] + B_l[i][j][b - r]: the states of one
+ * pass at bmax = the largest of budgets hold T^b for every b <= bmax.  Query q (called[q] = [2][n_levels], budgets[q]) is answered
+ * exactly as dg_dp_genotype_margins_pinned(pins, n_pins, called[q], 1, budgets[q], ...) answers it -- with n_pins = 0 (pins may be
+ * NULL) as dg_dp_genotype_margins does -- in every field of the record: the tie order of the alternative, NEG_INF / -1 where nothing
+ * is reachable, the better of the two orders of a cell under pins.  best_values (host) = [n_called], best_values[q] = V at budgets[q].
+ * Budgets may repeat and come in any order; a query whose budget no pair fits gets NEG_INF / -1 records beside its neighbours'
+ * answers, DG_OK.  Per-vertex joint marginals are not offered (they would be n_called * n_vertices words): the one-budget call keeps
+ * them.  Device: the schedule of dg_dp_genotype_margins once, with bmax + 1 planes (segments by joint_state_bytes at that size): the
+ * forward, recompute and backward recurrences, the score matrices and the pin masks are launched once; only the combination runs per
+ * distinct budget, in the same two launches per level (jt_combine_budgets_kernel: one more grid dimension over the distinct budgets,
+ * each workgroup serves the queries of its budget).  Beside that call's buffers: one row maximum per (distinct budget, position of
+ * the widest level) and bmax + 1 words for the sink's values; the scratch rows of T are shared among the budgets, not multiplied.
+ * Closing check per distinct budget b: the level maximum of T^b is V_b on every level, DG_ERR_STATE naming level and budget otherwise.
+ * Limits and errors are those of dg_dp_genotype_margins taken at bmax: DG_ERR_UNSUPPORTED for a widest level > 32767,
+ * bmax + 1 > 4096, n_called > 256; DG_ERR_ARG for a negative budget (the message names the first such query), n_called < 1, a null
+ * called, budgets, levels or best_values, an id outside its level (first (query, row, level) named), a bad pin as dg_dp_run_pinned
+ * refuses it; DG_ERR_STATE without a graph.  A failed call writes nothing.  Reads and writes nothing of a run, pinned or not.
+ * dg_dp_get_genotype_stats describes the call in its existing fields (entries and staging copies 0; pins and mask launches when pins
+ * are given).  Synchronises. */
+int dg_dp_genotype_margins_budgets(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n_called,
+                                   const int32_t *vertex_class, dg_dp_genotype_margin *levels, int32_t *best_values);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
