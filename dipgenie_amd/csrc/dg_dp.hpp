@@ -141,16 +141,25 @@ constexpr int PAIR_MAX_WIDTH = 255;                     // widths of both levels
 constexpr int PAIR_MAX_T = 2047;                        // in-edges into either level (11-bit score-delta rows)
 constexpr int PAIR_RCS[] = {1, 2, 4};                   // chunk sizes dp_sweep_pair_kernel is instantiated for
 constexpr int N_PAIR_RCS = (int)(sizeof PAIR_RCS / sizeof PAIR_RCS[0]);
+// Fan-in pairs (dp_sweep_pair_coop_kernel): the later level may hold BIG rows, vertices of composed in-degree PAIR_MAX_INDEG + 1 ..
+// PAIR_BIG_MAX_INDEG.  A big row has PAIR_BIG_MAX_INDEG wider records of its own (5-bit ranks) and a cooperative workgroup per
+// (slot block, chunk) whose four waves walk a quarter of them each; its PAIR_MAX_INDEG light records carry PAIR_ROW_BIG as in-degree.
+constexpr int PAIR_BIG_MAX_INDEG = 32;
+constexpr int PAIR_BIG_INLINE = 8;                      // big rows of a pair whose position rides in the kernel arguments (8 bits each)
+constexpr uint32_t PAIR_ROW_BIG = 15;                   // in-degree field of a light row record: the row is a big one
 struct PairDesc {                                       // pair of destination levels (l - 1, l); on the host and on the device (L2 prefetcher)
     int32_t l, nblocks;                                 // the later level; 64-slot blocks of composed column in-edges
     int32_t k0, k1, k2;                                 // widths of levels l - 2, l - 1, l
     int32_t dmax;                                       // largest composed in-degree among the vertices of level l
     int64_t row_first;                                  // first composed row record (PAIR_MAX_INDEG per vertex of level l)
     int64_t slot_first;                                 // first composed slot record
+    int32_t n_big, dmax_light;                          // big rows (0: a light pair, dp_sweep_pair_kernel); largest composed in-degree among the light rows
+    int64_t big_first;                                  // first entry of the big-row list (positions in level l, ascending); its records start at PAIR_BIG_MAX_INDEG * big_first
+    uint8_t big_in[PAIR_BIG_INLINE];                    // the pair's first big rows
 };
-struct PairHist {                                       // pair launches per chunk size, by index into PAIR_RCS
-    int64_t n[N_PAIR_RCS] = {};
-    void add(const PairHist &o, int64_t sign = 1) { for (int q = 0; q < N_PAIR_RCS; ++q) n[q] += sign * o.n[q]; }
+struct PairHist {                                       // pair launches per kernel: light pairs by index into PAIR_RCS, fan-in pairs N_PAIR_RCS further on
+    int64_t n[2 * N_PAIR_RCS] = {};
+    void add(const PairHist &o, int64_t sign = 1) { for (int q = 0; q < 2 * N_PAIR_RCS; ++q) n[q] += sign * o.n[q]; }
 };
 
 struct SweepHist {                                      // launches per variant, by SweepVariant::index()
@@ -189,6 +198,9 @@ struct DpOptions {
     int64_t partner_wide = 0;                           // partner_wide: the level state of dg_dp_best_partners / dg_dp_partner_marginals / dg_dp_call_margins in device memory: 0 never (LDS only), 1 for a call beyond the LDS limit, 2 always
     int64_t pair_levels = 1;                            // pair_levels: adjacent low-fan-in levels run as one composed launch (dg_dp_pairs.hip); next load
     int64_t pair_min = 4096;                            // pair_min: the composed tables are built and used only for a graph with at least this many pairs; next load
+    int64_t pair_fanin = 1;                             // pair_fanin: pairs whose later level has rows of composed in-degree 9..32 (big rows, dp_sweep_pair_coop_kernel); next load
+    int64_t pair_fanin_min = 4096;                      // pair_fanin_min: ... only on a graph that has at least this many of them; below, the pairs are chosen as with pair_fanin 0; next load
+    int64_t pair_fanin_max_big = 4, pair_fanin_max_indeg = PAIR_BIG_MAX_INDEG;     // pair_fanin_max_*: a fan-in pair has at most this many big rows / this largest composed in-degree; the gate measured on MHC-24: every big row adds four rows of workgroups, and from five big rows on a pair costs more than its two single launches (DESIGN s3.3); next load
     int64_t pair_digest = 0;                            // pair_digest: 1 = with digest 1 the pair launches stay, in the pair kernel's digest form (tests: the later level's digest; the earlier level's entry stays 0)
     int64_t test_force_pair_rc = 0;                     // test_force_pair_rc: n in PAIR_RCS = every pair launch takes chunks of n recombination counts; any other value: the cost model
     int64_t joint_state_bytes = (int64_t)8 << 30;       // joint_state_bytes: bound of the forward states of one segment of dg_dp_genotype_margins (a segment holds at least one level)
@@ -247,7 +259,7 @@ struct DpState {
     // level pairs: pair_at[l] = index of the pair whose later level is l, -2 for the earlier level of a pair, -1 otherwise (empty: no pairs)
     std::vector<PairDesc> pairs;
     std::vector<int32_t> pair_at;
-    DevBuf d_pairs, d_pair_at, d_prow, d_pslots;
+    DevBuf d_pairs, d_pair_at, d_prow, d_pslots, d_pbig, d_pbig_rows;   // d_pbig: the big rows' records (uint2), d_pbig_rows: their positions (int32)
     PairHist pair_hist;                                 // pair launches of the last run (dg_dp_get_pair_profile)
     DevBuf d_delta, d_bp, d_ring, d_digest, d_dblk_first, d_dtrans, d_grp, d_dead, d_heavy, d_rowrec, d_rowx, d_slots, d_ckpt, d_pfctl;
 #ifdef DG_SWEEP_PROBE
@@ -365,7 +377,7 @@ void sweep_prepare(const DpState &S, SweepLaunch &X);
 void sweep_init_state(const DpState &S, hipStream_t s);                  // level 0: every r starts at 0 (:534-535)
 int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s);
 int sweep_launch_pair(const DpState &S, SweepLaunch &X, int l, hipStream_t s);   // levels l - 1 and l (S.pair_at[l] >= 0) in one launch
-std::string pair_variant_name(int q);                                      // of PAIR_RCS[q], as rocprof prints the kernel
+std::string pair_variant_name(int q);                                      // of PairHist::n[q], as rocprof prints the kernel
 void sweep_warm_tables(const DpState &S, const SweepLaunch &X, int q0, int q1, hipStream_t s);
 int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool delta_resident, hipStream_t s);
 void sweep_prefetch_end(DpState &S, int le, hipStream_t s);

@@ -553,7 +553,7 @@ extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
 extern "C" int dg_dp_get_pair_profile(dg_ctx *c, char *buf, int cap) {
     if (!c || !c->dp || !buf || cap < 2) { dgi::set_error("dg_dp_get_pair_profile: no state"); return DG_ERR_STATE; }
     std::string out;
-    for (int q = 0; q < dgi::N_PAIR_RCS; ++q)
+    for (int q = 0; q < 2 * dgi::N_PAIR_RCS; ++q)
         if (const int64_t n = c->dp->pair_hist.n[q]) out += (out.empty() ? "" : " ") + dgi::pair_variant_name(q) + ':' + std::to_string(n);
     if ((int)out.size() + 1 > cap) { dgi::set_error("dg_dp_get_pair_profile: buffer too small (%zu needed)", out.size() + 1); return DG_ERR_ARG; }
     memcpy(buf, out.c_str(), out.size() + 1);
@@ -595,7 +595,8 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     // read by dg_dp_load_graph: in effect at the next load
     {"rowx", &DpO::use_rowx, 0, false}, {"lean_chain", &DpO::use_lean_chain, 0, false}, {"segment_cells", &DpO::segment_cells, 0, false},
     {"host_threads", &DpO::host_threads, 1, false}, {"host_tables", &DpO::host_tables, 0, false}, {"delta_cap_entries", &DpO::delta_cap_entries, 0, true},
-    {"pair_levels", &DpO::pair_levels, 0, false}, {"pair_min", &DpO::pair_min, 1, false},
+    {"pair_levels", &DpO::pair_levels, 0, false}, {"pair_min", &DpO::pair_min, 1, false}, {"pair_fanin", &DpO::pair_fanin, 0, false}, {"pair_fanin_min", &DpO::pair_fanin_min, 1, false},
+    {"pair_fanin_max_big", &DpO::pair_fanin_max_big, 0, false}, {"pair_fanin_max_indeg", &DpO::pair_fanin_max_indeg, 0, false},
     {"lattice_chunk_cells", &DpO::chunk_units_cfg, 1, false},   // 16-bit back-pointer units; below 1 is an error, else rounded up to even; empties the chunk pool at once
 };
 static int dp_option(dg_ctx *c, const char *what, const char *key, const int64_t *set, int64_t *get) {   // set or get, the other is null

@@ -526,25 +526,35 @@ __device__ __forceinline__ void merge_best_pair(int ov, uint32_t oo, uint32_t om
     bm = take ? om : bm;
 }
 
-// DG: empty -- the kernels the product runs, dp_sweep_pair_kernel<RC> -- or one trailing unsigned long long *digest (parity runs, options
-// digest + pair_digest): the head lane then also adds the oracle's term of every reachable cell of level l -- its predecessor is the
-// middle cell in bmid -- to digest[lvl]; level l - 1 is never materialised and keeps the 0 of the run's memset.
-template <int RC, typename... DG>
-__global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2,
-                                                            int nblocks, int rp_k, int pad_bytes, int dT1, int dT2, uint32_t buf_bytes,   // 16 dwords: preloaded
-                                                            int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl,
-                                                            DG... digest) {
-    constexpr bool DIGEST = sizeof...(DG) != 0;
-    publish_level(progress, lvl);
+// What a pair task needs before its stores (the pair kernels' leading scalars, as LevelHead is the fast kernels').
+struct PairHead {
+    const uint4 *pslots_l;              // the pair's composed slot records
+    const int32_t *cur;                 // padded start of the state buffer of level l - 2
+    const uint16_t *dm1, *dm2;          // score deltas of levels l - 1 and l (the zero slot where dT = 0)
+    int RP, k0, pad_bytes, dT1, dT2;
+    uint32_t buf_bytes;
+};
+
+// One wave's task of a pair launch: destination row i2, slot block g, planes r0 .. r0 + RC - 1.  recs: the row's records.
+// COOP: 0 = every row from its PAIR_MAX_INDEG light records (dp_sweep_pair_kernel); 1 = the same, big rows return (they are done by the
+// cooperative region of the same launch); 2 = cooperative, recs = the big row's PAIR_BIG_MAX_INDEG records: wave `part` of the workgroup
+// walks a quarter of the composed row in-edges -- at most PAIR_MAX_INDEG, one gather step, the depth of a light row --, waves 1..3 park
+// (value, ord, mid) per plane in LDS, wave 0 merges them and finishes the task.  No wave leaves before the barrier.
+// digest: null, or (DIGEST) the per-level accumulators.
+template <int RC, bool DIGEST, int COOP>
+__device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt,
+                                          int i2, int g, int r0, int lvl, unsigned long long *digest, int part = 0, uint4 *ex = nullptr) {
     const int lane = threadIdx.x & 63;
-    const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), r0 = (int)blockIdx.y * RC, i2 = (int)blockIdx.z;
-    const int RP = rp_k & 0x1FFF, k0 = rp_k >> 13;
-    if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
+    const int RP = H.RP, k0 = H.k0, pad_bytes = H.pad_bytes, dT1 = H.dT1, dT2 = H.dT2;
+    const uint16_t *dm1 = H.dm1, *dm2 = H.dm2;
+    constexpr int NREC = COOP == 2 ? PAIR_BIG_MAX_INDEG : PAIR_MAX_INDEG, RU1_SHIFT = COOP == 2 ? 27 : 25, RANK_MASK = COOP == 2 ? 31 : 7;
     // first load round: addresses from kernel arguments and the block index alone
-    const uint2 rec = prow_l[i2 * PAIR_MAX_INDEG + (lane & (PAIR_MAX_INDEG - 1))];   // composed row in-edge t in lanes t, t + 8, ...
-    const uint4 sl = pslots_l[g * 64 + lane];
-    const __amdgpu_buffer_rsrc_t cur_rsrc = state_rsrc(cur, buf_bytes);
-    const int du = __builtin_amdgcn_readfirstlane((int)(rec.x >> 25)) & 0xF;
+    const uint2 rec = recs[lane & (NREC - 1)];                          // composed row in-edge t in lanes t, t + NREC, ...
+    const uint4 sl = H.pslots_l[g * 64 + lane];
+    const __amdgpu_buffer_rsrc_t cur_rsrc = state_rsrc(H.cur, H.buf_bytes);
+    const int du = __builtin_amdgcn_readfirstlane((int)(rec.x >> 25)) & (COOP == 2 ? 0x3F : 0xF);
+    if (COOP == 1 && du > PAIR_MAX_INDEG) return;                       // (wave-uniform; no block barrier in the light region)
+    const int t_lo = COOP == 2 ? (du * part) >> 2 : 0, t_hi = COOP == 2 ? (du * (part + 1)) >> 2 : du;   // this wave's share of the composed row in-edges
     const int steps = __builtin_amdgcn_readfirstlane((int)(sl.z >> 16)) & 0xF;
     const bool act = sl.x != 0xFFFFFFFFu;
     const int j = (int)(sl.x & 0x7FFFu), wv = (int)((sl.x >> 15) & 1u) + (int)((sl.x >> 24) & 1u);
@@ -559,13 +569,13 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l,
     const int rowbytes = k0 * 4;
     // Source rows are r = r2 - w, w <= 4: rows -1 .. -4 land in the front padding (4 * max_k cells when pairs exist), a ragged last
     // chunk in the tail padding; the select discards both, so every load is issued unconditionally.
-    constexpr int U = RC >= 4 ? 4 : 8;
-    for (int t = 0; t < du; t += U) {
+    constexpr int U = COOP == 2 ? PAIR_MAX_INDEG : (RC >= 4 ? 4 : 8);
+    for (int t = t_lo; t < t_hi; t += U) {
         if (act) {
             int vals[U][RC], dl[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (t + u < du) {                                           // wave-uniform
+                if (t + u < t_hi) {                                         // wave-uniform
                     const uint32_t px = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, t + u), py = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, t + u);
                     const int iu = (int)(px & 0x7FFFu), w = (int)((px >> 15) & 1u) + (int)((px >> 24) & 1u) + wv;
                     const int off = ((iu * RP + (r0 - w)) * k0 + j) * 4 + pad_bytes;
@@ -576,13 +586,29 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l,
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (t + u < du) {
+                if (t + u < t_hi) {
                     const uint32_t px = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, t + u), py = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, t + u);
                     const int w = (int)((px >> 15) & 1u) + (int)((px >> 24) & 1u) + wv;
-                    const uint32_t ord = ((uint32_t)(BP_MAX_RANK - (int)((py >> 22) & 7u)) << 24) | ((uint32_t)(BP_MAX_RANK - (int)((py >> 25) & 7u)) << 8) | ordc;
+                    const uint32_t ord = ((uint32_t)(BP_MAX_RANK - (int)((py >> 22) & RANK_MASK)) << 24) | ((uint32_t)(BP_MAX_RANK - (int)((py >> RU1_SHIFT) & RANK_MASK)) << 8) | ordc;
                     const uint32_t mid = ((((px >> 16) & 0xFFu) << 16) | ((px >> 24) & 1u)) + lanemid;
                     relax_pair<RC>(vals[u], dl[u], ord, mid, r0, w, RP, bval, bord, bmid);
                 }
+            }
+        }
+    }
+    if (COOP == 2) {                                                    // partial bests of waves 1..3 -> wave 0
+        if (part > 0) {
+#pragma unroll
+            for (int q = 0; q < RC; ++q) ex[((part - 1) * RC + q) * 64 + lane] = make_uint4((uint32_t)bval[q], bord[q], bmid[q], 0u);
+        }
+        __syncthreads();
+        if (part > 0) return;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+#pragma unroll
+            for (int q = 0; q < RC; ++q) {
+                const uint4 o = ex[(p * RC + q) * 64 + lane];
+                merge_best_pair((int)o.x, o.y, o.z, true, bval[q], bord[q], bmid[q]);
             }
         }
     }
@@ -626,10 +652,55 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l,
             }
         }
     }
-    if constexpr (DIGEST) {
-        unsigned long long *const acc[] = {digest...};
-        if (dsum) atomicAdd(&acc[0][lvl], dsum);
+    if (DIGEST && dsum) atomicAdd(&digest[lvl], dsum);
+}
+
+// DG: empty -- the kernels the product runs, dp_sweep_pair_kernel<RC> -- or one trailing unsigned long long *digest (parity runs, options
+// digest + pair_digest): the head lane then also adds the oracle's term of every reachable cell of level l -- its predecessor is the
+// middle cell in bmid -- to digest[lvl]; level l - 1 is never materialised and keeps the 0 of the run's memset.
+template <int RC, typename... DG>
+__global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2,
+                                                            int nblocks, int rp_k, int pad_bytes, int dT1, int dT2, uint32_t buf_bytes,   // 16 dwords: preloaded
+                                                            int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl,
+                                                            DG... digest) {
+    constexpr bool DIGEST = sizeof...(DG) != 0;
+    publish_level(progress, lvl);
+    const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), r0 = (int)blockIdx.y * RC, i2 = (int)blockIdx.z;
+    if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
+    const PairHead H{pslots_l, cur, dm1, dm2, rp_k & 0x1FFF, rp_k >> 13, pad_bytes, dT1, dT2, buf_bytes};
+    unsigned long long *const acc[] = {nullptr, digest...};
+    pair_task<RC, DIGEST, 0>(H, prow_l + i2 * PAIR_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)]);
+}
+
+// The same for a fan-in pair: the later level holds n_big big rows (composed in-degree 9..32).  Workgroup z < 4 n_big = slot block
+// 4 x + (z & 3) of big row z >> 2, its four waves a quarter of the row's records each; the region is dispatched first, as in
+// dp_sweep_coop_kernel.  The rows beyond run the light task; a big row returns from it at once.  The first PAIR_BIG_INLINE big rows
+// ride in a preloaded scalar (8 bits each), later ones come from the pair's list.
+template <int RC, typename... DG>
+__global__ __launch_bounds__(256) void dp_sweep_pair_coop_kernel(const uint2 *prow_l, const uint4 *pslots_l, const uint2 *pbig_l, const int32_t *cur, const uint16_t *dm2,
+                                                                 unsigned long long big_in, int nblocks, int n_big, int rp_k, int dT2,        // 16 dwords: preloaded
+                                                                 const uint16_t *dm1, int dT1, int pad_bytes, uint32_t buf_bytes, const int32_t *__restrict__ big_rows,
+                                                                 int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl,
+                                                                 DG... digest) {
+    constexpr bool DIGEST = sizeof...(DG) != 0;
+    publish_level(progress, lvl);
+    const PairHead H{pslots_l, cur, dm1, dm2, rp_k & 0x1FFF, rp_k >> 13, pad_bytes, dT1, dT2, buf_bytes};
+    unsigned long long *const acc[] = {nullptr, digest...};
+    const int r0 = (int)blockIdx.y * RC;
+    const int zc = 4 * n_big;
+    if ((int)blockIdx.z < zc) {
+        __shared__ uint4 ex[3 * RC * 64];
+        const int hz = (int)blockIdx.z;
+        const int g = (int)blockIdx.x * 4 + (hz & 3);
+        if (g >= nblocks) return;                                       // workgroup-uniform: nobody is left at the barrier
+        const int h = hz >> 2;
+        const int i2 = h < PAIR_BIG_INLINE ? (int)((big_in >> (8 * h)) & 0xFFu) : big_rows[h];
+        pair_task<RC, DIGEST, 2>(H, pbig_l + h * PAIR_BIG_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)], (int)(threadIdx.x >> 6), ex);
+        return;
     }
+    const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), i2 = (int)blockIdx.z - zc;
+    if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
+    pair_task<RC, DIGEST, 1>(H, prow_l + i2 * PAIR_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)]);
 }
 
 // Sweep look-ahead: streams the graph tables (row records, slot records, in-edges, score deltas) of a batch of upcoming
@@ -683,7 +754,7 @@ __global__ void dp_pf_probe_wait_kernel(PfCtl *c, int token) {
 __global__ void dp_pf_probe_set_kernel(PfCtl *c, int token) { __hip_atomic_store(&c->probe, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__restrict__ descs, FastArgs F, PfCtl *ctl, int seq, int lb, int le, int ahead_near, int delta_resident, int far,
-                                                            const int32_t *__restrict__ pair_at, const PairDesc *__restrict__ pairs, const uint2 *__restrict__ prow, const uint4 *__restrict__ pslots) {
+                                                            const int32_t *__restrict__ pair_at, const PairDesc *__restrict__ pairs, const uint2 *__restrict__ prow, const uint4 *__restrict__ pslots, const uint2 *__restrict__ pbig) {
     __shared__ int dump[64];
     // a load whose data nobody wants: straight into an LDS dump word per lane (no destination register, nothing to wait for)
 #define DG_DROP_LOAD(PTR) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(PTR), (__attribute__((address_space(3))) void *)dump, 4, 0, 0)
@@ -730,6 +801,7 @@ __global__ __launch_bounds__(64) void dp_l2_prefetch_kernel(const LevelDesc *__r
             const PairDesc &p = pairs[pa];
             lines((const char *)(prow + p.row_first), 8LL * PAIR_MAX_INDEG * k2);
             lines((const char *)(pslots + p.slot_first), 1024LL * p.nblocks);
+            lines((const char *)(pbig + (long long)PAIR_BIG_MAX_INDEG * p.big_first), 8LL * PAIR_BIG_MAX_INDEG * p.n_big);
             if (delta_resident) {
                 const LevelDesc &d1 = descs[lp - 1];
                 if (d.delta_off >= 0 && (long long)T * T <= (128 << 10)) lines((const char *)(F.delta + d.delta_off), 2LL * T * T);
@@ -894,29 +966,31 @@ int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
     return DG_OK;
 }
 
-// the pair's chunk size by choose_rc's cost model: the wave's chain is the largest composed in-degree
+// the pair's chunk size by choose_rc's cost model: the wave's chain is the largest composed in-degree -- of a fan-in pair the largest among
+// the light rows or a quarter of the largest big row's, plus the LDS merge, and every big row adds four rows of workgroups
 static int choose_pair_rc(const DpState &S, const PairDesc &p) {
     for (int q = 0; q < N_PAIR_RCS; ++q) if (S.opt.test_force_pair_rc == PAIR_RCS[q]) return q;     // tests: this chunk size for every pair
     int best_q = 0;
     double best = 1e300;
+    const double rows = (double)p.k2 + 4.0 * p.n_big;
+    const double chain = p.n_big ? std::max((double)p.dmax_light, std::ceil(p.dmax / 4.0) + 1.0) : (double)p.dmax;
     for (int q = 0; q < N_PAIR_RCS; ++q) {
         const int rc = PAIR_RCS[q];
-        const double W = (double)p.k2 * p.nblocks * ((S.RP + rc - 1) / rc);
-        const double T = std::max(1.0, W / (double)S.opt.rc_cap) * ((double)S.opt.rc_t0_ns + (double)p.dmax * rc * (double)S.opt.rc_tg_ps * 1e-3) + W * (double)S.opt.rc_tw_ps * 1e-3;
+        const double W = rows * p.nblocks * ((S.RP + rc - 1) / rc);
+        const double T = std::max(1.0, W / (double)S.opt.rc_cap) * ((double)S.opt.rc_t0_ns + chain * rc * (double)S.opt.rc_tg_ps * 1e-3) + W * (double)S.opt.rc_tw_ps * 1e-3;
         if (T <= best) { best = T; best_q = q; }
     }
     return best_q;
 }
-std::string pair_variant_name(int q) { return "dp_sweep_pair_kernel<" + std::to_string(PAIR_RCS[q]) + ">"; }
+std::string pair_variant_name(int q) { return std::string(q < N_PAIR_RCS ? "dp_sweep_pair_kernel<" : "dp_sweep_pair_coop_kernel<") + std::to_string(PAIR_RCS[q % N_PAIR_RCS]) + ">"; }
 
-template <int Q = 0>
-static void launch_pair_rc(int q, dim3 grid, hipStream_t s, const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2, int nblocks, int rp_k,
-                           int pad_bytes, int dT1, int dT2, uint32_t buf_bytes, int32_t *nxt, uint16_t *bp1, uint16_t *bp2, int kk, int nt, int *progress, int lvl,
-                           unsigned long long *digest) {                // digest: null = the product's kernel
+// f(RC, DIGEST), each a std::integral_constant, for the run-time chunk index q and digest flag
+template <int Q = 0, class F>
+static void launch_pair_rc(int q, bool digest, F &f) {
     if constexpr (Q < N_PAIR_RCS) {
-        if (q != Q) launch_pair_rc<Q + 1>(q, grid, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl, digest);
-        else if (digest) hipLaunchKernelGGL((dp_sweep_pair_kernel<PAIR_RCS[Q], unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl, digest);
-        else hipLaunchKernelGGL((dp_sweep_pair_kernel<PAIR_RCS[Q]>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, lvl);
+        if (q != Q) return launch_pair_rc<Q + 1>(q, digest, f);
+        constexpr std::integral_constant<int, PAIR_RCS[Q]> RC{};
+        if (digest) f(RC, std::true_type{}); else f(RC, std::false_type{});
     }
 }
 
@@ -928,16 +1002,38 @@ int sweep_launch_pair(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
     const FastArgs &F = X.F;
     const int q = choose_pair_rc(S, p), rc = PAIR_RCS[q];
     const int nch = (S.RP + rc - 1) / rc;
-    const dim3 grid((unsigned)((p.nblocks + 3) / 4), (unsigned)nch, (unsigned)p.k2);
+    const dim3 grid((unsigned)((p.nblocks + 3) / 4), (unsigned)nch, (unsigned)(p.k2 + 4 * p.n_big));
     const int32_t *cur = (const int32_t *)(F.ring + (size_t)(DG_SLOT(l - 2) ^ X.flip) * F.slot_bytes);
     int32_t *nxt = (int32_t *)(F.ring + (size_t)(DG_SLOT(l - 1) ^ X.flip) * F.slot_bytes + F.pad_bytes);
     const int dT1 = d1.delta_off >= 0 ? d1.T : 0, dT2 = d2.delta_off >= 0 ? d2.T : 0;
     const uint16_t *dm1 = dT1 ? F.delta + d1.delta_off : F.delta_zero, *dm2 = dT2 ? F.delta + d2.delta_off : F.delta_zero;
     const int nt = (int64_t)d2.k2 * d2.k2 * S.RP >= S.opt.bp_nt_min_cells ? 1 : 0;
-    launch_pair_rc(q, grid, s, S.d_prow.as<uint2>() + p.row_first, S.d_pslots.as<uint4>() + p.slot_first, cur, dm1, dm2, p.nblocks, S.RP | (p.k0 << 13), F.pad_bytes, dT1, dT2,
-                   F.buf_bytes, nxt, F.bp ? F.bp + d1.bp_off : nullptr, F.bp ? F.bp + d2.bp_off : nullptr, p.k1 | (p.k2 << 8), nt, F.progress, l, X.digest ? F.digest : nullptr);
+    const uint2 *prow_l = S.d_prow.as<uint2>() + p.row_first;
+    const uint4 *pslots_l = S.d_pslots.as<uint4>() + p.slot_first;
+    const int rp_k = S.RP | (p.k0 << 13), kk = p.k1 | (p.k2 << 8), nblocks = p.nblocks, n_big = p.n_big, pad_bytes = F.pad_bytes;
+    const uint32_t buf_bytes = F.buf_bytes;
+    uint16_t *bp1 = F.bp ? F.bp + d1.bp_off : nullptr, *bp2 = F.bp ? F.bp + d2.bp_off : nullptr;
+    int *progress = F.progress;
+    unsigned long long *digest = F.digest;                              // (passed to the digest form only: the product's kernels take no such argument)
+    if (p.n_big == 0) {
+        auto light = [&](auto RC, auto DG) {
+            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l, digest);
+            else hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l);
+        };
+        launch_pair_rc(q, X.digest, light);
+    } else {
+        const uint2 *pbig_l = S.d_pbig.as<uint2>() + (size_t)PAIR_BIG_MAX_INDEG * (size_t)p.big_first;
+        const int32_t *big_rows = S.d_pbig_rows.as<int32_t>() + p.big_first;
+        unsigned long long big_in = 0;
+        for (int h = 0; h < PAIR_BIG_INLINE; ++h) big_in |= (unsigned long long)p.big_in[h] << (8 * h);
+        auto fanin = [&](auto RC, auto DG) {
+            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l, digest);
+            else hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l);
+        };
+        launch_pair_rc(q, X.digest, fanin);
+    }
     X.flip ^= 1;
-    X.pair_hist.n[q]++;
+    X.pair_hist.n[q + (p.n_big ? N_PAIR_RCS : 0)]++;
     return DG_OK;
 }
 
@@ -1004,7 +1100,7 @@ int sweep_prefetch_begin(DpState &S, const SweepLaunch &X, int lb, int le, bool 
     const int far = (int)S.opt.pf_far;
     hipLaunchKernelGGL(dp_l2_prefetch_kernel, dim3(PF_WORKGROUPS + (far > 0 ? PF_FAR_WORKGROUPS : 0)), dim3(64), 0, S.pf_stream, S.d_descs.as<LevelDesc>(), X.F,
                        S.d_pfctl.as<PfCtl>(), seq, lb, le, (int)S.opt.l2_prefetch, delta_resident ? 1 : 0, far,
-                       X.pairs_ok ? S.d_pair_at.as<int32_t>() : (const int32_t *)nullptr, S.d_pairs.as<PairDesc>(), S.d_prow.as<uint2>(), S.d_pslots.as<uint4>());
+                       X.pairs_ok ? S.d_pair_at.as<int32_t>() : (const int32_t *)nullptr, S.d_pairs.as<PairDesc>(), S.d_prow.as<uint2>(), S.d_pslots.as<uint4>(), S.d_pbig.as<uint2>());
     S.pf_active = true;
     return DG_OK;
 }

@@ -444,6 +444,10 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *   pair_levels 0|1       1 (default): adjacent low-fan-in levels run as one composed launch where the run allows it (unsegmented, all planes, digest 0,
  *                         fast 1, adaptive_rc 1, test_force_rc 0); 0: every level its own launch (next load)
  *   pair_min n            the composed tables are built and used only for a graph with at least n such pairs (default 4096; next load)
+ *   pair_fanin 0|1        1 (default): pairs whose later level has rows of composed in-degree 9..32 (big rows, walked by four waves each:
+ *                         dp_sweep_pair_coop_kernel) are chosen too, on a graph that has enough of them (pair_fanin_min); 0: never (next load)
+ *   pair_fanin_min n      ... only on a graph with at least n such pairs (default 4096); below, the pairs are exactly those of pair_fanin 0 (next load)
+ *   pair_fanin_max_big n, pair_fanin_max_indeg n   a fan-in pair has at most n big rows (default 4) / a largest composed in-degree of n (default and at most 32): the measured gate (next load)
  *   pair_digest 0|1       tests: 1 = with digest 1 the pair launches stay and run the pair kernel's digest form: the later level of a pair gets the
  *                         oracle's digest, the earlier level (never materialised) keeps 0; 0 (default): digest 1 refuses pair launches
  *   test_force_pair_rc n  tests: n one of the pair kernel's chunk sizes (1, 2, 4) = every pair launch takes it; any other value (default 0): the cost model
@@ -465,10 +469,12 @@ int dg_dp_get_launch_profile(dg_ctx *, char *buf, int cap);
  * ones for the chunk sizes that have them).  Needs no context.  DG_ERR_ARG: buf is null or too small. */
 int dg_dp_list_sweep_variants(char *buf, int cap);
 /* measurement: the level-pair launches of the last dg_dp_run (two adjacent low-fan-in levels composed into one launch, options
- * pair_levels / pair_min), as "dp_sweep_pair_kernel<rc>:count ...", empty if there were none.  dg_dp_get_launch_profile and
+ * pair_levels / pair_min), as "dp_sweep_pair_kernel<rc>:count ...", followed by the fan-in pairs (options pair_fanin / pair_fanin_min) as
+ * "dp_sweep_pair_coop_kernel<rc>:count ..."; empty if there were none.  dg_dp_get_launch_profile and
  * dg_dp_list_sweep_variants list the single-level launches only; dg_dp_timing::n_forward_launches counts both kinds. */
 int dg_dp_get_pair_profile(dg_ctx *, char *buf, int cap);
-/* parity: the names of every pair kernel the dispatch can launch, space-separated, in the order of the pair profile.  Needs no context. */
+/* parity: the names of every light pair kernel the dispatch can launch, space-separated, in the order of the pair profile (the fan-in form has
+ * dp_sweep_pair_coop_kernel<rc> for the same chunk sizes).  Needs no context. */
 int dg_dp_list_pair_variants(char *buf, int cap);
 
 /* ---- haploid (vertex, r) DP ---- */

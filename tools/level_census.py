@@ -34,9 +34,22 @@ comp = np.zeros(nV, np.int64); np.add.at(comp, g.out_dst, indeg[src])
 max_comp = np.zeros(L, np.int64); np.maximum.at(max_comp, lvl_of, comp)
 t_lvl = np.zeros(L, np.int64); np.add.at(t_lvl, lvl_of, indeg)
 lvl_ok = (min_in >= 1) & (max_in <= 64) & (width <= 255) & (t_lvl <= 2047)
-for limit in (4, 8, 16):
-    n_pairs, l = 0, 2
+n_big = np.zeros(L, np.int64); np.add.at(n_big, lvl_of, (comp > 8).astype(np.int64))
+for limit in (4, 8, 16, 32):
+    n_pairs, l, fanin = 0, 2, []
     while l < L:
-        if lvl_ok[l - 1] and lvl_ok[l] and max_comp[l] <= limit: n_pairs += 1; l += 2
+        if lvl_ok[l - 1] and lvl_ok[l] and max_comp[l] <= limit:
+            n_pairs += 1
+            if n_big[l]: fanin.append(l)
+            l += 2
         else: l += 1
-    print(f"level pairs, composed in-degree <= {limit}{' (the rule of pair_levels)' if limit == 8 else ''}: {n_pairs} = {100 * n_pairs / (L - 1):.1f} % of the launches")
+    rule = {8: " (the rule of pair_levels)", 32: " (the rule of pair_fanin: rows above 8 are big rows)"}.get(limit, "")
+    print(f"level pairs, composed in-degree <= {limit}{rule}: {n_pairs} = {100 * n_pairs / (L - 1):.1f} % of the launches; {L - 1 - n_pairs} launches in all")
+    if limit == 32 and fanin:
+        fanin = np.array(fanin)
+        print(f"  of them with a big row: {fanin.size}; big rows per pair p50 / p90 / p99 {np.percentile(n_big[fanin], [50, 90, 99]).astype(int).tolist()}, largest composed in-degree p50 / p90 {np.percentile(max_comp[fanin], [50, 90]).astype(int).tolist()}")
+        # the buckets of the measured gate (options pair_fanin_max_big / pair_fanin_max_indeg), greedy under the full rule: a narrower gate re-pairs the levels around the pairs it excludes
+        for lo_b, hi_b in ((1, 1), (2, 4), (5, 16), (17, 64), (65, 255)):
+            for lo_d, hi_d in ((9, 16), (17, 24), (25, 32)):
+                n = int(((n_big[fanin] >= lo_b) & (n_big[fanin] <= hi_b) & (max_comp[fanin] >= lo_d) & (max_comp[fanin] <= hi_d)).sum())
+                if n: print(f"    big rows {lo_b}..{hi_b}, largest composed in-degree {lo_d}..{hi_d}: {n} pairs")
