@@ -68,6 +68,10 @@ GENOTYPE_MARGIN = np.dtype([("vertex1", np.int32), ("vertex2", np.int32), ("valu
 # dg_dp_genotype_entry as a numpy record: one per (level, genotype) of Context.dp_genotype_table
 GENOTYPE_ENTRY = np.dtype([("class1", np.int32), ("class2", np.int32), ("vertex1", np.int32), ("vertex2", np.int32), ("value", np.int32), ("reserved", np.int32)])
 
+# dg_dp_phase_margin as a numpy record: one per pair of neighbouring het levels of Context.dp_phase_margins
+PHASE_MARGIN = np.dtype([("level_a", np.int32), ("level_b", np.int32), ("cis_value", np.int32), ("cis_vertex1", np.int32), ("cis_vertex2", np.int32),
+                         ("trans_value", np.int32), ("trans_vertex1", np.int32), ("trans_vertex2", np.int32), ("reserved", np.int32, (2,))])
+
 # dg_dp_pair_objective as a numpy record: what Context.dp_objective_paths and Context.dp_answer_objectives return
 PAIR_OBJECTIVE = np.dtype([("hom_shared", np.int32), ("hom_single", np.int32), ("het_single", np.int32), ("het_both", np.int32)])
 
@@ -96,7 +100,7 @@ SYMBOLS = [
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
     "dg_dp_run_pinned", "dg_dp_get_pin_stats", "dg_dp_genotype_margins_pinned", "dg_dp_genotype_table_pinned",
-    "dg_dp_genotype_margins_budgets",
+    "dg_dp_genotype_margins_budgets", "dg_dp_phase_margins", "dg_dp_get_phase_stats",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -126,6 +130,8 @@ lib.dg_dp_genotype_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void
 lib.dg_dp_get_genotype_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_genotype_margins_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_margins.argtypes[1:]
 lib.dg_dp_genotype_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_phase_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+lib.dg_dp_get_phase_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_genotype_table_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_table.argtypes[1:]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -627,6 +633,38 @@ class Context:
         out = np.zeros(8, np.int64)
         _check(lib.dg_dp_get_genotype_stats(self.h, out.ctypes.data, 8), "dg_dp_get_genotype_stats")
         return dict(pins=int(out[6]), mask_launches=int(out[7]))
+
+    def dp_phase_margins(self, called, budget, vertex_class=None):
+        """Phase margins: cis against trans for every pair of neighbouring het levels of one called pair.  called: int32
+        [2, n_levels], one cell per level, every id inside its level -- the two rows of dp_answer_paths are such a pair; budget >= 0;
+        vertex_class as for dp_genotype_margins.  A level is het where the classes of its two called vertices differ.  Returns
+        (records, best_value): a PHASE_MARGIN record array, one per pair of neighbouring het levels (level_a < level_b), ascending
+        (empty with fewer than two het levels), and the best value of any pair within the budget.  cis_value: the best value of any
+        ordered pair of paths within the budget that has the called ordered classes at both levels; trans_value: the same with the
+        classes at level_a swapped; cis_vertex1/2, trans_vertex1/2: the cells of level_a that attain them; NEG_INF and -1 where there
+        is none.  cis_value - trans_value is the phase margin of the two sites.  Leaves the last run's answers and what
+        dp_genotype_stats reports alone."""
+        p = np.ascontiguousarray(called, np.int32)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 2 or p.shape[0] != 2 or (g is not None and p.shape[1] != g.n_levels):
+            raise ValueError(f"called must have shape [2, n_levels], got {p.shape}")
+        cls = None
+        if vertex_class is not None:
+            cls = np.ascontiguousarray(vertex_class, np.int32)
+            if g is not None and cls.shape != (g.n_vertices,):
+                raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
+        records = np.zeros(max(p.shape[1] - 1, 1), PHASE_MARGIN)
+        n, best = C.c_int64(0), C.c_int32(0)
+        _check(lib.dg_dp_phase_margins(self.h, p.ctypes.data if p.size else None, int(budget), cls.ctypes.data if cls is not None else None, records.ctypes.data,
+                                       C.byref(n), C.byref(best)), "dg_dp_phase_margins")
+        return records[:n.value].copy(), best.value
+
+    def dp_phase_stats(self):
+        """of the last dp_phase_margins on this context: dict(het_levels, records, seeded_launches, readout_launches, segments,
+        peak_bytes)"""
+        out = np.zeros(6, np.int64)
+        _check(lib.dg_dp_get_phase_stats(self.h, out.ctypes.data, 6), "dg_dp_get_phase_stats")
+        return dict(zip(("het_levels", "records", "seeded_launches", "readout_launches", "segments", "peak_bytes"), out.tolist()))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

@@ -322,6 +322,9 @@ struct DpState {
     // (dg_dp_get_genotype_stats: segments, levels swept forward twice, peak bytes reserved, launches, table entries, staging copies, pins,
     // mask launches: the last two are 0 after an unpinned call) ----
     int64_t jt_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // dg_dp_phase_margins (dg_dp_joint.hip) likewise (dg_dp_get_phase_stats: het levels, records, backward launches on the seeded state,
+    // read-out launches, segments, peak bytes reserved)
+    int64_t ph_stats[6] = {0, 0, 0, 0, 0, 0};
     // ---- dg_dp_run_pinned (dg_dp_pins.hip): the call's pins sorted by level (uploaded once per call), whether the last run on the loaded
     // graph was a pinned one, and the statistics of the last pinned run (dg_dp_get_pin_stats: pins, pinned levels, mask launches, pairs
     // run as singles, batches issued plainly) ----
@@ -447,5 +450,8 @@ int dp_genotype_table(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_p
 int dp_genotype_margins_budgets(dg_ctx *c, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *vertex_class,
                                 dg_dp_genotype_margin *levels, int32_t *best_values);
 int dp_genotype_stats(dg_ctx *c, int64_t *out, int n);
+// phase margins: cis against trans for neighbouring het levels of one called pair, from the same pass with one more backward state
+int dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value);
+int dp_phase_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

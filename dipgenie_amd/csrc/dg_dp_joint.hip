@@ -39,6 +39,8 @@
 // dg_dp_genotype_margins_budgets answers every query at a budget of its own from the same pass run once at the largest budget: the
 // recurrences, score matrices and masks are launched once, jt_combine_budgets_kernel / jt_records_budgets_kernel (their comment has the
 // plan) take the places of jt_combine_kernel / jt_records_kernel.  The other entry points launch neither and reserve none of their buffers.
+// dg_dp_phase_margins (ph_call and the ph_* kernels, below jt_call: their comment has the plan) is the same schedule with a second rolling
+// backward state, seeded at every het level of the called pair; it launches none of the combination, record or table kernels.
 #include <algorithm>
 #include <cstring>
 
@@ -1032,7 +1034,294 @@ int jt_call(dg_ctx *c, const char *FN, const dg_dp_pin *pins, int64_t n_pins, co
     return DG_OK;
 }
 
+// ---- dg_dp_phase_margins: cis against trans for neighbouring het levels h_t < h_{t+1} of one called pair (include/dipgenie_hip.h has the
+// definition).  Beside B a second backward state S rolls down the levels: seeded at a het level e with B_e restricted to the cells of the
+// called ORDERED classes of e, carried down by jt_backward_kernel unchanged (launched a second time per level, on the score matrix the first
+// launch left in the call's buffer), read out at the next het level a below against F_a, then seeded again from B_a.  Both states mean "at
+// most r" and d is symmetric in the two haplotypes, so the one S answers both orders at a.  Every kernel is a gather as above: each word
+// has one owner, nothing depends on the order of lanes or workgroups; the classes of the level come as kernel arguments (the host has them):
+//   * ph_seed_kernel: grid (x blocks, k), row i = blockIdx.y: S[i][j][.] = B[i][j][.] where (cls i, cls j) = (c0, c1), NEG_INF elsewhere; a row
+//     of another class stores NEG_INF without a load of B;
+//   * ph_readout_kernel: one workgroup per row i.  The row's class is workgroup-uniform: a row of class c0 holds cells of the called order
+//     (its columns of class c1), a row of class c1 cells of the swapped order (its columns of class c0), any other row has nothing and its
+//     workgroup stores two empty keys and returns before a load of a state.  A lane takes a cell and walks r, as jt_combine_kernel does;
+//     part = [2][k] keys (value desc, i asc, j asc), [0] = cis, [1] = trans;
+//   * ph_finish_kernel: one workgroup reduces the two rows of keys to the record of the pair of sites, in a device array that is copied
+//     out once when the call ends.
+__global__ __launch_bounds__(JT_THREADS) void ph_seed_kernel(const int32_t *__restrict__ B, int32_t *__restrict__ S, int k, int B1, int b0, const int32_t *__restrict__ cls,
+                                                             int c0, int c1) {
+    const int i = (int)blockIdx.y;
+    const bool row = (cls ? cls[b0 + i] : b0 + i) == c0;                    // uniform per workgroup
+    const int n = k * B1;
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += (int)(gridDim.x * JT_THREADS)) {
+        const int j = x / B1;
+        const int64_t at = (int64_t)i * n + x;                              // ((i * k + j) * B1 + r)
+        int v = NEG_INF;
+        if (row && (cls ? cls[b0 + j] : b0 + j) == c1) v = B[at];
+        S[at] = v;
+    }
+}
+
+__global__ __launch_bounds__(JT_THREADS) void ph_readout_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ S, int k, int B1, int b0,
+                                                                const int32_t *__restrict__ cls, int c0, int c1, long long *__restrict__ part) {
+    __shared__ long long s_key[JT_THREADS / 64];
+    const int t = (int)threadIdx.x, i = (int)blockIdx.x;
+    const int ci = cls ? cls[b0 + i] : b0 + i;
+    if (ci != c0 && ci != c1) {                                             // uniform: no cell of either order in this row
+        if (t == 0) { part[i] = JT_NO_KEY; part[k + i] = JT_NO_KEY; }
+        return;
+    }
+    const int cj_want = ci == c0 ? c1 : c0;                                 // c0 != c1: the level is het
+    long long key = JT_NO_KEY;
+    for (int j = t; j < k; j += JT_THREADS) {
+        if ((cls ? cls[b0 + j] : b0 + j) != cj_want) continue;
+        const int32_t *f = F + ((int64_t)i * k + j) * B1, *sv = S + ((int64_t)i * k + j) * B1;
+        int best = NEG_INF;
+        for (int r = 0; r < B1; ++r) {
+            const int fv = f[r], bv = sv[B1 - 1 - r];
+            if (fv != NEG_INF && bv != NEG_INF) best = max(best, fv + bv);
+        }
+        if (best != NEG_INF) key = max(key, jt_key(best, i, j));
+    }
+    for (int d = 32; d; d >>= 1) key = max(key, __shfl_xor(key, d));
+    if ((t & 63) == 0) s_key[t >> 6] = key;
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) key = max(key, s_key[w]);
+        part[i] = ci == c0 ? key : JT_NO_KEY;
+        part[k + i] = ci == c0 ? JT_NO_KEY : key;
+    }
+}
+
+__global__ __launch_bounds__(JT_THREADS) void ph_finish_kernel(const long long *__restrict__ part, int k, int b0, int level_a, int level_b, dg_dp_phase_margin *__restrict__ rec) {
+    __shared__ long long s_key[2][JT_THREADS / 64];
+    const int t = (int)threadIdx.x;
+    long long cis = JT_NO_KEY, trans = JT_NO_KEY;
+    for (int i = t; i < k; i += JT_THREADS) { cis = max(cis, part[i]); trans = max(trans, part[k + i]); }
+    for (int d = 32; d; d >>= 1) { cis = max(cis, __shfl_xor(cis, d)); trans = max(trans, __shfl_xor(trans, d)); }
+    if ((t & 63) == 0) { s_key[0][t >> 6] = cis; s_key[1][t >> 6] = trans; }
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) { cis = max(cis, s_key[0][w]); trans = max(trans, s_key[1][w]); }
+        dg_dp_phase_margin r;
+        r.level_a = level_a; r.level_b = level_b;
+        r.cis_value = r.trans_value = NEG_INF;
+        r.cis_vertex1 = r.cis_vertex2 = r.trans_vertex1 = r.trans_vertex2 = -1;
+        if (cis != JT_NO_KEY) {
+            const uint32_t lo = (uint32_t)cis;
+            r.cis_vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+            r.cis_vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+            r.cis_value = (int)(cis >> 32);
+        }
+        if (trans != JT_NO_KEY) {
+            const uint32_t lo = (uint32_t)trans;
+            r.trans_vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+            r.trans_vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+            r.trans_value = (int)(trans >> 32);
+        }
+        r.reserved[0] = 0; r.reserved[1] = 0;
+        *rec = r;
+    }
+}
+
+// the schedule of jt_call (plan by joint_state_bytes, forward checkpoints, the segments from the last to the first, B rolling in two
+// states) with S beside B; none of that call's combination, record or table kernels, and nothing backward below the first het level
+int ph_call(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value) {
+    const char *FN = "dg_dp_phase_margins";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
+    DpState &S = *Sp;
+    if (!called || !records || !n_records || !best_value) { set_error("%s: called, records, n_records and best_value are required", FN); return DG_ERR_ARG; }
+    if (budget < 0) { set_error("%s: budget %d is negative", FN, budget); return DG_ERR_ARG; }
+    if ((int64_t)budget + 1 > JT_MAX_PLANES) { set_error("%s: budget + 1 = %lld exceeds %d planes", FN, (long long)budget + 1, JT_MAX_PLANES); return DG_ERR_UNSUPPORTED; }
+    const int L = S.L, nV = S.nV, B1 = budget + 1;
+    if (L < 2 || (int)S.descs.size() < L) { set_error("%s: the loaded graph has %d levels", FN, L); return DG_ERR_STATE; }
+    std::vector<JtLevel> lv((size_t)L);
+    int kmax = 1;
+    int64_t tmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const LevelDesc &d = S.descs[(size_t)std::max(l, 1)];
+        lv[l] = l ? JtLevel{d.b0, d.k2, d.in_base, d.T, d.delta_off >= 0, 0} : JtLevel{d.a0, d.k, 0u, 0, false, 0};
+        lv[l].cells = (int64_t)lv[l].k * lv[l].k * B1;
+        kmax = std::max(kmax, lv[l].k);
+        if (lv[l].coloured) tmax = std::max<int64_t>(tmax, lv[l].T);
+    }
+    if (kmax > JT_MAX_K) { set_error("%s: widest level %d exceeds %d", FN, kmax, JT_MAX_K); return DG_ERR_UNSUPPORTED; }
+    for (int row = 0; row < 2; ++row)
+        for (int l = 0; l < L; ++l) {
+            const int32_t v = called[(int64_t)row * L + l];
+            if ((uint32_t)(v - lv[l].a0) >= (uint32_t)lv[l].k) { set_error("%s: row %d level %d: vertex %d is not in its level", FN, row, l, v); return DG_ERR_ARG; }
+        }
+    // ---- the het levels, ascending, and the called ordered classes of every level ----
+    std::vector<int32_t> c0((size_t)L), c1((size_t)L);
+    std::vector<int> het;
+    for (int l = 0; l < L; ++l) {
+        c0[(size_t)l] = vertex_class ? vertex_class[called[l]] : called[l];
+        c1[(size_t)l] = vertex_class ? vertex_class[called[(int64_t)L + l]] : called[(int64_t)L + l];
+        if (c0[(size_t)l] != c1[(size_t)l]) het.push_back(l);
+    }
+    const int nh = (int)het.size(), nrec = std::max(nh - 1, 0);
+    const int h_first = nrec ? het.front() : L, h_last = nrec ? het.back() : L;        // fewer than two het levels: no backward state at all
+    hipStream_t s = c->stream;
+    // ---- the plan: segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
+    std::vector<int> seg{0};
+    {
+        int64_t in_seg = 0;
+        for (int l = 0; l < L; ++l) {
+            const int64_t bytes = 4 * lv[l].cells;
+            if (l > seg.back() && in_seg + bytes > S.opt.joint_state_bytes) { seg.push_back(l); in_seg = 0; }
+            in_seg += bytes;
+        }
+    }
+    const int n_seg = (int)seg.size();
+    seg.push_back(L);
+    std::vector<int64_t> ck_off((size_t)n_seg + 1, 0);                     // F of every segment's first level, int32 units
+    int64_t seg_cells = 1, roll_cells = 0, level_cells = 1;
+    for (int g = 0; g < n_seg; ++g) {
+        ck_off[g + 1] = ck_off[g] + lv[seg[g]].cells;
+        int64_t sum = 0;
+        for (int l = seg[g] + 1; l < seg[g + 1]; ++l) { sum += lv[l].cells; if (g + 1 < n_seg) roll_cells = std::max(roll_cells, lv[l].cells); }
+        seg_cells = std::max(seg_cells, sum);
+    }
+    for (int l = 0; l < L; ++l) level_cells = std::max(level_cells, lv[l].cells);
+    int64_t seeded = 0, readouts = 0;
+    JtMem M;
+    DevBuf d_cls, d_rec, d_V, d_part, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back, d_sback;
+    if (vertex_class) if (int rc = M.get(d_cls, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_rec, (int64_t)std::max(nrec, 1) * (int64_t)sizeof(dg_dp_phase_margin))) return rc;
+    if (int rc = M.get(d_V, 4)) return rc;
+    if (int rc = M.get(d_part, (int64_t)2 * kmax * 8)) return rc;
+    if (tmax) if (int rc = M.get(d_sc, tmax * tmax * 2)) return rc;
+    if (int rc = M.get(d_ck, ck_off[n_seg] * 4)) return rc;
+    if (vertex_class) DG_HIP(hipMemcpyAsync(d_cls.p, vertex_class, (size_t)nV * 4, hipMemcpyHostToDevice, s));
+    const int32_t *cls = vertex_class ? (const int32_t *)d_cls.as<int32_t>() : nullptr;
+    const LevelDesc *descs = S.d_descs.as<LevelDesc>();
+    const uint32_t *in_off = S.d_in_off.as<uint32_t>(), *in_edge = S.d_in_edge.as<uint32_t>();
+    const int32_t *in_dst = S.d_in_dst.as<int32_t>();
+    uint16_t *sc = d_sc.as<uint16_t>();
+    if (nrec) {                                                             // the in-edges grouped by source
+        if (int rc = M.get(d_oo, ((int64_t)nV + 1) * 4)) return rc;
+        if (int rc = M.get(d_ocur, (int64_t)nV * 4)) return rc;
+        if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
+        DG_HIP(hipMemsetAsync(d_ocur.p, 0, (size_t)nV * 4, s));
+        hipLaunchKernelGGL(jt_out_count_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>());
+        hipLaunchKernelGGL(jt_out_scan_kernel, dim3(1), dim3(1024), 0, s, d_ocur.as<uint32_t>(), d_oo.as<uint32_t>(), d_ocur.as<uint32_t>(), nV);
+        hipLaunchKernelGGL(jt_out_fill_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>(), d_oe.as<uint32_t>(), (uint32_t)S.n_edges);
+        DG_HIP(hipGetLastError());
+    }
+    auto scores = [&](int l) -> const uint16_t * {                          // the matrix of the transition into level l, in d_sc
+        const int T = lv[l].T;
+        if (!lv[l].coloured || T < 1) return nullptr;
+        hipLaunchKernelGGL(jt_scores_kernel, dim3(jt_blocks(T, 64), (unsigned)std::min(T, 16384)), dim3(JT_THREADS), 0, s, T, lv[l].in_base, lv[l - 1].a0, in_edge, in_dst,
+                           colour_csr(S), S.d_eflag.as<uint8_t>(), S.d_eself.as<uint16_t>(), sc);
+        return sc;
+    };
+    auto fill = [&](int32_t *st, int l, int pos) {                          // level l: 0 on every plane of the cell (pos, pos)
+        hipLaunchKernelGGL(jt_fill_kernel, dim3(jt_blocks(lv[l].cells, 65536)), dim3(JT_THREADS), 0, s, st, lv[l].cells, ((int64_t)pos * lv[l].k + pos) * B1, B1);
+    };
+    auto forward = [&](const int32_t *prev, int32_t *cur, int l) {
+        const uint16_t *m = scores(l);
+        hipLaunchKernelGGL(jt_forward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, prev, cur, lv[l - 1].k, lv[l].k, B1,
+                           lv[l].a0, lv[l].in_base, lv[l].T, in_off, in_edge, m);
+    };
+    auto backward = [&](const int32_t *next, int32_t *cur, int l, const uint16_t *m) {      // level l from level l + 1, whose scores are m
+        hipLaunchKernelGGL(jt_backward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, next, cur, lv[l].k, lv[l + 1].k, B1,
+                           lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base, lv[l + 1].T, d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
+    };
+    // ---- pass 1: the state at every segment's first level ----
+    int32_t *ck = d_ck.as<int32_t>();
+    fill(ck, 0, 0);
+    if (n_seg > 1) {
+        if (int rc = M.get(d_roll, 2 * roll_cells * 4)) return rc;
+        int32_t *roll = d_roll.as<int32_t>();
+        const int32_t *prev = ck;
+        int g = 0;
+        for (int l = 1; l <= seg[n_seg - 1]; ++l) {
+            int32_t *dst = l == seg[g + 1] ? ck + ck_off[++g] : roll + (l & 1) * roll_cells;
+            forward(prev, dst, l);
+            prev = dst;
+        }
+        DG_HIP(hipGetLastError());
+        DG_HIP(hipStreamSynchronize(s));                                    // the rolling states go before the segment buffers come
+        M.drop(d_roll);
+    }
+    // ---- the segments, last first, down to the one that holds the first het level ----
+    if (int rc = M.get(d_seg, seg_cells * 4)) return rc;
+    if (nrec) {
+        if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
+        if (int rc = M.get(d_sback, 2 * level_cells * 4)) return rc;
+    }
+    int32_t *back = d_back.as<int32_t>(), *sback = d_sback.as<int32_t>();
+    std::vector<const int32_t *> Fp((size_t)L, nullptr);
+    int t = nh - 1;                                                         // index of the next het level on the way down
+    for (int g = n_seg - 1; g >= 0; --g) {
+        const int a = seg[g], e = seg[g + 1];
+        if (e <= h_first && g < n_seg - 1) break;                           // nothing is read out below the first het level
+        Fp[a] = ck + ck_off[g];
+        int64_t at = 0;
+        for (int l = a + 1; l < e; ++l) {
+            int32_t *dst = d_seg.as<int32_t>() + at;
+            at += lv[l].cells;
+            forward(Fp[l - 1], dst, l);
+            Fp[l] = dst;
+        }
+        if (e == L) {
+            const int sink = nV - 1 - lv[L - 1].a0;
+            DG_HIP(hipMemcpyAsync(d_V.p, Fp[L - 1] + ((int64_t)sink * lv[L - 1].k + sink) * B1 + budget, 4, hipMemcpyDeviceToDevice, s));
+        }
+        for (int l = e - 1; l >= a && l >= h_first; --l) {
+            int32_t *cur = back + (l & 1) * level_cells, *scur = sback + (l & 1) * level_cells;
+            if (l == L - 1) fill(cur, l, nV - 1 - lv[l].a0);
+            else {
+                const uint16_t *m = scores(l + 1);
+                backward(back + ((l + 1) & 1) * level_cells, cur, l, m);
+                if (l < h_last) { backward(sback + ((l + 1) & 1) * level_cells, scur, l, m); ++seeded; }
+            }
+            if (t < 0 || l != het[(size_t)t]) continue;
+            if (t < nh - 1) {                                               // the record of (h_t, h_{t + 1})
+                hipLaunchKernelGGL(ph_readout_kernel, dim3((unsigned)lv[l].k), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)scur, lv[l].k, B1, lv[l].a0, cls, c0[(size_t)l], c1[(size_t)l],
+                                   d_part.as<long long>());
+                hipLaunchKernelGGL(ph_finish_kernel, dim3(1), dim3(JT_THREADS), 0, s, (const long long *)d_part.as<long long>(), lv[l].k, lv[l].a0, l, het[(size_t)t + 1],
+                                   d_rec.as<dg_dp_phase_margin>() + t);
+                ++readouts;
+            }
+            if (t > 0) hipLaunchKernelGGL(ph_seed_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, (const int32_t *)cur, scur, lv[l].k, B1,
+                                          lv[l].a0, cls, c0[(size_t)l], c1[(size_t)l]);
+            --t;
+        }
+        DG_HIP(hipGetLastError());
+    }
+    // the caller's arrays are written only if the call succeeds
+    std::vector<dg_dp_phase_margin> recs((size_t)nrec);
+    int32_t V = NEG_INF;
+    if (nrec) DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_phase_margin), hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(&V, d_V.p, 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipStreamSynchronize(s));
+    for (int q = 0; q < nrec; ++q)
+        if (std::max(recs[(size_t)q].cis_value, recs[(size_t)q].trans_value) > V) {
+            set_error("%s: record %d (levels %d, %d): cis %d, trans %d exceed the sink's value %d at budget %d", FN, q, recs[(size_t)q].level_a, recs[(size_t)q].level_b,
+                      recs[(size_t)q].cis_value, recs[(size_t)q].trans_value, V, budget);
+            return DG_ERR_STATE;
+        }
+    S.ph_stats[0] = nh; S.ph_stats[1] = nrec; S.ph_stats[2] = seeded; S.ph_stats[3] = readouts; S.ph_stats[4] = n_seg; S.ph_stats[5] = M.peak;
+    if (nrec) memcpy(records, recs.data(), recs.size() * sizeof(dg_dp_phase_margin));
+    *n_records = nrec;
+    *best_value = V;
+    return DG_OK;
+}
+
 }  // namespace
+
+int dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value) {
+    return ph_call(c, called, budget, vertex_class, records, n_records, best_value);
+}
+
+int dp_phase_stats(dg_ctx *c, int64_t *out, int n) {
+    if (!out || n < 6) { set_error("dg_dp_get_phase_stats: out needs 6 words"); return DG_ERR_ARG; }
+    if (!c->dp) { set_error("dg_dp_get_phase_stats: no graph loaded"); return DG_ERR_STATE; }
+    for (int q = 0; q < 6; ++q) out[q] = c->dp->ph_stats[q];
+    return DG_OK;
+}
 
 int dp_genotype_margins(dg_ctx *c, bool pinned, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, int64_t n, int32_t budget, const int32_t *vertex_class,
                         dg_dp_genotype_margin *levels, int32_t *vertex_values, int32_t *best_value) {
@@ -1094,4 +1383,15 @@ extern "C" int dg_dp_genotype_margins_budgets(dg_ctx *c, const dg_dp_pin *pins, 
 extern "C" int dg_dp_get_genotype_stats(dg_ctx *c, int64_t *out, int n) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_genotype_stats(c, out, n);
+}
+
+extern "C" int dg_dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records,
+                                   int32_t *best_value) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_phase_margins(c, called, budget, vertex_class, records, n_records, best_value);
+}
+
+extern "C" int dg_dp_get_phase_stats(dg_ctx *c, int64_t *out, int n) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_phase_stats(c, out, n);
 }

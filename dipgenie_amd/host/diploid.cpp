@@ -96,7 +96,7 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty() && p.opt.pins_file.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty() && p.opt.pins_file.empty() && p.opt.phase_margins.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
@@ -110,6 +110,8 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.genotype_table.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_genotype_table || !be.free_buf)) return "--genotype-table: this backend has no dp_genotype_table";
     // and --budget-genotype-margins: the answers at the listed limits stay behind, one joint pass describes them all
     if (!p.opt.budget_genotype_margins.empty() && (!be.dp_answer_paths || !be.dp_genotype_margins_budgets)) return "--budget-genotype-margins: this backend has no dp_genotype_margins_budgets";
+    // and --phase-margins: the called pair is the answer that stays behind
+    if (!p.opt.phase_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_phase_margins)) return "--phase-margins: this backend has no dp_phase_margins";
     // and --pins: the same run under the file's cell constraints
     if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
     // and --pinned-genotype-margins / --pinned-genotype-table: the joint pass under the same constraints
@@ -513,6 +515,63 @@ std::string write_genotype_margins(Pipeline &p, const ExpandedGraph &g, const Ge
     return "";
 }
 
+// level_a  level_b  vertex1_a  segment1_a  vertex2_a  segment2_a  vertex1_b  segment1_b  vertex2_b  segment2_b  cis_value  trans_value
+// trans_vertex1  trans_vertex2  margin: one row per pair of neighbouring het levels (the alleles of the answer's two vertices differ) of
+// the answer at -R, ascending.  cis: the best pair of paths within -R with the answer's ordered alleles at both levels -- the answer
+// itself is one, so it must be the run's DP value; trans: the best with the alleles at level_a swapped, and its cell there; '.' where no
+// such pair exists.  Without a pair of paths that fits -R, or with fewer than two het levels, the file holds the header alone.
+std::string write_phase_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls) {
+    const double t0 = now_s();
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    PhaseMargins &pm = p.sum.phase_margins;
+    pm = PhaseMargins();
+    pm.set = true;
+    std::vector<int32_t> paths(2 * (size_t)L, 0);
+    if (be.dp_answer_paths(be.ctx, p.opt.R, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+    std::vector<dg_dp_phase_margin> rec((size_t)std::max(L - 1, 1));
+    int64_t n = 0;
+    if (paths[0] >= 0) {
+        int32_t best = 0;
+        if (be.dp_phase_margins(be.ctx, paths.data(), p.opt.R, cls.data(), rec.data(), &n, &best) != 0) return backend_error(be, "dp_phase_margins");
+        int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+        if (be.dp_phase_stats && be.dp_phase_stats(be.ctx, stats, 6) != 0) return backend_error(be, "dp_phase_stats");
+        pm.het_levels = stats[0];
+        pm.segments = stats[4];
+        if (best != p.sum.dp_value) return "--phase-margins: the joint pass finds " + std::to_string(best) + ", the run's DP value is " + std::to_string(p.sum.dp_value);
+    }
+    std::string text = "level_a\tlevel_b\tvertex1_a\tsegment1_a\tvertex2_a\tsegment2_a\tvertex1_b\tsegment1_b\tvertex2_b\tsegment2_b\tcis_value\ttrans_value\ttrans_vertex1\ttrans_vertex2\tmargin\n";
+    for (int64_t q = 0; q < n; ++q) {
+        const dg_dp_phase_margin &r = rec[(size_t)q];
+        if (r.cis_value != p.sum.dp_value)
+            return "--phase-margins: levels " + std::to_string(r.level_a) + ", " + std::to_string(r.level_b) + ": the answer's phase is worth " + std::to_string(r.cis_value) + ", the run's DP value is " +
+                   std::to_string(p.sum.dp_value);
+        text += std::to_string(r.level_a) + '\t' + std::to_string(r.level_b);
+        for (const int l : {r.level_a, r.level_b})
+            for (int h = 0; h < 2; ++h) {
+                const int32_t v = paths[(size_t)h * L + l];
+                text += '\t' + std::to_string(v) + '\t' + segment_name(p, g, v);
+            }
+        text += '\t' + std::to_string(r.cis_value) + '\t';
+        if (r.trans_vertex1 >= 0) {
+            const int32_t margin = r.cis_value - r.trans_value;
+            text += std::to_string(r.trans_value) + '\t' + std::to_string(r.trans_vertex1) + '\t' + std::to_string(r.trans_vertex2) + '\t' + std::to_string(margin);
+            pm.with_alternative++;
+            if (margin == 0) pm.margin0++;
+            else if (margin > 0 && (pm.min_positive_margin < 0 || margin < pm.min_positive_margin)) pm.min_positive_margin = margin;
+        } else text += ".\t.\t.\t.";
+        text += '\n';
+    }
+    pm.records = n;
+    std::ofstream f(p.opt.phase_margins, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open phase margins file " + p.opt.phase_margins;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + p.opt.phase_margins + " failed";
+    pm.wall_s = now_s() - t0;
+    return "";
+}
+
 // r and the columns of --genotype-margins: per listed limit r with an answer, in the order of the list, the levels 1 .. L - 2 with the
 // answer at r as the called cells and the alternative within r.  ONE device call serves every limit (dp_genotype_margins_budgets: the
 // joint pass at the largest of them).  A limit nobody fits is left out: it has no paths to call.  On every level the called cell must be
@@ -728,15 +787,15 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         }
     }
     const bool pinned_joint = !opt.pinned_genotype_margins.empty() || !opt.pinned_genotype_table.empty();
-    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table, known before the DP too
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : "--budget-genotype-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : "--phase-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
-    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty()) {  // all these tables speak of alleles
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty()) {  // all these tables speak of alleles
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
@@ -803,6 +862,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         t0 = now_s();
         if (failed(write_budget_genotype_margins(*this, g, classes, budgets, answers), err)) return -1;
         stamp("budget_genotype_margins", t0);
+    }
+    if (!opt.phase_margins.empty()) {                                     // after the genotype options: each of them alone is exactly what it was
+        t0 = now_s();
+        if (failed(write_phase_margins(*this, g, classes), err)) return -1;
+        stamp("phase_margins", t0);
     }
     if (pinned_joint) {                                                   // the same under --pins: one pass serves both files
         t0 = now_s();

@@ -164,6 +164,14 @@ static int b_dp_genotype_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_genotype_stats(x, out, n) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_phase_margins(void *c, const int32_t *called, int32_t budget, const int32_t *cls, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_phase_margins(x, called, budget, cls, records, n_records, best) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_phase_stats(void *c, int64_t *out, int n) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_phase_stats(x, out, n) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_answer_objectives(x, budgets, n, out) : DG_ERR_NO_DEVICE;
@@ -282,6 +290,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --genotype-margins FILE   (MI355X build, -p2) per level: the genotype of the answer at -R against the best other genotype, both haplotypes free, and the margin (TSV)\n");
     fprintf(fp, "    --budget-genotype-margins FILE   (MI355X build, -p2, with --budgets) the rows of --genotype-margins for the answer at every listed limit that has one, each against the best other genotype within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
     fprintf(fp, "    --genotype-table FILE     (MI355X build, -p2) per level one row for every genotype a pair of paths within -R passes through: its best cell, value, distance to the DP value, whether the answer has it (TSV)\n");
+    fprintf(fp, "    --phase-margins FILE      (MI355X build, -p2) per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps the answer's phase between them (cis) against the best that switches it (trans), and the margin (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --pins FILE           (MI355X build, -p2) run the DP under cell constraints: rows level, vertex1, vertex2 [, require|forbid|require-ordered|forbid-ordered], tab-separated, . = any vertex, ids as --genotype-table prints them\n");
@@ -307,7 +316,7 @@ int main(int argc, char **argv) {
     std::vector<int> shard_devices;
     std::string budgets_arg;
     bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
-    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false;
+    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -337,6 +346,12 @@ int main(int argc, char **argv) {
                 have_budget_margins = true;                            // (a missing value is an empty file name: refused below)
                 const char *v = val("--budget-genotype-margins");
                 p.opt.budget_genotype_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--phase-margins", 15) && (argv[i][15] == 0 || argv[i][15] == '=')) {
+                have_phase_margins = true;                             // (a missing value is an empty file name: refused below)
+                const char *v = val("--phase-margins");
+                p.opt.phase_margins = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--genotype-table", 16) && (argv[i][16] == 0 || argv[i][16] == '=')) {
@@ -459,6 +474,13 @@ int main(int argc, char **argv) {
         if (p.opt.genotype_table.empty()) { fprintf(stderr, "[E::main] --genotype-table needs a file name\n"); return 1; }
         if (sharded) { fprintf(stderr, "[E::main] --genotype-table does not go with --gpus / --shard-transport\n"); return 1; }
     }
+    // --phase-margins FILE: the same; it describes the unconstrained DP (the library has no pinned form of the call)
+    if (have_phase_margins) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --phase-margins describes the phase of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.phase_margins.empty()) { fprintf(stderr, "[E::main] --phase-margins needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --phase-margins does not go with --gpus / --shard-transport\n"); return 1; }
+        if (have_pins) { fprintf(stderr, "[E::main] --phase-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
+    }
     // --objective-table FILE: the same
     if (have_objective_table) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
@@ -508,6 +530,8 @@ int main(int argc, char **argv) {
     p.be.dp_genotype_margins_budgets = b_dp_genotype_margins_budgets;
     p.be.dp_genotype_margins_pinned = b_dp_genotype_margins_pinned;
     p.be.dp_genotype_table_pinned = b_dp_genotype_table_pinned;
+    p.be.dp_phase_margins = b_dp_phase_margins;
+    p.be.dp_phase_stats = b_dp_phase_stats;
     p.be.dp_run_pinned = b_dp_pinned;
     p.be.dp_pin_stats = b_dp_pin_stats;
     p.be.free_buf = dg_free;
@@ -601,6 +625,13 @@ int main(int argc, char **argv) {
                     if (bm.rows[i].min_positive_margin >= 0) fprintf(f, "%d}", bm.rows[i].min_positive_margin); else fprintf(f, "null}");
                 }
                 fprintf(f, "], \"segments\": %lld, \"wall_s\": %.6f}", (long long)bm.segments, bm.wall_s);
+            }
+            if (p.sum.phase_margins.set) {                              // a recount of FILE: with_alternative = rows with a reachable trans; min_positive_margin null: none is positive
+                const dg::PhaseMargins &pm = p.sum.phase_margins;
+                fprintf(f, ", \"phase_margins\": {\"het_levels\": %lld, \"records\": %lld, \"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", (long long)pm.het_levels,
+                        (long long)pm.records, (long long)pm.with_alternative, (long long)pm.margin0);
+                if (pm.min_positive_margin >= 0) fprintf(f, "%d", pm.min_positive_margin); else fprintf(f, "null");
+                fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)pm.segments, pm.wall_s);
             }
             if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
                 fprintf(f, ", \"objectives\": [");

@@ -96,6 +96,10 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // its own budget, from one joint pass (dg_dp_genotype_margins_budgets)
     int (*dp_genotype_margins_budgets)(void *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n_called, const int32_t *vertex_class,
                                        dg_dp_genotype_margin *levels, int32_t *best_values) = nullptr;
+    // optional (--phase-margins): cis against trans for every pair of neighbouring het levels of one called pair (dg_dp_phase_margins),
+    // and that call's statistics (dg_dp_get_phase_stats)
+    int (*dp_phase_margins)(void *, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value) = nullptr;
+    int (*dp_phase_stats)(void *, int64_t *out, int n) = nullptr;
 };
 
 // one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
@@ -131,6 +135,7 @@ struct Options {
     std::vector<PinRow> pin_rows;
     std::string pinned_genotype_margins; // (ours) --pinned-genotype-margins, with --pins: the file of --genotype-margins for the DP under the pins, the called cells those of the pinned answer at -R
     std::string pinned_genotype_table;   // (ours) --pinned-genotype-table, with --pins: the file of --genotype-table for the DP under the pins
+    std::string phase_margins;   // (ours) --phase-margins: TSV with one row per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps its phase against the best that switches it (diploid)
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -241,6 +246,13 @@ struct BudgetGenotypeMargins { // --budget-genotype-margins: per listed limit wi
     double wall_s = 0;
 };
 
+struct PhaseMargins {         // --phase-margins: over the pairs of neighbouring het levels of the answer at -R
+    bool set = false;
+    int64_t het_levels = 0, records = 0, with_alternative = 0, margin0 = 0, segments = 0;   // with_alternative: records whose trans is reachable
+    int32_t min_positive_margin = -1;            // -1: no record with a positive margin
+    double wall_s = 0;
+};
+
 struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
     bool set = false;
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
@@ -267,6 +279,7 @@ struct Summary {              // what tests and the CLI report
     BudgetGenotypeMargins budget_genotype_margins;
     GenotypeMargins pinned_genotype_margins;   // --pinned-genotype-margins: the same fields, of the DP under --pins
     GenotypeTable pinned_genotype_table;       // --pinned-genotype-table
+    PhaseMargins phase_margins;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
     PinSummary pins;

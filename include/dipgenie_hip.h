@@ -384,6 +384,48 @@ int dg_dp_genotype_table_pinned(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins,
  * are given).  Synchronises. */
 int dg_dp_genotype_margins_budgets(dg_ctx *, const dg_dp_pin *pins, int64_t n_pins, const int32_t *called, const int32_t *budgets, int64_t n_called,
                                    const int32_t *vertex_class, dg_dp_genotype_margin *levels, int32_t *best_values);
+/* Phase margins: cis against trans for neighbouring heterozygous sites of a called pair of cells per level.  d, F, B, "reachable",
+ * budget and vertex_class are those of dg_dp_genotype_margins.  called (host) = [2][n_levels] vertex ids, one cell per level, every id
+ * inside its level; c_h[l] = the class of called[h][l].  The het levels are those with c_0[l] != c_1[l], ascending:
+ * h_0 < ... < h_{m-1}.  For a neighbouring pair (a, e) = (h_t, h_{t+1}) and an ordered pair of classes X at a, W(X) = the largest value
+ * of any ORDERED pair (p, q) of source -> sink paths with r(p) + r(q) <= b, (cls p[a], cls q[a]) = X and
+ * (cls p[e], cls q[e]) = (c_0[e], c_1[e]); NEG_INF if there is none.  cis = W(c_0[a], c_1[a]), trans = W(c_1[a], c_0[a]);
+ * cis - trans is the phase margin of the two sites: what the answer loses by switching the phase between them.  By the symmetry of d,
+ * trans is also the value of the pairs that keep the called order at a and swap it at e.  Recurrence, over l = e - 1 .. a:
+ * S_e[i][j][r] = B_e[i][j][r] where (cls i, cls j) = (c_0[e], c_1[e]), NEG_INF elsewhere; S_l from S_{l+1} by the backward recurrence,
+ * unchanged; U_a[i][j] = max over r = 0..b with both reachable of F_a[i][j][r] + S_a[i][j][b - r]; cis = the maximum of U_a over the
+ * cells of classes (c_0[a], c_1[a]), trans over those of classes (c_1[a], c_0[a]); after the read-out S_a is seeded again from B_a with
+ * the called ordered classes of a.  So one more rolling backward state answers every neighbouring pair in the same pass. */
+typedef struct dg_dp_phase_margin {
+    int32_t level_a, level_b;             /* the two neighbouring het levels, level_a < level_b */
+    int32_t cis_value;                    /* W of the called order at level_a; NEG_INF if nothing is reachable */
+    int32_t cis_vertex1, cis_vertex2;     /* the cell of level_a (haplotype 1, haplotype 2) that attains it; among equals the smallest position of vertex1, then of vertex2; -1, -1 if there is none */
+    int32_t trans_value;                  /* W of the swapped order at level_a; NEG_INF if nothing is reachable */
+    int32_t trans_vertex1, trans_vertex2; /* its cell, ties as above; -1, -1 if there is none */
+    int32_t reserved[2];                  /* written as 0 */
+} dg_dp_phase_margin;
+/* records (host) has room for n_levels - 1 entries; the call writes *n_records = m - 1 of them (0 when m < 2: DG_OK), ascending by
+ * level, and *best_value = V_b.  A budget that no pair fits is an answer: NEG_INF / -1 in every record, DG_OK.  The call checks that
+ * max(cis, trans) <= V_b in every record, DG_ERR_STATE naming the record otherwise.  Not checked, but true: if called is a pair of
+ * real paths with r1 + r2 <= b, cis >= its score (dg_dp_score_paths); if called is an optimal pair at b, cis = V_b in every record.
+ * Device: the schedule of dg_dp_genotype_margins (segments by option joint_state_bytes, forward checkpoints, the segments from the last
+ * to the first, B rolling in two states) with two more states of the widest level for S, reserved by this call only.  From the level
+ * below h_{m-1} down to h_0 the backward kernel runs a second time per level, on S, with the score matrix the first launch used;
+ * below h_0 nothing backward is launched.  At every het level but the last a read-out kernel forms U on the rows of the two called
+ * classes and a one-workgroup finish writes the record on the device; at every het level but the first a seed kernel writes S from B
+ * under the class mask.  The records are copied out once, at the end.  The combination, record and table kernels of the other entry
+ * points are not launched.  Limits and errors are those of dg_dp_genotype_margins with n_called = 1: DG_ERR_STATE without a graph;
+ * DG_ERR_ARG for a null called, records, n_records or best_value, a negative budget, an id outside its level (the message names the
+ * first such (row 0|1, level)); DG_ERR_UNSUPPORTED for a widest level > 32767 or budget + 1 > 4096.  Needs dg_dp_load_graph only, reads
+ * and writes nothing of a run, and leaves what dg_dp_get_genotype_stats reports as it was.  A failed call writes nothing.  Synchronises.
+ * There is no pinned variant: pins are ordered, and the single seeded state rests on the symmetry of the unpinned DP in its two
+ * haplotypes (trans read off the same S as cis); under ordered pins the two orders would need a state each. */
+int dg_dp_phase_margins(dg_ctx *, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records,
+                        int64_t *n_records, int32_t *best_value);
+/* measurement: the last successful dg_dp_phase_margins on this context: out[0] = het levels, out[1] = records, out[2] = backward
+ * launches on the seeded state S, out[3] = read-out launches, out[4] = segments, out[5] = peak bytes of device memory the call had
+ * reserved; n >= 6 (zeros before the first call).  DG_ERR_ARG: null out or n < 6.  DG_ERR_STATE: no DP state on this context yet. */
+int dg_dp_get_phase_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
