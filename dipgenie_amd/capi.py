@@ -100,7 +100,7 @@ SYMBOLS = [
     "dg_dp_objective_paths", "dg_dp_answer_objectives", "dg_dp_get_partner_route", "dg_dp_get_pair_profile", "dg_dp_list_pair_variants",
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
     "dg_dp_run_pinned", "dg_dp_get_pin_stats", "dg_dp_genotype_margins_pinned", "dg_dp_genotype_table_pinned",
-    "dg_dp_genotype_margins_budgets", "dg_dp_phase_margins", "dg_dp_get_phase_stats",
+    "dg_dp_genotype_margins_budgets", "dg_dp_phase_margins", "dg_dp_get_phase_stats", "dg_dp_phase_margins_budgets", "dg_dp_get_phase_budget_stats",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -132,6 +132,8 @@ lib.dg_dp_genotype_margins_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 lib.dg_dp_genotype_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_phase_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
 lib.dg_dp_get_phase_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+lib.dg_dp_phase_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_get_phase_budget_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_genotype_table_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_table.argtypes[1:]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -665,6 +667,42 @@ class Context:
         out = np.zeros(6, np.int64)
         _check(lib.dg_dp_get_phase_stats(self.h, out.ctypes.data, 6), "dg_dp_get_phase_stats")
         return dict(zip(("het_levels", "records", "seeded_launches", "readout_launches", "segments", "peak_bytes"), out.tolist()))
+
+    def dp_phase_margins_budgets(self, called, budgets, vertex_class=None):
+        """dp_phase_margins for many called pairs, each at a budget of its own, from one joint pass at the largest of them.  called:
+        int32 [n, 2, n_levels]; budgets: n integers >= 0, in any order, repeats allowed; vertex_class as for dp_genotype_margins.
+        Returns (records, best_values): a list of n PHASE_MARGIN record arrays, query q exactly what dp_phase_margins(called[q],
+        budgets[q], vertex_class) answers (empty with fewer than two het levels), and int32 [n]: the best value of any pair within
+        budgets[q].  Queries whose seeded states coincide -- the same ordered classes at the same het level -- share them on the
+        device.  At most 256 queries.  Leaves the last run's answers and what dp_phase_stats / dp_genotype_stats report alone."""
+        p = np.ascontiguousarray(called, np.int32)
+        b = np.ascontiguousarray(budgets, np.int32)
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+            raise ValueError(f"called must have shape [n, 2, n_levels], got {p.shape}")
+        if b.shape != (p.shape[0],):
+            raise ValueError(f"budgets must have shape [{p.shape[0]}], got {b.shape}")
+        cls = None
+        if vertex_class is not None:
+            cls = np.ascontiguousarray(vertex_class, np.int32)
+            if g is not None and cls.shape != (g.n_vertices,):
+                raise ValueError(f"vertex_class must have shape [{g.n_vertices}], got {cls.shape}")
+        n = p.shape[0]
+        records = np.zeros(max(n * max(p.shape[2] - 1, 0), 1), PHASE_MARGIN)
+        off = np.zeros(n + 1, np.int64)
+        best = np.zeros(n, np.int32)
+        _check(lib.dg_dp_phase_margins_budgets(self.h, p.ctypes.data if p.size else None, b.ctypes.data if b.size else None, n, cls.ctypes.data if cls is not None else None,
+                                               records.ctypes.data, off.ctypes.data, best.ctypes.data if best.size else None), "dg_dp_phase_margins_budgets")
+        return [records[off[q]:off[q + 1]].copy() for q in range(n)], best
+
+    PHASE_BUDGET_STATS = ("queries", "records", "seed_keys", "slot_levels", "backward_launches", "readout_launches", "max_live_slots", "slots_allocated", "segments", "peak_bytes")
+
+    def dp_phase_budget_stats(self):
+        """of the last dp_phase_margins_budgets on this context: dict(queries, records, seed_keys, slot_levels, backward_launches,
+        readout_launches, max_live_slots, slots_allocated, segments, peak_bytes)"""
+        out = np.zeros(10, np.int64)
+        _check(lib.dg_dp_get_phase_budget_stats(self.h, out.ctypes.data, 10), "dg_dp_get_phase_budget_stats")
+        return dict(zip(self.PHASE_BUDGET_STATS, out.tolist()))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

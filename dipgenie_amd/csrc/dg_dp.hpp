@@ -325,6 +325,9 @@ struct DpState {
     // dg_dp_phase_margins (dg_dp_joint.hip) likewise (dg_dp_get_phase_stats: het levels, records, backward launches on the seeded state,
     // read-out launches, segments, peak bytes reserved)
     int64_t ph_stats[6] = {0, 0, 0, 0, 0, 0};
+    // dg_dp_phase_margins_budgets likewise (dg_dp_get_phase_budget_stats: queries, records, seed keys created, slot-levels, backward launches
+    // on the slots, read-out launches, largest number of live slots, slots allocated, segments, peak bytes reserved)
+    int64_t phb_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // ---- dg_dp_run_pinned (dg_dp_pins.hip): the call's pins sorted by level (uploaded once per call), whether the last run on the loaded
     // graph was a pinned one, and the statistics of the last pinned run (dg_dp_get_pin_stats: pins, pinned levels, mask launches, pairs
     // run as singles, batches issued plainly) ----
@@ -453,5 +456,9 @@ int dp_genotype_stats(dg_ctx *c, int64_t *out, int n);
 // phase margins: cis against trans for neighbouring het levels of one called pair, from the same pass with one more backward state
 int dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value);
 int dp_phase_stats(dg_ctx *c, int64_t *out, int n);
+// the same for many called pairs, each at a budget of its own, from one pass at the largest: a pool of seeded states, one per live seed key
+int dp_phase_margins_budgets(dg_ctx *c, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *record_off,
+                             int32_t *best_values);
+int dp_phase_budget_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

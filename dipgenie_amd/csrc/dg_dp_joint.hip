@@ -41,8 +41,12 @@
 // plan) take the places of jt_combine_kernel / jt_records_kernel.  The other entry points launch neither and reserve none of their buffers.
 // dg_dp_phase_margins (ph_call and the ph_* kernels, below jt_call: their comment has the plan) is the same schedule with a second rolling
 // backward state, seeded at every het level of the called pair; it launches none of the combination, record or table kernels.
+// dg_dp_phase_margins_budgets (phb_call and the phb_* kernels, below ph_call: their comment has the plan) is that schedule once at the
+// largest budget for many called pairs, with a pool of seeded states, one per live seed key, planned on the host before the first launch.
 #include <algorithm>
 #include <cstring>
+#include <functional>
+#include <map>
 
 #include "dg_dp_setops.hpp"
 
@@ -1310,6 +1314,418 @@ int ph_call(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *ver
     return DG_OK;
 }
 
+// ---- dg_dp_phase_margins_budgets: many called pairs, each at a budget of its own, from one pass at B1 = bmax + 1 (F, B and S mean "at most
+// r": planes 0..b are the states of a call at budget b).  Between a het level e and the next one below it S depends only on its seed key
+// (e, c0[e], c1[e]) and on B, not on the query, so the one S of ph_call becomes a pool of slots, one per live key; the host plans the slots
+// before the first launch (phb_call) and the kernels below are ph_call's with one more grid dimension and the slot, classes and budget from a
+// table that is uploaded once.  A slot is two rolling states of the widest level: state (slot, parity of the level).  Gathers as above: every
+// word has one owner lane (a slot belongs to one key, a read-out to one query), no atomics, nothing depends on the order of workgroups.
+//   * phb_backward_kernel: grid (x blocks, k, live slots of the level): jt_backward_kernel's recurrence on the slot slots[blockIdx.z];
+//   * phb_seed_kernel: grid (x blocks, k, keys created at the level): ph_seed_kernel on the slot and classes of seeds[blockIdx.z];
+//   * phb_readout_kernel: grid (k, read-outs of the level): ph_readout_kernel on the slot, classes and budget b of reads[blockIdx.y], with
+//     U = max over r = 0..b of F[r] + S[b - r]; part = [read-outs][2][k] keys;
+//   * phb_finish_kernel: one workgroup per read-out writes the record reads[blockIdx.x].rec.
+struct PhbSeed { int32_t slot, c0, c1; };
+struct PhbRead { int32_t slot, c0, c1, budget, rec, level_b; };
+
+__global__ __launch_bounds__(JT_THREADS) void phb_backward_kernel(int32_t *__restrict__ pool, int64_t state_cells, int par, const int32_t *__restrict__ slots, int k, int kn, int B1,
+                                                                  int a0, int b0n, uint32_t in_base, int T, const uint32_t *__restrict__ oo, const uint32_t *__restrict__ oe,
+                                                                  const uint32_t *__restrict__ in_edge, const int32_t *__restrict__ in_dst, const uint16_t *__restrict__ sc) {
+    const int64_t slot = slots[blockIdx.z];
+    const int32_t *next = pool + (slot * 2 + (par ^ 1)) * state_cells;      // level l + 1
+    int32_t *cur = pool + (slot * 2 + par) * state_cells;                   // level l
+    const int i = (int)blockIdx.y;
+    const uint32_t ou0 = oo[a0 + i], ou1 = oo[a0 + i + 1];
+    const int n = k * B1;
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += (int)(gridDim.x * JT_THREADS)) {
+        const int j = x / B1, r = x - j * B1;
+        const uint32_t ov0 = oo[a0 + j], ov1 = oo[a0 + j + 1];
+        int best = NEG_INF;
+        for (uint32_t ou = ou0; ou < ou1; ++ou) {
+            const uint32_t eu = oe[ou] - in_base;                           // rank among the in-edges of level l + 1
+            if (eu >= (uint32_t)T) continue;
+            const uint32_t pi = (uint32_t)(in_dst[in_base + eu] - b0n);
+            const int r1 = r - (int)(in_edge[in_base + eu] >> 31);
+            if (pi >= (uint32_t)kn || r1 < 0) continue;
+            for (uint32_t ov = ov0; ov < ov1; ++ov) {
+                const uint32_t ev = oe[ov] - in_base;
+                if (ev >= (uint32_t)T) continue;
+                const uint32_t pj = (uint32_t)(in_dst[in_base + ev] - b0n);
+                const int r2 = r1 - (int)(in_edge[in_base + ev] >> 31);
+                if (pj >= (uint32_t)kn || r2 < 0) continue;
+                const int s = next[((int64_t)pi * kn + pj) * B1 + r2];
+                if (s == NEG_INF) continue;
+                const int d = sc ? (int)sc[(int64_t)eu * T + ev] : 0;
+                best = max(best, s + d);
+            }
+        }
+        cur[((int64_t)i * k + j) * B1 + r] = best;
+    }
+}
+
+__global__ __launch_bounds__(JT_THREADS) void phb_seed_kernel(const int32_t *__restrict__ B, int32_t *__restrict__ pool, int64_t state_cells, int par,
+                                                              const PhbSeed *__restrict__ seeds, int k, int B1, int b0, const int32_t *__restrict__ cls) {
+    const PhbSeed sd = seeds[blockIdx.z];
+    int32_t *S = pool + ((int64_t)sd.slot * 2 + par) * state_cells;
+    const int i = (int)blockIdx.y;
+    const bool row = (cls ? cls[b0 + i] : b0 + i) == sd.c0;                 // uniform per workgroup
+    const int n = k * B1;
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += (int)(gridDim.x * JT_THREADS)) {
+        const int j = x / B1;
+        const int64_t at = (int64_t)i * n + x;                              // ((i * k + j) * B1 + r)
+        int v = NEG_INF;
+        if (row && (cls ? cls[b0 + j] : b0 + j) == sd.c1) v = B[at];
+        S[at] = v;
+    }
+}
+
+__global__ __launch_bounds__(JT_THREADS) void phb_readout_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ pool, int64_t state_cells, int par,
+                                                                 const PhbRead *__restrict__ reads, int k, int B1, int b0, const int32_t *__restrict__ cls,
+                                                                 long long *__restrict__ part_all) {
+    __shared__ long long s_key[JT_THREADS / 64];
+    const int t = (int)threadIdx.x, i = (int)blockIdx.x;
+    const PhbRead rd = reads[blockIdx.y];
+    const int32_t *S = pool + ((int64_t)rd.slot * 2 + par) * state_cells;
+    long long *part = part_all + (int64_t)blockIdx.y * 2 * k;
+    const int c0 = rd.c0, c1 = rd.c1, b = rd.budget;                        // b < B1
+    const int ci = cls ? cls[b0 + i] : b0 + i;
+    if (ci != c0 && ci != c1) {                                             // uniform: no cell of either order in this row
+        if (t == 0) { part[i] = JT_NO_KEY; part[k + i] = JT_NO_KEY; }
+        return;
+    }
+    const int cj_want = ci == c0 ? c1 : c0;                                 // c0 != c1: the level is het
+    long long key = JT_NO_KEY;
+    for (int j = t; j < k; j += JT_THREADS) {
+        if ((cls ? cls[b0 + j] : b0 + j) != cj_want) continue;
+        const int32_t *f = F + ((int64_t)i * k + j) * B1, *sv = S + ((int64_t)i * k + j) * B1;
+        int best = NEG_INF;
+        for (int r = 0; r <= b; ++r) {
+            const int fv = f[r], bv = sv[b - r];
+            if (fv != NEG_INF && bv != NEG_INF) best = max(best, fv + bv);
+        }
+        if (best != NEG_INF) key = max(key, jt_key(best, i, j));
+    }
+    for (int d = 32; d; d >>= 1) key = max(key, __shfl_xor(key, d));
+    if ((t & 63) == 0) s_key[t >> 6] = key;
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) key = max(key, s_key[w]);
+        part[i] = ci == c0 ? key : JT_NO_KEY;
+        part[k + i] = ci == c0 ? JT_NO_KEY : key;
+    }
+}
+
+__global__ __launch_bounds__(JT_THREADS) void phb_finish_kernel(const long long *__restrict__ part_all, const PhbRead *__restrict__ reads, int k, int b0, int level_a,
+                                                                dg_dp_phase_margin *__restrict__ rec) {
+    __shared__ long long s_key[2][JT_THREADS / 64];
+    const int t = (int)threadIdx.x;
+    const PhbRead rd = reads[blockIdx.x];
+    const long long *part = part_all + (int64_t)blockIdx.x * 2 * k;
+    long long cis = JT_NO_KEY, trans = JT_NO_KEY;
+    for (int i = t; i < k; i += JT_THREADS) { cis = max(cis, part[i]); trans = max(trans, part[k + i]); }
+    for (int d = 32; d; d >>= 1) { cis = max(cis, __shfl_xor(cis, d)); trans = max(trans, __shfl_xor(trans, d)); }
+    if ((t & 63) == 0) { s_key[0][t >> 6] = cis; s_key[1][t >> 6] = trans; }
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < JT_THREADS / 64; ++w) { cis = max(cis, s_key[0][w]); trans = max(trans, s_key[1][w]); }
+        dg_dp_phase_margin r;
+        r.level_a = level_a; r.level_b = rd.level_b;
+        r.cis_value = r.trans_value = NEG_INF;
+        r.cis_vertex1 = r.cis_vertex2 = r.trans_vertex1 = r.trans_vertex2 = -1;
+        if (cis != JT_NO_KEY) {
+            const uint32_t lo = (uint32_t)cis;
+            r.cis_vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+            r.cis_vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+            r.cis_value = (int)(cis >> 32);
+        }
+        if (trans != JT_NO_KEY) {
+            const uint32_t lo = (uint32_t)trans;
+            r.trans_vertex1 = b0 + (JT_MAX_K - (int)((lo >> 15) & 0x7FFFu));
+            r.trans_vertex2 = b0 + (JT_MAX_K - (int)(lo & 0x7FFFu));
+            r.trans_value = (int)(trans >> 32);
+        }
+        r.reserved[0] = 0; r.reserved[1] = 0;
+        rec[rd.rec] = r;
+    }
+}
+
+// ph_call's schedule once at the largest budget, with the slot pool in place of its one S.  The plan (het levels, keys, slots, the
+// per-level launch tables) is a function of called, vertex_class and the graph, made and uploaded before the first launch: the level loop
+// has the launches of ph_call's and nothing that waits for the device.
+int phb_call(dg_ctx *c, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *record_off,
+             int32_t *best_values) {
+    const char *FN = "dg_dp_phase_margins_budgets";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
+    DpState &S = *Sp;
+    if (n < 1) { set_error("%s: n_called = %lld", FN, (long long)n); return DG_ERR_ARG; }
+    if (!called || !budgets || !records || !record_off || !best_values) { set_error("%s: called, budgets, records, record_off and best_values are required", FN); return DG_ERR_ARG; }
+    if (n > JT_MAX_QUERIES) { set_error("%s: %lld called pairs exceed %d per call", FN, (long long)n, JT_MAX_QUERIES); return DG_ERR_UNSUPPORTED; }
+    int32_t budget = 0;                                                     // the pass runs at the largest budget
+    for (int64_t q = 0; q < n; ++q) {
+        if (budgets[q] < 0) { set_error("%s: query %lld: budget %d is negative", FN, (long long)q, budgets[q]); return DG_ERR_ARG; }
+        budget = std::max(budget, budgets[q]);
+    }
+    if ((int64_t)budget + 1 > JT_MAX_PLANES) { set_error("%s: budget + 1 = %lld exceeds %d planes", FN, (long long)budget + 1, JT_MAX_PLANES); return DG_ERR_UNSUPPORTED; }
+    const int L = S.L, nV = S.nV, B1 = budget + 1;
+    if (L < 2 || (int)S.descs.size() < L) { set_error("%s: the loaded graph has %d levels", FN, L); return DG_ERR_STATE; }
+    std::vector<JtLevel> lv((size_t)L);
+    int kmax = 1;
+    int64_t tmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const LevelDesc &d = S.descs[(size_t)std::max(l, 1)];
+        lv[l] = l ? JtLevel{d.b0, d.k2, d.in_base, d.T, d.delta_off >= 0, 0} : JtLevel{d.a0, d.k, 0u, 0, false, 0};
+        lv[l].cells = (int64_t)lv[l].k * lv[l].k * B1;
+        kmax = std::max(kmax, lv[l].k);
+        if (lv[l].coloured) tmax = std::max<int64_t>(tmax, lv[l].T);
+    }
+    if (kmax > JT_MAX_K) { set_error("%s: widest level %d exceeds %d", FN, kmax, JT_MAX_K); return DG_ERR_UNSUPPORTED; }
+    for (int64_t q = 0; q < n; ++q)
+        for (int row = 0; row < 2; ++row)
+            for (int l = 0; l < L; ++l) {
+                const int32_t v = called[(q * 2 + row) * L + l];
+                if ((uint32_t)(v - lv[l].a0) >= (uint32_t)lv[l].k) {
+                    set_error("%s: query %lld row %d level %d: vertex %d is not in its level", FN, (long long)q, row, l, v);
+                    return DG_ERR_ARG;
+                }
+            }
+    // ---- the plan.  Per query: its het levels ascending with the called ordered classes there (het_*[het_off[q] ..)), its records' place.
+    // q carries on h_0 <= l < h_last; its key there is (e, c0[e], c1[e]) with e its nearest het level above l.  The key of a query changes
+    // only at its own het levels, so the levels below walk at_q: per level, the queries that are het there (ascending), and nothing else ----
+    struct Key { int32_t e, c0, c1; bool operator<(const Key &o) const { return e != o.e ? e < o.e : c0 != o.c0 ? c0 < o.c0 : c1 < o.c1; } };
+    std::vector<int64_t> roff((size_t)n + 1, 0), het_off((size_t)n + 1, 0), at_off((size_t)L + 1, 0);
+    std::vector<int32_t> het_l, het_c0, het_c1;
+    int h_first = L;                                                        // the smallest h_0 of a query with a record; L: nothing backward at all
+    for (int64_t q = 0; q < n; ++q) {
+        for (int l = 0; l < L; ++l) {
+            const int32_t v0 = called[(q * 2) * L + l], v1 = called[(q * 2 + 1) * L + l];
+            const int32_t a = vertex_class ? vertex_class[v0] : v0, b = vertex_class ? vertex_class[v1] : v1;
+            if (a != b) { het_l.push_back(l); het_c0.push_back(a); het_c1.push_back(b); }
+        }
+        het_off[(size_t)q + 1] = (int64_t)het_l.size();
+        const int64_t nh = het_off[(size_t)q + 1] - het_off[(size_t)q];
+        roff[(size_t)q + 1] = roff[(size_t)q] + std::max<int64_t>(nh - 1, 0);
+        if (nh < 2) continue;
+        h_first = std::min(h_first, (int)het_l[(size_t)het_off[(size_t)q]]);
+        for (int64_t x = het_off[(size_t)q]; x < het_off[(size_t)q + 1]; ++x) ++at_off[(size_t)het_l[(size_t)x] + 1];
+    }
+    const int64_t nrec = roff[(size_t)n];
+    for (int l = 0; l < L; ++l) at_off[(size_t)l + 1] += at_off[(size_t)l];
+    std::vector<int32_t> at_q((size_t)at_off[(size_t)L]);                   // the queries with a record that are het on l: at_q[at_off[l] .. at_off[l + 1])
+    std::vector<int64_t> het_at((size_t)n);                                 // going down the levels: where in het_* the next het level of q stands
+    {
+        std::vector<int64_t> next(at_off.begin(), at_off.end() - 1);
+        for (int64_t q = 0; q < n; ++q) {
+            het_at[(size_t)q] = het_off[(size_t)q + 1] - 1;
+            if (het_off[(size_t)q + 1] - het_off[(size_t)q] < 2) continue;
+            for (int64_t x = het_off[(size_t)q]; x < het_off[(size_t)q + 1]; ++x) at_q[(size_t)next[(size_t)het_l[(size_t)x]]++] = (int32_t)q;
+        }
+    }
+    // the levels from the top: the slots live on l, the read-outs at l, the keys seeded at l (live on l - 1, not on l)
+    std::vector<int32_t> live_off((size_t)L + 1, 0), read_off((size_t)L + 1, 0), seed_off((size_t)L + 1, 0), live_tab;   // tables in descending level order: entry L - 1 - l
+    std::vector<PhbRead> read_tab;
+    std::vector<PhbSeed> seed_tab;
+    int64_t keys_created = 0, slot_levels = 0, back_launches = 0, read_launches = 0, max_live = 0, max_part = 1;
+    int n_slots = 0;
+    {
+        struct Held { int32_t slot, queries; };
+        std::map<Key, Held> live;                                           // the keys live on the level at hand -> slot, and how many queries carry it
+        std::vector<std::map<Key, Held>::iterator> freed;
+        std::vector<Key> born;
+        std::vector<int32_t> free_slots;                                    // kept descending: the smallest is taken first
+        for (int l = L - 1; l >= 0; --l) {
+            const size_t at = (size_t)(L - 1 - l);
+            for (const auto &kv : live) live_tab.push_back(kv.second.slot);
+            live_off[at + 1] = (int32_t)live_tab.size();
+            const int64_t nl = (int64_t)live.size();
+            if (nl) { slot_levels += nl; ++back_launches; max_live = std::max(max_live, nl); }
+            freed.clear();
+            born.clear();
+            for (int64_t i = at_off[(size_t)l]; i < at_off[(size_t)l + 1]; ++i) {
+                const int64_t q = at_q[(size_t)i], x = het_at[(size_t)q]--, t = x - het_off[(size_t)q];   // (het_l[x] == l)
+                if (x + 1 < het_off[(size_t)q + 1]) {                       // q carries on l: its record of (l, e), and it leaves the key of e here
+                    const int32_t e = het_l[(size_t)x + 1];
+                    const auto it = live.find(Key{e, het_c0[(size_t)x + 1], het_c1[(size_t)x + 1]});
+                    read_tab.push_back(PhbRead{it->second.slot, het_c0[(size_t)x], het_c1[(size_t)x], budgets[q], (int32_t)(roff[(size_t)q] + t), e});
+                    if (--it->second.queries == 0) freed.push_back(it);
+                }
+                if (t > 0) born.push_back(Key{l, het_c0[(size_t)x], het_c1[(size_t)x]});   // and carries the key of l below
+            }
+            read_off[at + 1] = (int32_t)read_tab.size();
+            const int64_t nr = read_off[at + 1] - read_off[at];
+            if (nr) { ++read_launches; max_part = std::max(max_part, nr * 2 * lv[l].k); }
+            for (const auto &it : freed) { free_slots.push_back(it->second.slot); live.erase(it); }
+            std::sort(free_slots.begin(), free_slots.end(), std::greater<int32_t>());
+            std::sort(born.begin(), born.end());
+            for (size_t i = 0; i < born.size(); ++i) {
+                if (i && !(born[i - 1] < born[i])) { ++live.find(born[i])->second.queries; continue; }
+                int32_t slot;
+                if (free_slots.empty()) slot = n_slots++;                   // a key seeded here may take a slot freed here
+                else { slot = free_slots.back(); free_slots.pop_back(); }
+                live.emplace(born[i], Held{slot, 1});
+                seed_tab.push_back(PhbSeed{slot, born[i].c0, born[i].c1});
+                ++keys_created;
+            }
+            seed_off[at + 1] = (int32_t)seed_tab.size();
+        }
+    }
+    hipStream_t s = c->stream;
+    // ---- segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
+    std::vector<int> seg{0};
+    {
+        int64_t in_seg = 0;
+        for (int l = 0; l < L; ++l) {
+            const int64_t bytes = 4 * lv[l].cells;
+            if (l > seg.back() && in_seg + bytes > S.opt.joint_state_bytes) { seg.push_back(l); in_seg = 0; }
+            in_seg += bytes;
+        }
+    }
+    const int n_seg = (int)seg.size();
+    seg.push_back(L);
+    std::vector<int64_t> ck_off((size_t)n_seg + 1, 0);                     // F of every segment's first level, int32 units
+    int64_t seg_cells = 1, roll_cells = 0, level_cells = 1;
+    for (int g = 0; g < n_seg; ++g) {
+        ck_off[g + 1] = ck_off[g] + lv[seg[g]].cells;
+        int64_t sum = 0;
+        for (int l = seg[g] + 1; l < seg[g + 1]; ++l) { sum += lv[l].cells; if (g + 1 < n_seg) roll_cells = std::max(roll_cells, lv[l].cells); }
+        seg_cells = std::max(seg_cells, sum);
+    }
+    for (int l = 0; l < L; ++l) level_cells = std::max(level_cells, lv[l].cells);
+    JtMem M;
+    DevBuf d_cls, d_rec, d_V, d_part, d_live, d_reads, d_seeds, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back, d_pool;
+    if (vertex_class) if (int rc = M.get(d_cls, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_rec, std::max<int64_t>(nrec, 1) * (int64_t)sizeof(dg_dp_phase_margin))) return rc;
+    if (int rc = M.get(d_V, (int64_t)B1 * 4)) return rc;
+    if (int rc = M.get(d_part, max_part * 8)) return rc;
+    if (tmax) if (int rc = M.get(d_sc, tmax * tmax * 2)) return rc;
+    if (int rc = M.get(d_ck, ck_off[n_seg] * 4)) return rc;
+    if (vertex_class) DG_HIP(hipMemcpyAsync(d_cls.p, vertex_class, (size_t)nV * 4, hipMemcpyHostToDevice, s));
+    const int32_t *cls = vertex_class ? (const int32_t *)d_cls.as<int32_t>() : nullptr;
+    const LevelDesc *descs = S.d_descs.as<LevelDesc>();
+    const uint32_t *in_off = S.d_in_off.as<uint32_t>(), *in_edge = S.d_in_edge.as<uint32_t>();
+    const int32_t *in_dst = S.d_in_dst.as<int32_t>();
+    uint16_t *sc = d_sc.as<uint16_t>();
+    if (nrec) {                                                             // the launch tables, once; the in-edges grouped by source
+        if (int rc = M.get(d_live, (int64_t)std::max<size_t>(live_tab.size(), 1) * 4)) return rc;
+        if (int rc = M.get(d_reads, (int64_t)std::max<size_t>(read_tab.size(), 1) * (int64_t)sizeof(PhbRead))) return rc;
+        if (int rc = M.get(d_seeds, (int64_t)std::max<size_t>(seed_tab.size(), 1) * (int64_t)sizeof(PhbSeed))) return rc;
+        if (!live_tab.empty()) DG_HIP(hipMemcpyAsync(d_live.p, live_tab.data(), live_tab.size() * 4, hipMemcpyHostToDevice, s));
+        if (!read_tab.empty()) DG_HIP(hipMemcpyAsync(d_reads.p, read_tab.data(), read_tab.size() * sizeof(PhbRead), hipMemcpyHostToDevice, s));
+        if (!seed_tab.empty()) DG_HIP(hipMemcpyAsync(d_seeds.p, seed_tab.data(), seed_tab.size() * sizeof(PhbSeed), hipMemcpyHostToDevice, s));
+        if (int rc = M.get(d_oo, ((int64_t)nV + 1) * 4)) return rc;
+        if (int rc = M.get(d_ocur, (int64_t)nV * 4)) return rc;
+        if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
+        DG_HIP(hipMemsetAsync(d_ocur.p, 0, (size_t)nV * 4, s));
+        hipLaunchKernelGGL(jt_out_count_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>());
+        hipLaunchKernelGGL(jt_out_scan_kernel, dim3(1), dim3(1024), 0, s, d_ocur.as<uint32_t>(), d_oo.as<uint32_t>(), d_ocur.as<uint32_t>(), nV);
+        hipLaunchKernelGGL(jt_out_fill_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>(), d_oe.as<uint32_t>(), (uint32_t)S.n_edges);
+        DG_HIP(hipGetLastError());
+    }
+    auto scores = [&](int l) -> const uint16_t * {                          // the matrix of the transition into level l, in d_sc
+        const int T = lv[l].T;
+        if (!lv[l].coloured || T < 1) return nullptr;
+        hipLaunchKernelGGL(jt_scores_kernel, dim3(jt_blocks(T, 64), (unsigned)std::min(T, 16384)), dim3(JT_THREADS), 0, s, T, lv[l].in_base, lv[l - 1].a0, in_edge, in_dst,
+                           colour_csr(S), S.d_eflag.as<uint8_t>(), S.d_eself.as<uint16_t>(), sc);
+        return sc;
+    };
+    auto fill = [&](int32_t *st, int l, int pos) {                          // level l: 0 on every plane of the cell (pos, pos)
+        hipLaunchKernelGGL(jt_fill_kernel, dim3(jt_blocks(lv[l].cells, 65536)), dim3(JT_THREADS), 0, s, st, lv[l].cells, ((int64_t)pos * lv[l].k + pos) * B1, B1);
+    };
+    auto forward = [&](const int32_t *prev, int32_t *cur, int l) {
+        const uint16_t *m = scores(l);
+        hipLaunchKernelGGL(jt_forward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, prev, cur, lv[l - 1].k, lv[l].k, B1,
+                           lv[l].a0, lv[l].in_base, lv[l].T, in_off, in_edge, m);
+    };
+    // ---- pass 1: the state at every segment's first level ----
+    int32_t *ck = d_ck.as<int32_t>();
+    fill(ck, 0, 0);
+    if (n_seg > 1) {
+        if (int rc = M.get(d_roll, 2 * roll_cells * 4)) return rc;
+        int32_t *roll = d_roll.as<int32_t>();
+        const int32_t *prev = ck;
+        int g = 0;
+        for (int l = 1; l <= seg[n_seg - 1]; ++l) {
+            int32_t *dst = l == seg[g + 1] ? ck + ck_off[++g] : roll + (l & 1) * roll_cells;
+            forward(prev, dst, l);
+            prev = dst;
+        }
+        DG_HIP(hipGetLastError());
+        DG_HIP(hipStreamSynchronize(s));                                    // the rolling states go before the segment buffers come
+        M.drop(d_roll);
+    }
+    // ---- the segments, last first, down to the one that holds the smallest first het level ----
+    if (int rc = M.get(d_seg, seg_cells * 4)) return rc;
+    if (nrec) {
+        if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
+        if (int rc = M.get(d_pool, (int64_t)std::max(n_slots, 1) * 2 * level_cells * 4)) return rc;
+    }
+    int32_t *back = d_back.as<int32_t>(), *pool = d_pool.as<int32_t>();
+    const int32_t *live_d = d_live.as<int32_t>();
+    const PhbRead *reads_d = d_reads.as<PhbRead>();
+    const PhbSeed *seeds_d = d_seeds.as<PhbSeed>();
+    dg_dp_phase_margin *rec_d = d_rec.as<dg_dp_phase_margin>();
+    std::vector<const int32_t *> Fp((size_t)L, nullptr);
+    for (int g = n_seg - 1; g >= 0; --g) {
+        const int a = seg[g], e = seg[g + 1];
+        if (e <= h_first && g < n_seg - 1) break;                           // nothing is read out below the first het level
+        Fp[a] = ck + ck_off[g];
+        int64_t at = 0;
+        for (int l = a + 1; l < e; ++l) {
+            int32_t *dst = d_seg.as<int32_t>() + at;
+            at += lv[l].cells;
+            forward(Fp[l - 1], dst, l);
+            Fp[l] = dst;
+        }
+        if (e == L) {                                                       // V_b for every budget: the sink's planes
+            const int sink = nV - 1 - lv[L - 1].a0;
+            DG_HIP(hipMemcpyAsync(d_V.p, Fp[L - 1] + ((int64_t)sink * lv[L - 1].k + sink) * B1, (size_t)B1 * 4, hipMemcpyDeviceToDevice, s));
+        }
+        for (int l = e - 1; l >= a && l >= h_first; --l) {
+            const size_t lx = (size_t)(L - 1 - l);
+            const int par = l & 1;
+            int32_t *cur = back + par * level_cells;
+            const unsigned xb = jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS);
+            if (l == L - 1) fill(cur, l, nV - 1 - lv[l].a0);
+            else {
+                const uint16_t *m = scores(l + 1);
+                hipLaunchKernelGGL(jt_backward_kernel, dim3(xb, (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, (const int32_t *)(back + (par ^ 1) * level_cells), cur, lv[l].k, lv[l + 1].k, B1,
+                                   lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base, lv[l + 1].T, d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
+                if (const int nl = live_off[lx + 1] - live_off[lx])         // every live slot down one level, on the same matrix
+                    hipLaunchKernelGGL(phb_backward_kernel, dim3(xb, (unsigned)lv[l].k, (unsigned)nl), dim3(JT_THREADS), 0, s, pool, level_cells, par, live_d + live_off[lx], lv[l].k,
+                                       lv[l + 1].k, B1, lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base, lv[l + 1].T, d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
+            }
+            if (const int nr = read_off[lx + 1] - read_off[lx]) {           // before the seeds: a slot freed here may be seeded here
+                hipLaunchKernelGGL(phb_readout_kernel, dim3((unsigned)lv[l].k, (unsigned)nr), dim3(JT_THREADS), 0, s, Fp[l], (const int32_t *)pool, level_cells, par,
+                                   reads_d + read_off[lx], lv[l].k, B1, lv[l].a0, cls, d_part.as<long long>());
+                hipLaunchKernelGGL(phb_finish_kernel, dim3((unsigned)nr), dim3(JT_THREADS), 0, s, (const long long *)d_part.as<long long>(), reads_d + read_off[lx], lv[l].k, lv[l].a0, l, rec_d);
+            }
+            if (const int ns = seed_off[lx + 1] - seed_off[lx])
+                hipLaunchKernelGGL(phb_seed_kernel, dim3(xb, (unsigned)lv[l].k, (unsigned)ns), dim3(JT_THREADS), 0, s, (const int32_t *)cur, pool, level_cells, par, seeds_d + seed_off[lx],
+                                   lv[l].k, B1, lv[l].a0, cls);
+        }
+        DG_HIP(hipGetLastError());
+    }
+    // the caller's arrays are written only if the call succeeds
+    std::vector<dg_dp_phase_margin> recs((size_t)nrec);
+    std::vector<int32_t> Vs((size_t)B1, NEG_INF);
+    if (nrec) DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_phase_margin), hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(Vs.data(), d_V.p, Vs.size() * 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipStreamSynchronize(s));
+    for (int64_t q = 0; q < n; ++q)
+        for (int64_t x = roff[(size_t)q]; x < roff[(size_t)q + 1]; ++x)
+            if (std::max(recs[(size_t)x].cis_value, recs[(size_t)x].trans_value) > Vs[(size_t)budgets[q]]) {
+                set_error("%s: query %lld record %lld (levels %d, %d): cis %d, trans %d exceed the sink's value %d at budget %d", FN, (long long)q, (long long)(x - roff[(size_t)q]),
+                          recs[(size_t)x].level_a, recs[(size_t)x].level_b, recs[(size_t)x].cis_value, recs[(size_t)x].trans_value, Vs[(size_t)budgets[q]], budgets[q]);
+                return DG_ERR_STATE;
+            }
+    const int64_t st[10] = {n, nrec, keys_created, slot_levels, back_launches, read_launches, max_live, nrec ? n_slots : 0, n_seg, M.peak};
+    for (int x = 0; x < 10; ++x) S.phb_stats[x] = st[x];
+    if (nrec) memcpy(records, recs.data(), recs.size() * sizeof(dg_dp_phase_margin));
+    for (int64_t q = 0; q <= n; ++q) record_off[q] = roff[(size_t)q];
+    for (int64_t q = 0; q < n; ++q) best_values[q] = Vs[(size_t)budgets[q]];
+    return DG_OK;
+}
+
 }  // namespace
 
 int dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value) {
@@ -1320,6 +1736,18 @@ int dp_phase_stats(dg_ctx *c, int64_t *out, int n) {
     if (!out || n < 6) { set_error("dg_dp_get_phase_stats: out needs 6 words"); return DG_ERR_ARG; }
     if (!c->dp) { set_error("dg_dp_get_phase_stats: no graph loaded"); return DG_ERR_STATE; }
     for (int q = 0; q < 6; ++q) out[q] = c->dp->ph_stats[q];
+    return DG_OK;
+}
+
+int dp_phase_margins_budgets(dg_ctx *c, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *record_off,
+                             int32_t *best_values) {
+    return phb_call(c, called, budgets, n, vertex_class, records, record_off, best_values);
+}
+
+int dp_phase_budget_stats(dg_ctx *c, int64_t *out, int n) {
+    if (!out || n < 10) { set_error("dg_dp_get_phase_budget_stats: out needs 10 words"); return DG_ERR_ARG; }
+    if (!c->dp) { set_error("dg_dp_get_phase_budget_stats: no graph loaded"); return DG_ERR_STATE; }
+    for (int q = 0; q < 10; ++q) out[q] = c->dp->phb_stats[q];
     return DG_OK;
 }
 
@@ -1394,4 +1822,15 @@ extern "C" int dg_dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t bud
 extern "C" int dg_dp_get_phase_stats(dg_ctx *c, int64_t *out, int n) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_phase_stats(c, out, n);
+}
+
+extern "C" int dg_dp_phase_margins_budgets(dg_ctx *c, const int32_t *called, const int32_t *budgets, int64_t n_called, const int32_t *vertex_class, dg_dp_phase_margin *records,
+                                           int64_t *record_off, int32_t *best_values) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_phase_margins_budgets(c, called, budgets, n_called, vertex_class, records, record_off, best_values);
+}
+
+extern "C" int dg_dp_get_phase_budget_stats(dg_ctx *c, int64_t *out, int n) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_phase_budget_stats(c, out, n);
 }

@@ -112,6 +112,8 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.budget_genotype_margins.empty() && (!be.dp_answer_paths || !be.dp_genotype_margins_budgets)) return "--budget-genotype-margins: this backend has no dp_genotype_margins_budgets";
     // and --phase-margins: the called pair is the answer that stays behind
     if (!p.opt.phase_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_phase_margins)) return "--phase-margins: this backend has no dp_phase_margins";
+    // and --budget-phase-margins: the answers at the listed limits stay behind, one joint pass describes the phase of them all
+    if (!p.opt.budget_phase_margins.empty() && (!be.dp_answer_paths || !be.dp_phase_margins_budgets)) return "--budget-phase-margins: this backend has no dp_phase_margins_budgets";
     // and --pins: the same run under the file's cell constraints
     if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
     // and --pinned-genotype-margins / --pinned-genotype-table: the joint pass under the same constraints
@@ -572,6 +574,82 @@ std::string write_phase_margins(Pipeline &p, const ExpandedGraph &g, const std::
     return "";
 }
 
+// r and the columns of --phase-margins: per listed limit r with an answer, in the order of the list, one row per pair of neighbouring het
+// levels of the answer at r, cis and trans within r.  ONE device call serves every limit (dp_phase_margins_budgets: the joint pass at the
+// largest of them; answers at neighbouring limits share most of their seeded states).  A limit nobody fits is left out: it has no paths
+// to call.  In every record cis must be the run's DP value at r.
+std::string write_budget_phase_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &cls, const std::vector<int32_t> &budgets, const std::vector<ChainAnswer> &answers) {
+    const double t0 = now_s();
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    BudgetPhaseMargins &bp = p.sum.budget_phase_margins;
+    bp = BudgetPhaseMargins();
+    bp.set = true;
+    std::vector<int32_t> called, limits, values;                     // [n][2][L], [n], the run's DP value at each
+    std::vector<int32_t> paths(2 * (size_t)L);
+    for (const int r : p.opt.budgets) {
+        const size_t q = (size_t)(std::find(budgets.begin(), budgets.end(), (int32_t)r) - budgets.begin());
+        if (q >= answers.size() || !answers[q].reachable()) continue;
+        if (be.dp_answer_paths(be.ctx, r, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+        if (paths[0] < 0) continue;
+        called.insert(called.end(), paths.begin(), paths.end());
+        limits.push_back(r);
+        values.push_back(answers[q].res.value);
+    }
+    const int64_t n = (int64_t)limits.size();
+    std::vector<dg_dp_phase_margin> rec((size_t)std::max<int64_t>(n * (L - 1), 1));
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    std::vector<int32_t> best((size_t)n);
+    if (n > 0) {
+        if (be.dp_phase_margins_budgets(be.ctx, called.data(), limits.data(), n, cls.data(), rec.data(), off.data(), best.data()) != 0) return backend_error(be, "dp_phase_margins_budgets");
+        int64_t stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (be.dp_phase_budget_stats && be.dp_phase_budget_stats(be.ctx, stats, 10) != 0) return backend_error(be, "dp_phase_budget_stats");
+        bp.seed_keys = stats[2];
+        bp.slot_levels = stats[3];
+        bp.segments = stats[8];
+    }
+    std::string text = "r\tlevel_a\tlevel_b\tvertex1_a\tsegment1_a\tvertex2_a\tsegment2_a\tvertex1_b\tsegment1_b\tvertex2_b\tsegment2_b\tcis_value\ttrans_value\ttrans_vertex1\ttrans_vertex2\tmargin\n";
+    for (int64_t q = 0; q < n; ++q) {
+        BudgetPhaseMargins::Row row;
+        row.r = limits[(size_t)q];
+        const int32_t *qp = &called[(size_t)q * 2 * (size_t)L];
+        if (best[(size_t)q] != values[(size_t)q])
+            return "--budget-phase-margins: limit " + std::to_string(row.r) + ": the joint pass finds " + std::to_string(best[(size_t)q]) + ", the run's DP value is " + std::to_string(values[(size_t)q]);
+        for (int l = 0; l < L; ++l) row.het_levels += cls[(size_t)qp[l]] != cls[(size_t)qp[(size_t)L + l]];
+        for (int64_t x = off[(size_t)q]; x < off[(size_t)q + 1]; ++x) {
+            const dg_dp_phase_margin &r = rec[(size_t)x];
+            if (r.cis_value != values[(size_t)q])
+                return "--budget-phase-margins: limit " + std::to_string(row.r) + " levels " + std::to_string(r.level_a) + ", " + std::to_string(r.level_b) + ": the answer's phase is worth " +
+                       std::to_string(r.cis_value) + ", the run's DP value is " + std::to_string(values[(size_t)q]);
+            text += std::to_string(row.r) + '\t' + std::to_string(r.level_a) + '\t' + std::to_string(r.level_b);
+            for (const int l : {r.level_a, r.level_b})
+                for (int h = 0; h < 2; ++h) {
+                    const int32_t v = qp[(size_t)h * L + l];
+                    text += '\t' + std::to_string(v) + '\t' + segment_name(p, g, v);
+                }
+            text += '\t' + std::to_string(r.cis_value) + '\t';
+            if (r.trans_vertex1 >= 0) {
+                const int32_t margin = r.cis_value - r.trans_value;
+                text += std::to_string(r.trans_value) + '\t' + std::to_string(r.trans_vertex1) + '\t' + std::to_string(r.trans_vertex2) + '\t' + std::to_string(margin);
+                row.with_alternative++;
+                if (margin == 0) row.margin0++;
+                else if (margin > 0 && (row.min_positive_margin < 0 || margin < row.min_positive_margin)) row.min_positive_margin = margin;
+            } else text += ".\t.\t.\t.";
+            text += '\n';
+        }
+        row.records = off[(size_t)q + 1] - off[(size_t)q];
+        bp.rows.push_back(row);
+    }
+    const std::string &path = p.opt.budget_phase_margins;
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open budget phase margins file " + path;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + path + " failed";
+    bp.wall_s = now_s() - t0;
+    return "";
+}
+
 // r and the columns of --genotype-margins: per listed limit r with an answer, in the order of the list, the levels 1 .. L - 2 with the
 // answer at r as the called cells and the alternative within r.  ONE device call serves every limit (dp_genotype_margins_budgets: the
 // joint pass at the largest of them).  A limit nobody fits is left out: it has no paths to call.  On every level the called cell must be
@@ -787,15 +865,15 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         }
     }
     const bool pinned_joint = !opt.pinned_genotype_margins.empty() || !opt.pinned_genotype_table.empty();
-    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : "--phase-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : !opt.phase_margins.empty() ? "--phase-margins" : "--budget-phase-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
-    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty()) {  // all these tables speak of alleles
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty()) {  // all these tables speak of alleles
         classes = allele_classes(g);
         if (!opt.dump_prefix.empty() && failed(write_raw_int32(opt.dump_prefix + ".cls", classes), err)) return -1;
     }
@@ -867,6 +945,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         t0 = now_s();
         if (failed(write_phase_margins(*this, g, classes), err)) return -1;
         stamp("phase_margins", t0);
+    }
+    if (!opt.budget_phase_margins.empty()) {                              // after --phase-margins: that option alone is exactly what it was
+        t0 = now_s();
+        if (failed(write_budget_phase_margins(*this, g, classes, budgets, answers), err)) return -1;
+        stamp("budget_phase_margins", t0);
     }
     if (pinned_joint) {                                                   // the same under --pins: one pass serves both files
         t0 = now_s();

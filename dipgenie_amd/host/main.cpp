@@ -172,6 +172,15 @@ static int b_dp_phase_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_phase_stats(x, out, n) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_phase_margins_budgets(void *c, const int32_t *called, const int32_t *budgets, int64_t n, const int32_t *cls, dg_dp_phase_margin *records, int64_t *record_off,
+                                      int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_phase_margins_budgets(x, called, budgets, n, cls, records, record_off, best) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_phase_budget_stats(void *c, int64_t *out, int n) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_phase_budget_stats(x, out, n) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_answer_objectives(x, budgets, n, out) : DG_ERR_NO_DEVICE;
@@ -291,6 +300,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --budget-genotype-margins FILE   (MI355X build, -p2, with --budgets) the rows of --genotype-margins for the answer at every listed limit that has one, each against the best other genotype within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
     fprintf(fp, "    --genotype-table FILE     (MI355X build, -p2) per level one row for every genotype a pair of paths within -R passes through: its best cell, value, distance to the DP value, whether the answer has it (TSV)\n");
     fprintf(fp, "    --phase-margins FILE      (MI355X build, -p2) per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps the answer's phase between them (cis) against the best that switches it (trans), and the margin (TSV)\n");
+    fprintf(fp, "    --budget-phase-margins FILE   (MI355X build, -p2, with --budgets) the rows of --phase-margins for the answer at every listed limit that has one, each within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --pins FILE           (MI355X build, -p2) run the DP under cell constraints: rows level, vertex1, vertex2 [, require|forbid|require-ordered|forbid-ordered], tab-separated, . = any vertex, ids as --genotype-table prints them\n");
@@ -316,7 +326,7 @@ int main(int argc, char **argv) {
     std::vector<int> shard_devices;
     std::string budgets_arg;
     bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
-    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false;
+    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false, have_budget_phase = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -346,6 +356,12 @@ int main(int argc, char **argv) {
                 have_budget_margins = true;                            // (a missing value is an empty file name: refused below)
                 const char *v = val("--budget-genotype-margins");
                 p.opt.budget_genotype_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--budget-phase-margins", 22) && (argv[i][22] == 0 || argv[i][22] == '=')) {
+                have_budget_phase = true;                              // (a missing value is an empty file name: refused below)
+                const char *v = val("--budget-phase-margins");
+                p.opt.budget_phase_margins = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--phase-margins", 15) && (argv[i][15] == 0 || argv[i][15] == '=')) {
@@ -435,6 +451,14 @@ int main(int argc, char **argv) {
         if (sharded) { fprintf(stderr, "[E::main] --budget-genotype-margins does not go with --gpus / --shard-transport\n"); return 1; }
         if (have_pins) { fprintf(stderr, "[E::main] --budget-genotype-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
     }
+    // --budget-phase-margins FILE: the same
+    if (have_budget_phase) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --budget-phase-margins describes the phase of the diploid route (-p2)\n"); return 1; }
+        if (!have_budgets) { fprintf(stderr, "[E::main] --budget-phase-margins needs --budgets\n"); return 1; }
+        if (p.opt.budget_phase_margins.empty()) { fprintf(stderr, "[E::main] --budget-phase-margins needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --budget-phase-margins does not go with --gpus / --shard-transport\n"); return 1; }
+        if (have_pins) { fprintf(stderr, "[E::main] --budget-phase-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
+    }
     // --budgets all|a,b,c: checked here, before any device is asked for
     if (!p.opt.budget_table.empty() && !have_budgets) { fprintf(stderr, "[E::main] --budget-table needs --budgets\n"); return 1; }
     if (have_budgets) {
@@ -454,6 +478,10 @@ int main(int argc, char **argv) {
                 if (std::find(p.opt.budgets.begin(), p.opt.budgets.end(), r) == p.opt.budgets.end()) p.opt.budgets.push_back(r);
                 a = b + 1;
             }
+        }
+        // one device call takes 256 called pairs: a longer list is refused here, not after the DP run
+        if (have_budget_phase && p.opt.budgets.size() > 256) {
+            fprintf(stderr, "[E::main] --budget-phase-margins: --budgets lists %zu limits; one call answers 256 at the most\n", p.opt.budgets.size()); return 1;
         }
     }
     // --site-margins FILE: checked here too, before any device is asked for
@@ -532,6 +560,8 @@ int main(int argc, char **argv) {
     p.be.dp_genotype_table_pinned = b_dp_genotype_table_pinned;
     p.be.dp_phase_margins = b_dp_phase_margins;
     p.be.dp_phase_stats = b_dp_phase_stats;
+    p.be.dp_phase_margins_budgets = b_dp_phase_margins_budgets;
+    p.be.dp_phase_budget_stats = b_dp_phase_budget_stats;
     p.be.dp_run_pinned = b_dp_pinned;
     p.be.dp_pin_stats = b_dp_pin_stats;
     p.be.free_buf = dg_free;
@@ -632,6 +662,18 @@ int main(int argc, char **argv) {
                         (long long)pm.records, (long long)pm.with_alternative, (long long)pm.margin0);
                 if (pm.min_positive_margin >= 0) fprintf(f, "%d", pm.min_positive_margin); else fprintf(f, "null");
                 fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)pm.segments, pm.wall_s);
+            }
+            if (p.sum.budget_phase_margins.set) {                       // per listed limit with an answer the fields of phase_margins; one device call
+                const dg::BudgetPhaseMargins &bp = p.sum.budget_phase_margins;
+                fprintf(f, ", \"budget_phase_margins\": {\"budgets\": [");
+                for (size_t i = 0; i < bp.rows.size(); ++i) {
+                    const dg::BudgetPhaseMargins::Row &row = bp.rows[i];
+                    fprintf(f, "%s{\"r\": %d, \"het_levels\": %lld, \"records\": %lld, \"with_alternative\": %lld, \"margin0\": %lld, \"min_positive_margin\": ", i ? ", " : "", row.r,
+                            (long long)row.het_levels, (long long)row.records, (long long)row.with_alternative, (long long)row.margin0);
+                    if (row.min_positive_margin >= 0) fprintf(f, "%d}", row.min_positive_margin); else fprintf(f, "null}");
+                }
+                fprintf(f, "], \"seed_keys\": %lld, \"slot_levels\": %lld, \"segments\": %lld, \"wall_s\": %.6f}", (long long)bp.seed_keys, (long long)bp.slot_levels, (long long)bp.segments,
+                        bp.wall_s);
             }
             if (have_objective_table) {                                 // one entry per row of the table; null fields: unreachable
                 fprintf(f, ", \"objectives\": [");

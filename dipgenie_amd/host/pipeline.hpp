@@ -100,6 +100,11 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     // and that call's statistics (dg_dp_get_phase_stats)
     int (*dp_phase_margins)(void *, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value) = nullptr;
     int (*dp_phase_stats)(void *, int64_t *out, int n) = nullptr;
+    // optional (--budget-phase-margins): the records of dp_phase_margins for one called pair per listed limit, each at its own budget, from
+    // one joint pass (dg_dp_phase_margins_budgets), and that call's statistics (dg_dp_get_phase_budget_stats)
+    int (*dp_phase_margins_budgets)(void *, const int32_t *called, const int32_t *budgets, int64_t n_called, const int32_t *vertex_class, dg_dp_phase_margin *records,
+                                    int64_t *record_off, int32_t *best_values) = nullptr;
+    int (*dp_phase_budget_stats)(void *, int64_t *out, int n) = nullptr;
 };
 
 // one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
@@ -136,6 +141,7 @@ struct Options {
     std::string pinned_genotype_margins; // (ours) --pinned-genotype-margins, with --pins: the file of --genotype-margins for the DP under the pins, the called cells those of the pinned answer at -R
     std::string pinned_genotype_table;   // (ours) --pinned-genotype-table, with --pins: the file of --genotype-table for the DP under the pins
     std::string phase_margins;   // (ours) --phase-margins: TSV with one row per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps its phase against the best that switches it (diploid)
+    std::string budget_phase_margins; // (ours) --budget-phase-margins, with --budgets: the rows of --phase-margins for the answer at every listed limit that has one, behind a column r, from one joint pass (diploid)
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -253,6 +259,14 @@ struct PhaseMargins {         // --phase-margins: over the pairs of neighbouring
     double wall_s = 0;
 };
 
+struct BudgetPhaseMargins {   // --budget-phase-margins: per listed limit with an answer the fields of PhaseMargins; one device call for all
+    bool set = false;
+    struct Row { int32_t r = 0; int64_t het_levels = 0, records = 0, with_alternative = 0, margin0 = 0; int32_t min_positive_margin = -1; };
+    std::vector<Row> rows;
+    int64_t seed_keys = 0, slot_levels = 0, segments = 0;   // of the call: distinct seeded states, the sum over the levels of the live ones
+    double wall_s = 0;
+};
+
 struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
     bool set = false;
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
@@ -280,6 +294,7 @@ struct Summary {              // what tests and the CLI report
     GenotypeMargins pinned_genotype_margins;   // --pinned-genotype-margins: the same fields, of the DP under --pins
     GenotypeTable pinned_genotype_table;       // --pinned-genotype-table
     PhaseMargins phase_margins;
+    BudgetPhaseMargins budget_phase_margins;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
     PinSummary pins;

@@ -426,6 +426,38 @@ int dg_dp_phase_margins(dg_ctx *, const int32_t *called, int32_t budget, const i
  * launches on the seeded state S, out[3] = read-out launches, out[4] = segments, out[5] = peak bytes of device memory the call had
  * reserved; n >= 6 (zeros before the first call).  DG_ERR_ARG: null out or n < 6.  DG_ERR_STATE: no DP state on this context yet. */
 int dg_dp_get_phase_stats(dg_ctx *, int64_t *out, int n);
+/* Phase margins for many called pairs, each at a budget of its own, from ONE joint pass.  Query q = (called[q] = [2][n_levels],
+ * budgets[q]) gets records[record_off[q] .. record_off[q + 1]) and best_values[q] = V at budgets[q]; its records are, field for field,
+ * what dg_dp_phase_margins(called[q], budgets[q], vertex_class) writes (reserved words, NEG_INF / -1 of a budget nobody fits, ties).
+ * called (host) = [n_called][2][n_levels]; budgets (host) = [n_called], >= 0, in any order, repeats allowed; records (host) has room for
+ * n_called * (n_levels - 1) entries; record_off (host) = [n_called + 1], record_off[0] = 0; a query with fewer than two het levels gets
+ * an empty range.  Why one pass serves all: F, B and the seeded state S mean "at most r", so the states of a pass with bmax + 1 planes
+ * (bmax = the largest of budgets) hold on planes 0..b exactly the states of a call at budget b, and query q reads out
+ * U = max over r = 0..b_q of F[r] + S[b_q - r].  S is seeded again from B at every het level and never accumulates: between a het
+ * level e and the next one below it S depends only on its seed key (e, c_0[e], c_1[e]) and on B, not on the query that asked for it.
+ * Device: the schedule of dg_dp_phase_margins at bmax + 1 planes with a pool of slots in place of the one S, a slot being two rolling
+ * states of the widest level.  The host plans before the first launch: going down the levels a query carries on h_0 <= l < h_last with
+ * the key of its nearest het level above l; the live keys of a level are the distinct keys of the carrying queries, one slot each; a
+ * slot is freed when no query carries its key any more and may be taken by a key seeded at that same level; the number of slots is the
+ * largest live count.  The per-level tables (slot lists; per read-out slot, classes, budget, record; per seed slot, classes) are uploaded
+ * once.  Per level with a live slot ONE backward launch carries every live slot down (a grid dimension over the slot list, the
+ * recurrence and the score matrix of the B launch); per level with read-outs ONE read-out launch (a grid dimension over the queries)
+ * and one finish launch; then one seed launch over the keys created there.  V_b of every budget comes from the sink's bmax + 1 planes
+ * of F, copied once.  Closing check per query: max(cis, trans) <= V at budgets[q] in every record, DG_ERR_STATE naming query and record.
+ * Keys with the classes swapped, (e, c_1, c_0), are each other's transpose in the unpinned DP and could share a slot; they do not here.
+ * Limits and errors are those of dg_dp_phase_margins taken at bmax, and: DG_ERR_ARG for n_called < 1, a null called, budgets, records,
+ * record_off or best_values, a negative budget (the message names the first such query), an id outside its level (the first such
+ * (query, row, level)); DG_ERR_UNSUPPORTED for n_called > 256.  A failed call writes nothing, the statistics included.  Reads and
+ * writes nothing of a run and leaves what dg_dp_get_phase_stats and dg_dp_get_genotype_stats report as it was.  Synchronises.  There is
+ * no pinned variant, for the reason given above. */
+int dg_dp_phase_margins_budgets(dg_ctx *, const int32_t *called, const int32_t *budgets, int64_t n_called, const int32_t *vertex_class,
+                                dg_dp_phase_margin *records, int64_t *record_off, int32_t *best_values);
+/* measurement: the last successful dg_dp_phase_margins_budgets on this context: out[0] = queries, out[1] = records, out[2] = distinct
+ * seed keys created, out[3] = slot-levels (the sum over the levels of the live slots: the backward work on S), out[4] = backward
+ * launches on S, out[5] = read-out launches, out[6] = the largest number of live slots, out[7] = slots allocated, out[8] = segments,
+ * out[9] = peak bytes of device memory the call had reserved; n >= 10 (zeros before the first call).  DG_ERR_ARG: null out or n < 10.
+ * DG_ERR_STATE: no DP state on this context yet. */
+int dg_dp_get_phase_budget_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
