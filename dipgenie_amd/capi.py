@@ -72,6 +72,10 @@ GENOTYPE_ENTRY = np.dtype([("class1", np.int32), ("class2", np.int32), ("vertex1
 PHASE_MARGIN = np.dtype([("level_a", np.int32), ("level_b", np.int32), ("cis_value", np.int32), ("cis_vertex1", np.int32), ("cis_vertex2", np.int32),
                          ("trans_value", np.int32), ("trans_vertex1", np.int32), ("trans_vertex2", np.int32), ("reserved", np.int32, (2,))])
 
+# dg_dp_recombination_margin as a numpy record: one per transition of Context.dp_recombination_margins
+RECOMBINATION_MARGIN = np.dtype([("level", np.int32), ("value", np.int32, (3,)), ("from1", np.int32, (3,)), ("from2", np.int32, (3,)), ("to1", np.int32, (3,)),
+                                 ("to2", np.int32, (3,))])
+
 # dg_dp_pair_objective as a numpy record: what Context.dp_objective_paths and Context.dp_answer_objectives return
 PAIR_OBJECTIVE = np.dtype([("hom_shared", np.int32), ("hom_single", np.int32), ("het_single", np.int32), ("het_both", np.int32)])
 
@@ -101,6 +105,7 @@ SYMBOLS = [
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
     "dg_dp_run_pinned", "dg_dp_get_pin_stats", "dg_dp_genotype_margins_pinned", "dg_dp_genotype_table_pinned",
     "dg_dp_genotype_margins_budgets", "dg_dp_phase_margins", "dg_dp_get_phase_stats", "dg_dp_phase_margins_budgets", "dg_dp_get_phase_budget_stats",
+    "dg_dp_recombination_margins", "dg_dp_get_recombination_stats",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -134,6 +139,8 @@ lib.dg_dp_phase_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_
 lib.dg_dp_get_phase_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_phase_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.dg_dp_get_phase_budget_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+lib.dg_dp_recombination_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+lib.dg_dp_get_recombination_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_genotype_table_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_table.argtypes[1:]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -703,6 +710,40 @@ class Context:
         out = np.zeros(10, np.int64)
         _check(lib.dg_dp_get_phase_budget_stats(self.h, out.ctypes.data, 10), "dg_dp_get_phase_budget_stats")
         return dict(zip(self.PHASE_BUDGET_STATS, out.tolist()))
+
+    def dp_recombination_margins(self, budget, called=None):
+        """Recombination margins: what a crossover at each transition is worth.  budget >= 0; called: None or int32 [n, 2, n_levels]
+        (n <= 256), one cell per level and row, every id inside its level -- the two rows of dp_answer_paths are such a pair.  Returns
+        (records, called_out, best_value): a RECOMBINATION_MARGIN record array, one per transition level -> level + 1: value[s] is the
+        best value of any ordered pair of paths within the budget whose two hops of that transition weigh s together (s = 0, 1, 2),
+        from1/from2 -> to1/to2 the hop pair that attains it (among equals the smallest positions, in that order), NEG_INF and -1
+        where there is none; called_out: None without called, else int32 [n, n_levels - 1, 2] = (s_called, called_value): the weights
+        of the two called hops summed (-1 if either is no edge) and the best value of any pair that takes exactly them (NEG_INF if
+        none does); best_value: that of any pair within the budget, the largest of value[.] at every transition.  Leaves the last
+        run's answers and what the other statistics report alone."""
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        p = None
+        if called is not None:
+            p = np.ascontiguousarray(called, np.int32)
+            if p.ndim != 3 or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+                raise ValueError(f"called must have shape [n, 2, n_levels], got {p.shape}")
+        n = 0 if p is None else p.shape[0]
+        n_levels = g.n_levels if g is not None else (p.shape[2] if p is not None else 2)
+        records = np.zeros(max(n_levels - 1, 1), RECOMBINATION_MARGIN)
+        out = np.zeros((n, max(n_levels - 1, 0), 2), np.int32)
+        best = C.c_int32(0)
+        _check(lib.dg_dp_recombination_margins(self.h, int(budget), p.ctypes.data if n and p.size else None, n, records.ctypes.data, out.ctypes.data if out.size else None,
+                                               C.byref(best)), "dg_dp_recombination_margins")
+        return records[:n_levels - 1], (out if called is not None else None), best.value
+
+    RECOMBINATION_STATS = ("transitions", "edge_launches", "finish_launches", "segments", "levels_twice", "peak_bytes", "launches")
+
+    def dp_recombination_stats(self):
+        """of the last dp_recombination_margins on this context: dict(transitions, edge_launches, finish_launches, segments,
+        levels_twice, peak_bytes, launches)"""
+        out = np.zeros(7, np.int64)
+        _check(lib.dg_dp_get_recombination_stats(self.h, out.ctypes.data, 7), "dg_dp_get_recombination_stats")
+        return dict(zip(self.RECOMBINATION_STATS, out.tolist()))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

@@ -43,6 +43,11 @@
 // backward state, seeded at every het level of the called pair; it launches none of the combination, record or table kernels.
 // dg_dp_phase_margins_budgets (phb_call and the phb_* kernels, below ph_call: their comment has the plan) is that schedule once at the
 // largest budget for many called pairs, with a pool of seeded states, one per live seed key, planned on the host before the first launch.
+// dg_dp_recombination_margins (rb_call and the rb_* kernels, below phb_call: their comment has the plan) is jt_call's schedule with one more
+// gather per level in place of the combination and record kernels: per transition l -> l + 1 the best F_l + d + B_{l+1} over the hop pairs
+// the backward kernel walks, bucketed by the number of weight-1 hops in the pair, with the hop pair that attains it, and per called pair what
+// its own two hops are worth.  It launches none of the combination, record, table or phase kernels and reserves none of their buffers.  Out of
+// scope there: a form with a budget per query, a pinned form, more than one GPU, windows of several transitions.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -1726,7 +1731,357 @@ int phb_call(dg_ctx *c, const int32_t *called, const int32_t *budgets, int64_t n
     return DG_OK;
 }
 
+// ---- dg_dp_recombination_margins: per transition l -> l + 1 and s = 0, 1, 2 the best pair of paths that takes a hop pair of weight
+// sum s there, E[s] = max F_l[i][j][r] + d + B_{l+1}[i'][j'][b - s - r], with the hop pair that attains it (include/dipgenie_hip.h has the
+// definition).  A key is two words, compared one after the other, larger = better:
+//   word 0 = value << 32 | (JT_MAX_K - i)           value descending, then i ascending        (JT_NO_KEY: no hop pair)
+//   word 1 = (JT_MAX_K - j) << 30 | (JT_MAX_K - i') << 15 | (JT_MAX_K - j')                    then j, i', j' ascending
+// so the winner is a function of the set of candidates alone, not of the order lanes or workgroups meet them in.  F, B and d are symmetric
+// in the two haplotypes: the tuple (j, i, j', i') is worth what (i, j, i', j') is and, where i > j, comes before it in the tie order, so
+// the cells j >= i hold every winner and the lanes of j < i do nothing.
+//   * rb_edges_kernel: grid (x blocks, k) as jt_backward_kernel: row i = blockIdx.y, the lanes stride over (j, r).  A lane loads
+//     F_l[i][j][r] once, and only where that is reachable walks out(i) x out(j) with three running maxima of F + d + B_{l+1}[i'][j'][b - s - r],
+//     one per s: inside a cell i and j are fixed, so a candidate is one signed 64-bit word value << 32 | (JT_MAX_K - i') << 15 | (JT_MAX_K - j')
+//     and the update one maximum; the cell's winners are folded into the lane's two-word keys once per cell, and the workgroup reduces per s
+//     (__shfl_xor, one LDS slot per wave) to part[s][i][blockIdx.x];
+//   * rb_finish_kernel: workgroup s < 3 reduces part[s][.][.] to the words of the level's record that belong to s (workgroup 0 the
+//     level too); the workgroups from 3 on answer called_out, one wave per query: the lanes search the in-edges of the two called
+//     destinations for the called sources (the first such in-edge: parallel edges share weight and score), then stride over r.
+__device__ __forceinline__ bool rb_better(long long a0, long long a1, long long b0, long long b1) { return a0 > b0 || (a0 == b0 && a1 > b1); }
+
+// F = level l [k][k][B1], next = B of level l + 1 [kn][kn][B1]; a0 / b0n = first vertex of level l / l + 1, in_base / T = the in-edges of
+// level l + 1, sc = their scores (null: all zero); oo / oe = the out-index; part = [3][k][gridDim.x][2]
+__global__ __launch_bounds__(JT_THREADS) void rb_edges_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ next, int k, int kn, int B1, int a0, int b0n,
+                                                              uint32_t in_base, int T, const uint32_t *__restrict__ oo, const uint32_t *__restrict__ oe,
+                                                              const uint32_t *__restrict__ in_edge, const int32_t *__restrict__ in_dst, const uint16_t *__restrict__ sc,
+                                                              long long *__restrict__ part) {
+    __shared__ long long s_key[3][JT_THREADS / 64][2];
+    const int t = (int)threadIdx.x, i = (int)blockIdx.y;
+    const uint32_t ou0 = oo[a0 + i], ou1 = oo[a0 + i + 1];
+    const int n = k * B1;
+    long long a0k = JT_NO_KEY, a1k = JT_NO_KEY, a2k = JT_NO_KEY, b0k = 0, b1k = 0, b2k = 0;      // the lane's best key per s
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += (int)(gridDim.x * JT_THREADS)) {
+        const int j = x / B1, r = x - j * B1;
+        if (j < i) continue;
+        const int f = F[((int64_t)i * k + j) * B1 + r];
+        if (f == NEG_INF) continue;                                         // nothing of B is read for an unreachable cell
+        const uint32_t ov0 = oo[a0 + j], ov1 = oo[a0 + j + 1];
+        // inside one cell i and j are fixed: a candidate is value << 32 | (JT_MAX_K - i') << 15 | (JT_MAX_K - j'), one signed maximum per s
+        long long c0 = JT_NO_KEY, c1 = JT_NO_KEY, c2 = JT_NO_KEY;
+        for (uint32_t ou = ou0; ou < ou1; ++ou) {
+            const uint32_t eu = oe[ou] - in_base;                           // rank among the in-edges of level l + 1
+            if (eu >= (uint32_t)T) continue;
+            const uint32_t pi = (uint32_t)(in_dst[in_base + eu] - b0n);
+            const int w1 = (int)(in_edge[in_base + eu] >> 31);
+            if (pi >= (uint32_t)kn || B1 - 1 - r - w1 < 0) continue;
+            const uint32_t hi = (uint32_t)(JT_MAX_K - (int)pi) << 15;
+            for (uint32_t ov = ov0; ov < ov1; ++ov) {
+                const uint32_t ev = oe[ov] - in_base;
+                if (ev >= (uint32_t)T) continue;
+                const uint32_t pj = (uint32_t)(in_dst[in_base + ev] - b0n);
+                const int w = w1 + (int)(in_edge[in_base + ev] >> 31);
+                const int r2 = B1 - 1 - r - w;                              // what is left for B
+                if (pj >= (uint32_t)kn || r2 < 0) continue;
+                const int s = next[((int64_t)pi * kn + pj) * B1 + r2];
+                if (s == NEG_INF) continue;
+                const int v = f + s + (sc ? (int)sc[(int64_t)eu * T + ev] : 0);
+                const long long cand = (long long)(((unsigned long long)(uint32_t)v << 32) | hi | (uint32_t)(JT_MAX_K - (int)pj));
+                if (w == 0) c0 = max(c0, cand);
+                else if (w == 1) c1 = max(c1, cand);
+                else c2 = max(c2, cand);
+            }
+        }
+        auto fold = [&](long long c, long long &a, long long &b) {           // the cell's winner of one s against the lane's
+            if (c == JT_NO_KEY) return;
+            const long long ca = (long long)(((unsigned long long)c & 0xFFFFFFFF00000000ull) | (uint32_t)(JT_MAX_K - i));
+            const long long cb = ((long long)(JT_MAX_K - j) << 30) | (c & 0x3FFFFFFF);
+            if (rb_better(ca, cb, a, b)) { a = ca; b = cb; }
+        };
+        fold(c0, a0k, b0k);
+        fold(c1, a1k, b1k);
+        fold(c2, a2k, b2k);
+    }
+    auto reduce = [&](int s, long long a, long long b) {                    // the wave's best key of bucket s into its LDS slot
+        for (int d = 32; d; d >>= 1) {
+            const long long oa = __shfl_xor(a, d), ob = __shfl_xor(b, d);
+            if (rb_better(oa, ob, a, b)) { a = oa; b = ob; }
+        }
+        if ((t & 63) == 0) { s_key[s][t >> 6][0] = a; s_key[s][t >> 6][1] = b; }
+    };
+    reduce(0, a0k, b0k);
+    reduce(1, a1k, b1k);
+    reduce(2, a2k, b2k);
+    __syncthreads();
+    if (t < 3) {
+        long long a = s_key[t][0][0], b = s_key[t][0][1];
+        for (int w = 1; w < JT_THREADS / 64; ++w)
+            if (rb_better(s_key[t][w][0], s_key[t][w][1], a, b)) { a = s_key[t][w][0]; b = s_key[t][w][1]; }
+        long long *out = part + (((int64_t)t * k + i) * gridDim.x + blockIdx.x) * 2;
+        out[0] = a; out[1] = b;
+    }
+}
+
+// grid: 3 + ceil(n / 4) workgroups.  part = [3][k][nx][2] of rb_edges_kernel; rec = the record of level l; F, next, sc and the level's
+// numbers as above; called = [n][2][L] (validated by the host); cout = [n][L - 1][2]
+__global__ __launch_bounds__(JT_THREADS) void rb_finish_kernel(const long long *__restrict__ part, int k, int nx, int a0, int b0n, int l, dg_dp_recombination_margin *__restrict__ rec,
+                                                               const int32_t *__restrict__ F, const int32_t *__restrict__ next, int kn, int B1, uint32_t in_base, int T,
+                                                               const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge, const uint16_t *__restrict__ sc,
+                                                               const int32_t *__restrict__ called, int n, int L, int32_t *__restrict__ cout) {
+    __shared__ long long s_key[JT_THREADS / 64][2];
+    const int t = (int)threadIdx.x;
+    if (blockIdx.x < 3) {                                                   // uniform per workgroup
+        const int s = (int)blockIdx.x;
+        const long long *p = part + (int64_t)s * k * nx * 2;
+        long long a = JT_NO_KEY, b = 0;
+        for (int64_t x = t; x < (int64_t)k * nx; x += JT_THREADS)
+            if (rb_better(p[2 * x], p[2 * x + 1], a, b)) { a = p[2 * x]; b = p[2 * x + 1]; }
+        for (int d = 32; d; d >>= 1) {
+            const long long oa = __shfl_xor(a, d), ob = __shfl_xor(b, d);
+            if (rb_better(oa, ob, a, b)) { a = oa; b = ob; }
+        }
+        if ((t & 63) == 0) { s_key[t >> 6][0] = a; s_key[t >> 6][1] = b; }
+        __syncthreads();
+        if (t == 0) {
+            for (int w = 1; w < JT_THREADS / 64; ++w)
+                if (rb_better(s_key[w][0], s_key[w][1], a, b)) { a = s_key[w][0]; b = s_key[w][1]; }
+            if (s == 0) rec->level = l;
+            if (a == JT_NO_KEY) { rec->value[s] = NEG_INF; rec->from1[s] = rec->from2[s] = rec->to1[s] = rec->to2[s] = -1; }
+            else {
+                rec->value[s] = (int)(a >> 32);
+                rec->from1[s] = a0 + (JT_MAX_K - (int)(a & 0x7FFF));
+                rec->from2[s] = a0 + (JT_MAX_K - (int)((b >> 30) & 0x7FFF));
+                rec->to1[s] = b0n + (JT_MAX_K - (int)((b >> 15) & 0x7FFF));
+                rec->to2[s] = b0n + (JT_MAX_K - (int)(b & 0x7FFF));
+            }
+        }
+        return;
+    }
+    const int q = ((int)blockIdx.x - 3) * (JT_THREADS / 64) + (t >> 6), lane = t & 63;      // uniform per wave
+    if (q >= n) return;
+    uint32_t e[2];                                                          // the first in-edge of each called hop, UINT32_MAX: no edge
+    int pos[2], posn[2];
+    for (int h = 0; h < 2; ++h) {
+        const int u = called[((int64_t)q * 2 + h) * L + l], v = called[((int64_t)q * 2 + h) * L + l + 1];
+        pos[h] = u - a0; posn[h] = v - b0n;
+        uint32_t at = UINT32_MAX;
+        for (uint32_t x = in_off[v] + (uint32_t)lane; x < in_off[v + 1]; x += 64)
+            if ((in_edge[x] & 0x7FFFFFFFu) == (uint32_t)pos[h] && x - in_base < (uint32_t)T) at = min(at, x);
+        for (int d = 32; d; d >>= 1) at = min(at, (uint32_t)__shfl_xor((int)at, d));
+        e[h] = at;
+    }
+    int s = -1, best = NEG_INF;
+    if (e[0] != UINT32_MAX && e[1] != UINT32_MAX) {
+        s = (int)(in_edge[e[0]] >> 31) + (int)(in_edge[e[1]] >> 31);
+        const int d = sc ? (int)sc[(int64_t)(e[0] - in_base) * T + (e[1] - in_base)] : 0;
+        const int32_t *f = F + ((int64_t)pos[0] * k + pos[1]) * B1, *b = next + ((int64_t)posn[0] * kn + posn[1]) * B1;
+        for (int r = lane; r <= B1 - 1 - s; r += 64) {
+            const int fv = f[r], bv = b[B1 - 1 - s - r];
+            if (fv != NEG_INF && bv != NEG_INF) best = max(best, fv + d + bv);
+        }
+        for (int w = 32; w; w >>= 1) best = max(best, __shfl_xor(best, w));
+    }
+    if (lane == 0) {
+        int32_t *out = cout + ((int64_t)q * (L - 1) + l) * 2;
+        out[0] = s; out[1] = best;
+    }
+}
+
+// jt_call's schedule (plan by joint_state_bytes, forward checkpoints of pass 1, the segments from the last to the first with F
+// recomputed, B rolling in two states) with the two rb_* launches per level l < L - 1 in place of that call's combination, record and
+// table launches.  B crosses a segment boundary in its rolling state as it does there.  B_0 is not formed: nothing reads it.
+int rb_call(dg_ctx *c, int32_t budget, const int32_t *called, int64_t n, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_value) {
+    const char *FN = "dg_dp_recombination_margins";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
+    DpState &S = *Sp;
+    if (!records || !best_value) { set_error("%s: records and best_value are required", FN); return DG_ERR_ARG; }
+    if (n < 0 || (n > 0 && (!called || !called_out))) { set_error("%s: n_called = %lld needs called and called_out", FN, (long long)n); return DG_ERR_ARG; }
+    if (budget < 0) { set_error("%s: budget %d is negative", FN, budget); return DG_ERR_ARG; }
+    if (n > JT_MAX_QUERIES) { set_error("%s: %lld called pairs exceed %d per call", FN, (long long)n, JT_MAX_QUERIES); return DG_ERR_UNSUPPORTED; }
+    if ((int64_t)budget + 1 > JT_MAX_PLANES) { set_error("%s: budget + 1 = %lld exceeds %d planes", FN, (long long)budget + 1, JT_MAX_PLANES); return DG_ERR_UNSUPPORTED; }
+    const int L = S.L, nV = S.nV, B1 = budget + 1;
+    if (L < 2 || (int)S.descs.size() < L) { set_error("%s: the loaded graph has %d levels", FN, L); return DG_ERR_STATE; }
+    std::vector<JtLevel> lv((size_t)L);
+    int kmax = 1;
+    int64_t tmax = 0, part_keys = 1;
+    for (int l = 0; l < L; ++l) {
+        const LevelDesc &d = S.descs[(size_t)std::max(l, 1)];
+        lv[l] = l ? JtLevel{d.b0, d.k2, d.in_base, d.T, d.delta_off >= 0, 0} : JtLevel{d.a0, d.k, 0u, 0, false, 0};
+        lv[l].cells = (int64_t)lv[l].k * lv[l].k * B1;
+        kmax = std::max(kmax, lv[l].k);
+        if (lv[l].coloured) tmax = std::max<int64_t>(tmax, lv[l].T);
+        if (l < L - 1) part_keys = std::max(part_keys, (int64_t)3 * lv[l].k * jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS));
+    }
+    if (kmax > JT_MAX_K) { set_error("%s: widest level %d exceeds %d", FN, kmax, JT_MAX_K); return DG_ERR_UNSUPPORTED; }
+    for (int64_t q = 0; q < n; ++q)
+        for (int row = 0; row < 2; ++row)
+            for (int l = 0; l < L; ++l) {
+                const int32_t v = called[(q * 2 + row) * L + l];
+                if ((uint32_t)(v - lv[l].a0) >= (uint32_t)lv[l].k) {
+                    set_error("%s: query %lld row %d level %d: vertex %d is not in its level", FN, (long long)q, row, l, v);
+                    return DG_ERR_ARG;
+                }
+            }
+    hipStream_t s = c->stream;
+    // ---- the plan: segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
+    std::vector<int> seg{0};
+    {
+        int64_t in_seg = 0;
+        for (int l = 0; l < L; ++l) {
+            const int64_t bytes = 4 * lv[l].cells;
+            if (l > seg.back() && in_seg + bytes > S.opt.joint_state_bytes) { seg.push_back(l); in_seg = 0; }
+            in_seg += bytes;
+        }
+    }
+    const int n_seg = (int)seg.size();
+    seg.push_back(L);
+    std::vector<int64_t> ck_off((size_t)n_seg + 1, 0);                     // F of every segment's first level, int32 units
+    int64_t seg_cells = 1, roll_cells = 0, level_cells = 1;
+    for (int g = 0; g < n_seg; ++g) {
+        ck_off[g + 1] = ck_off[g] + lv[seg[g]].cells;
+        int64_t sum = 0;
+        for (int l = seg[g] + 1; l < seg[g + 1]; ++l) { sum += lv[l].cells; if (g + 1 < n_seg) roll_cells = std::max(roll_cells, lv[l].cells); }
+        seg_cells = std::max(seg_cells, sum);
+    }
+    for (int l = 1; l < L; ++l) level_cells = std::max(level_cells, lv[l].cells);      // B of the levels 1 .. L - 1
+    int64_t launches = 0, twice = 0, edge_launches = 0, finish_launches = 0;
+    JtMem M;
+    DevBuf d_called, d_rec, d_cout, d_V, d_part, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back;
+    if (n) if (int rc = M.get(d_called, n * 2 * L * 4)) return rc;
+    if (n) if (int rc = M.get(d_cout, n * (L - 1) * 2 * 4)) return rc;
+    if (int rc = M.get(d_rec, ((int64_t)L - 1) * (int64_t)sizeof(dg_dp_recombination_margin))) return rc;
+    if (int rc = M.get(d_V, 4)) return rc;
+    if (int rc = M.get(d_part, part_keys * 16)) return rc;
+    if (int rc = M.get(d_oo, ((int64_t)nV + 1) * 4)) return rc;
+    if (int rc = M.get(d_ocur, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
+    if (tmax) if (int rc = M.get(d_sc, tmax * tmax * 2)) return rc;
+    if (int rc = M.get(d_ck, ck_off[n_seg] * 4)) return rc;
+    if (n) DG_HIP(hipMemcpyAsync(d_called.p, called, (size_t)(n * 2 * L) * 4, hipMemcpyHostToDevice, s));
+    const LevelDesc *descs = S.d_descs.as<LevelDesc>();
+    const uint32_t *in_off = S.d_in_off.as<uint32_t>(), *in_edge = S.d_in_edge.as<uint32_t>();
+    const int32_t *in_dst = S.d_in_dst.as<int32_t>();
+    uint16_t *sc = d_sc.as<uint16_t>();
+    // the in-edges grouped by source
+    DG_HIP(hipMemsetAsync(d_ocur.p, 0, (size_t)nV * 4, s));
+    hipLaunchKernelGGL(jt_out_count_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>());
+    hipLaunchKernelGGL(jt_out_scan_kernel, dim3(1), dim3(1024), 0, s, d_ocur.as<uint32_t>(), d_oo.as<uint32_t>(), d_ocur.as<uint32_t>(), nV);
+    hipLaunchKernelGGL(jt_out_fill_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>(), d_oe.as<uint32_t>(), (uint32_t)S.n_edges);
+    DG_HIP(hipGetLastError());
+    launches += 3;
+    auto scores = [&](int l) -> const uint16_t * {                          // the matrix of the transition into level l, in d_sc
+        const int T = lv[l].T;
+        if (!lv[l].coloured || T < 1) return nullptr;
+        hipLaunchKernelGGL(jt_scores_kernel, dim3(jt_blocks(T, 64), (unsigned)std::min(T, 16384)), dim3(JT_THREADS), 0, s, T, lv[l].in_base, lv[l - 1].a0, in_edge, in_dst,
+                           colour_csr(S), S.d_eflag.as<uint8_t>(), S.d_eself.as<uint16_t>(), sc);
+        ++launches;
+        return sc;
+    };
+    auto fill = [&](int32_t *st, int l, int pos) {                          // level l: 0 on every plane of the cell (pos, pos)
+        hipLaunchKernelGGL(jt_fill_kernel, dim3(jt_blocks(lv[l].cells, 65536)), dim3(JT_THREADS), 0, s, st, lv[l].cells, ((int64_t)pos * lv[l].k + pos) * B1, B1);
+        ++launches;
+    };
+    auto forward = [&](const int32_t *prev, int32_t *cur, int l) {
+        const uint16_t *m = scores(l);
+        hipLaunchKernelGGL(jt_forward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, prev, cur, lv[l - 1].k, lv[l].k, B1,
+                           lv[l].a0, lv[l].in_base, lv[l].T, in_off, in_edge, m);
+        ++launches;
+    };
+    // ---- pass 1: the state at every segment's first level ----
+    int32_t *ck = d_ck.as<int32_t>();
+    fill(ck, 0, 0);
+    if (n_seg > 1) {
+        if (int rc = M.get(d_roll, 2 * roll_cells * 4)) return rc;
+        int32_t *roll = d_roll.as<int32_t>();
+        const int32_t *prev = ck;
+        int g = 0;
+        for (int l = 1; l <= seg[n_seg - 1]; ++l) {
+            int32_t *dst;
+            if (l == seg[g + 1]) dst = ck + ck_off[++g];
+            else { dst = roll + (l & 1) * roll_cells; ++twice; }
+            forward(prev, dst, l);
+            prev = dst;
+        }
+        DG_HIP(hipGetLastError());
+        DG_HIP(hipStreamSynchronize(s));                                    // the rolling states go before the segment buffers come
+        M.drop(d_roll);
+    }
+    // ---- the segments, last first ----
+    if (int rc = M.get(d_seg, seg_cells * 4)) return rc;
+    if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
+    int32_t *back = d_back.as<int32_t>();
+    std::vector<const int32_t *> Fp((size_t)L, nullptr);
+    for (int g = n_seg - 1; g >= 0; --g) {
+        const int a = seg[g], e = seg[g + 1];
+        Fp[a] = ck + ck_off[g];
+        int64_t at = 0;
+        for (int l = a + 1; l < e; ++l) {
+            int32_t *dst = d_seg.as<int32_t>() + at;
+            at += lv[l].cells;
+            forward(Fp[l - 1], dst, l);
+            Fp[l] = dst;
+        }
+        for (int l = e - 1; l >= a; --l) {
+            int32_t *cur = back + (l & 1) * level_cells;
+            if (l == L - 1) {
+                const int sink = nV - 1 - lv[l].a0;
+                fill(cur, l, sink);
+                DG_HIP(hipMemcpyAsync(d_V.p, Fp[l] + ((int64_t)sink * lv[l].k + sink) * B1 + budget, 4, hipMemcpyDeviceToDevice, s));
+                continue;
+            }
+            const int32_t *next = back + ((l + 1) & 1) * level_cells;
+            const uint16_t *m = scores(l + 1);
+            const unsigned nx = jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS);
+            hipLaunchKernelGGL(rb_edges_kernel, dim3(nx, (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, Fp[l], next, lv[l].k, lv[l + 1].k, B1, lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base,
+                               lv[l + 1].T, (const uint32_t *)d_oo.as<uint32_t>(), (const uint32_t *)d_oe.as<uint32_t>(), in_edge, in_dst, m, d_part.as<long long>());
+            hipLaunchKernelGGL(rb_finish_kernel, dim3(3 + (unsigned)((n + JT_THREADS / 64 - 1) / (JT_THREADS / 64))), dim3(JT_THREADS), 0, s, (const long long *)d_part.as<long long>(),
+                               lv[l].k, (int)nx, lv[l].a0, lv[l + 1].a0, l, d_rec.as<dg_dp_recombination_margin>() + l, Fp[l], next, lv[l + 1].k, B1, lv[l + 1].in_base, lv[l + 1].T,
+                               in_off, in_edge, m, (const int32_t *)d_called.as<int32_t>(), (int)n, L, d_cout.as<int32_t>());
+            ++edge_launches; ++finish_launches; launches += 2;
+            if (l > 0) {
+                hipLaunchKernelGGL(jt_backward_kernel, dim3(nx, (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, next, cur, lv[l].k, lv[l + 1].k, B1, lv[l].a0, lv[l + 1].a0,
+                                   lv[l + 1].in_base, lv[l + 1].T, d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
+                ++launches;
+            }
+        }
+        DG_HIP(hipGetLastError());
+    }
+    // the caller's arrays are written only if the call succeeds
+    std::vector<dg_dp_recombination_margin> recs((size_t)L - 1);
+    std::vector<int32_t> couts((size_t)(n * (L - 1) * 2));
+    int32_t V = NEG_INF;
+    DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_recombination_margin), hipMemcpyDeviceToHost, s));
+    if (n) DG_HIP(hipMemcpyAsync(couts.data(), d_cout.p, couts.size() * 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(&V, d_V.p, 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipStreamSynchronize(s));
+    // the closing check: at every transition the best pair of paths takes some hop pair of it
+    for (int l = 0; l < L - 1; ++l) {
+        const dg_dp_recombination_margin &r = recs[(size_t)l];
+        if (std::max(r.value[0], std::max(r.value[1], r.value[2])) != V) {
+            set_error("%s: level %d: the values %d, %d, %d of its transition do not reach the sink's value %d at budget %d", FN, l, r.value[0], r.value[1], r.value[2], V, budget);
+            return DG_ERR_STATE;
+        }
+    }
+    S.rb_stats[0] = L - 1; S.rb_stats[1] = edge_launches; S.rb_stats[2] = finish_launches; S.rb_stats[3] = n_seg; S.rb_stats[4] = twice; S.rb_stats[5] = M.peak;
+    S.rb_stats[6] = launches;
+    memcpy(records, recs.data(), recs.size() * sizeof(dg_dp_recombination_margin));
+    if (n) memcpy(called_out, couts.data(), couts.size() * 4);
+    *best_value = V;
+    return DG_OK;
+}
+
 }  // namespace
+
+int dp_recombination_margins(dg_ctx *c, int32_t budget, const int32_t *called, int64_t n, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_value) {
+    return rb_call(c, budget, called, n, records, called_out, best_value);
+}
+
+int dp_recombination_stats(dg_ctx *c, int64_t *out, int n) {
+    if (!out || n < 7) { set_error("dg_dp_get_recombination_stats: out needs 7 words"); return DG_ERR_ARG; }
+    if (!c->dp) { set_error("dg_dp_get_recombination_stats: no graph loaded"); return DG_ERR_STATE; }
+    for (int q = 0; q < 7; ++q) out[q] = c->dp->rb_stats[q];
+    return DG_OK;
+}
 
 int dp_phase_margins(dg_ctx *c, const int32_t *called, int32_t budget, const int32_t *vertex_class, dg_dp_phase_margin *records, int64_t *n_records, int32_t *best_value) {
     return ph_call(c, called, budget, vertex_class, records, n_records, best_value);
@@ -1833,4 +2188,15 @@ extern "C" int dg_dp_phase_margins_budgets(dg_ctx *c, const int32_t *called, con
 extern "C" int dg_dp_get_phase_budget_stats(dg_ctx *c, int64_t *out, int n) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_phase_budget_stats(c, out, n);
+}
+
+extern "C" int dg_dp_recombination_margins(dg_ctx *c, int32_t budget, const int32_t *called, int64_t n_called, dg_dp_recombination_margin *records, int32_t *called_out,
+                                           int32_t *best_value) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_recombination_margins(c, budget, called, n_called, records, called_out, best_value);
+}
+
+extern "C" int dg_dp_get_recombination_stats(dg_ctx *c, int64_t *out, int n) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_recombination_stats(c, out, n);
 }

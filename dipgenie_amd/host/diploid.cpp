@@ -96,7 +96,7 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     dg_dp_graph view = p.dpg.view(p.opt.R);
     view.n_vertices = g.n; view.n_levels = (int32_t)g.level_off.size() - 1;
     view.level_off = g.level_off.data(); view.out_off = g.adj_off.data(); view.out_dst = g.adj_dst.data(); view.out_w = g.adj_w.data();
-    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty() && p.opt.pins_file.empty() && p.opt.phase_margins.empty()) {
+    if (p.opt.budgets.empty() && p.opt.site_margins.empty() && p.opt.objective_table.empty() && p.opt.genotype_margins.empty() && p.opt.genotype_table.empty() && p.opt.pins_file.empty() && p.opt.phase_margins.empty() && p.opt.recombination_margins.empty()) {
         if (be.dp_solve_diploid(be.ctx, &view, &answers[0].res) != 0) return backend_error(be, "dp_solve_diploid");
         return "";
     }
@@ -114,6 +114,9 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     if (!p.opt.phase_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_phase_margins)) return "--phase-margins: this backend has no dp_phase_margins";
     // and --budget-phase-margins: the answers at the listed limits stay behind, one joint pass describes the phase of them all
     if (!p.opt.budget_phase_margins.empty() && (!be.dp_answer_paths || !be.dp_phase_margins_budgets)) return "--budget-phase-margins: this backend has no dp_phase_margins_budgets";
+    // and --recombination-margins: the called hops are those of the answer that stays behind
+    if (!p.opt.recombination_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_recombination_margins || !be.dp_score_paths))
+        return "--recombination-margins: this backend has no dp_recombination_margins";
     // and --pins: the same run under the file's cell constraints
     if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
     // and --pinned-genotype-margins / --pinned-genotype-table: the joint pass under the same constraints
@@ -574,6 +577,82 @@ std::string write_phase_margins(Pipeline &p, const ExpandedGraph &g, const std::
     return "";
 }
 
+// level  vertex1_from segment1_from vertex1_to segment1_to w1  vertex2_from segment2_from vertex2_to segment2_to w2  s_called value
+// value_s0 value_s1 value_s2  alt_s alt_value margin  alt_from1 alt_to1 alt_from2 alt_to2: one row per transition level -> level + 1.  The
+// two hops of the answer at -R with their weights, s_called = w1 + w2, value = the best pair of paths within -R that takes exactly these
+// two hops -- the answer is one, so it must be the run's DP value; value_s = the best pair that spends s crossovers at this transition;
+// alt_s = the best other s (among equals the smaller), its value and hop pair, margin = value - alt_value; '.' where there is none.
+// A row with s_called > 0 is a breakpoint of the answer: margin 0 there says the crossover can be dropped or moved at no cost.  Without a
+// pair of paths that fits -R the file holds the header alone.
+std::string write_recombination_margins(Pipeline &p, const ExpandedGraph &g) {
+    const double t0 = now_s();
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    RecombinationMargins &rm = p.sum.recombination_margins;
+    rm = RecombinationMargins();
+    rm.set = true;
+    std::vector<int32_t> paths(2 * (size_t)L, 0);
+    if (be.dp_answer_paths(be.ctx, p.opt.R, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+    const int64_t T = paths[0] >= 0 ? L - 1 : 0;
+    std::vector<dg_dp_recombination_margin> rec((size_t)std::max(L - 1, 1));
+    std::vector<int32_t> out(2 * (size_t)std::max(L - 1, 1), 0);
+    dg_dp_pair_score score = {};
+    if (T) {
+        int32_t best = 0;
+        if (be.dp_recombination_margins(be.ctx, p.opt.R, paths.data(), 1, rec.data(), out.data(), &best) != 0) return backend_error(be, "dp_recombination_margins");
+        int64_t stats[7] = {0, 0, 0, 0, 0, 0, 0};
+        if (be.dp_recombination_stats && be.dp_recombination_stats(be.ctx, stats, 7) != 0) return backend_error(be, "dp_recombination_stats");
+        rm.segments = stats[3];
+        if (best != p.sum.dp_value) return "--recombination-margins: the joint pass finds " + std::to_string(best) + ", the run's DP value is " + std::to_string(p.sum.dp_value);
+        if (be.dp_score_paths(be.ctx, paths.data(), 1, &score) != 0) return backend_error(be, "dp_score_paths");
+    }
+    auto weight = [&](int32_t u, int32_t v) -> std::string {             // of the hop u -> v (parallel edges share it)
+        for (int64_t e = g.adj_off[(size_t)u]; e < g.adj_off[(size_t)u + 1]; ++e)
+            if (g.adj_dst[(size_t)e] == v) return std::to_string((int)g.adj_w[(size_t)e]);
+        return ".";
+    };
+    std::string text = "level\tvertex1_from\tsegment1_from\tvertex1_to\tsegment1_to\tw1\tvertex2_from\tsegment2_from\tvertex2_to\tsegment2_to\tw2\ts_called\tvalue\tvalue_s0\tvalue_s1\tvalue_s2\t"
+                       "alt_s\talt_value\tmargin\talt_from1\talt_to1\talt_from2\talt_to2\n";
+    for (int64_t l = 0; l < T; ++l) {
+        const dg_dp_recombination_margin &r = rec[(size_t)l];
+        const int32_t s_called = out[2 * (size_t)l], value = out[2 * (size_t)l + 1];
+        if (s_called < 0 || value != p.sum.dp_value)
+            return "--recombination-margins: level " + std::to_string(l) + ": the answer's hops are worth " + std::to_string(value) + " (s_called " + std::to_string(s_called) + "), the run's DP value is " +
+                   std::to_string(p.sum.dp_value);
+        text += std::to_string(l);
+        for (int h = 0; h < 2; ++h) {
+            const int32_t u = paths[(size_t)h * L + l], v = paths[(size_t)h * L + l + 1];
+            text += '\t' + std::to_string(u) + '\t' + segment_name(p, g, u) + '\t' + std::to_string(v) + '\t' + segment_name(p, g, v) + '\t' + weight(u, v);
+        }
+        text += '\t' + std::to_string(s_called) + '\t' + std::to_string(value);
+        int alt = -1;
+        for (int s = 0; s < 3; ++s) {
+            text += '\t' + (r.from1[s] >= 0 ? std::to_string(r.value[s]) : std::string("."));
+            if (s != s_called && r.from1[s] >= 0 && (alt < 0 || r.value[s] > r.value[alt])) alt = s;      // ties: the smaller s
+        }
+        rm.called_recombinations += s_called;
+        if (alt >= 0) {
+            const int32_t margin = value - r.value[alt];
+            text += '\t' + std::to_string(alt) + '\t' + std::to_string(r.value[alt]) + '\t' + std::to_string(margin) + '\t' + std::to_string(r.from1[alt]) + '\t' + std::to_string(r.to1[alt]) + '\t' +
+                    std::to_string(r.from2[alt]) + '\t' + std::to_string(r.to2[alt]);
+            if (s_called > 0 && margin == 0) rm.breakpoints_margin0++;
+            else if (s_called > 0 && margin > 0 && (rm.min_positive_breakpoint_margin < 0 || margin < rm.min_positive_breakpoint_margin)) rm.min_positive_breakpoint_margin = margin;
+            if (s_called == 0 && r.value[alt] == p.sum.dp_value) rm.co_optimal_elsewhere++;
+        } else text += "\t.\t.\t.\t.\t.\t.\t.";
+        text += '\n';
+    }
+    rm.transitions = T;
+    if (T && rm.called_recombinations != (int64_t)score.r1 + score.r2)
+        return "--recombination-margins: the answer's hops spend " + std::to_string(rm.called_recombinations) + " crossovers, dp_score_paths counts " + std::to_string(score.r1) + " + " + std::to_string(score.r2);
+    std::ofstream f(p.opt.recombination_margins, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open recombination margins file " + p.opt.recombination_margins;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + p.opt.recombination_margins + " failed";
+    rm.wall_s = now_s() - t0;
+    return "";
+}
+
 // r and the columns of --phase-margins: per listed limit r with an answer, in the order of the list, one row per pair of neighbouring het
 // levels of the answer at r, cis and trans within r.  ONE device call serves every limit (dp_phase_margins_budgets: the joint pass at the
 // largest of them; answers at neighbouring limits share most of their seeded states).  A limit nobody fits is left out: it has no paths
@@ -865,11 +944,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         }
     }
     const bool pinned_joint = !opt.pinned_genotype_margins.empty() || !opt.pinned_genotype_table.empty();
-    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty() || !opt.recombination_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : !opt.phase_margins.empty() ? "--phase-margins" : "--budget-phase-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : !opt.phase_margins.empty() ? "--phase-margins" : !opt.budget_phase_margins.empty() ? "--budget-phase-margins" : "--recombination-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
@@ -950,6 +1029,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         t0 = now_s();
         if (failed(write_budget_phase_margins(*this, g, classes, budgets, answers), err)) return -1;
         stamp("budget_phase_margins", t0);
+    }
+    if (!opt.recombination_margins.empty()) {                             // after the phase options: each of them alone is exactly what it was
+        t0 = now_s();
+        if (failed(write_recombination_margins(*this, g), err)) return -1;
+        stamp("recombination_margins", t0);
     }
     if (pinned_joint) {                                                   // the same under --pins: one pass serves both files
         t0 = now_s();

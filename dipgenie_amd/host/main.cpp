@@ -181,6 +181,18 @@ static int b_dp_phase_budget_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_phase_budget_stats(x, out, n) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_recombination_margins(void *c, int32_t budget, const int32_t *called, int64_t n, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_recombination_margins(x, budget, called, n, records, called_out, best) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_recombination_stats(void *c, int64_t *out, int n) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_recombination_stats(x, out, n) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_score_paths(void *c, const int32_t *paths, int64_t n, dg_dp_pair_score *out) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_score_paths(x, paths, n, out) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_answer_objectives(void *c, const int32_t *budgets, int32_t n, dg_dp_pair_objective *out) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_answer_objectives(x, budgets, n, out) : DG_ERR_NO_DEVICE;
@@ -301,6 +313,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --genotype-table FILE     (MI355X build, -p2) per level one row for every genotype a pair of paths within -R passes through: its best cell, value, distance to the DP value, whether the answer has it (TSV)\n");
     fprintf(fp, "    --phase-margins FILE      (MI355X build, -p2) per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps the answer's phase between them (cis) against the best that switches it (trans), and the margin (TSV)\n");
     fprintf(fp, "    --budget-phase-margins FILE   (MI355X build, -p2, with --budgets) the rows of --phase-margins for the answer at every listed limit that has one, each within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
+    fprintf(fp, "    --recombination-margins FILE   (MI355X build, -p2) per transition level -> level + 1: the two hops of the answer at -R, the crossovers they spend there, and the best pair of paths within -R that spends 0, 1 or 2 there; the best other number against the answer's is the margin of the breakpoint, or of its absence (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --pins FILE           (MI355X build, -p2) run the DP under cell constraints: rows level, vertex1, vertex2 [, require|forbid|require-ordered|forbid-ordered], tab-separated, . = any vertex, ids as --genotype-table prints them\n");
@@ -326,7 +339,7 @@ int main(int argc, char **argv) {
     std::vector<int> shard_devices;
     std::string budgets_arg;
     bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
-    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false, have_budget_phase = false;
+    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false, have_budget_phase = false, have_recombination = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -362,6 +375,12 @@ int main(int argc, char **argv) {
                 have_budget_phase = true;                              // (a missing value is an empty file name: refused below)
                 const char *v = val("--budget-phase-margins");
                 p.opt.budget_phase_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--recombination-margins", 23) && (argv[i][23] == 0 || argv[i][23] == '=')) {
+                have_recombination = true;                             // (a missing value is an empty file name: refused below)
+                const char *v = val("--recombination-margins");
+                p.opt.recombination_margins = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--phase-margins", 15) && (argv[i][15] == 0 || argv[i][15] == '=')) {
@@ -509,6 +528,13 @@ int main(int argc, char **argv) {
         if (sharded) { fprintf(stderr, "[E::main] --phase-margins does not go with --gpus / --shard-transport\n"); return 1; }
         if (have_pins) { fprintf(stderr, "[E::main] --phase-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
     }
+    // --recombination-margins FILE: the same; it too describes the unconstrained DP
+    if (have_recombination) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --recombination-margins describes the crossovers of the diploid route (-p2)\n"); return 1; }
+        if (p.opt.recombination_margins.empty()) { fprintf(stderr, "[E::main] --recombination-margins needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --recombination-margins does not go with --gpus / --shard-transport\n"); return 1; }
+        if (have_pins) { fprintf(stderr, "[E::main] --recombination-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
+    }
     // --objective-table FILE: the same
     if (have_objective_table) {
         if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --objective-table describes the pairs of paths of the diploid route (-p2)\n"); return 1; }
@@ -562,6 +588,9 @@ int main(int argc, char **argv) {
     p.be.dp_phase_stats = b_dp_phase_stats;
     p.be.dp_phase_margins_budgets = b_dp_phase_margins_budgets;
     p.be.dp_phase_budget_stats = b_dp_phase_budget_stats;
+    p.be.dp_recombination_margins = b_dp_recombination_margins;
+    p.be.dp_recombination_stats = b_dp_recombination_stats;
+    p.be.dp_score_paths = b_dp_score_paths;
     p.be.dp_run_pinned = b_dp_pinned;
     p.be.dp_pin_stats = b_dp_pin_stats;
     p.be.free_buf = dg_free;
@@ -662,6 +691,13 @@ int main(int argc, char **argv) {
                         (long long)pm.records, (long long)pm.with_alternative, (long long)pm.margin0);
                 if (pm.min_positive_margin >= 0) fprintf(f, "%d", pm.min_positive_margin); else fprintf(f, "null");
                 fprintf(f, ", \"segments\": %lld, \"wall_s\": %.6f}", (long long)pm.segments, pm.wall_s);
+            }
+            if (p.sum.recombination_margins.set) {                      // a recount of FILE: breakpoints = rows with s_called > 0; min_positive_breakpoint_margin null: none is positive
+                const dg::RecombinationMargins &rm = p.sum.recombination_margins;
+                fprintf(f, ", \"recombination_margins\": {\"transitions\": %lld, \"called_recombinations\": %lld, \"breakpoints_margin0\": %lld, \"min_positive_breakpoint_margin\": ",
+                        (long long)rm.transitions, (long long)rm.called_recombinations, (long long)rm.breakpoints_margin0);
+                if (rm.min_positive_breakpoint_margin >= 0) fprintf(f, "%d", rm.min_positive_breakpoint_margin); else fprintf(f, "null");
+                fprintf(f, ", \"co_optimal_elsewhere\": %lld, \"segments\": %lld, \"wall_s\": %.6f}", (long long)rm.co_optimal_elsewhere, (long long)rm.segments, rm.wall_s);
             }
             if (p.sum.budget_phase_margins.set) {                       // per listed limit with an answer the fields of phase_margins; one device call
                 const dg::BudgetPhaseMargins &bp = p.sum.budget_phase_margins;

@@ -105,6 +105,12 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     int (*dp_phase_margins_budgets)(void *, const int32_t *called, const int32_t *budgets, int64_t n_called, const int32_t *vertex_class, dg_dp_phase_margin *records,
                                     int64_t *record_off, int32_t *best_values) = nullptr;
     int (*dp_phase_budget_stats)(void *, int64_t *out, int n) = nullptr;
+    // optional (--recombination-margins): per transition the best pair of paths with 0, 1 or 2 crossovers there and what the called hops are
+    // worth (dg_dp_recombination_margins), that call's statistics (dg_dp_get_recombination_stats), and the score of a pair of paths
+    // (dg_dp_score_paths: r1 + r2 of the answer, against the called crossovers)
+    int (*dp_recombination_margins)(void *, int32_t budget, const int32_t *called, int64_t n_called, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_value) = nullptr;
+    int (*dp_recombination_stats)(void *, int64_t *out, int n) = nullptr;
+    int (*dp_score_paths)(void *, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out) = nullptr;
 };
 
 // one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
@@ -142,6 +148,7 @@ struct Options {
     std::string pinned_genotype_table;   // (ours) --pinned-genotype-table, with --pins: the file of --genotype-table for the DP under the pins
     std::string phase_margins;   // (ours) --phase-margins: TSV with one row per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps its phase against the best that switches it (diploid)
     std::string budget_phase_margins; // (ours) --budget-phase-margins, with --budgets: the rows of --phase-margins for the answer at every listed limit that has one, behind a column r, from one joint pass (diploid)
+    std::string recombination_margins; // (ours) --recombination-margins: TSV with one row per transition: the crossovers the answer at -R spends there against the best pair of paths that spends another number there (diploid)
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -267,6 +274,13 @@ struct BudgetPhaseMargins {   // --budget-phase-margins: per listed limit with a
     double wall_s = 0;
 };
 
+struct RecombinationMargins { // --recombination-margins: over the transitions of the answer at -R
+    bool set = false;
+    int64_t transitions = 0, called_recombinations = 0, breakpoints_margin0 = 0, co_optimal_elsewhere = 0, segments = 0;   // breakpoints: rows with s_called > 0
+    int32_t min_positive_breakpoint_margin = -1; // -1: no breakpoint with a positive margin
+    double wall_s = 0;
+};
+
 struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
     bool set = false;
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
@@ -295,6 +309,7 @@ struct Summary {              // what tests and the CLI report
     GenotypeTable pinned_genotype_table;       // --pinned-genotype-table
     PhaseMargins phase_margins;
     BudgetPhaseMargins budget_phase_margins;
+    RecombinationMargins recombination_margins;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
     PinSummary pins;

@@ -458,6 +458,49 @@ int dg_dp_phase_margins_budgets(dg_ctx *, const int32_t *called, const int32_t *
  * out[9] = peak bytes of device memory the call had reserved; n >= 10 (zeros before the first call).  DG_ERR_ARG: null out or n < 10.
  * DG_ERR_STATE: no DP state on this context yet. */
 int dg_dp_get_phase_budget_stats(dg_ctx *, int64_t *out, int n);
+/* Recombination margins: what a crossover at each transition is worth.  F, B, d, "reachable" and V_b are those of
+ * dg_dp_genotype_margins; both states mean "at most r".  For the transition t = l -> l + 1 (0 <= l < n_levels - 1) and s in {0, 1, 2}:
+ *   E_t[s] = max over the ORDERED hop pairs (i -> i', w1), (j -> j', w2) of that transition with w1 + w2 = s, s <= b, and over
+ *            r = 0 .. b - s with F_l[i][j][r] and B_{l+1}[i'][j'][b - s - r] both reachable, of
+ *            F_l[i][j][r] + d(i, j -> i', j') + B_{l+1}[i'][j'][b - s - r];
+ * NEG_INF where there is none: the value of the best pair of paths that spends exactly s of its crossovers at t.  The argument is the
+ * hop pair that attains E_t[s]: value descending, then the smallest (i, j, i', j') in that lexicographic order of positions inside the
+ * levels.  d is symmetric in the two haplotypes, so the winning tuple has i <= j.  The loader refuses parallel edges of different
+ * weights, so a hop is its two vertices. */
+typedef struct dg_dp_recombination_margin {
+    int32_t level;                        /* l: the transition l -> l + 1 */
+    int32_t value[3];                     /* E_t[0], E_t[1], E_t[2]; NEG_INF if no pair of paths spends that many there */
+    int32_t from1[3], from2[3];           /* the vertices i, j of level l of the winning hop pair per s; -1 with NEG_INF */
+    int32_t to1[3], to2[3];               /* the vertices i', j' of level l + 1; -1 with NEG_INF */
+} dg_dp_recombination_margin;
+/* records (host) = [n_levels - 1], ascending by level; they do not depend on called.  called (host) = [n_called][2][n_levels] vertex
+ * ids, one cell per level, every id inside its level, or NULL with n_called = 0; called_out (host) = [n_called][n_levels - 1][2]:
+ * per query and transition s_called = the sum of the weights of the two called hops (called[q][h][l] -> called[q][h][l + 1]), -1 if
+ * either is no edge, and called_value = the value above restricted to the called ordered hop pair (NEG_INF if it is unreachable, no
+ * edge, or s_called > b).  *best_value = V_b.  Closing check: max over s of E_t[s] == V_b at every transition, DG_ERR_STATE naming the
+ * level otherwise.  A budget nobody fits is an answer: NEG_INF / -1 in every record, DG_OK.
+ * Device: rb_call, the schedule of dg_dp_genotype_margins (segments by option joint_state_bytes, forward checkpoints, the segments
+ * from the last to the first with F recomputed, B rolling in two states) with that call's combination, record and table launches
+ * replaced, per level l < n_levels - 1, by two gathers that run after the transition's score matrix is formed and while B_{l+1} is
+ * still the "next" state: rb_edges_kernel (row i = blockIdx.y, the lanes over (j >= i, r): F_l[i][j][r] loaded once, out(i) x out(j)
+ * walked, three running maxima, one per s, of one 64-bit word value | i' | j' each; wave and workgroup reduction to one two-word key
+ * (value, i | j, i', j') per (s, row, workgroup of the row)) and rb_finish_kernel (one workgroup per s reduces the keys to the level's record in a device array that is
+ * copied out once; in the same launch one wave per query finds the ranks of the called hops among the in-edges, reads d and walks r).
+ * B_0 is not formed: nothing reads it.  No atomics, every word has one owner, nothing depends on the order of lanes or workgroups.
+ * Limits and errors are those of dg_dp_phase_margins: DG_ERR_UNSUPPORTED for a widest level > 32767, budget + 1 > 4096 or
+ * n_called > 256; DG_ERR_ARG for a null records or best_value, n_called < 0, n_called > 0 with a null called or called_out, a negative
+ * budget, an id outside its level (the message names the first such (query, row, level)); DG_ERR_STATE without a graph.  Results are
+ * staged on the host: a refused or failed call writes nothing, the statistics included.  Needs dg_dp_load_graph only, reads and writes
+ * nothing of a run, and leaves what the genotype, phase and pin statistics report as it was.  Synchronises.
+ * Not here: a form with a budget per query, a pinned form, more than one GPU, and windows of several transitions -- a breakpoint
+ * that can slide by one level shows as margin 0 at both transitions, and that is the intended reading. */
+int dg_dp_recombination_margins(dg_ctx *, int32_t budget, const int32_t *called, int64_t n_called, dg_dp_recombination_margin *records,
+                                int32_t *called_out, int32_t *best_value);
+/* measurement: the last successful dg_dp_recombination_margins on this context: out[0] = transitions, out[1] = edge-kernel launches,
+ * out[2] = finish launches, out[3] = segments, out[4] = levels swept forward twice, out[5] = peak bytes of device memory the call had
+ * reserved, out[6] = launches in all; n >= 7 (zeros before the first call).  DG_ERR_ARG: null out or n < 7.  DG_ERR_STATE: no DP state
+ * on this context yet. */
+int dg_dp_get_recombination_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
