@@ -105,7 +105,7 @@ SYMBOLS = [
     "dg_sketch_tag_reads", "dg_dp_genotype_margins", "dg_dp_get_genotype_stats", "dg_dp_genotype_table",
     "dg_dp_run_pinned", "dg_dp_get_pin_stats", "dg_dp_genotype_margins_pinned", "dg_dp_genotype_table_pinned",
     "dg_dp_genotype_margins_budgets", "dg_dp_phase_margins", "dg_dp_get_phase_stats", "dg_dp_phase_margins_budgets", "dg_dp_get_phase_budget_stats",
-    "dg_dp_recombination_margins", "dg_dp_get_recombination_stats",
+    "dg_dp_recombination_margins", "dg_dp_get_recombination_stats", "dg_dp_recombination_margins_budgets", "dg_dp_get_recombination_budget_stats",
 ]
 
 lib.dg_create.restype = C.c_void_p
@@ -141,6 +141,8 @@ lib.dg_dp_phase_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, 
 lib.dg_dp_get_phase_budget_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_recombination_margins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
 lib.dg_dp_get_recombination_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+lib.dg_dp_recombination_margins_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.dg_dp_get_recombination_budget_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.dg_dp_genotype_table_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + lib.dg_dp_genotype_table.argtypes[1:]
 lib.dg_dp_objective_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.dg_dp_answer_objectives.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -744,6 +746,40 @@ class Context:
         out = np.zeros(7, np.int64)
         _check(lib.dg_dp_get_recombination_stats(self.h, out.ctypes.data, 7), "dg_dp_get_recombination_stats")
         return dict(zip(self.RECOMBINATION_STATS, out.tolist()))
+
+    def dp_recombination_margins_budgets(self, budgets, called=None):
+        """dp_recombination_margins for every listed budget from one joint pass at the largest of them.  budgets: n integers >= 0
+        (1 <= n <= 256), in any order, repeats allowed; called: None or int32 [n, 2, n_levels], the pair of cells per level of query q.
+        Returns (records, called_out, best_values): a RECOMBINATION_MARGIN record array [n, n_levels - 1], called_out int32
+        [n, n_levels - 1, 2] (None without called) and int32 [n]; query q is exactly what dp_recombination_margins(budgets[q],
+        called[q:q + 1]) answers, s_called and called_value at its own budget, best_values[q] the best value of any pair within
+        budgets[q].  Queries of one budget share one set of records, computed once.  Leaves the last run's answers and what every
+        other statistics call reports alone."""
+        b = np.ascontiguousarray(budgets, np.int32).reshape(-1)
+        n = b.shape[0]
+        g = getattr(self, "_g", None)                      # (no graph loaded: the library answers DG_ERR_STATE)
+        p = None
+        if called is not None:
+            p = np.ascontiguousarray(called, np.int32)
+            if p.ndim != 3 or p.shape[0] != n or p.shape[1] != 2 or (g is not None and p.shape[2] != g.n_levels):
+                raise ValueError(f"called must have shape [{n}, 2, n_levels], got {p.shape}")
+        n_levels = g.n_levels if g is not None else (p.shape[2] if p is not None else 2)
+        T = max(n_levels - 1, 0)
+        records = np.zeros((max(n, 1), max(T, 1)), RECOMBINATION_MARGIN)
+        out = np.zeros((max(n, 1), max(T, 1), 2), np.int32)
+        best = np.zeros(max(n, 1), np.int32)
+        _check(lib.dg_dp_recombination_margins_budgets(self.h, b.ctypes.data if n else None, n, p.ctypes.data if p is not None and p.size else None, records.ctypes.data,
+                                                       out.ctypes.data, best.ctypes.data), "dg_dp_recombination_margins_budgets")
+        return records[:n, :T], (out[:n, :T] if called is not None else None), best[:n]
+
+    RECOMBINATION_BUDGET_STATS = ("queries", "distinct_budgets", "transitions", "edge_launches", "finish_launches", "segments", "levels_twice", "peak_bytes", "launches")
+
+    def dp_recombination_budget_stats(self):
+        """of the last dp_recombination_margins_budgets on this context: dict(queries, distinct_budgets, transitions, edge_launches,
+        finish_launches, segments, levels_twice, peak_bytes, launches)"""
+        out = np.zeros(9, np.int64)
+        _check(lib.dg_dp_get_recombination_budget_stats(self.h, out.ctypes.data, 9), "dg_dp_get_recombination_budget_stats")
+        return dict(zip(self.RECOMBINATION_BUDGET_STATS, out.tolist()))
 
     def dp_objective_paths(self, paths):
         """paths: int32 [n, 2, n_levels], as for dp_score_paths.  Returns a PAIR_OBJECTIVE record array of n entries: the hom colours

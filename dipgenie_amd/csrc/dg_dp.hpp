@@ -331,6 +331,9 @@ struct DpState {
     // dg_dp_recombination_margins likewise (dg_dp_get_recombination_stats: transitions, edge-kernel launches, finish launches, segments,
     // levels swept forward twice, peak bytes reserved, launches in all)
     int64_t rb_stats[7] = {0, 0, 0, 0, 0, 0, 0};
+    // dg_dp_recombination_margins_budgets likewise (dg_dp_get_recombination_budget_stats: queries, distinct budgets, transitions, edge-kernel
+    // launches, finish launches, segments, levels swept forward twice, peak bytes reserved, launches in all)
+    int64_t rbb_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // ---- dg_dp_run_pinned (dg_dp_pins.hip): the call's pins sorted by level (uploaded once per call), whether the last run on the loaded
     // graph was a pinned one, and the statistics of the last pinned run (dg_dp_get_pin_stats: pins, pinned levels, mask launches, pairs
     // run as singles, batches issued plainly) ----
@@ -466,5 +469,9 @@ int dp_phase_budget_stats(dg_ctx *c, int64_t *out, int n);
 // recombination margins: per transition the best pair of paths that spends 0, 1 or 2 crossovers there, from the same pass with one more gather
 int dp_recombination_margins(dg_ctx *c, int32_t budget, const int32_t *called, int64_t n, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_value);
 int dp_recombination_stats(dg_ctx *c, int64_t *out, int n);
+// the same for every listed budget from one pass at the largest: only the planes paired in the gather depend on the budget
+int dp_recombination_margins_budgets(dg_ctx *c, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records, int32_t *called_out,
+                                     int32_t *best_values);
+int dp_recombination_budget_stats(dg_ctx *c, int64_t *out, int n);
 
 }  // namespace dgi

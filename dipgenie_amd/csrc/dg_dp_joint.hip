@@ -47,7 +47,10 @@
 // gather per level in place of the combination and record kernels: per transition l -> l + 1 the best F_l + d + B_{l+1} over the hop pairs
 // the backward kernel walks, bucketed by the number of weight-1 hops in the pair, with the hop pair that attains it, and per called pair what
 // its own two hops are worth.  It launches none of the combination, record, table or phase kernels and reserves none of their buffers.  Out of
-// scope there: a form with a budget per query, a pinned form, more than one GPU, windows of several transitions.
+// scope there: a pinned form, more than one GPU, windows of several transitions.
+// dg_dp_recombination_margins_budgets (rbb_call and the rb_*_budgets kernels, below rb_call: their comment has the plan) is that schedule
+// once at the largest budget for queries with a budget each: the two gathers get one more grid dimension over the distinct budgets and
+// pair the planes of the one pass per budget.  rb_call and its kernels are launched by the one-budget call alone, these by this one.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -2070,10 +2073,382 @@ int rb_call(dg_ctx *c, int32_t budget, const int32_t *called, int64_t n, dg_dp_r
     return DG_OK;
 }
 
+// ---- dg_dp_recombination_margins_budgets: the records above for every listed budget from ONE pass at the largest, bmax.  Both states
+// mean "at most r", so plane p of F_l and of B_{l+1} at bmax is plane p at any budget b <= bmax, and
+// E^b_t[s] = max F_l[i][j][r] + d + B_{l+1}[i'][j'][b - s - r] over r <= b - s pairs planes of the one pass: only the pairing depends on b.
+// The host sorts the distinct budgets bud[0 .. nd); the two kernels are the two above with one more dimension:
+//   * rb_edges_budgets_kernel: grid (x blocks, k, nd).  Workgroup (x, i, d) is rb_edges_kernel's (x, i) at budget b = bud[d]: its lanes stride
+//     over (j, r <= b), the state stride stays bmax + 1 and the B plane is b - w - r; part[d][s][i][x].  A row of budget b has k * (b + 1)
+//     lanes, so only its first rbb_nx(k, b, gridDim.x) workgroups have any: the others return without a store and the finish kernel reads
+//     only those (both call rbb_nx);
+//   * rb_finish_budgets_kernel: workgroup 3 * d + s reduces part[d][s] to the words of record [d][l] that belong to s; the workgroups from
+//     3 * nd on answer called_out, one wave per query, with the query's own budget in the r loop.
+__device__ __forceinline__ int rbb_nx(int k, int b, int nx) { return min(nx, (k * (b + 1) + JT_THREADS - 1) / JT_THREADS); }
+
+// as rb_edges_kernel; B1 = bmax + 1 = the stride of both states, bud = the distinct budgets, part = [gridDim.z][3][k][gridDim.x][2]
+__global__ __launch_bounds__(JT_THREADS) void rb_edges_budgets_kernel(const int32_t *__restrict__ F, const int32_t *__restrict__ next, int k, int kn, int B1, const int32_t *__restrict__ bud,
+                                                               int a0, int b0n, uint32_t in_base, int T, const uint32_t *__restrict__ oo, const uint32_t *__restrict__ oe,
+                                                               const uint32_t *__restrict__ in_edge, const int32_t *__restrict__ in_dst, const uint16_t *__restrict__ sc,
+                                                               long long *__restrict__ part) {
+    __shared__ long long s_key[3][JT_THREADS / 64][2];
+    const int t = (int)threadIdx.x, i = (int)blockIdx.y, bq = bud[blockIdx.z], b1 = bq + 1;
+    const int nxd = rbb_nx(k, bq, (int)gridDim.x);
+    if ((int)blockIdx.x >= nxd) return;                                     // uniform per workgroup: no lane of this budget's row is here
+    const uint32_t ou0 = oo[a0 + i], ou1 = oo[a0 + i + 1];
+    const int n = k * b1;
+    long long a0k = JT_NO_KEY, a1k = JT_NO_KEY, a2k = JT_NO_KEY, b0k = 0, b1k = 0, b2k = 0;      // the lane's best key per s
+    for (int x = (int)(blockIdx.x * JT_THREADS + threadIdx.x); x < n; x += nxd * JT_THREADS) {
+        const int j = x / b1, r = x - j * b1;                               // r <= bq
+        if (j < i) continue;
+        const int f = F[((int64_t)i * k + j) * B1 + r];
+        if (f == NEG_INF) continue;
+        const uint32_t ov0 = oo[a0 + j], ov1 = oo[a0 + j + 1];
+        long long c0 = JT_NO_KEY, c1 = JT_NO_KEY, c2 = JT_NO_KEY;
+        for (uint32_t ou = ou0; ou < ou1; ++ou) {
+            const uint32_t eu = oe[ou] - in_base;
+            if (eu >= (uint32_t)T) continue;
+            const uint32_t pi = (uint32_t)(in_dst[in_base + eu] - b0n);
+            const int w1 = (int)(in_edge[in_base + eu] >> 31);
+            if (pi >= (uint32_t)kn || bq - r - w1 < 0) continue;
+            const uint32_t hi = (uint32_t)(JT_MAX_K - (int)pi) << 15;
+            for (uint32_t ov = ov0; ov < ov1; ++ov) {
+                const uint32_t ev = oe[ov] - in_base;
+                if (ev >= (uint32_t)T) continue;
+                const uint32_t pj = (uint32_t)(in_dst[in_base + ev] - b0n);
+                const int w = w1 + (int)(in_edge[in_base + ev] >> 31);
+                const int r2 = bq - r - w;                                  // what this budget leaves for B
+                if (pj >= (uint32_t)kn || r2 < 0) continue;
+                const int s = next[((int64_t)pi * kn + pj) * B1 + r2];
+                if (s == NEG_INF) continue;
+                const int v = f + s + (sc ? (int)sc[(int64_t)eu * T + ev] : 0);
+                const long long cand = (long long)(((unsigned long long)(uint32_t)v << 32) | hi | (uint32_t)(JT_MAX_K - (int)pj));
+                if (w == 0) c0 = max(c0, cand);
+                else if (w == 1) c1 = max(c1, cand);
+                else c2 = max(c2, cand);
+            }
+        }
+        auto fold = [&](long long c, long long &a, long long &b) {
+            if (c == JT_NO_KEY) return;
+            const long long ca = (long long)(((unsigned long long)c & 0xFFFFFFFF00000000ull) | (uint32_t)(JT_MAX_K - i));
+            const long long cb = ((long long)(JT_MAX_K - j) << 30) | (c & 0x3FFFFFFF);
+            if (rb_better(ca, cb, a, b)) { a = ca; b = cb; }
+        };
+        fold(c0, a0k, b0k);
+        fold(c1, a1k, b1k);
+        fold(c2, a2k, b2k);
+    }
+    auto reduce = [&](int s, long long a, long long b) {
+        for (int d = 32; d; d >>= 1) {
+            const long long oa = __shfl_xor(a, d), ob = __shfl_xor(b, d);
+            if (rb_better(oa, ob, a, b)) { a = oa; b = ob; }
+        }
+        if ((t & 63) == 0) { s_key[s][t >> 6][0] = a; s_key[s][t >> 6][1] = b; }
+    };
+    reduce(0, a0k, b0k);
+    reduce(1, a1k, b1k);
+    reduce(2, a2k, b2k);
+    __syncthreads();
+    if (t < 3) {
+        long long a = s_key[t][0][0], b = s_key[t][0][1];
+        for (int w = 1; w < JT_THREADS / 64; ++w)
+            if (rb_better(s_key[t][w][0], s_key[t][w][1], a, b)) { a = s_key[t][w][0]; b = s_key[t][w][1]; }
+        long long *out = part + ((((int64_t)blockIdx.z * 3 + t) * k + i) * gridDim.x + blockIdx.x) * 2;
+        out[0] = a; out[1] = b;
+    }
+}
+
+// grid: 3 * nd + ceil(n / 4) workgroups.  part = [nd][3][k][nx][2]; rec = the records [nd][L - 1]; qb = the queries' budgets [n]; the rest
+// as rb_finish_kernel
+__global__ __launch_bounds__(JT_THREADS) void rb_finish_budgets_kernel(const long long *__restrict__ part, int k, int nx, int nd, const int32_t *__restrict__ bud, int a0, int b0n, int l,
+                                                                dg_dp_recombination_margin *__restrict__ rec, const int32_t *__restrict__ F, const int32_t *__restrict__ next, int kn,
+                                                                int B1, uint32_t in_base, int T, const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_edge,
+                                                                const uint16_t *__restrict__ sc, const int32_t *__restrict__ called, const int32_t *__restrict__ qb, int n, int L,
+                                                                int32_t *__restrict__ cout) {
+    __shared__ long long s_key[JT_THREADS / 64][2];
+    const int t = (int)threadIdx.x;
+    if ((int)blockIdx.x < 3 * nd) {                                         // uniform per workgroup
+        const int d = (int)blockIdx.x / 3, s = (int)blockIdx.x - 3 * d;
+        const int nxd = rbb_nx(k, bud[d], nx);                              // the workgroups of this budget's rows that stored a key
+        const long long *p = part + ((int64_t)d * 3 + s) * k * nx * 2;
+        long long a = JT_NO_KEY, b = 0;
+        for (int64_t x = t; x < (int64_t)k * nxd; x += JT_THREADS) {
+            const int64_t at = (x / nxd) * nx + x % nxd;
+            if (rb_better(p[2 * at], p[2 * at + 1], a, b)) { a = p[2 * at]; b = p[2 * at + 1]; }
+        }
+        for (int w = 32; w; w >>= 1) {
+            const long long oa = __shfl_xor(a, w), ob = __shfl_xor(b, w);
+            if (rb_better(oa, ob, a, b)) { a = oa; b = ob; }
+        }
+        if ((t & 63) == 0) { s_key[t >> 6][0] = a; s_key[t >> 6][1] = b; }
+        __syncthreads();
+        if (t == 0) {
+            for (int w = 1; w < JT_THREADS / 64; ++w)
+                if (rb_better(s_key[w][0], s_key[w][1], a, b)) { a = s_key[w][0]; b = s_key[w][1]; }
+            dg_dp_recombination_margin *r = rec + (int64_t)d * (L - 1) + l;
+            if (s == 0) r->level = l;
+            if (a == JT_NO_KEY) { r->value[s] = NEG_INF; r->from1[s] = r->from2[s] = r->to1[s] = r->to2[s] = -1; }
+            else {
+                r->value[s] = (int)(a >> 32);
+                r->from1[s] = a0 + (JT_MAX_K - (int)(a & 0x7FFF));
+                r->from2[s] = a0 + (JT_MAX_K - (int)((b >> 30) & 0x7FFF));
+                r->to1[s] = b0n + (JT_MAX_K - (int)((b >> 15) & 0x7FFF));
+                r->to2[s] = b0n + (JT_MAX_K - (int)(b & 0x7FFF));
+            }
+        }
+        return;
+    }
+    const int q = ((int)blockIdx.x - 3 * nd) * (JT_THREADS / 64) + (t >> 6), lane = t & 63;      // uniform per wave
+    if (q >= n) return;
+    const int bq = qb[q];
+    uint32_t e[2];                                                          // the first in-edge of each called hop, UINT32_MAX: no edge
+    int pos[2], posn[2];
+    for (int h = 0; h < 2; ++h) {
+        const int u = called[((int64_t)q * 2 + h) * L + l], v = called[((int64_t)q * 2 + h) * L + l + 1];
+        pos[h] = u - a0; posn[h] = v - b0n;
+        uint32_t at = UINT32_MAX;
+        for (uint32_t x = in_off[v] + (uint32_t)lane; x < in_off[v + 1]; x += 64)
+            if ((in_edge[x] & 0x7FFFFFFFu) == (uint32_t)pos[h] && x - in_base < (uint32_t)T) at = min(at, x);
+        for (int d = 32; d; d >>= 1) at = min(at, (uint32_t)__shfl_xor((int)at, d));
+        e[h] = at;
+    }
+    int s = -1, best = NEG_INF;
+    if (e[0] != UINT32_MAX && e[1] != UINT32_MAX) {
+        s = (int)(in_edge[e[0]] >> 31) + (int)(in_edge[e[1]] >> 31);
+        const int d = sc ? (int)sc[(int64_t)(e[0] - in_base) * T + (e[1] - in_base)] : 0;
+        const int32_t *f = F + ((int64_t)pos[0] * k + pos[1]) * B1, *b = next + ((int64_t)posn[0] * kn + posn[1]) * B1;
+        for (int r = lane; r <= bq - s; r += 64) {
+            const int fv = f[r], bv = b[bq - s - r];
+            if (fv != NEG_INF && bv != NEG_INF) best = max(best, fv + d + bv);
+        }
+        for (int w = 32; w; w >>= 1) best = max(best, __shfl_xor(best, w));
+    }
+    if (lane == 0) {
+        int32_t *out = cout + ((int64_t)q * (L - 1) + l) * 2;
+        out[0] = s; out[1] = best;
+    }
+}
+
+// rb_call's schedule run once at B1 = bmax + 1 with the two rb_*_budgets launches per level: as many launches as rb_call(bmax) issues.
+int rbb_call(dg_ctx *c, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_values) {
+    const char *FN = "dg_dp_recombination_margins_budgets";
+    DpState *Sp = c->dp;
+    if (!Sp || !Sp->loaded) { set_error("%s: no graph loaded", FN); return DG_ERR_STATE; }
+    DpState &S = *Sp;
+    if (n < 1) { set_error("%s: n = %lld", FN, (long long)n); return DG_ERR_ARG; }
+    if (!budgets || !records || !best_values) { set_error("%s: budgets, records and best_values are required", FN); return DG_ERR_ARG; }
+    if (called && !called_out) { set_error("%s: called needs called_out", FN); return DG_ERR_ARG; }
+    if (n > JT_MAX_QUERIES) { set_error("%s: %lld queries exceed %d per call", FN, (long long)n, JT_MAX_QUERIES); return DG_ERR_UNSUPPORTED; }
+    int32_t budget = 0;                                                     // the pass runs at the largest budget
+    for (int64_t q = 0; q < n; ++q) {
+        if (budgets[q] < 0) { set_error("%s: query %lld: budget %d is negative", FN, (long long)q, budgets[q]); return DG_ERR_ARG; }
+        budget = std::max(budget, budgets[q]);
+    }
+    if ((int64_t)budget + 1 > JT_MAX_PLANES) { set_error("%s: budget + 1 = %lld exceeds %d planes", FN, (long long)budget + 1, JT_MAX_PLANES); return DG_ERR_UNSUPPORTED; }
+    std::vector<int32_t> bud(budgets, budgets + n);                        // the distinct budgets, ascending
+    std::sort(bud.begin(), bud.end());
+    bud.erase(std::unique(bud.begin(), bud.end()), bud.end());
+    const int nd = (int)bud.size();
+    const int L = S.L, nV = S.nV, B1 = budget + 1;
+    if (L < 2 || (int)S.descs.size() < L) { set_error("%s: the loaded graph has %d levels", FN, L); return DG_ERR_STATE; }
+    std::vector<JtLevel> lv((size_t)L);
+    int kmax = 1;
+    int64_t tmax = 0, part_keys = 1;
+    for (int l = 0; l < L; ++l) {
+        const LevelDesc &d = S.descs[(size_t)std::max(l, 1)];
+        lv[l] = l ? JtLevel{d.b0, d.k2, d.in_base, d.T, d.delta_off >= 0, 0} : JtLevel{d.a0, d.k, 0u, 0, false, 0};
+        lv[l].cells = (int64_t)lv[l].k * lv[l].k * B1;
+        kmax = std::max(kmax, lv[l].k);
+        if (lv[l].coloured) tmax = std::max<int64_t>(tmax, lv[l].T);
+        if (l < L - 1) part_keys = std::max(part_keys, (int64_t)nd * 3 * lv[l].k * jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS));
+    }
+    if (kmax > JT_MAX_K) { set_error("%s: widest level %d exceeds %d", FN, kmax, JT_MAX_K); return DG_ERR_UNSUPPORTED; }
+    if (called)
+        for (int64_t q = 0; q < n; ++q)
+            for (int row = 0; row < 2; ++row)
+                for (int l = 0; l < L; ++l) {
+                    const int32_t v = called[(q * 2 + row) * L + l];
+                    if ((uint32_t)(v - lv[l].a0) >= (uint32_t)lv[l].k) {
+                        set_error("%s: query %lld row %d level %d: vertex %d is not in its level", FN, (long long)q, row, l, v);
+                        return DG_ERR_ARG;
+                    }
+                }
+    const int64_t nc = called ? n : 0;                                      // the queries the finish kernel answers
+    hipStream_t s = c->stream;
+    // ---- the plan: segments [seg[g], seg[g + 1]) whose forward states fit joint_state_bytes (at least one level each) ----
+    std::vector<int> seg{0};
+    {
+        int64_t in_seg = 0;
+        for (int l = 0; l < L; ++l) {
+            const int64_t bytes = 4 * lv[l].cells;
+            if (l > seg.back() && in_seg + bytes > S.opt.joint_state_bytes) { seg.push_back(l); in_seg = 0; }
+            in_seg += bytes;
+        }
+    }
+    const int n_seg = (int)seg.size();
+    seg.push_back(L);
+    std::vector<int64_t> ck_off((size_t)n_seg + 1, 0);                     // F of every segment's first level, int32 units
+    int64_t seg_cells = 1, roll_cells = 0, level_cells = 1;
+    for (int g = 0; g < n_seg; ++g) {
+        ck_off[g + 1] = ck_off[g] + lv[seg[g]].cells;
+        int64_t sum = 0;
+        for (int l = seg[g] + 1; l < seg[g + 1]; ++l) { sum += lv[l].cells; if (g + 1 < n_seg) roll_cells = std::max(roll_cells, lv[l].cells); }
+        seg_cells = std::max(seg_cells, sum);
+    }
+    for (int l = 1; l < L; ++l) level_cells = std::max(level_cells, lv[l].cells);      // B of the levels 1 .. L - 1
+    int64_t launches = 0, twice = 0, edge_launches = 0, finish_launches = 0;
+    JtMem M;
+    DevBuf d_called, d_qb, d_bud, d_rec, d_cout, d_V, d_part, d_oo, d_ocur, d_oe, d_sc, d_ck, d_roll, d_seg, d_back;
+    const int64_t n_rec = (int64_t)nd * (L - 1);
+    if (nc) if (int rc = M.get(d_called, nc * 2 * L * 4)) return rc;
+    if (nc) if (int rc = M.get(d_cout, nc * (L - 1) * 2 * 4)) return rc;
+    if (int rc = M.get(d_qb, n * 4)) return rc;
+    if (int rc = M.get(d_bud, (int64_t)nd * 4)) return rc;
+    if (int rc = M.get(d_rec, n_rec * (int64_t)sizeof(dg_dp_recombination_margin))) return rc;
+    if (int rc = M.get(d_V, (int64_t)B1 * 4)) return rc;
+    if (int rc = M.get(d_part, part_keys * 16)) return rc;
+    if (int rc = M.get(d_oo, ((int64_t)nV + 1) * 4)) return rc;
+    if (int rc = M.get(d_ocur, (int64_t)nV * 4)) return rc;
+    if (int rc = M.get(d_oe, S.n_edges * 4)) return rc;
+    if (tmax) if (int rc = M.get(d_sc, tmax * tmax * 2)) return rc;
+    if (int rc = M.get(d_ck, ck_off[n_seg] * 4)) return rc;
+    if (nc) DG_HIP(hipMemcpyAsync(d_called.p, called, (size_t)(nc * 2 * L) * 4, hipMemcpyHostToDevice, s));
+    DG_HIP(hipMemcpyAsync(d_qb.p, budgets, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    DG_HIP(hipMemcpyAsync(d_bud.p, bud.data(), (size_t)nd * 4, hipMemcpyHostToDevice, s));      // (bud outlives the call's last synchronisation)
+    const LevelDesc *descs = S.d_descs.as<LevelDesc>();
+    const uint32_t *in_off = S.d_in_off.as<uint32_t>(), *in_edge = S.d_in_edge.as<uint32_t>();
+    const int32_t *in_dst = S.d_in_dst.as<int32_t>();
+    uint16_t *sc = d_sc.as<uint16_t>();
+    // the in-edges grouped by source
+    DG_HIP(hipMemsetAsync(d_ocur.p, 0, (size_t)nV * 4, s));
+    hipLaunchKernelGGL(jt_out_count_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>());
+    hipLaunchKernelGGL(jt_out_scan_kernel, dim3(1), dim3(1024), 0, s, d_ocur.as<uint32_t>(), d_oo.as<uint32_t>(), d_ocur.as<uint32_t>(), nV);
+    hipLaunchKernelGGL(jt_out_fill_kernel, dim3((unsigned)(L - 1)), dim3(JT_THREADS), 0, s, descs, L, nV, in_edge, d_ocur.as<uint32_t>(), d_oe.as<uint32_t>(), (uint32_t)S.n_edges);
+    DG_HIP(hipGetLastError());
+    launches += 3;
+    auto scores = [&](int l) -> const uint16_t * {                          // the matrix of the transition into level l, in d_sc
+        const int T = lv[l].T;
+        if (!lv[l].coloured || T < 1) return nullptr;
+        hipLaunchKernelGGL(jt_scores_kernel, dim3(jt_blocks(T, 64), (unsigned)std::min(T, 16384)), dim3(JT_THREADS), 0, s, T, lv[l].in_base, lv[l - 1].a0, in_edge, in_dst,
+                           colour_csr(S), S.d_eflag.as<uint8_t>(), S.d_eself.as<uint16_t>(), sc);
+        ++launches;
+        return sc;
+    };
+    auto fill = [&](int32_t *st, int l, int pos) {                          // level l: 0 on every plane of the cell (pos, pos)
+        hipLaunchKernelGGL(jt_fill_kernel, dim3(jt_blocks(lv[l].cells, 65536)), dim3(JT_THREADS), 0, s, st, lv[l].cells, ((int64_t)pos * lv[l].k + pos) * B1, B1);
+        ++launches;
+    };
+    auto forward = [&](const int32_t *prev, int32_t *cur, int l) {
+        const uint16_t *m = scores(l);
+        hipLaunchKernelGGL(jt_forward_kernel, dim3(jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS), (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, prev, cur, lv[l - 1].k, lv[l].k, B1,
+                           lv[l].a0, lv[l].in_base, lv[l].T, in_off, in_edge, m);
+        ++launches;
+    };
+    // ---- pass 1: the state at every segment's first level ----
+    int32_t *ck = d_ck.as<int32_t>();
+    fill(ck, 0, 0);
+    if (n_seg > 1) {
+        if (int rc = M.get(d_roll, 2 * roll_cells * 4)) return rc;
+        int32_t *roll = d_roll.as<int32_t>();
+        const int32_t *prev = ck;
+        int g = 0;
+        for (int l = 1; l <= seg[n_seg - 1]; ++l) {
+            int32_t *dst;
+            if (l == seg[g + 1]) dst = ck + ck_off[++g];
+            else { dst = roll + (l & 1) * roll_cells; ++twice; }
+            forward(prev, dst, l);
+            prev = dst;
+        }
+        DG_HIP(hipGetLastError());
+        DG_HIP(hipStreamSynchronize(s));                                    // the rolling states go before the segment buffers come
+        M.drop(d_roll);
+    }
+    // ---- the segments, last first ----
+    if (int rc = M.get(d_seg, seg_cells * 4)) return rc;
+    if (int rc = M.get(d_back, 2 * level_cells * 4)) return rc;
+    int32_t *back = d_back.as<int32_t>();
+    std::vector<const int32_t *> Fp((size_t)L, nullptr);
+    for (int g = n_seg - 1; g >= 0; --g) {
+        const int a = seg[g], e = seg[g + 1];
+        Fp[a] = ck + ck_off[g];
+        int64_t at = 0;
+        for (int l = a + 1; l < e; ++l) {
+            int32_t *dst = d_seg.as<int32_t>() + at;
+            at += lv[l].cells;
+            forward(Fp[l - 1], dst, l);
+            Fp[l] = dst;
+        }
+        for (int l = e - 1; l >= a; --l) {
+            int32_t *cur = back + (l & 1) * level_cells;
+            if (l == L - 1) {
+                const int sink = nV - 1 - lv[l].a0;
+                fill(cur, l, sink);
+                DG_HIP(hipMemcpyAsync(d_V.p, Fp[l] + ((int64_t)sink * lv[l].k + sink) * B1, (size_t)B1 * 4, hipMemcpyDeviceToDevice, s));      // V_b for every plane b
+                continue;
+            }
+            const int32_t *next = back + ((l + 1) & 1) * level_cells;
+            const uint16_t *m = scores(l + 1);
+            const unsigned nx = jt_blocks((int64_t)lv[l].k * B1, JT_X_BLOCKS);
+            hipLaunchKernelGGL(rb_edges_budgets_kernel, dim3(nx, (unsigned)lv[l].k, (unsigned)nd), dim3(JT_THREADS), 0, s, Fp[l], next, lv[l].k, lv[l + 1].k, B1,
+                               (const int32_t *)d_bud.as<int32_t>(), lv[l].a0, lv[l + 1].a0, lv[l + 1].in_base, lv[l + 1].T, (const uint32_t *)d_oo.as<uint32_t>(),
+                               (const uint32_t *)d_oe.as<uint32_t>(), in_edge, in_dst, m, d_part.as<long long>());
+            hipLaunchKernelGGL(rb_finish_budgets_kernel, dim3(3 * (unsigned)nd + (unsigned)((nc + JT_THREADS / 64 - 1) / (JT_THREADS / 64))), dim3(JT_THREADS), 0, s,
+                               (const long long *)d_part.as<long long>(), lv[l].k, (int)nx, nd, (const int32_t *)d_bud.as<int32_t>(), lv[l].a0, lv[l + 1].a0, l,
+                               d_rec.as<dg_dp_recombination_margin>(), Fp[l], next, lv[l + 1].k, B1, lv[l + 1].in_base, lv[l + 1].T, in_off, in_edge, m,
+                               (const int32_t *)d_called.as<int32_t>(), (const int32_t *)d_qb.as<int32_t>(), (int)nc, L, d_cout.as<int32_t>());
+            ++edge_launches; ++finish_launches; launches += 2;
+            if (l > 0) {
+                hipLaunchKernelGGL(jt_backward_kernel, dim3(nx, (unsigned)lv[l].k), dim3(JT_THREADS), 0, s, next, cur, lv[l].k, lv[l + 1].k, B1, lv[l].a0, lv[l + 1].a0,
+                                   lv[l + 1].in_base, lv[l + 1].T, d_oo.as<uint32_t>(), d_oe.as<uint32_t>(), in_edge, in_dst, m);
+                ++launches;
+            }
+        }
+        DG_HIP(hipGetLastError());
+    }
+    // the caller's arrays are written only if the call succeeds
+    std::vector<dg_dp_recombination_margin> recs((size_t)n_rec);
+    std::vector<int32_t> couts((size_t)(nc * (L - 1) * 2));
+    std::vector<int32_t> Vs((size_t)B1, NEG_INF);
+    DG_HIP(hipMemcpyAsync(recs.data(), d_rec.p, recs.size() * sizeof(dg_dp_recombination_margin), hipMemcpyDeviceToHost, s));
+    if (nc) DG_HIP(hipMemcpyAsync(couts.data(), d_cout.p, couts.size() * 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipMemcpyAsync(Vs.data(), d_V.p, (size_t)B1 * 4, hipMemcpyDeviceToHost, s));
+    DG_HIP(hipStreamSynchronize(s));
+    // the closing check, per distinct budget: at every transition the best pair of paths within it takes some hop pair
+    for (int d = 0; d < nd; ++d)
+        for (int l = 0; l < L - 1; ++l) {
+            const dg_dp_recombination_margin &r = recs[(size_t)d * (L - 1) + l];
+            const int32_t V = Vs[(size_t)bud[d]];
+            if (std::max(r.value[0], std::max(r.value[1], r.value[2])) != V) {
+                set_error("%s: level %d: the values %d, %d, %d of its transition do not reach the sink's value %d at budget %d", FN, l, r.value[0], r.value[1], r.value[2], V, bud[d]);
+                return DG_ERR_STATE;
+            }
+        }
+    const int64_t st[9] = {n, nd, L - 1, edge_launches, finish_launches, n_seg, twice, M.peak, launches};
+    for (int x = 0; x < 9; ++x) S.rbb_stats[x] = st[x];
+    for (int64_t q = 0; q < n; ++q) {                                       // queries of one budget share one set of records
+        const int d = (int)(std::lower_bound(bud.begin(), bud.end(), budgets[q]) - bud.begin());
+        memcpy(records + q * (L - 1), recs.data() + (size_t)d * (L - 1), (size_t)(L - 1) * sizeof(dg_dp_recombination_margin));
+        best_values[q] = Vs[(size_t)budgets[q]];
+    }
+    if (nc) memcpy(called_out, couts.data(), couts.size() * 4);
+    return DG_OK;
+}
+
 }  // namespace
 
 int dp_recombination_margins(dg_ctx *c, int32_t budget, const int32_t *called, int64_t n, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_value) {
     return rb_call(c, budget, called, n, records, called_out, best_value);
+}
+
+int dp_recombination_margins_budgets(dg_ctx *c, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records, int32_t *called_out,
+                                     int32_t *best_values) {
+    return rbb_call(c, budgets, n, called, records, called_out, best_values);
+}
+
+int dp_recombination_budget_stats(dg_ctx *c, int64_t *out, int n) {
+    if (!out || n < 9) { set_error("dg_dp_get_recombination_budget_stats: out needs 9 words"); return DG_ERR_ARG; }
+    if (!c->dp) { set_error("dg_dp_get_recombination_budget_stats: no graph loaded"); return DG_ERR_STATE; }
+    for (int q = 0; q < 9; ++q) out[q] = c->dp->rbb_stats[q];
+    return DG_OK;
 }
 
 int dp_recombination_stats(dg_ctx *c, int64_t *out, int n) {
@@ -2199,4 +2574,15 @@ extern "C" int dg_dp_recombination_margins(dg_ctx *c, int32_t budget, const int3
 extern "C" int dg_dp_get_recombination_stats(dg_ctx *c, int64_t *out, int n) {
     if (int rc = dgi::bind(c)) return rc;
     return dgi::dp_recombination_stats(c, out, n);
+}
+
+extern "C" int dg_dp_recombination_margins_budgets(dg_ctx *c, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records, int32_t *called_out,
+                                                   int32_t *best_values) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_recombination_margins_budgets(c, budgets, n, called, records, called_out, best_values);
+}
+
+extern "C" int dg_dp_get_recombination_budget_stats(dg_ctx *c, int64_t *out, int n) {
+    if (int rc = dgi::bind(c)) return rc;
+    return dgi::dp_recombination_budget_stats(c, out, n);
 }

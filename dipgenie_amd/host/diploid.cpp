@@ -117,6 +117,9 @@ std::string run_dp(const Pipeline &p, const ExpandedGraph &g, const std::vector<
     // and --recombination-margins: the called hops are those of the answer that stays behind
     if (!p.opt.recombination_margins.empty() && (!be.dp_load_graph || !be.dp_run_budgets || !be.dp_answer_paths || !be.dp_recombination_margins || !be.dp_score_paths))
         return "--recombination-margins: this backend has no dp_recombination_margins";
+    // and --budget-recombination-margins: the answers at the listed limits stay behind, one joint pass describes the crossovers of them all
+    if (!p.opt.budget_recombination_margins.empty() && (!be.dp_answer_paths || !be.dp_recombination_margins_budgets || !be.dp_score_paths))
+        return "--budget-recombination-margins: this backend has no dp_recombination_margins_budgets";
     // and --pins: the same run under the file's cell constraints
     if (!p.opt.pins_file.empty() && (!be.dp_load_graph || !be.dp_run_pinned || !be.dp_pin_stats || !be.dp_answer_paths)) return "--pins: this backend has no dp_run_pinned";
     // and --pinned-genotype-margins / --pinned-genotype-table: the joint pass under the same constraints
@@ -577,6 +580,41 @@ std::string write_phase_margins(Pipeline &p, const ExpandedGraph &g, const std::
     return "";
 }
 
+// one row of the --recombination-margins file (its comment is below), without the newline: transition l of the pair `paths` ([2][L]) against its record; counts what -J reports into rm
+static void recombination_row(const Pipeline &p, const ExpandedGraph &g, const int32_t *paths, int64_t l, const dg_dp_recombination_margin &r, int32_t s_called, int32_t value,
+                              int32_t dp_value, RecombinationMargins &rm, std::string &text) {
+    const int L = (int)g.level_off.size() - 1;
+    auto weight = [&](int32_t u, int32_t v) -> std::string {             // of the hop u -> v (parallel edges share it)
+        for (int64_t e = g.adj_off[(size_t)u]; e < g.adj_off[(size_t)u + 1]; ++e)
+            if (g.adj_dst[(size_t)e] == v) return std::to_string((int)g.adj_w[(size_t)e]);
+        return ".";
+    };
+    text += std::to_string(l);
+    for (int h = 0; h < 2; ++h) {
+        const int32_t u = paths[(size_t)h * L + l], v = paths[(size_t)h * L + l + 1];
+        text += '\t' + std::to_string(u) + '\t' + segment_name(p, g, u) + '\t' + std::to_string(v) + '\t' + segment_name(p, g, v) + '\t' + weight(u, v);
+    }
+    text += '\t' + std::to_string(s_called) + '\t' + std::to_string(value);
+    int alt = -1;
+    for (int s = 0; s < 3; ++s) {
+        text += '\t' + (r.from1[s] >= 0 ? std::to_string(r.value[s]) : std::string("."));
+        if (s != s_called && r.from1[s] >= 0 && (alt < 0 || r.value[s] > r.value[alt])) alt = s;      // ties: the smaller s
+    }
+    rm.called_recombinations += s_called;
+    if (alt >= 0) {
+        const int32_t margin = value - r.value[alt];
+        text += '\t' + std::to_string(alt) + '\t' + std::to_string(r.value[alt]) + '\t' + std::to_string(margin) + '\t' + std::to_string(r.from1[alt]) + '\t' + std::to_string(r.to1[alt]) + '\t' +
+                std::to_string(r.from2[alt]) + '\t' + std::to_string(r.to2[alt]);
+        if (s_called > 0 && margin == 0) rm.breakpoints_margin0++;
+        else if (s_called > 0 && margin > 0 && (rm.min_positive_breakpoint_margin < 0 || margin < rm.min_positive_breakpoint_margin)) rm.min_positive_breakpoint_margin = margin;
+        if (s_called == 0 && r.value[alt] == dp_value) rm.co_optimal_elsewhere++;
+    } else text += "\t.\t.\t.\t.\t.\t.\t.";
+}
+
+static const char *const RECOMBINATION_COLUMNS =
+    "level\tvertex1_from\tsegment1_from\tvertex1_to\tsegment1_to\tw1\tvertex2_from\tsegment2_from\tvertex2_to\tsegment2_to\tw2\ts_called\tvalue\tvalue_s0\tvalue_s1\tvalue_s2\t"
+    "alt_s\talt_value\tmargin\talt_from1\talt_to1\talt_from2\talt_to2\n";
+
 // level  vertex1_from segment1_from vertex1_to segment1_to w1  vertex2_from segment2_from vertex2_to segment2_to w2  s_called value
 // value_s0 value_s1 value_s2  alt_s alt_value margin  alt_from1 alt_to1 alt_from2 alt_to2: one row per transition level -> level + 1.  The
 // two hops of the answer at -R with their weights, s_called = w1 + w2, value = the best pair of paths within -R that takes exactly these
@@ -606,39 +644,13 @@ std::string write_recombination_margins(Pipeline &p, const ExpandedGraph &g) {
         if (best != p.sum.dp_value) return "--recombination-margins: the joint pass finds " + std::to_string(best) + ", the run's DP value is " + std::to_string(p.sum.dp_value);
         if (be.dp_score_paths(be.ctx, paths.data(), 1, &score) != 0) return backend_error(be, "dp_score_paths");
     }
-    auto weight = [&](int32_t u, int32_t v) -> std::string {             // of the hop u -> v (parallel edges share it)
-        for (int64_t e = g.adj_off[(size_t)u]; e < g.adj_off[(size_t)u + 1]; ++e)
-            if (g.adj_dst[(size_t)e] == v) return std::to_string((int)g.adj_w[(size_t)e]);
-        return ".";
-    };
-    std::string text = "level\tvertex1_from\tsegment1_from\tvertex1_to\tsegment1_to\tw1\tvertex2_from\tsegment2_from\tvertex2_to\tsegment2_to\tw2\ts_called\tvalue\tvalue_s0\tvalue_s1\tvalue_s2\t"
-                       "alt_s\talt_value\tmargin\talt_from1\talt_to1\talt_from2\talt_to2\n";
+    std::string text = RECOMBINATION_COLUMNS;
     for (int64_t l = 0; l < T; ++l) {
-        const dg_dp_recombination_margin &r = rec[(size_t)l];
         const int32_t s_called = out[2 * (size_t)l], value = out[2 * (size_t)l + 1];
         if (s_called < 0 || value != p.sum.dp_value)
             return "--recombination-margins: level " + std::to_string(l) + ": the answer's hops are worth " + std::to_string(value) + " (s_called " + std::to_string(s_called) + "), the run's DP value is " +
                    std::to_string(p.sum.dp_value);
-        text += std::to_string(l);
-        for (int h = 0; h < 2; ++h) {
-            const int32_t u = paths[(size_t)h * L + l], v = paths[(size_t)h * L + l + 1];
-            text += '\t' + std::to_string(u) + '\t' + segment_name(p, g, u) + '\t' + std::to_string(v) + '\t' + segment_name(p, g, v) + '\t' + weight(u, v);
-        }
-        text += '\t' + std::to_string(s_called) + '\t' + std::to_string(value);
-        int alt = -1;
-        for (int s = 0; s < 3; ++s) {
-            text += '\t' + (r.from1[s] >= 0 ? std::to_string(r.value[s]) : std::string("."));
-            if (s != s_called && r.from1[s] >= 0 && (alt < 0 || r.value[s] > r.value[alt])) alt = s;      // ties: the smaller s
-        }
-        rm.called_recombinations += s_called;
-        if (alt >= 0) {
-            const int32_t margin = value - r.value[alt];
-            text += '\t' + std::to_string(alt) + '\t' + std::to_string(r.value[alt]) + '\t' + std::to_string(margin) + '\t' + std::to_string(r.from1[alt]) + '\t' + std::to_string(r.to1[alt]) + '\t' +
-                    std::to_string(r.from2[alt]) + '\t' + std::to_string(r.to2[alt]);
-            if (s_called > 0 && margin == 0) rm.breakpoints_margin0++;
-            else if (s_called > 0 && margin > 0 && (rm.min_positive_breakpoint_margin < 0 || margin < rm.min_positive_breakpoint_margin)) rm.min_positive_breakpoint_margin = margin;
-            if (s_called == 0 && r.value[alt] == p.sum.dp_value) rm.co_optimal_elsewhere++;
-        } else text += "\t.\t.\t.\t.\t.\t.\t.";
+        recombination_row(p, g, paths.data(), l, rec[(size_t)l], s_called, value, p.sum.dp_value, rm, text);
         text += '\n';
     }
     rm.transitions = T;
@@ -650,6 +662,73 @@ std::string write_recombination_margins(Pipeline &p, const ExpandedGraph &g) {
     f.close();
     if (!f.good()) return "write to " + p.opt.recombination_margins + " failed";
     rm.wall_s = now_s() - t0;
+    return "";
+}
+
+// r and the columns of --recombination-margins: per listed limit r with an answer, in the order of the list, one row per transition with the
+// two hops of the answer at r against the best pairs of paths within r.  ONE device call serves every limit
+// (dp_recombination_margins_budgets: the joint pass at the largest of them) and one dp_score_paths call scores all answers.  A limit nobody
+// fits is left out: it has no paths to call.  At every transition the answer's hops must be worth the run's DP value at r, and its called
+// crossovers must add up to the r1 + r2 of its score.
+std::string write_budget_recombination_margins(Pipeline &p, const ExpandedGraph &g, const std::vector<int32_t> &budgets, const std::vector<ChainAnswer> &answers) {
+    const double t0 = now_s();
+    const Backend &be = p.be;
+    const int L = (int)g.level_off.size() - 1;
+    const std::string O = "--budget-recombination-margins: limit ";
+    BudgetRecombinationMargins &br = p.sum.budget_recombination_margins;
+    br = BudgetRecombinationMargins();
+    br.set = true;
+    std::vector<int32_t> called, limits, values;                     // [n][2][L], [n], the run's DP value at each
+    std::vector<int32_t> paths(2 * (size_t)L);
+    for (const int r : p.opt.budgets) {
+        const size_t q = (size_t)(std::find(budgets.begin(), budgets.end(), (int32_t)r) - budgets.begin());
+        if (q >= answers.size() || !answers[q].reachable()) continue;
+        if (be.dp_answer_paths(be.ctx, r, paths.data()) != 0) return backend_error(be, "dp_answer_paths");
+        if (paths[0] < 0) continue;
+        called.insert(called.end(), paths.begin(), paths.end());
+        limits.push_back(r);
+        values.push_back(answers[q].res.value);
+    }
+    const int64_t n = (int64_t)limits.size(), T = L - 1;
+    std::vector<dg_dp_recombination_margin> rec((size_t)std::max<int64_t>(n * T, 1));
+    std::vector<int32_t> out(2 * (size_t)std::max<int64_t>(n * T, 1), 0), best((size_t)n);
+    std::vector<dg_dp_pair_score> scores((size_t)n);
+    if (n > 0) {
+        if (be.dp_recombination_margins_budgets(be.ctx, limits.data(), n, called.data(), rec.data(), out.data(), best.data()) != 0) return backend_error(be, "dp_recombination_margins_budgets");
+        int64_t stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (be.dp_recombination_budget_stats && be.dp_recombination_budget_stats(be.ctx, stats, 9) != 0) return backend_error(be, "dp_recombination_budget_stats");
+        br.segments = stats[5];
+        if (be.dp_score_paths(be.ctx, called.data(), n, scores.data()) != 0) return backend_error(be, "dp_score_paths");
+    }
+    std::string text = std::string("r\t") + RECOMBINATION_COLUMNS;
+    for (int64_t q = 0; q < n; ++q) {
+        BudgetRecombinationMargins::Row row;
+        row.r = limits[(size_t)q];
+        const int32_t dp_value = values[(size_t)q];
+        if (best[(size_t)q] != dp_value) return O + std::to_string(row.r) + ": the joint pass finds " + std::to_string(best[(size_t)q]) + ", the run's DP value is " + std::to_string(dp_value);
+        for (int64_t l = 0; l < T; ++l) {
+            const size_t x = (size_t)(q * T + l);
+            const int32_t s_called = out[2 * x], value = out[2 * x + 1];
+            if (s_called < 0 || value != dp_value)
+                return O + std::to_string(row.r) + " level " + std::to_string(l) + ": the answer's hops are worth " + std::to_string(value) + " (s_called " + std::to_string(s_called) +
+                       "), the run's DP value is " + std::to_string(dp_value);
+            text += std::to_string(row.r) + '\t';
+            recombination_row(p, g, &called[(size_t)q * 2 * (size_t)L], l, rec[x], s_called, value, dp_value, row.counts, text);
+            text += '\n';
+        }
+        row.counts.transitions = T;
+        if (row.counts.called_recombinations != (int64_t)scores[(size_t)q].r1 + scores[(size_t)q].r2)
+            return O + std::to_string(row.r) + ": the answer's hops spend " + std::to_string(row.counts.called_recombinations) + " crossovers, dp_score_paths counts " +
+                   std::to_string(scores[(size_t)q].r1) + " + " + std::to_string(scores[(size_t)q].r2);
+        br.rows.push_back(row);
+    }
+    const std::string &path = p.opt.budget_recombination_margins;
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    if (!f.is_open()) return "cannot open budget recombination margins file " + path;
+    f.write(text.data(), (std::streamsize)text.size());
+    f.close();
+    if (!f.good()) return "write to " + path + " failed";
+    br.wall_s = now_s() - t0;
     return "";
 }
 
@@ -944,11 +1023,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         }
     }
     const bool pinned_joint = !opt.pinned_genotype_margins.empty() || !opt.pinned_genotype_table.empty();
-    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty() || !opt.recombination_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
+    if (!opt.genotype_margins.empty() || !opt.genotype_table.empty() || pinned_joint || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty() || !opt.recombination_margins.empty() || !opt.budget_recombination_margins.empty()) {   // the limits of dg_dp_genotype_margins / dg_dp_genotype_table / dg_dp_phase_margins, known before the DP too
         int64_t widest = 1;
         for (int l = 0; l < L; ++l) widest = std::max<int64_t>(widest, g.level_off[l + 1] - g.level_off[l]);
         if (widest > 32767 || (int64_t)R + 1 > 4096) {
-            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : !opt.phase_margins.empty() ? "--phase-margins" : !opt.budget_phase_margins.empty() ? "--budget-phase-margins" : "--recombination-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
+            err = std::string(pinned_joint ? (opt.pinned_genotype_margins.empty() ? "--pinned-genotype-table" : "--pinned-genotype-margins") : !opt.genotype_margins.empty() ? "--genotype-margins" : !opt.genotype_table.empty() ? "--genotype-table" : !opt.budget_genotype_margins.empty() ? "--budget-genotype-margins" : !opt.phase_margins.empty() ? "--phase-margins" : !opt.budget_phase_margins.empty() ? "--budget-phase-margins" : !opt.recombination_margins.empty() ? "--recombination-margins" : "--budget-recombination-margins") + ": widest level " + std::to_string(widest) + " (at most 32767), R + 1 = " + std::to_string(R + 1) + " (at most 4096)";
             return -1;
         }
     }
@@ -1034,6 +1113,11 @@ int Pipeline::diploid(ExpandedGraph &g, const std::vector<uint8_t> &color_homo_b
         t0 = now_s();
         if (failed(write_recombination_margins(*this, g), err)) return -1;
         stamp("recombination_margins", t0);
+    }
+    if (!opt.budget_recombination_margins.empty()) {                      // after --recombination-margins: that option alone is exactly what it was
+        t0 = now_s();
+        if (failed(write_budget_recombination_margins(*this, g, budgets, answers), err)) return -1;
+        stamp("budget_recombination_margins", t0);
     }
     if (pinned_joint) {                                                   // the same under --pins: one pass serves both files
         t0 = now_s();

@@ -189,6 +189,14 @@ static int b_dp_recombination_stats(void *c, int64_t *out, int n) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_get_recombination_stats(x, out, n) : DG_ERR_NO_DEVICE;
 }
+static int b_dp_recombination_margins_budgets(void *c, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_recombination_margins_budgets(x, budgets, n, called, records, called_out, best) : DG_ERR_NO_DEVICE;
+}
+static int b_dp_recombination_budget_stats(void *c, int64_t *out, int n) {
+    dg_ctx *x = ((LazyCtx *)c)->get();
+    return x ? dg_dp_get_recombination_budget_stats(x, out, n) : DG_ERR_NO_DEVICE;
+}
 static int b_dp_score_paths(void *c, const int32_t *paths, int64_t n, dg_dp_pair_score *out) {
     dg_ctx *x = ((LazyCtx *)c)->get();
     return x ? dg_dp_score_paths(x, paths, n, out) : DG_ERR_NO_DEVICE;
@@ -314,6 +322,7 @@ static void usage(FILE *fp, const dg::Options &o) {   // main.cpp:90-110
     fprintf(fp, "    --phase-margins FILE      (MI355X build, -p2) per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps the answer's phase between them (cis) against the best that switches it (trans), and the margin (TSV)\n");
     fprintf(fp, "    --budget-phase-margins FILE   (MI355X build, -p2, with --budgets) the rows of --phase-margins for the answer at every listed limit that has one, each within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
     fprintf(fp, "    --recombination-margins FILE   (MI355X build, -p2) per transition level -> level + 1: the two hops of the answer at -R, the crossovers they spend there, and the best pair of paths within -R that spends 0, 1 or 2 there; the best other number against the answer's is the margin of the breakpoint, or of its absence (TSV)\n");
+    fprintf(fp, "    --budget-recombination-margins FILE   (MI355X build, -p2, with --budgets) the rows of --recombination-margins for the answer at every listed limit that has one, each within that limit, behind a first column r; one joint pass serves all limits (TSV)\n");
     fprintf(fp, "    --objective-table FILE   (MI355X build, -p2) per limit of --budgets (without it: -R): r, DP value, objective, hom_shared, hom_single, het_single, het_both (TSV)\n");
     fprintf(fp, "    --tag-reads FILE      (MI355X build, -p2) per read: its minimizers found only in haplotype 1 / only in haplotype 2 / in both of the answer at -R, and the haplotype they support (TSV)\n");
     fprintf(fp, "    --pins FILE           (MI355X build, -p2) run the DP under cell constraints: rows level, vertex1, vertex2 [, require|forbid|require-ordered|forbid-ordered], tab-separated, . = any vertex, ids as --genotype-table prints them\n");
@@ -339,7 +348,7 @@ int main(int argc, char **argv) {
     std::vector<int> shard_devices;
     std::string budgets_arg;
     bool have_budgets = false, have_site_margins = false, have_objective_table = false, have_tag_reads = false, have_genotype_margins = false, have_genotype_table = false, have_pins = false;
-    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false, have_budget_phase = false, have_recombination = false;
+    bool have_pinned_margins = false, have_pinned_table = false, have_budget_margins = false, have_phase_margins = false, have_budget_phase = false, have_recombination = false, have_budget_recombination = false;
     {
         int w = 1;
         for (int i = 1; i < argc; ++i) {
@@ -375,6 +384,12 @@ int main(int argc, char **argv) {
                 have_budget_phase = true;                              // (a missing value is an empty file name: refused below)
                 const char *v = val("--budget-phase-margins");
                 p.opt.budget_phase_margins = v ? v : "";
+                continue;
+            }
+            if (!strncmp(argv[i], "--budget-recombination-margins", 30) && (argv[i][30] == 0 || argv[i][30] == '=')) {
+                have_budget_recombination = true;                      // (a missing value is an empty file name: refused below)
+                const char *v = val("--budget-recombination-margins");
+                p.opt.budget_recombination_margins = v ? v : "";
                 continue;
             }
             if (!strncmp(argv[i], "--recombination-margins", 23) && (argv[i][23] == 0 || argv[i][23] == '=')) {
@@ -478,6 +493,14 @@ int main(int argc, char **argv) {
         if (sharded) { fprintf(stderr, "[E::main] --budget-phase-margins does not go with --gpus / --shard-transport\n"); return 1; }
         if (have_pins) { fprintf(stderr, "[E::main] --budget-phase-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
     }
+    // --budget-recombination-margins FILE: as --budget-phase-margins
+    if (have_budget_recombination) {
+        if (p.opt.ploidy != 2) { fprintf(stderr, "[E::main] --budget-recombination-margins describes the crossovers of the diploid route (-p2)\n"); return 1; }
+        if (!have_budgets) { fprintf(stderr, "[E::main] --budget-recombination-margins needs --budgets\n"); return 1; }
+        if (p.opt.budget_recombination_margins.empty()) { fprintf(stderr, "[E::main] --budget-recombination-margins needs a file name\n"); return 1; }
+        if (sharded) { fprintf(stderr, "[E::main] --budget-recombination-margins does not go with --gpus / --shard-transport\n"); return 1; }
+        if (have_pins) { fprintf(stderr, "[E::main] --budget-recombination-margins does not go with --pins: it describes the unconstrained DP\n"); return 1; }
+    }
     // --budgets all|a,b,c: checked here, before any device is asked for
     if (!p.opt.budget_table.empty() && !have_budgets) { fprintf(stderr, "[E::main] --budget-table needs --budgets\n"); return 1; }
     if (have_budgets) {
@@ -501,6 +524,9 @@ int main(int argc, char **argv) {
         // one device call takes 256 called pairs: a longer list is refused here, not after the DP run
         if (have_budget_phase && p.opt.budgets.size() > 256) {
             fprintf(stderr, "[E::main] --budget-phase-margins: --budgets lists %zu limits; one call answers 256 at the most\n", p.opt.budgets.size()); return 1;
+        }
+        if (have_budget_recombination && p.opt.budgets.size() > 256) {
+            fprintf(stderr, "[E::main] --budget-recombination-margins: --budgets lists %zu limits; one call answers 256 at the most\n", p.opt.budgets.size()); return 1;
         }
     }
     // --site-margins FILE: checked here too, before any device is asked for
@@ -591,6 +617,8 @@ int main(int argc, char **argv) {
     p.be.dp_recombination_margins = b_dp_recombination_margins;
     p.be.dp_recombination_stats = b_dp_recombination_stats;
     p.be.dp_score_paths = b_dp_score_paths;
+    p.be.dp_recombination_margins_budgets = b_dp_recombination_margins_budgets;
+    p.be.dp_recombination_budget_stats = b_dp_recombination_budget_stats;
     p.be.dp_run_pinned = b_dp_pinned;
     p.be.dp_pin_stats = b_dp_pin_stats;
     p.be.free_buf = dg_free;
@@ -698,6 +726,18 @@ int main(int argc, char **argv) {
                         (long long)rm.transitions, (long long)rm.called_recombinations, (long long)rm.breakpoints_margin0);
                 if (rm.min_positive_breakpoint_margin >= 0) fprintf(f, "%d", rm.min_positive_breakpoint_margin); else fprintf(f, "null");
                 fprintf(f, ", \"co_optimal_elsewhere\": %lld, \"segments\": %lld, \"wall_s\": %.6f}", (long long)rm.co_optimal_elsewhere, (long long)rm.segments, rm.wall_s);
+            }
+            if (p.sum.budget_recombination_margins.set) {               // per listed limit with an answer the counts of recombination_margins; one device call
+                const dg::BudgetRecombinationMargins &br = p.sum.budget_recombination_margins;
+                fprintf(f, ", \"budget_recombination_margins\": {\"budgets\": [");
+                for (size_t i = 0; i < br.rows.size(); ++i) {
+                    const dg::RecombinationMargins &rm = br.rows[i].counts;
+                    fprintf(f, "%s{\"r\": %d, \"transitions\": %lld, \"called_recombinations\": %lld, \"breakpoints_margin0\": %lld, \"min_positive_breakpoint_margin\": ", i ? ", " : "", br.rows[i].r,
+                            (long long)rm.transitions, (long long)rm.called_recombinations, (long long)rm.breakpoints_margin0);
+                    if (rm.min_positive_breakpoint_margin >= 0) fprintf(f, "%d", rm.min_positive_breakpoint_margin); else fprintf(f, "null");
+                    fprintf(f, ", \"co_optimal_elsewhere\": %lld}", (long long)rm.co_optimal_elsewhere);
+                }
+                fprintf(f, "], \"segments\": %lld, \"wall_s\": %.6f}", (long long)br.segments, br.wall_s);
             }
             if (p.sum.budget_phase_margins.set) {                       // per listed limit with an answer the fields of phase_margins; one device call
                 const dg::BudgetPhaseMargins &bp = p.sum.budget_phase_margins;

@@ -36,7 +36,7 @@ void Pipeline::read_gfa_from(const GfaGraph &g) {
     // graph: one vertex per segment, forward-strand arcs only (:60-91); walks -> paths, named sample.hap (:108-125)
     n_vtx = g.n_seg();
     node_seq.assign(g.seg_seq.begin(), g.seg_seq.end());
-    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty() || !opt.recombination_margins.empty()) node_name.assign(g.seg_name.begin(), g.seg_name.end());
+    if (!opt.site_margins.empty() || !opt.genotype_margins.empty() || !opt.genotype_table.empty() || !opt.budget_genotype_margins.empty() || !opt.phase_margins.empty() || !opt.budget_phase_margins.empty() || !opt.recombination_margins.empty() || !opt.budget_recombination_margins.empty()) node_name.assign(g.seg_name.begin(), g.seg_name.end());
     adj_list.assign(n_vtx, {});
     for (uint32_t seg = 0; seg < n_vtx; ++seg)
         for (uint32_t arc : g.arcs[(size_t)2 * seg]) adj_list[seg].push_back(arc >> 1);

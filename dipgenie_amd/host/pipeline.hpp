@@ -111,6 +111,11 @@ struct Backend {     // same signatures as the C ABI, plus an opaque ctx
     int (*dp_recombination_margins)(void *, int32_t budget, const int32_t *called, int64_t n_called, dg_dp_recombination_margin *records, int32_t *called_out, int32_t *best_value) = nullptr;
     int (*dp_recombination_stats)(void *, int64_t *out, int n) = nullptr;
     int (*dp_score_paths)(void *, const int32_t *paths, int64_t n_pairs, dg_dp_pair_score *out) = nullptr;
+    // optional (--budget-recombination-margins): the records of dp_recombination_margins for one called pair per listed limit, each at its
+    // own budget, from one joint pass (dg_dp_recombination_margins_budgets), and that call's statistics
+    int (*dp_recombination_margins_budgets)(void *, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records, int32_t *called_out,
+                                            int32_t *best_values) = nullptr;
+    int (*dp_recombination_budget_stats)(void *, int64_t *out, int n) = nullptr;
 };
 
 // one row of a --pins file: level, vertex ids as --genotype-table prints them (-1: any), require / forbid, the unordered genotype (two
@@ -149,6 +154,7 @@ struct Options {
     std::string phase_margins;   // (ours) --phase-margins: TSV with one row per pair of neighbouring het levels of the answer at -R: the best pair of paths that keeps its phase against the best that switches it (diploid)
     std::string budget_phase_margins; // (ours) --budget-phase-margins, with --budgets: the rows of --phase-margins for the answer at every listed limit that has one, behind a column r, from one joint pass (diploid)
     std::string recombination_margins; // (ours) --recombination-margins: TSV with one row per transition: the crossovers the answer at -R spends there against the best pair of paths that spends another number there (diploid)
+    std::string budget_recombination_margins; // (ours) --budget-recombination-margins, with --budgets: the rows of --recombination-margins for the answer at every listed limit that has one, behind a column r, from one joint pass (diploid)
     std::string tag_reads;       // (ours) --tag-reads: TSV with one row per read: which haplotype of the answer at -R its minimizers support (diploid)
 };
 
@@ -281,6 +287,14 @@ struct RecombinationMargins { // --recombination-margins: over the transitions o
     double wall_s = 0;
 };
 
+struct BudgetRecombinationMargins {   // --budget-recombination-margins: per listed limit with an answer the counts of RecombinationMargins; one device call for all
+    bool set = false;
+    struct Row { int32_t r = 0; RecombinationMargins counts; };
+    std::vector<Row> rows;
+    int64_t segments = 0;
+    double wall_s = 0;
+};
+
 struct ReadTags {             // --tag-reads: hap1 / hap2 = reads with more private minimizers of that haplotype; tie: as many of both (> 0); no_evidence: none of either
     bool set = false;
     int64_t reads = 0, hap1 = 0, hap2 = 0, tie = 0, no_evidence = 0;
@@ -310,6 +324,7 @@ struct Summary {              // what tests and the CLI report
     PhaseMargins phase_margins;
     BudgetPhaseMargins budget_phase_margins;
     RecombinationMargins recombination_margins;
+    BudgetRecombinationMargins budget_recombination_margins;
     std::vector<ObjectiveRow> objective_rows;   // --objective-table: the listed budgets in order (without --budgets: -R)
     ReadTags read_tags;
     PinSummary pins;

@@ -492,8 +492,8 @@ typedef struct dg_dp_recombination_margin {
  * budget, an id outside its level (the message names the first such (query, row, level)); DG_ERR_STATE without a graph.  Results are
  * staged on the host: a refused or failed call writes nothing, the statistics included.  Needs dg_dp_load_graph only, reads and writes
  * nothing of a run, and leaves what the genotype, phase and pin statistics report as it was.  Synchronises.
- * Not here: a form with a budget per query, a pinned form, more than one GPU, and windows of several transitions -- a breakpoint
- * that can slide by one level shows as margin 0 at both transitions, and that is the intended reading. */
+ * A budget per query: dg_dp_recombination_margins_budgets below.  Not here: a pinned form, more than one GPU, and windows of several
+ * transitions -- a breakpoint that can slide by one level shows as margin 0 at both transitions, and that is the intended reading. */
 int dg_dp_recombination_margins(dg_ctx *, int32_t budget, const int32_t *called, int64_t n_called, dg_dp_recombination_margin *records,
                                 int32_t *called_out, int32_t *best_value);
 /* measurement: the last successful dg_dp_recombination_margins on this context: out[0] = transitions, out[1] = edge-kernel launches,
@@ -501,6 +501,42 @@ int dg_dp_recombination_margins(dg_ctx *, int32_t budget, const int32_t *called,
  * reserved, out[6] = launches in all; n >= 7 (zeros before the first call).  DG_ERR_ARG: null out or n < 7.  DG_ERR_STATE: no DP state
  * on this context yet. */
 int dg_dp_get_recombination_stats(dg_ctx *, int64_t *out, int n);
+/* The same for every listed budget from ONE joint pass.  n queries (1 .. 256); query q has the budget budgets[q] >= 0, in any order, with
+ * repeats.  called (host) = NULL or [n][2][n_levels], one pair of cells per level for every query, every id inside its level; with a
+ * non-null called, called_out is required.  records (host) = [n][n_levels - 1], called_out (host) = [n][n_levels - 1][2],
+ * best_values (host) = [n].  Query q gets, field for field, what dg_dp_recombination_margins(budgets[q], called[q], 1, ...) writes: the
+ * tie order of the hop pair, NEG_INF / -1 where nothing is reachable, s_called and called_value at that query's own budget, and
+ * best_values[q] = V_{budgets[q]}.  Queries of one budget share one set of records: they are computed once per DISTINCT budget and
+ * copied to each such query.  A budget nobody fits gives its queries NEG_INF / -1 records and DG_OK while their neighbours get answers.
+ * Why one pass suffices: both states mean "at most r", so plane p of F_l and of B_{l+1} computed at bmax = the largest budget is plane
+ * p at any b <= bmax, and E^b_t[s] = max F_l[i][j][r] + d + B_{l+1}[i'][j'][b - s - r] reads planes of that one pass; V_b is plane b of
+ * the sink's cell.  Only the planes paired in the gather depend on b.
+ * Closing check, per distinct budget b: max over s of E^b_t[s] == V_b at every transition; DG_ERR_STATE naming the level and the budget
+ * otherwise.
+ * Device: the schedule of dg_dp_recombination_margins run once with bmax + 1 planes (the plan by joint_state_bytes at that size, forward
+ * checkpoints, the segments from the last to the first with F recomputed, B rolling in two states, one score matrix per transition,
+ * B_0 not formed), with two launches per transition whatever the number of budgets, so a call issues as many launches as
+ * dg_dp_recombination_margins(bmax).  The host sorts the distinct budgets bud[0 .. nd).  rb_edges_budgets_kernel is rb_edges_kernel
+ * with one more grid dimension: workgroup (x, i, d) handles row i at budget bud[d], its lanes stride over (j >= i, r <= bud[d]), the
+ * state stride is bmax + 1 and the B plane bud[d] - w - r; the same three running 64-bit maxima, packed candidate, two-word key and
+ * wave and workgroup reduction, to part[d][s][i][x].  A row of budget b has k * (b + 1) lanes, so of the x workgroups of a row only
+ * the first ceil(k * (b + 1) / 256) (at most 4096, the lanes striding beyond) store a key and are read.  rb_finish_budgets_kernel:
+ * 3 * nd workgroups reduce part[d][s] to record d of the level in a device array [nd][n_levels - 1] that is copied out once; the
+ * workgroups behind them answer called_out, one wave per query, with the query's own budget in the r loop.  V_b for all planes is one
+ * copy of bmax + 1 words.  No atomics, every word has one owner, nothing depends on the order of lanes or workgroups.
+ * Limits and errors are those of dg_dp_recombination_margins at the largest budget: DG_ERR_UNSUPPORTED for a widest level > 32767,
+ * bmax + 1 > 4096 or n > 256; DG_ERR_ARG for n < 1, a null budgets, records or best_values, called without called_out, a negative
+ * budget (the message names the first such query), an id outside its level (the first such (query, row, level)); DG_ERR_STATE without
+ * a graph.  Results and statistics are staged on the host: a refused or failed call writes nothing.  Needs dg_dp_load_graph only,
+ * reads and writes nothing of a run, and leaves every other statistics block as it was, that of dg_dp_recombination_margins included.
+ * Synchronises.  Not here: a pinned form, more than one GPU, windows of several transitions. */
+int dg_dp_recombination_margins_budgets(dg_ctx *, const int32_t *budgets, int64_t n, const int32_t *called, dg_dp_recombination_margin *records,
+                                        int32_t *called_out, int32_t *best_values);
+/* measurement: the last successful dg_dp_recombination_margins_budgets on this context: out[0] = queries, out[1] = distinct budgets,
+ * out[2] = transitions, out[3] = edge-kernel launches, out[4] = finish launches, out[5] = segments, out[6] = levels swept forward
+ * twice, out[7] = peak bytes of device memory the call had reserved, out[8] = launches in all; n >= 9 (zeros before the first call).
+ * DG_ERR_ARG: null out or n < 9.  DG_ERR_STATE: no DP state on this context yet. */
+int dg_dp_get_recombination_budget_stats(dg_ctx *, int64_t *out, int n);
 /* What a pair of source -> sink paths is worth in the objective that the sweep's value approximates: every colour counts once, however
  * many vertices of a path carry it.  Hom(p) = the union of the hom colour lists of p's vertices, Het(p) that of its het lists; hom ids
  * and het ids are two separate id spaces, as in the transition score (an id present in both kinds is two colours).  All four numbers are
