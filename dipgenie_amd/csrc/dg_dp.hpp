@@ -145,8 +145,18 @@ constexpr int N_PAIR_RCS = (int)(sizeof PAIR_RCS / sizeof PAIR_RCS[0]);
 // PAIR_BIG_MAX_INDEG.  A big row has PAIR_BIG_MAX_INDEG wider records of its own (5-bit ranks) and a cooperative workgroup per
 // (slot block, chunk) whose four waves walk a quarter of them each; its PAIR_MAX_INDEG light records carry PAIR_ROW_BIG as in-degree.
 constexpr int PAIR_BIG_MAX_INDEG = 32;
-constexpr int PAIR_BIG_INLINE = 8;                      // big rows of a pair whose position rides in the kernel arguments (8 bits each)
+constexpr int PAIR_BIG_INLINE = 8;                      // big rows of a narrow pair whose position rides in the kernel arguments (8 bits each); entries of PairDesc::big_in
 constexpr uint32_t PAIR_ROW_BIG = 15;                   // in-degree field of a light row record: the row is a big one
+// Wide pairs (option pair_wide): one of the three levels (source l - 2, middle l - 1, later l) is wider than PAIR_MAX_WIDTH.  The same
+// records with 10-bit positions (PairLayout<true>), the same kernels instantiated for them (template parameter WIDE).
+constexpr int PAIR_WIDE_MAX_WIDTH = 1023;               // widths of all three levels of a wide pair (10-bit positions in the records)
+constexpr int PAIR_WIDE_BIG_INLINE = 4;                 // big rows of a wide pair whose position rides in the kernel arguments (16 bits each)
+// Where the fields of a pair's records lie (dg_dp_pairs.hip writes them, pair_task reads them).  Row-record and slot x: source position,
+// w1 at W1, middle position at MID, w2 at W2, (row records) composed in-degree at DEG; slot z: destination column at bit 20; the winner's
+// mid word: middle row at MID_ROW, middle column at MID_COL, w2u + w2v below; kk = k1 | k2 << KK.  y and the ord word are the same in both.
+template <bool WIDE> struct PairLayout;
+template <> struct PairLayout<false> { static constexpr uint32_t POS = 0x7FFFu, W1 = 15, MID = 16, MID_MASK = 0xFFu, W2 = 24, DEG = 25, COL_MASK = 0xFFu, MID_ROW = 16, MID_COL = 8, MID_W = 0xFFu, KK = 8; };
+template <> struct PairLayout<true> { static constexpr uint32_t POS = 0x3FFu, W1 = 10, MID = 11, MID_MASK = 0x3FFu, W2 = 21, DEG = 22, COL_MASK = 0x3FFu, MID_ROW = 13, MID_COL = 3, MID_W = 0x7u, KK = 10; };
 struct PairDesc {                                       // pair of destination levels (l - 1, l); on the host and on the device (L2 prefetcher)
     int32_t l, nblocks;                                 // the later level; 64-slot blocks of composed column in-edges
     int32_t k0, k1, k2;                                 // widths of levels l - 2, l - 1, l
@@ -155,11 +165,14 @@ struct PairDesc {                                       // pair of destination l
     int64_t slot_first;                                 // first composed slot record
     int32_t n_big, dmax_light;                          // big rows (0: a light pair, dp_sweep_pair_kernel); largest composed in-degree among the light rows
     int64_t big_first;                                  // first entry of the big-row list (positions in level l, ascending); its records start at PAIR_BIG_MAX_INDEG * big_first
-    uint8_t big_in[PAIR_BIG_INLINE];                    // the pair's first big rows
+    uint16_t big_in[PAIR_BIG_INLINE];                   // the pair's first big rows (a wide pair passes the first PAIR_WIDE_BIG_INLINE of them)
+    int32_t wide;                                       // 1: its records are PairLayout<true>'s (one of k0, k1, k2 exceeds PAIR_MAX_WIDTH)
 };
-struct PairHist {                                       // pair launches per kernel: light pairs by index into PAIR_RCS, fan-in pairs N_PAIR_RCS further on
-    int64_t n[2 * N_PAIR_RCS] = {};
-    void add(const PairHist &o, int64_t sign = 1) { for (int q = 0; q < 2 * N_PAIR_RCS; ++q) n[q] += sign * o.n[q]; }
+// pair launches per kernel: light pairs by index into PAIR_RCS, fan-in pairs N_PAIR_RCS further on, then the same two of the wide layout
+constexpr int PAIR_HIST_WIDE = 2 * N_PAIR_RCS, N_PAIR_HIST = 2 * PAIR_HIST_WIDE;
+struct PairHist {
+    int64_t n[N_PAIR_HIST] = {};
+    void add(const PairHist &o, int64_t sign = 1) { for (int q = 0; q < N_PAIR_HIST; ++q) n[q] += sign * o.n[q]; }
 };
 
 struct SweepHist {                                      // launches per variant, by SweepVariant::index()
@@ -201,6 +214,11 @@ struct DpOptions {
     int64_t pair_fanin = 1;                             // pair_fanin: pairs whose later level has rows of composed in-degree 9..32 (big rows, dp_sweep_pair_coop_kernel); next load
     int64_t pair_fanin_min = 4096;                      // pair_fanin_min: ... only on a graph that has at least this many of them; below, the pairs are chosen as with pair_fanin 0; next load
     int64_t pair_fanin_max_big = 4, pair_fanin_max_indeg = PAIR_BIG_MAX_INDEG;     // pair_fanin_max_*: a fan-in pair has at most this many big rows / this largest composed in-degree; the gate measured on MHC-24: every big row adds four rows of workgroups, and from five big rows on a pair costs more than its two single launches (DESIGN s3.3); next load
+    int64_t pair_wide = 1;                              // pair_wide: pairs with a level of 256..1,023 vertices (10-bit records: the WIDE instantiations of the pair kernels); next load
+    int64_t pair_wide_min = 1024;                       // pair_wide_min: ... only on a graph that has at least this many of them; below, the pairs are chosen as with pair_wide 0; next load
+    int64_t pair_wide_fanin = 1;                        // pair_wide_fanin: 0 = a wide pair has no big rows; next load
+    int64_t pair_wide_max_width = PAIR_WIDE_MAX_WIDTH;  // pair_wide_max_width: widest level of a wide pair (measurement: 511 against 1,023); next load
+    int64_t pair_wide_rc = 0;                           // pair_wide_rc: n in PAIR_RCS = every wide pair launch takes chunks of n recombination counts (measurement); any other value: the cost model
     int64_t pair_digest = 0;                            // pair_digest: 1 = with digest 1 the pair launches stay, in the pair kernel's digest form (tests: the later level's digest; the earlier level's entry stays 0)
     int64_t test_force_pair_rc = 0;                     // test_force_pair_rc: n in PAIR_RCS = every pair launch takes chunks of n recombination counts; any other value: the cost model
     int64_t joint_state_bytes = (int64_t)8 << 30;       // joint_state_bytes: bound of the forward states of one segment of dg_dp_genotype_margins (a segment holds at least one level)

@@ -19,13 +19,24 @@
 //                          y = delta column of level l | delta column of level l - 1 << 16
 //                          z = rv2 | rv1 << 8 | steps of the segmented max << 16 | destination column << 20
 //
-// Eligible: both levels on the lean fast form without a dead column, both narrower than 256, at most 2,047 in-edges each, every
-// vertex of level l with a composed in-degree of at most PAIR_MAX_INDEG, score deltas resident in one window.  Pairs are chosen
-// greedily left to right and are disjoint.  Fan-in pairs (options pair_fanin, pair_fanin_min): the same rule with a composed in-degree
-// of at most PAIR_BIG_MAX_INDEG, the vertices above PAIR_MAX_INDEG listed as the pair's big rows.  The greedy choice under the wider
-// rule pairs other levels than the one above, so it is taken as a whole, and only where it holds at least pair_fanin_min pairs with a
-// big row; on every other graph the pairs are those of the narrow rule.  Built on the host from the in-CSR that the loader has just put
-// on the device (read back: two copies), so the in-edge order is the loader's by construction; the tables are filled by up to 16 threads.
+// Wide pairs (PairLayout<true> in dg_dp.hpp): the same records with 10-bit positions -- x = source | w1 << 10 | middle << 11 | w2 << 21 |
+// composed in-degree << 22, the destination column of slot z 10 bits wide -- for pairs in which one of the three levels holds 256..1,023
+// vertices; the first PAIR_WIDE_BIG_INLINE big rows ride in the kernel arguments, 16 bits each.
+//
+// Eligible: both levels on the lean fast form without a dead column, at most 2,047 in-edges each, every vertex of level l with a
+// composed in-degree of at most PAIR_MAX_INDEG, score deltas resident in one window.  Pairs are chosen greedily left to right and
+// are disjoint.  The widths, by rule:
+//   narrow rule   levels l - 1 and l at most PAIR_MAX_WIDTH (255) wide; the source level l - 2 up to 32,767 (15-bit source positions);
+//   wide rule     (options pair_wide, pair_wide_min, pair_wide_fanin) levels l - 1 and l at most PAIR_WIDE_MAX_WIDTH (1,023) wide.  A pair
+//                 takes the wide layout exactly when one of its three levels exceeds 255, and then the source level too is at most
+//                 1,023 wide -- except that a source beyond 1,023 over two narrow levels keeps the narrow layout.
+// Fan-in pairs (options pair_fanin, pair_fanin_min): either rule with a composed in-degree of at most PAIR_BIG_MAX_INDEG, the vertices
+// above PAIR_MAX_INDEG listed as the pair's big rows.  The greedy choice under a wider rule pairs other levels than the one under a
+// narrower rule, so a wider choice is taken as a whole: with big rows only where it holds at least pair_fanin_min pairs with a big
+// row, with wide levels only where it holds at least pair_wide_min pairs in the wide layout.  On every other graph the pairs are
+// those of the narrow rule without big rows.
+// Built on the host from the in-CSR that the loader has just put on the device (read back: two copies), so the in-edge order is the
+// loader's by construction; the tables are filled by up to 16 threads.
 #include <sched.h>
 
 #include <algorithm>
@@ -80,9 +91,11 @@ int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S) {
     DG_HIP(hipStreamSynchronize(c->stream));
     const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)16, S.opt.host_threads, (int64_t)cpu_share()}));
     auto indeg = [&](int v) { return (int)(in_off[v + 1] - in_off[v]); };
+    // the widest level any rule in use takes: the wide form's cap when it is on (its own rule below decides per pair)
+    const int wide_cap = (int)std::min<int64_t>(S.opt.pair_wide_max_width, PAIR_WIDE_MAX_WIDTH), any_cap = S.opt.pair_wide ? std::max(wide_cap, PAIR_MAX_WIDTH) : PAIR_MAX_WIDTH;
     auto level_ok = [&](int l) {
         const LevelDesc &d = S.descs[l];
-        return d.fast_ok == 1 && d.ndead == 0 && d.k2 <= PAIR_MAX_WIDTH && d.T <= PAIR_MAX_T && !d.bp_wide;
+        return d.fast_ok == 1 && d.ndead == 0 && d.k2 <= any_cap && d.T <= PAIR_MAX_T && !d.bp_wide;
     };
     // composed in-degree of every vertex of a level l that could be the later level of a pair (lean levels: at most 64 * 64), and per level
     // what the choice needs: smallest, largest, largest among the light rows, rows above PAIR_MAX_INDEG; cmin = 0: not eligible
@@ -105,18 +118,24 @@ int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S) {
         }
     });
     const int max_big = (int)std::min<int64_t>(S.opt.pair_fanin_max_big, PAIR_MAX_WIDTH), max_indeg = (int)std::min<int64_t>(S.opt.pair_fanin_max_indeg, PAIR_BIG_MAX_INDEG);
-    // greedy from the left, disjoint; fanin: big rows allowed.  Returns the number of pairs that have one.
-    auto choose = [&](bool fanin, std::vector<PairDesc> &pairs, std::vector<int32_t> &at) {
+    // greedy from the left, disjoint; fanin: big rows allowed; wide: levels up to wide_cap allowed.  A pair takes the wide layout exactly
+    // when one of its three levels exceeds PAIR_MAX_WIDTH -- but a source beyond wide_cap over two narrow levels keeps the narrow one, whose
+    // source positions have 15 bits.  Returns the number of pairs that have a big row; n_wide: of those in the wide layout.
+    auto choose = [&](bool fanin, bool wide, std::vector<PairDesc> &pairs, std::vector<int32_t> &at, int64_t &n_wide) {
         int64_t n_fanin = 0;
+        n_wide = 0;
         pairs.clear(); at.assign((size_t)L, -1);
         for (int l = 2; l < L; ++l) {
             const LevelSum &s = sum[(size_t)l];
             if (s.cmin < 1) continue;
-            if (s.cmax > PAIR_MAX_INDEG && !(fanin && s.cmax <= max_indeg && s.n_big <= max_big)) continue;
             const LevelDesc &d = S.descs[l];
+            const int k0 = S.descs[l - 1].k;
+            const bool wide_level = d.k > PAIR_MAX_WIDTH || d.k2 > PAIR_MAX_WIDTH, wide_layout = wide_level || (wide && k0 > PAIR_MAX_WIDTH && k0 <= wide_cap);
+            if (wide_level && !(wide && k0 <= wide_cap && d.k <= wide_cap && d.k2 <= wide_cap)) continue;
+            if (s.cmax > PAIR_MAX_INDEG && !(fanin && s.cmax <= max_indeg && s.n_big <= max_big && !(wide_layout && !S.opt.pair_wide_fanin))) continue;
             PairDesc p{};
-            p.l = l; p.k0 = S.descs[l - 1].k; p.k1 = d.k; p.k2 = d.k2; p.dmax = s.cmax; p.n_big = s.n_big; p.dmax_light = s.cmax_light;
-            n_fanin += s.n_big > 0;
+            p.l = l; p.k0 = k0; p.k1 = d.k; p.k2 = d.k2; p.dmax = s.cmax; p.n_big = s.n_big; p.dmax_light = s.cmax_light; p.wide = wide_layout;
+            n_fanin += s.n_big > 0; n_wide += wide_layout;
             at[(size_t)l] = (int32_t)pairs.size(); at[(size_t)l - 1] = -2;
             pairs.push_back(p);
             ++l;                                                        // disjoint: the next pair starts after this one
@@ -125,12 +144,25 @@ int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S) {
     };
     std::vector<int32_t> at;
     std::vector<PairDesc> pairs;
-    int64_t n_fanin = choose(false, pairs, at);
-    if (S.opt.pair_fanin) {
+    // the rule's choice with or without wide levels: the fan-in choice as a whole where it holds enough pairs with a big row, else the light one
+    int64_t n_fanin = 0, n_wide = 0;
+    auto choose_fanin = [&](bool wide, std::vector<PairDesc> &pairs, std::vector<int32_t> &at, int64_t &n_fanin, int64_t &n_wide) {
+        n_fanin = choose(false, wide, pairs, at, n_wide);
+        if (!S.opt.pair_fanin) return;
         std::vector<int32_t> at_f;
         std::vector<PairDesc> pairs_f;
-        const int64_t nf = choose(true, pairs_f, at_f);
-        if (nf >= std::max<int64_t>(S.opt.pair_fanin_min, 1)) { pairs.swap(pairs_f); at.swap(at_f); n_fanin = nf; }
+        int64_t nw = 0;
+        const int64_t nf = choose(true, wide, pairs_f, at_f, nw);
+        if (nf >= std::max<int64_t>(S.opt.pair_fanin_min, 1)) { pairs.swap(pairs_f); at.swap(at_f); n_fanin = nf; n_wide = nw; }
+    };
+    choose_fanin(false, pairs, at, n_fanin, n_wide);
+    // wide pairs take levels the choice above pairs otherwise: the wider choice as a whole, where it holds enough pairs in the wide layout
+    if (S.opt.pair_wide) {
+        std::vector<int32_t> at_w;
+        std::vector<PairDesc> pairs_w;
+        int64_t nf = 0, nw = 0;
+        choose_fanin(true, pairs_w, at_w, nf, nw);
+        if (nw >= std::max<int64_t>(S.opt.pair_wide_min, 1)) { pairs.swap(pairs_w); at.swap(at_w); n_fanin = nf; n_wide = nw; }
     }
     if ((int64_t)pairs.size() < std::max<int64_t>(S.opt.pair_min, 1)) return DG_OK;
     // slot blocks of every pair (a column never straddles a block), then the pairs' places in the tables
@@ -166,6 +198,9 @@ int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S) {
             uint32_t *blk = pslots.get() + 4 * p.slot_first;                // the open block
             int32_t *const br = big_rows.get() + p.big_first;
             uint32_t used = 0, maxdv = 1, h = 0;
+            typedef PairLayout<false> Y0;
+            typedef PairLayout<true> Y1;
+            const uint32_t W1 = p.wide ? Y1::W1 : Y0::W1, MID = p.wide ? Y1::MID : Y0::MID, W2 = p.wide ? Y1::W2 : Y0::W2, DEG = p.wide ? Y1::DEG : Y0::DEG;
             auto close_block = [&]() {
                 uint32_t steps = 0;
                 while ((1u << steps) < maxdv) ++steps;
@@ -188,20 +223,20 @@ int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S) {
                     for (uint32_t e1 = in_off[mv]; e1 < in_off[mv + 1]; ++e1, ++t) {
                         const uint32_t src = in_edge[e1] & 0x7FFFu, w1 = in_edge[e1] >> 31, r1 = e1 - in_off[mv];
                         const uint32_t i2 = e2 - d2.in_base, i1 = e1 - d1.in_base;          // delta row / column of either level
-                        rec[2 * t] = src | (w1 << 15) | (m << 16) | (w2 << 24) | (n << 25);
+                        rec[2 * t] = src | (w1 << W1) | (m << MID) | (w2 << W2) | (n << DEG);
                         rec[2 * t + 1] = i2 | (i1 << 11) | (r2 << 22) | (r1 << ru1_shift);
                         uint32_t *const sl = blk + 4 * (used + t);
-                        sl[0] = src | (w1 << 15) | (m << 16) | (w2 << 24);
+                        sl[0] = src | (w1 << W1) | (m << MID) | (w2 << W2);
                         sl[1] = i2 | (i1 << 16);
                         sl[2] = r2 | (r1 << 8) | ((uint32_t)c2 << 20);
                         sl[3] = 0;
                     }
                 }
-                for (; t < cap; ++t) { rec[2 * t] = n << 25; rec[2 * t + 1] = 0; }
+                for (; t < cap; ++t) { rec[2 * t] = n << DEG; rec[2 * t + 1] = 0; }
                 if (big) {
-                    for (t = 0; t < (uint32_t)PAIR_MAX_INDEG; ++t) { light[2 * t] = PAIR_ROW_BIG << 25; light[2 * t + 1] = 0; }
+                    for (t = 0; t < (uint32_t)PAIR_MAX_INDEG; ++t) { light[2 * t] = PAIR_ROW_BIG << DEG; light[2 * t + 1] = 0; }
                     br[h] = c2;
-                    if (h < (uint32_t)PAIR_BIG_INLINE) p.big_in[h] = (uint8_t)c2;
+                    if (h < (uint32_t)PAIR_BIG_INLINE) p.big_in[h] = (uint16_t)c2;
                     ++h;
                 }
                 used += n; maxdv = std::max(maxdv, n);
@@ -222,8 +257,8 @@ int dp_build_pairs(dg_ctx *c, const dg_dp_graph *g, DpState &S) {
     if (int rc = up(S.d_pbig_rows, big_rows.get(), 4 * (size_t)n_big)) return rc;
     DG_HIP(hipStreamSynchronize(c->stream));                            // the staging buffers die here
     if (getenv("DG_DEBUG"))
-        fprintf(stderr, "[dipgenie_hip] load: %zu level pairs (%.1f %% of the launches), %lld of them with big rows (%lld big rows), composed tables %.1f MB, built in %.3f s by %d threads\n",
-                pairs.size(), 100.0 * (double)pairs.size() / std::max(1, L - 1), (long long)n_fanin, (long long)n_big, 4e-6 * (double)(prow_words + pslot_words + pbig_words), wall_s() - t0, nt);
+        fprintf(stderr, "[dipgenie_hip] load: %zu level pairs (%.1f %% of the launches), %lld of them with big rows (%lld big rows), %lld in the wide layout, composed tables %.1f MB, built in %.3f s by %d threads\n",
+                pairs.size(), 100.0 * (double)pairs.size() / std::max(1, L - 1), (long long)n_fanin, (long long)n_big, (long long)n_wide, 4e-6 * (double)(prow_words + pslot_words + pbig_words), wall_s() - t0, nt);
     S.pairs.swap(pairs); S.pair_at.swap(at);
     return DG_OK;
 }

@@ -553,7 +553,7 @@ extern "C" int dg_dp_get_launch_profile(dg_ctx *c, char *buf, int cap) {
 extern "C" int dg_dp_get_pair_profile(dg_ctx *c, char *buf, int cap) {
     if (!c || !c->dp || !buf || cap < 2) { dgi::set_error("dg_dp_get_pair_profile: no state"); return DG_ERR_STATE; }
     std::string out;
-    for (int q = 0; q < 2 * dgi::N_PAIR_RCS; ++q)
+    for (int q = 0; q < dgi::N_PAIR_HIST; ++q)
         if (const int64_t n = c->dp->pair_hist.n[q]) out += (out.empty() ? "" : " ") + dgi::pair_variant_name(q) + ':' + std::to_string(n);
     if ((int)out.size() + 1 > cap) { dgi::set_error("dg_dp_get_pair_profile: buffer too small (%zu needed)", out.size() + 1); return DG_ERR_ARG; }
     memcpy(buf, out.c_str(), out.size() + 1);
@@ -586,6 +586,7 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"graph_batch", &DpO::graph_batch, -1, false}, {"l2_prefetch", &DpO::l2_prefetch, 0, false}, {"delta_overlap", &DpO::delta_overlap, 0, false}, {"pf_far", &DpO::pf_far, 0, false},
     {"side_stream", &DpO::side_stream, -1, false}, {"plane_limit", &DpO::plane_limit, 0, false}, {"test_poison_level", &DpO::test_poison_level, 0, false},
     {"test_poison_byte", &DpO::test_poison_byte, 0, false}, {"test_force_rc", &DpO::test_force_rc, 0, false}, {"pair_digest", &DpO::pair_digest, 0, false}, {"test_force_pair_rc", &DpO::test_force_pair_rc, 0, false},
+    {"pair_wide_rc", &DpO::pair_wide_rc, 0, false},
     {"score_slab_bytes", &DpO::score_slab_bytes, 0, true}, {"partner_slab_bytes", &DpO::partner_slab_bytes, 0, true},
     {"partner_wide", &DpO::partner_wide, 0, false},                // 0..2: clamped from above below
     {"joint_state_bytes", &DpO::joint_state_bytes, 0, true},
@@ -597,6 +598,8 @@ static const struct DpOptionKey { const char *key; int64_t DpO::*field; int64_t 
     {"host_threads", &DpO::host_threads, 1, false}, {"host_tables", &DpO::host_tables, 0, false}, {"delta_cap_entries", &DpO::delta_cap_entries, 0, true},
     {"pair_levels", &DpO::pair_levels, 0, false}, {"pair_min", &DpO::pair_min, 1, false}, {"pair_fanin", &DpO::pair_fanin, 0, false}, {"pair_fanin_min", &DpO::pair_fanin_min, 1, false},
     {"pair_fanin_max_big", &DpO::pair_fanin_max_big, 0, false}, {"pair_fanin_max_indeg", &DpO::pair_fanin_max_indeg, 0, false},
+    {"pair_wide", &DpO::pair_wide, 0, false}, {"pair_wide_min", &DpO::pair_wide_min, 1, false}, {"pair_wide_fanin", &DpO::pair_wide_fanin, 0, false},
+    {"pair_wide_max_width", &DpO::pair_wide_max_width, 0, true},
     {"lattice_chunk_cells", &DpO::chunk_units_cfg, 1, false},   // 16-bit back-pointer units; below 1 is an error, else rounded up to even; empties the chunk pool at once
 };
 static int dp_option(dg_ctx *c, const char *what, const char *key, const int64_t *set, int64_t *get) {   // set or get, the other is null

@@ -500,8 +500,8 @@ __global__ __launch_bounds__(256) void dp_sweep_coop_kernel(const uint4 *rowrec_
 // is the plain fast kernel's -- one wave per (destination row, slot block, chunk of RC planes), the leading scalars preloaded,
 // two load rounds: {composed row records, composed slot records}, then {both score deltas, RC values} per composed row in-edge.
 // Each lane keeps per plane (value, ord, mid): ord = (255 - ru2) << 24 | (255 - rv2) << 16 | (255 - ru1) << 8 | (255 - rv1) makes the
-// plain lexicographic max the reference's order over both levels; mid = middle row << 16 | middle column << 8 | w2u + w2v rides
-// along with the winner, so the head lane addresses the middle cell without another load.  The state of level l - 1 is never
+// plain lexicographic max the reference's order over both levels; mid = middle row << 16 | middle column << 8 | w2u + w2v (in the wide
+// layout: middle row << 13 | middle column << 3 | w2u + w2v, 10-bit positions: PairLayout in dg_dp.hpp) rides along with the winner, so the head lane addresses the middle cell without another load.  The state of level l - 1 is never
 // written.  The head stores value and back-pointer of its cell of level l, and the back-pointer ru1 << 8 | rv1 of the middle cell
 // it won through: cells that share a middle cell store the same word, middle cells nobody wins through stay unwritten (the walk
 // reaches a middle cell only from a winner).
@@ -540,10 +540,12 @@ struct PairHead {
 // cooperative region of the same launch); 2 = cooperative, recs = the big row's PAIR_BIG_MAX_INDEG records: wave `part` of the workgroup
 // walks a quarter of the composed row in-edges -- at most PAIR_MAX_INDEG, one gather step, the depth of a light row --, waves 1..3 park
 // (value, ord, mid) per plane in LDS, wave 0 merges them and finishes the task.  No wave leaves before the barrier.
-// digest: null, or (DIGEST) the per-level accumulators.
-template <int RC, bool DIGEST, int COOP>
+// digest: null, or (DIGEST) the per-level accumulators.  WIDE: the records' layout (PairLayout: 10-bit positions for levels up to
+// PAIR_WIDE_MAX_WIDTH wide); it changes the shifts and masks of the decode and of the mid word, nothing else.
+template <int RC, bool DIGEST, int COOP, bool WIDE>
 __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt,
                                           int i2, int g, int r0, int lvl, unsigned long long *digest, int part = 0, uint4 *ex = nullptr) {
+    typedef PairLayout<WIDE> Y;
     const int lane = threadIdx.x & 63;
     const int RP = H.RP, k0 = H.k0, pad_bytes = H.pad_bytes, dT1 = H.dT1, dT2 = H.dT2;
     const uint16_t *dm1 = H.dm1, *dm2 = H.dm2;
@@ -552,14 +554,14 @@ __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, 
     const uint2 rec = recs[lane & (NREC - 1)];                          // composed row in-edge t in lanes t, t + NREC, ...
     const uint4 sl = H.pslots_l[g * 64 + lane];
     const __amdgpu_buffer_rsrc_t cur_rsrc = state_rsrc(H.cur, H.buf_bytes);
-    const int du = __builtin_amdgcn_readfirstlane((int)(rec.x >> 25)) & (COOP == 2 ? 0x3F : 0xF);
+    const int du = __builtin_amdgcn_readfirstlane((int)(rec.x >> Y::DEG)) & (COOP == 2 ? 0x3F : 0xF);
     if (COOP == 1 && du > PAIR_MAX_INDEG) return;                       // (wave-uniform; no block barrier in the light region)
     const int t_lo = COOP == 2 ? (du * part) >> 2 : 0, t_hi = COOP == 2 ? (du * (part + 1)) >> 2 : du;   // this wave's share of the composed row in-edges
     const int steps = __builtin_amdgcn_readfirstlane((int)(sl.z >> 16)) & 0xF;
     const bool act = sl.x != 0xFFFFFFFFu;
-    const int j = (int)(sl.x & 0x7FFFu), wv = (int)((sl.x >> 15) & 1u) + (int)((sl.x >> 24) & 1u);
-    const uint32_t lanemid = (((sl.x >> 16) & 0xFFu) << 8) | ((sl.x >> 24) & 1u);
-    const int j2 = act ? (int)((sl.z >> 20) & 0xFFu) : -1 - lane;
+    const int j = (int)(sl.x & Y::POS), wv = (int)((sl.x >> Y::W1) & 1u) + (int)((sl.x >> Y::W2) & 1u);
+    const uint32_t lanemid = (((sl.x >> Y::MID) & Y::MID_MASK) << Y::MID_COL) | ((sl.x >> Y::W2) & 1u);
+    const int j2 = act ? (int)((sl.z >> 20) & Y::COL_MASK) : -1 - lane;
     const int c2 = dT2 ? (int)(sl.y & 0xFFFFu) : 0, c1 = dT1 ? (int)(sl.y >> 16) : 0;
     const uint32_t ordc = ((uint32_t)(BP_MAX_RANK - (int)(sl.z & 0xFFu)) << 16) | (uint32_t)(BP_MAX_RANK - (int)((sl.z >> 8) & 0xFFu));
     int bval[RC];
@@ -577,7 +579,7 @@ __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, 
             for (int u = 0; u < U; ++u) {
                 if (t + u < t_hi) {                                         // wave-uniform
                     const uint32_t px = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, t + u), py = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, t + u);
-                    const int iu = (int)(px & 0x7FFFu), w = (int)((px >> 15) & 1u) + (int)((px >> 24) & 1u) + wv;
+                    const int iu = (int)(px & Y::POS), w = (int)((px >> Y::W1) & 1u) + (int)((px >> Y::W2) & 1u) + wv;
                     const int off = ((iu * RP + (r0 - w)) * k0 + j) * 4 + pad_bytes;
                     dl[u] = (int)dm2[(int)(py & 0x7FFu) * dT2 + c2] + (int)dm1[(int)((py >> 11) & 0x7FFu) * dT1 + c1];
 #pragma unroll
@@ -588,9 +590,9 @@ __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, 
             for (int u = 0; u < U; ++u) {
                 if (t + u < t_hi) {
                     const uint32_t px = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, t + u), py = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, t + u);
-                    const int w = (int)((px >> 15) & 1u) + (int)((px >> 24) & 1u) + wv;
+                    const int w = (int)((px >> Y::W1) & 1u) + (int)((px >> Y::W2) & 1u) + wv;
                     const uint32_t ord = ((uint32_t)(BP_MAX_RANK - (int)((py >> 22) & RANK_MASK)) << 24) | ((uint32_t)(BP_MAX_RANK - (int)((py >> RU1_SHIFT) & RANK_MASK)) << 8) | ordc;
-                    const uint32_t mid = ((((px >> 16) & 0xFFu) << 16) | ((px >> 24) & 1u)) + lanemid;
+                    const uint32_t mid = ((((px >> Y::MID) & Y::MID_MASK) << Y::MID_ROW) | ((px >> Y::W2) & 1u)) + lanemid;
                     relax_pair<RC>(vals[u], dl[u], ord, mid, r0, w, RP, bval, bord, bmid);
                 }
             }
@@ -630,7 +632,7 @@ __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, 
     const bool head = act & ((lane == 0) | (pj2 != j2));
     unsigned long long dsum = 0;
     if (head) {
-        const int k1 = kk & 0xFF, k2 = kk >> 8;
+        const int k1 = kk & (int)Y::COL_MASK, k2 = kk >> Y::KK;
 #pragma unroll
         for (int q = 0; q < RC; ++q) {
             const int r2 = r0 + q;
@@ -642,12 +644,12 @@ __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, 
                     if (nt) store_bp_nt(&bp2[idx], b2); else bp2[idx] = (uint16_t)b2;
                     if (bord[q]) {                                          // reachable: mark the middle cell it came through (row r2 - w2u - w2v >= 0)
                         const uint32_t m = bmid[q];
-                        bp1[((int)(m >> 16) * RP + r2 - (int)(m & 0xFFu)) * k1 + (int)((m >> 8) & 0xFFu)] = (uint16_t)~bord[q];
+                        bp1[((int)(m >> Y::MID_ROW) * RP + r2 - (int)(m & Y::MID_W)) * k1 + (int)((m >> Y::MID_COL) & Y::MID_MASK)] = (uint16_t)~bord[q];
                     }
                 }
                 if (DIGEST && bval[q] != NEG_INF) {
                     const unsigned long long o = ((unsigned long long)r2 * k2 + i2) * k2 + j2;   // oracle's r-major index
-                    dsum += digest_term(bval[q], o, bmid[q] >> 16, (bmid[q] >> 8) & 0xFFu);
+                    dsum += digest_term(bval[q], o, bmid[q] >> Y::MID_ROW, (bmid[q] >> Y::MID_COL) & Y::MID_MASK);
                 }
             }
         }
@@ -658,7 +660,11 @@ __device__ __forceinline__ void pair_task(const PairHead &H, const uint2 *recs, 
 // DG: empty -- the kernels the product runs, dp_sweep_pair_kernel<RC> -- or one trailing unsigned long long *digest (parity runs, options
 // digest + pair_digest): the head lane then also adds the oracle's term of every reachable cell of level l -- its predecessor is the
 // middle cell in bmid -- to digest[lvl]; level l - 1 is never materialised and keeps the 0 of the run's memset.
-template <int RC, typename... DG>
+// WIDE: the record layout (PairLayout).  The tracer prints the instantiations as dp_sweep_pair_kernel<RC, false> and <RC, true>; the pair
+// profile calls them dp_sweep_pair_kernel<RC> and dp_sweep_pair_wide_kernel<RC>.  The narrow instantiations are, instruction for
+// instruction, what dp_sweep_pair_kernel<RC> was before the wide layout existed (a body shared through an inlined function instead
+// made the compiler order their scalar instructions differently).
+template <int RC, bool WIDE, typename... DG>
 __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l, const uint4 *pslots_l, const int32_t *cur, const uint16_t *dm1, const uint16_t *dm2,
                                                             int nblocks, int rp_k, int pad_bytes, int dT1, int dT2, uint32_t buf_bytes,   // 16 dwords: preloaded
                                                             int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl,
@@ -669,16 +675,17 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_kernel(const uint2 *prow_l,
     if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
     const PairHead H{pslots_l, cur, dm1, dm2, rp_k & 0x1FFF, rp_k >> 13, pad_bytes, dT1, dT2, buf_bytes};
     unsigned long long *const acc[] = {nullptr, digest...};
-    pair_task<RC, DIGEST, 0>(H, prow_l + i2 * PAIR_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)]);
+    pair_task<RC, DIGEST, 0, WIDE>(H, prow_l + i2 * PAIR_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)]);
 }
 
 // The same for a fan-in pair: the later level holds n_big big rows (composed in-degree 9..32).  Workgroup z < 4 n_big = slot block
 // 4 x + (z & 3) of big row z >> 2, its four waves a quarter of the row's records each; the region is dispatched first, as in
 // dp_sweep_coop_kernel.  The rows beyond run the light task; a big row returns from it at once.  The first PAIR_BIG_INLINE big rows
-// ride in a preloaded scalar (8 bits each), later ones come from the pair's list.
-template <int RC, typename... DG>
+// ride in a preloaded scalar (8 bits each; of a wide pair the first PAIR_WIDE_BIG_INLINE, 16 bits each), later ones come from the pair's
+// list.  In the pair profile: dp_sweep_pair_coop_kernel<RC> (narrow) and dp_sweep_pair_coop_wide_kernel<RC>.
+template <int RC, bool WIDE, typename... DG>
 __global__ __launch_bounds__(256) void dp_sweep_pair_coop_kernel(const uint2 *prow_l, const uint4 *pslots_l, const uint2 *pbig_l, const int32_t *cur, const uint16_t *dm2,
-                                                                 unsigned long long big_in, int nblocks, int n_big, int rp_k, int dT2,        // 16 dwords: preloaded
+                                                                 unsigned long long big_in, int nblocks, int n_big, int rp_k, int dT2,   // 16 dwords: preloaded
                                                                  const uint16_t *dm1, int dT1, int pad_bytes, uint32_t buf_bytes, const int32_t *__restrict__ big_rows,
                                                                  int32_t *__restrict__ nxt, uint16_t *__restrict__ bp1, uint16_t *__restrict__ bp2, int kk, int nt, int *progress, int lvl,
                                                                  DG... digest) {
@@ -694,13 +701,14 @@ __global__ __launch_bounds__(256) void dp_sweep_pair_coop_kernel(const uint2 *pr
         const int g = (int)blockIdx.x * 4 + (hz & 3);
         if (g >= nblocks) return;                                       // workgroup-uniform: nobody is left at the barrier
         const int h = hz >> 2;
-        const int i2 = h < PAIR_BIG_INLINE ? (int)((big_in >> (8 * h)) & 0xFFu) : big_rows[h];
-        pair_task<RC, DIGEST, 2>(H, pbig_l + h * PAIR_BIG_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)], (int)(threadIdx.x >> 6), ex);
+        const int i2 = WIDE ? (h < PAIR_WIDE_BIG_INLINE ? (int)((big_in >> (16 * h)) & 0xFFFFu) : big_rows[h])
+                            : (h < PAIR_BIG_INLINE ? (int)((big_in >> (8 * h)) & 0xFFu) : big_rows[h]);
+        pair_task<RC, DIGEST, 2, WIDE>(H, pbig_l + h * PAIR_BIG_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)], (int)(threadIdx.x >> 6), ex);
         return;
     }
     const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), i2 = (int)blockIdx.z - zc;
     if (g >= nblocks) return;                                           // wave-uniform; no block barrier below
-    pair_task<RC, DIGEST, 1>(H, prow_l + i2 * PAIR_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)]);
+    pair_task<RC, DIGEST, 1, WIDE>(H, prow_l + i2 * PAIR_MAX_INDEG, nxt, bp1, bp2, kk, nt, i2, g, r0, lvl, acc[sizeof...(DG)]);
 }
 
 // Sweep look-ahead: streams the graph tables (row records, slot records, in-edges, score deltas) of a batch of upcoming
@@ -967,9 +975,11 @@ int sweep_launch_level(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
 }
 
 // the pair's chunk size by choose_rc's cost model: the wave's chain is the largest composed in-degree -- of a fan-in pair the largest among
-// the light rows or a quarter of the largest big row's, plus the LDS merge, and every big row adds four rows of workgroups
+// the light rows or a quarter of the largest big row's, plus the LDS merge, and every big row adds four rows of workgroups.  Wide pairs
+// take the same model and constants: measured on MHC-24 it puts all but a handful at chunks of 4, the best single setting (DESIGN s3.3).
 static int choose_pair_rc(const DpState &S, const PairDesc &p) {
     for (int q = 0; q < N_PAIR_RCS; ++q) if (S.opt.test_force_pair_rc == PAIR_RCS[q]) return q;     // tests: this chunk size for every pair
+    for (int q = 0; q < N_PAIR_RCS; ++q) if (p.wide && S.opt.pair_wide_rc == PAIR_RCS[q]) return q;  // measurement: ... for every wide pair
     int best_q = 0;
     double best = 1e300;
     const double rows = (double)p.k2 + 4.0 * p.n_big;
@@ -982,7 +992,10 @@ static int choose_pair_rc(const DpState &S, const PairDesc &p) {
     }
     return best_q;
 }
-std::string pair_variant_name(int q) { return std::string(q < N_PAIR_RCS ? "dp_sweep_pair_kernel<" : "dp_sweep_pair_coop_kernel<") + std::to_string(PAIR_RCS[q % N_PAIR_RCS]) + ">"; }
+std::string pair_variant_name(int q) {
+    static const char *const kernels[] = {"dp_sweep_pair_kernel<", "dp_sweep_pair_coop_kernel<", "dp_sweep_pair_wide_kernel<", "dp_sweep_pair_coop_wide_kernel<"};
+    return std::string(kernels[q / N_PAIR_RCS]) + std::to_string(PAIR_RCS[q % N_PAIR_RCS]) + ">";
+}
 
 // f(RC, DIGEST), each a std::integral_constant, for the run-time chunk index q and digest flag
 template <int Q = 0, class F>
@@ -1010,30 +1023,39 @@ int sweep_launch_pair(const DpState &S, SweepLaunch &X, int l, hipStream_t s) {
     const int nt = (int64_t)d2.k2 * d2.k2 * S.RP >= S.opt.bp_nt_min_cells ? 1 : 0;
     const uint2 *prow_l = S.d_prow.as<uint2>() + p.row_first;
     const uint4 *pslots_l = S.d_pslots.as<uint4>() + p.slot_first;
-    const int rp_k = S.RP | (p.k0 << 13), kk = p.k1 | (p.k2 << 8), nblocks = p.nblocks, n_big = p.n_big, pad_bytes = F.pad_bytes;
+    const int rp_k = S.RP | (p.k0 << 13), kk = p.k1 | (p.k2 << (p.wide ? PairLayout<true>::KK : PairLayout<false>::KK)), nblocks = p.nblocks, n_big = p.n_big, pad_bytes = F.pad_bytes;
     const uint32_t buf_bytes = F.buf_bytes;
     uint16_t *bp1 = F.bp ? F.bp + d1.bp_off : nullptr, *bp2 = F.bp ? F.bp + d2.bp_off : nullptr;
     int *progress = F.progress;
     unsigned long long *digest = F.digest;                              // (passed to the digest form only: the product's kernels take no such argument)
     if (p.n_big == 0) {
         auto light = [&](auto RC, auto DG) {
-            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l, digest);
-            else hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l);
+            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value, false, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l, digest);
+            else hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value, false>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l);
         };
-        launch_pair_rc(q, X.digest, light);
+        auto light_wide = [&](auto RC, auto DG) {
+            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value, true, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l, digest);
+            else hipLaunchKernelGGL((dp_sweep_pair_kernel<RC.value, true>), grid, dim3(256), 0, s, prow_l, pslots_l, cur, dm1, dm2, nblocks, rp_k, pad_bytes, dT1, dT2, buf_bytes, nxt, bp1, bp2, kk, nt, progress, l);
+        };
+        if (p.wide) launch_pair_rc(q, X.digest, light_wide); else launch_pair_rc(q, X.digest, light);
     } else {
         const uint2 *pbig_l = S.d_pbig.as<uint2>() + (size_t)PAIR_BIG_MAX_INDEG * (size_t)p.big_first;
         const int32_t *big_rows = S.d_pbig_rows.as<int32_t>() + p.big_first;
         unsigned long long big_in = 0;
-        for (int h = 0; h < PAIR_BIG_INLINE; ++h) big_in |= (unsigned long long)p.big_in[h] << (8 * h);
+        if (p.wide) for (int h = 0; h < PAIR_WIDE_BIG_INLINE; ++h) big_in |= (unsigned long long)p.big_in[h] << (16 * h);
+        else for (int h = 0; h < PAIR_BIG_INLINE; ++h) big_in |= (unsigned long long)p.big_in[h] << (8 * h);
         auto fanin = [&](auto RC, auto DG) {
-            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l, digest);
-            else hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l);
+            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value, false, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l, digest);
+            else hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value, false>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l);
         };
-        launch_pair_rc(q, X.digest, fanin);
+        auto fanin_wide = [&](auto RC, auto DG) {
+            if constexpr (DG.value) hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value, true, unsigned long long *>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l, digest);
+            else hipLaunchKernelGGL((dp_sweep_pair_coop_kernel<RC.value, true>), grid, dim3(256), 0, s, prow_l, pslots_l, pbig_l, cur, dm2, big_in, nblocks, n_big, rp_k, dT2, dm1, dT1, pad_bytes, buf_bytes, big_rows, nxt, bp1, bp2, kk, nt, progress, l);
+        };
+        if (p.wide) launch_pair_rc(q, X.digest, fanin_wide); else launch_pair_rc(q, X.digest, fanin);
     }
     X.flip ^= 1;
-    X.pair_hist.n[q + (p.n_big ? N_PAIR_RCS : 0)]++;
+    X.pair_hist.n[q + (p.n_big ? N_PAIR_RCS : 0) + (p.wide ? PAIR_HIST_WIDE : 0)]++;
     return DG_OK;
 }
 

@@ -601,6 +601,12 @@ int dg_dp_get_level_digest(dg_ctx *, uint64_t *out, int64_t n);
  *                         dp_sweep_pair_coop_kernel) are chosen too, on a graph that has enough of them (pair_fanin_min); 0: never (next load)
  *   pair_fanin_min n      ... only on a graph with at least n such pairs (default 4096); below, the pairs are exactly those of pair_fanin 0 (next load)
  *   pair_fanin_max_big n, pair_fanin_max_indeg n   a fan-in pair has at most n big rows (default 4) / a largest composed in-degree of n (default and at most 32): the measured gate (next load)
+ *   pair_wide 0|1         1 (default): pairs in which the source, middle or later level holds 256..1,023 vertices are chosen too (records with 10-bit
+ *                         positions: dp_sweep_pair_wide_kernel, dp_sweep_pair_coop_wide_kernel), on a graph that has enough of them (pair_wide_min); 0: never (next load)
+ *   pair_wide_min n       ... only on a graph with at least n such pairs (default 1024); below, the pairs are exactly those of pair_wide 0 (next load)
+ *   pair_wide_fanin 0|1   1 (default): a wide pair may have big rows, under the gate of pair_fanin_max_*; 0: light wide pairs only (next load)
+ *   pair_wide_max_width n, pair_wide_rc n   measurement: the widest level of a wide pair (default and at most 1023; next load) / n one of the chunk
+ *                         sizes (1, 2, 4) = every wide pair launch takes it, any other value (default 0): the cost model
  *   pair_digest 0|1       tests: 1 = with digest 1 the pair launches stay and run the pair kernel's digest form: the later level of a pair gets the
  *                         oracle's digest, the earlier level (never materialised) keeps 0; 0 (default): digest 1 refuses pair launches
  *   test_force_pair_rc n  tests: n one of the pair kernel's chunk sizes (1, 2, 4) = every pair launch takes it; any other value (default 0): the cost model
@@ -623,11 +629,12 @@ int dg_dp_get_launch_profile(dg_ctx *, char *buf, int cap);
 int dg_dp_list_sweep_variants(char *buf, int cap);
 /* measurement: the level-pair launches of the last dg_dp_run (two adjacent low-fan-in levels composed into one launch, options
  * pair_levels / pair_min), as "dp_sweep_pair_kernel<rc>:count ...", followed by the fan-in pairs (options pair_fanin / pair_fanin_min) as
- * "dp_sweep_pair_coop_kernel<rc>:count ..."; empty if there were none.  dg_dp_get_launch_profile and
+ * "dp_sweep_pair_coop_kernel<rc>:count ...", then the wide pairs (options pair_wide / pair_wide_min) as "dp_sweep_pair_wide_kernel<rc>:count ..."
+ * and "dp_sweep_pair_coop_wide_kernel<rc>:count ..."; empty if there were none.  dg_dp_get_launch_profile and
  * dg_dp_list_sweep_variants list the single-level launches only; dg_dp_timing::n_forward_launches counts both kinds. */
 int dg_dp_get_pair_profile(dg_ctx *, char *buf, int cap);
 /* parity: the names of every light pair kernel the dispatch can launch, space-separated, in the order of the pair profile (the fan-in form has
- * dp_sweep_pair_coop_kernel<rc> for the same chunk sizes).  Needs no context. */
+ * dp_sweep_pair_coop_kernel<rc>, the wide forms dp_sweep_pair_wide_kernel<rc> and dp_sweep_pair_coop_wide_kernel<rc> for the same chunk sizes).  Needs no context. */
 int dg_dp_list_pair_variants(char *buf, int cap);
 
 /* ---- haploid (vertex, r) DP ---- */

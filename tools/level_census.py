@@ -53,3 +53,33 @@ for limit in (4, 8, 16, 32):
             for lo_d, hi_d in ((9, 16), (17, 24), (25, 32)):
                 n = int(((n_big[fanin] >= lo_b) & (n_big[fanin] <= hi_b) & (max_comp[fanin] >= lo_d) & (max_comp[fanin] <= hi_d)).sum())
                 if n: print(f"    big rows {lo_b}..{hi_b}, largest composed in-degree {lo_d}..{hi_d}: {n} pairs")
+# wide levels and wide pairs (options pair_wide / pair_wide_fanin / pair_wide_max_width): a level wider than 255 pairs only in the wide
+# layout, whose three levels -- the source level too -- are at most `cap` wide; everything else as shipped (composed in-degree <= 32, at
+# most 4 big rows; greedy from the left)
+wide = width > 255
+cells = width.astype(np.int64) ** 2
+wruns = np.diff(np.flatnonzero(np.diff(np.concatenate([[0], wide.astype(np.int8), [0]]))))[::2]
+print(f"levels wider than 255: {int(wide.sum())} of {L - 1} = {100 * wide.sum() / (L - 1):.1f} %, holding {100 * cells[wide].sum() / cells.sum():.1f} % of all cells; widest level {int(width.max())}, most in-edges in one level {int(t_lvl.max())}")
+if wruns.size: print(f"  in {wruns.size} runs, mean length {wruns.mean():.1f} (p90 {int(np.percentile(wruns, 90))}, max {int(wruns.max())})")
+def greedy(cap, light_wide):
+    ok = (min_in >= 1) & (max_in <= 64) & (t_lvl <= 2047)
+    out, l = [], 2
+    while l < L:
+        lv_wide = width[l - 1] > 255 or width[l] > 255
+        layout = lv_wide or 255 < width[l - 2] <= cap
+        fits = ok[l - 1] and ok[l] and max(width[l - 1], width[l]) <= (cap if cap else 255) and not (lv_wide and width[l - 2] > cap)
+        if fits and max_comp[l] <= 32 and n_big[l] <= 4 and not (layout and light_wide and n_big[l]):
+            out.append((l, bool(layout) and cap > 0))
+            l += 2
+        else: l += 1
+    return out
+base = greedy(0, False)
+print(f"level pairs as shipped without wide pairs (composed in-degree <= 32, at most 4 big rows): {len(base)}; {L - 1 - len(base)} launches in all")
+for cap in (511, 1023):
+    for light_wide in (False, True):
+        ch = greedy(cap, light_wide)
+        wl = np.array([l for (l, w) in ch if w], np.int64)
+        mid_cells = cells[wl - 1].sum() if wl.size else 0
+        light = int((max_comp[wl] <= 8).sum()) if wl.size else 0
+        src_only = int(((width[wl - 1] <= 255) & (width[wl] <= 255)).sum()) if wl.size else 0      # wide by their source level alone
+        print(f"  width <= {cap}{', wide pairs only when light' if light_wide else ''}: {len(ch)} pairs, {L - 1 - len(ch)} launches; {wl.size} in the wide layout ({light} of them light, {src_only} by their source level alone), their middle levels hold {100 * mid_cells / cells.sum():.1f} % of all cells")
